@@ -19,14 +19,17 @@ one all-reduce that proves the rank count and ONE 24-byte all-gather of per-rank
 `python bench.py --gpus N` started WITHOUT a launcher spawns the N ranks itself (torch.distributed.run,
 127.0.0.1); started under torchrun (the driver's way) it checks WORLD_SIZE == N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (+ `roofline_valu`)
-and `cpu_baseline` objects.  The oracle (oracle/) is only used for the cpu_baseline legs.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run (`python bench.py --gpus 1
+--steps N --warmup W`) sets up, warms up, times the N steps and prints the headline: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step), the workload's `config` and `ranks`.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/*.npy; the inputs are
+seeded, so two builds can be compared output for output.
 
-The default command (`python bench.py --gpus 1`) measures the headline metric first (timed region and
-workload as BASELINE.json's metric names them) and AFTER it, outside that timed region, the other
-BASELINE configs on the same GPU, each with its own `roofline` and `cpu_baseline`, under `workloads`:
-`extract_only` (configs[1] as written: extraction alone), `stereo_1241x376` (configs[2]) and `lba_50kf`
-(configs[4]).  `--no-workloads` skips them.
+`--full` adds everything else, outside the headline's timed region: `roofline` (+ `roofline_valu`) and
+`cpu_baseline` objects (the oracle, oracle/, is only used for the cpu_baseline legs), and after the headline
+the other BASELINE configs on the same GPU, each with its own `roofline` and `cpu_baseline`, under
+`workloads`: `extract_only` (configs[1] as written: extraction alone), `stereo_1241x376` (configs[2]) and
+`lba_50kf` (configs[4]).  `--full --no-workloads` skips those.
 """
 import argparse
 import importlib
@@ -279,6 +282,67 @@ def ctypes_ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+DUMP_BUDGET = 64 << 20      # bytes of .npy data that --dump-outputs writes at most
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 where the path computes float64, float32 otherwise."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the budget of %d" % (total, DUMP_BUDGET))
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(d / (k + ".npy"), v)
+
+
+def dump_sample(nframes, nbatches, per_frame_bytes):
+    """The frames of a batch whose features are dumped: a fixed, seeded sample (at most 64) that keeps the dump within DUMP_BUDGET."""
+    s = int(min(nframes, 64, max(1, (DUMP_BUDGET - (1 << 20)) // (nbatches * per_frame_bytes))))
+    return np.sort(np.random.default_rng(0).choice(nframes, s, replace=False))
+
+
+def features_dump(ext, nframes, pick):
+    """One handle's last batch: every frame's keypoint count, and keypoints (x, y, size, angle, response, octave, class_id) and descriptor
+    bytes of the frames `pick`, zero past each frame's count."""
+    kps, desc, counts = ext.download(nframes)
+    n = int(counts[pick].max())
+    k = np.zeros((len(pick), n, 7), np.float32)
+    d = np.zeros((len(pick), n, 32), np.float32)
+    for j, f in enumerate(pick):
+        c = int(counts[f])
+        k[j, :c] = np.stack([kps[f, :c][name].astype(np.float32) for name in kps.dtype.names], 1)
+        d[j, :c] = desc[f, :c]
+    return counts, k, d
+
+
+def masked(rows, counts, fill):
+    """Per-frame result rows with the entries past the frame's keypoint count set to `fill` (the library leaves them unspecified)."""
+    rows = rows.copy()
+    rows[np.arange(rows.shape[1])[None, :] >= np.asarray(counts)[:, None]] = fill
+    return rows
+
+
+def dump_extract_match(dirname, exts, mts, B, nbatches, per_step, issued):
+    """The timed path's last step: the batches its handle pairs still hold (each pair keeps only its last batch, so the last len(exts) of
+    the step).  Per batch: keypoint and match counts of every frame; keypoints, descriptors and SearchByBoW matches (index into frame
+    i + 1's keypoints, -1 = none) of a seeded sample of frames."""
+    first = issued - per_step
+    held = range(max(first, issued - len(exts)), issued)
+    pick = dump_sample(B, len(held), exts[0].capacity * (7 + 32 + 1) * 4)
+    out = {"sample_frames": pick}
+    for j in held:
+        k, tag = j % len(exts), "batch%d_" % ((j - first) % nbatches)
+        counts, out[tag + "keypoints"], out[tag + "descriptors"] = features_dump(exts[k], B, pick)
+        out[tag + "counts"] = counts
+        if mts[k] is not None:
+            m, _, nm = mts[k].download(B)
+            out[tag + "matches"] = masked(m[pick, :out[tag + "keypoints"].shape[1]], counts[pick], -1)
+            out[tag + "nmatches"] = nm
+    write_outputs(dirname, out)
+
+
 def bench_extract_match(a, orbx, torch, grp, dev_t, local, rank_info):
     rank, world = grp.rank, grp.world
     W, H, B, nf = a.width, a.height, a.batch, a.nfeatures
@@ -354,6 +418,8 @@ def bench_extract_match(a, orbx, torch, grp, dev_t, local, rank_info):
     sync_all()
     elapsed = time.perf_counter() - t0
     nbatches_timed = nbatches * passes[0]
+    if a.dump_outputs and rank == 0:      # before anything below runs another batch on the handles
+        dump_extract_match(a.dump_outputs, exts, mts, B, nbatches, nbatches_timed, issued[0])
     # per-launch kernel time of every stage inside the overlapped pipeline: each launch covers B frames
     stage_ms, timed = {}, []
     for k, e in enumerate(exts):
@@ -371,7 +437,7 @@ def bench_extract_match(a, orbx, torch, grp, dev_t, local, rank_info):
     # the same stages with nothing else on the GPU: one handle pair, synchronised after every call (outside the timed region).
     # This is what `rocprofv3 --kernel-trace --stats` of a --streams 1 run reports as the kernels' average durations.
     alone_ms, alone_match = {}, (0.0, 0.0)
-    if timed:
+    if timed and a.full:
         k0 = timed[0]
         exts[k0].set_profiling(True)
         if mts[k0] is not None:
@@ -452,76 +518,78 @@ def bench_extract_match(a, orbx, torch, grp, dev_t, local, rank_info):
     if rank != 0:
         return None
     K = float(counts.mean())
-    alg = algorithmic_bytes(W, H, K)
-    merge_orient(alg, stage_ms, alone_ms)
-    if mt is not None:
-        stage_ms["match_distances"] = float(match_split[0])   # k_bow_topk
-        stage_ms["match_replay"] = float(match_split[1])      # k_bow_order + k_bow_greedy (sequential greedy assignment, latency bound)
-        alone_ms["match_distances"], alone_ms["match_replay"] = float(alone_match[0]), float(alone_match[1])
-        alg["match_distances"] = alg.pop("match")
-        alg["match_replay"] = 8 * int(K)                      # reads the candidate lists' heads, writes one result per query
-    else:
-        alg.pop("match")
-    # dominant kernel = the longest stage when nothing else runs (= rocprofv3's per-kernel average of a --streams 1 run; the contended
-    # event spans below additionally contain the time a launch waits behind the other stream pairs' workgroups)
-    ref_ms = alone_ms if alone_ms else stage_ms
-    dom = max((k for k in ref_ms if alg.get(k, 0) > 0), key=lambda k: ref_ms[k])
-    bytes_per_launch = alg[dom] * B
-    achieved = bytes_per_launch / (ref_ms[dom] * 1e-3) / 1e9
-    copy_bw = measured_copy_bandwidth(torch, dev_t)
-    whole_bytes = sum(alg.values()) * B * nbatches_timed
-    whole_gbs = whole_bytes / (t / a.steps) / 1e9
-    roofline = {"bound": "hbm", "kernel": STAGE_KERNEL.get(dom, dom), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": pmc_traffic(dom, B),
-                "algorithmic_bytes_per_launch": int(bytes_per_launch), "avg_launch_ms": round(ref_ms[dom], 4), "frames_per_launch": B,
-                "timing": "HIP events on the library's stream, launches synchronised (no other stream active)",
-                "contended": {"avg_launch_ms": round(stage_ms.get(dom, 0.0), 4),
-                              "achieved": round(bytes_per_launch / (max(stage_ms.get(dom, 0.0), 1e-9) * 1e-3) / 1e9, 2),
-                              "note": "event span of the same launch inside the %d-stream pipeline (includes queueing behind the other streams)" % NS},
-                "dominant_by_contended_span": (lambda d2: {"kernel": STAGE_KERNEL.get(d2, d2) + (" (7 launches)" if d2 == "pyramid" else ""),
-                                                          "span_ms": round(stage_ms[d2], 4), "achieved": round(alg[d2] * B / (stage_ms[d2] * 1e-3) / 1e9, 2),
-                                                          "frac": round(alg[d2] * B / (stage_ms[d2] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                                          "note": "the stage with the longest event span inside the pipeline of this command (what a rocprofv3 trace of this "
-                                                                  "command ranks first by total kernel time); for the seven dependent k_resize launches the span is mostly queueing"})(
-                    max((k for k in stage_ms if alg.get(k, 0) > 0), key=lambda k: stage_ms[k])),
-                "rocprof": {"alone": "profiles/*_alone_kernel_stats.csv = rocprofv3 --kernel-trace --stats of `bench.py --alone` (every launch synchronised; average durations = stage_ms_alone)",
-                            "this_command": "profiles/*_kernel_stats.csv of this command (durations stretched by the concurrency of the three streams)"},
-                "stage_ms_alone": {k: round(v, 4) for k, v in alone_ms.items()},
-                "stage_ms_contended": {k: round(v, 4) for k, v in stage_ms.items()},
-                "stage_frac_of_hbm_peak_alone": {k: round(alg[k] * B / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for k, v in alone_ms.items() if alg.get(k, 0) > 0 and v > 0},
-                "measured_copy_GBs": round(copy_bw, 1), "frac_of_measured_copy": round(achieved / copy_bw, 5),
-                # the two longest kernels of the path (the detector and the matcher's distance kernel) are within a few per cent of each other: whichever
-                # is `kernel` above on this box, both are priced here (the matcher's is a popcount kernel: its bytes are 2 x 32 KB of descriptors per
-                # frame pair, its bound is VALU issue - roofline_valu -, its HBM fraction says nothing about it)
-                "longest_kernels_alone": {STAGE_KERNEL.get(k, k): {"avg_launch_ms": round(ref_ms[k], 4), "achieved": round(alg[k] * B / (ref_ms[k] * 1e-3) / 1e9, 2),
-                                                                   "frac": round(alg[k] * B / (ref_ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
-                                          for k in sorted((k for k in ref_ms if alg.get(k, 0) > 0), key=lambda k: -ref_ms[k])[:3]},
-                "whole_path": {"algorithmic_bytes_per_frame": int(sum(alg.values())), "achieved": round(whole_gbs, 2), "frac": round(whole_gbs / HBM_PEAK_GBS, 5),
-                               "note": "all stages' algorithmic bytes / wall time per step (the driver-visible rate)"}}
-    # the bound the path actually runs into: VALU issue (integer byte arithmetic), from the committed SQ_INSTS_VALU pass
-    valu = {k: pmc_valu(k, B) for k in alg}
-    roofline_valu = None
-    if any(v for v in valu.values()):
-        tot = sum(v for v in valu.values() if v)      # (alg has an "octree" key with 0 bytes: the quadtree's instructions are in the sum)
-        rate = tot * nbatches_timed / (t / a.steps) / 1e9
-        dv = valu.get(dom)
-        # the same instructions priced kernel by kernel with the static opcode mix: seconds per batch if every SIMD issued without a bubble
-        def kcyc(stage):
-            kn = STAGE_KERNEL.get(stage, stage).split("<")[0].split(" ")[0]
-            return VALU["mix"].get(kn, VALU["cycles_half_rate_class"])
-        t_mix = sum(v * kcyc(k) for k, v in valu.items() if v) / (256 * 4 * VALU["clock_GHz"] * 1e9)
-        peak_mix = tot / t_mix / 1e9 if t_mix > 0 else VALU_PEAK_GINST
-        roofline_valu = {"bound": "valu_issue", "unit": "G wave-instr/s", "peak": round(VALU_PEAK_GINST, 1),
-                         "achieved": round(rate, 2), "frac": round(rate / VALU_PEAK_GINST, 4),
-                         "peak_basis": "measured: %.2f cycles per wave64 instruction per SIMD for the half-rate class (left shifts, 32-bit min / max, bcnt, perm, alignbyte, dot2 / dot4, sad, "
-                                       "cndmask, packed-16), %.2f for add / sub / and / or / xor / mov / f32 add / fma / two-operand 16-bit, at %.2f GHz" % (VALU["cycles_half_rate_class"], VALU["cycles_full_rate_class"], VALU["clock_GHz"]),
-                         "evidence": VALU["evidence"],
-                         "peak_static_mix": round(peak_mix, 1), "frac_static_mix": round(rate / peak_mix, 4),
-                         "peak_guide_2cycle": round(VALU["peak_guide_2cycle"], 1), "frac_guide_2cycle": round(rate / VALU["peak_guide_2cycle"], 4),
-                         "cycles_per_instr_static_mix": {STAGE_KERNEL.get(k, k): round(kcyc(k), 2) for k, v in valu.items() if v},
-                         "valu_insts_per_batch": int(tot), "source": "profiles/latest_sq_counters.json (SQ_INSTS_VALU pass of this command)",
-                         "dominant_kernel": ({"kernel": STAGE_KERNEL.get(dom, dom), "valu_insts_per_launch": int(dv),
-                                              "frac_alone": round(dv / (ref_ms[dom] * 1e-3) / 1e9 / VALU_PEAK_GINST, 4)} if dv else None)}
+    roofline = roofline_valu = None
+    if a.full:      # stage spans alone, copy bandwidth and committed counters: runs of their own, beside the headline
+        alg = algorithmic_bytes(W, H, K)
+        merge_orient(alg, stage_ms, alone_ms)
+        if mt is not None:
+            stage_ms["match_distances"] = float(match_split[0])   # k_bow_topk
+            stage_ms["match_replay"] = float(match_split[1])      # k_bow_order + k_bow_greedy (sequential greedy assignment, latency bound)
+            alone_ms["match_distances"], alone_ms["match_replay"] = float(alone_match[0]), float(alone_match[1])
+            alg["match_distances"] = alg.pop("match")
+            alg["match_replay"] = 8 * int(K)                      # reads the candidate lists' heads, writes one result per query
+        else:
+            alg.pop("match")
+        # dominant kernel = the longest stage when nothing else runs (= rocprofv3's per-kernel average of a --streams 1 run; the contended
+        # event spans below additionally contain the time a launch waits behind the other stream pairs' workgroups)
+        ref_ms = alone_ms if alone_ms else stage_ms
+        dom = max((k for k in ref_ms if alg.get(k, 0) > 0), key=lambda k: ref_ms[k])
+        bytes_per_launch = alg[dom] * B
+        achieved = bytes_per_launch / (ref_ms[dom] * 1e-3) / 1e9
+        copy_bw = measured_copy_bandwidth(torch, dev_t)
+        whole_bytes = sum(alg.values()) * B * nbatches_timed
+        whole_gbs = whole_bytes / (t / a.steps) / 1e9
+        roofline = {"bound": "hbm", "kernel": STAGE_KERNEL.get(dom, dom), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": pmc_traffic(dom, B),
+                    "algorithmic_bytes_per_launch": int(bytes_per_launch), "avg_launch_ms": round(ref_ms[dom], 4), "frames_per_launch": B,
+                    "timing": "HIP events on the library's stream, launches synchronised (no other stream active)",
+                    "contended": {"avg_launch_ms": round(stage_ms.get(dom, 0.0), 4),
+                                  "achieved": round(bytes_per_launch / (max(stage_ms.get(dom, 0.0), 1e-9) * 1e-3) / 1e9, 2),
+                                  "note": "event span of the same launch inside the %d-stream pipeline (includes queueing behind the other streams)" % NS},
+                    "dominant_by_contended_span": (lambda d2: {"kernel": STAGE_KERNEL.get(d2, d2) + (" (7 launches)" if d2 == "pyramid" else ""),
+                                                              "span_ms": round(stage_ms[d2], 4), "achieved": round(alg[d2] * B / (stage_ms[d2] * 1e-3) / 1e9, 2),
+                                                              "frac": round(alg[d2] * B / (stage_ms[d2] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                                              "note": "the stage with the longest event span inside the pipeline of this command (what a rocprofv3 trace of this "
+                                                                      "command ranks first by total kernel time); for the seven dependent k_resize launches the span is mostly queueing"})(
+                        max((k for k in stage_ms if alg.get(k, 0) > 0), key=lambda k: stage_ms[k])),
+                    "rocprof": {"alone": "profiles/*_alone_kernel_stats.csv = rocprofv3 --kernel-trace --stats of `bench.py --alone` (every launch synchronised; average durations = stage_ms_alone)",
+                                "this_command": "profiles/*_kernel_stats.csv of this command (durations stretched by the concurrency of the three streams)"},
+                    "stage_ms_alone": {k: round(v, 4) for k, v in alone_ms.items()},
+                    "stage_ms_contended": {k: round(v, 4) for k, v in stage_ms.items()},
+                    "stage_frac_of_hbm_peak_alone": {k: round(alg[k] * B / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for k, v in alone_ms.items() if alg.get(k, 0) > 0 and v > 0},
+                    "measured_copy_GBs": round(copy_bw, 1), "frac_of_measured_copy": round(achieved / copy_bw, 5),
+                    # the two longest kernels of the path (the detector and the matcher's distance kernel) are within a few per cent of each other: whichever
+                    # is `kernel` above on this box, both are priced here (the matcher's is a popcount kernel: its bytes are 2 x 32 KB of descriptors per
+                    # frame pair, its bound is VALU issue - roofline_valu -, its HBM fraction says nothing about it)
+                    "longest_kernels_alone": {STAGE_KERNEL.get(k, k): {"avg_launch_ms": round(ref_ms[k], 4), "achieved": round(alg[k] * B / (ref_ms[k] * 1e-3) / 1e9, 2),
+                                                                       "frac": round(alg[k] * B / (ref_ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
+                                              for k in sorted((k for k in ref_ms if alg.get(k, 0) > 0), key=lambda k: -ref_ms[k])[:3]},
+                    "whole_path": {"algorithmic_bytes_per_frame": int(sum(alg.values())), "achieved": round(whole_gbs, 2), "frac": round(whole_gbs / HBM_PEAK_GBS, 5),
+                                   "note": "all stages' algorithmic bytes / wall time per step (the driver-visible rate)"}}
+        # the bound the path actually runs into: VALU issue (integer byte arithmetic), from the committed SQ_INSTS_VALU pass
+        valu = {k: pmc_valu(k, B) for k in alg}
+        roofline_valu = None
+        if any(v for v in valu.values()):
+            tot = sum(v for v in valu.values() if v)      # (alg has an "octree" key with 0 bytes: the quadtree's instructions are in the sum)
+            rate = tot * nbatches_timed / (t / a.steps) / 1e9
+            dv = valu.get(dom)
+            # the same instructions priced kernel by kernel with the static opcode mix: seconds per batch if every SIMD issued without a bubble
+            def kcyc(stage):
+                kn = STAGE_KERNEL.get(stage, stage).split("<")[0].split(" ")[0]
+                return VALU["mix"].get(kn, VALU["cycles_half_rate_class"])
+            t_mix = sum(v * kcyc(k) for k, v in valu.items() if v) / (256 * 4 * VALU["clock_GHz"] * 1e9)
+            peak_mix = tot / t_mix / 1e9 if t_mix > 0 else VALU_PEAK_GINST
+            roofline_valu = {"bound": "valu_issue", "unit": "G wave-instr/s", "peak": round(VALU_PEAK_GINST, 1),
+                             "achieved": round(rate, 2), "frac": round(rate / VALU_PEAK_GINST, 4),
+                             "peak_basis": "measured: %.2f cycles per wave64 instruction per SIMD for the half-rate class (left shifts, 32-bit min / max, bcnt, perm, alignbyte, dot2 / dot4, sad, "
+                                           "cndmask, packed-16), %.2f for add / sub / and / or / xor / mov / f32 add / fma / two-operand 16-bit, at %.2f GHz" % (VALU["cycles_half_rate_class"], VALU["cycles_full_rate_class"], VALU["clock_GHz"]),
+                             "evidence": VALU["evidence"],
+                             "peak_static_mix": round(peak_mix, 1), "frac_static_mix": round(rate / peak_mix, 4),
+                             "peak_guide_2cycle": round(VALU["peak_guide_2cycle"], 1), "frac_guide_2cycle": round(rate / VALU["peak_guide_2cycle"], 4),
+                             "cycles_per_instr_static_mix": {STAGE_KERNEL.get(k, k): round(kcyc(k), 2) for k, v in valu.items() if v},
+                             "valu_insts_per_batch": int(tot), "source": "profiles/latest_sq_counters.json (SQ_INSTS_VALU pass of this command)",
+                             "dominant_kernel": ({"kernel": STAGE_KERNEL.get(dom, dom), "valu_insts_per_launch": int(dv),
+                                                  "frac_alone": round(dv / (ref_ms[dom] * 1e-3) / 1e9 / VALU_PEAK_GINST, 4)} if dv else None)}
     metric = "frames/s ORB extract+match (1000 feat, 640x480)" if not a.no_match else "frames/s ORB extract (1000 feat, 640x480)"
     wl = ("batch of %d synthetic %dx%d frames per GPU (%d distinct resident batches per step, one launch set per batch)" % (B, W, H, nbatches)) if a.workload == "batch" else \
          ("one synthetic sequence of %d %dx%d frames per GPU (BASELINE config 4), resident as %d batches of %d" % (B * nbatches, W, H, nbatches, B))
@@ -537,8 +605,9 @@ def bench_extract_match(a, orbx, torch, grp, dev_t, local, rank_info):
                       per_rank=[{"frames": r[0], "seconds": round(r[1], 6), "keypoints": r[2], "frames_per_s": round(r[0] / r[1], 1),
                                  "launch_issue_seconds": round(r[3], 6), "issue_frac": round(r[3] / r[1], 3), "numa_node": int(r[4]), "bound_cores": int(r[5]),
                                  "device": (rank_info.get("devices") or [None] * len(per_rank))[i]} for i, r in enumerate(per_rank)]),
-        "roofline": roofline,
     }
+    if roofline:
+        out["roofline"] = roofline
     if roofline_valu:
         out["roofline_valu"] = roofline_valu
     if status:
@@ -552,7 +621,7 @@ def bench_extract_match(a, orbx, torch, grp, dev_t, local, rank_info):
         out["workloads"] = {"extract_only": extract_only}
         if match_mfma:
             out["workloads"]["extract_match_mfma_opt_in"] = match_mfma
-    if _STALE:
+    if _STALE and roofline:
         out["roofline"]["traffic_note"] = "profiles/%s measured on other kernel sources: counters withheld" % ", ".join(_STALE)
     return out
 
@@ -637,65 +706,76 @@ def bench_stereo(a, orbx, torch, grp, dev_t, local, rank_info):
         step(i, a.alone)
     sync_all(); grp.barrier(); sync_all()
     elapsed = time.perf_counter() - t0
-    # ONE handle pair, every step synchronised: the latency chain of a 64-pair batch (what a caller that waits for each batch's result gets; this is
-    # the "17k pairs/s" figure of tools/bench_configs.py, against the pipelined `value` of three handle pairs)
-    nchain = max(3, a.steps // 2)
-    sync_all()
-    tcs = time.perf_counter()
-    for i in range(nchain):
-        step(0, False)
-        mts[0].sync()
-    chain = (time.perf_counter() - tcs) / nchain
-    # every stage with nothing else on the GPU (HIP events on the library's streams, calls synchronised)
-    ext.set_profiling(True)
-    mt.sync()
-    try:
-        mt.last_timing()
-    except orbx.OrbxError:
-        pass
-    for _ in range(3):
-        step(0, True)
-    alone = dict(ext.last_timing()[1])
-    alone["stereo_match"] = float(mt.last_timing())
-    ext.set_profiling(False)
-    u, z = mt.download_stereo(B)
-    cnt = ext.download(2 * B)[2]
+    k = (a.steps - 1) % NS                   # the handle pair of the last timed step
+    if a.dump_outputs and grp.rank == 0:      # before the runs below use handle pair 0 again
+        pick = dump_sample(2 * B, 1, exts[k].capacity * (7 + 32 + 1) * 4 + mts[k].max_features * 2 * 4)
+        counts, kp, de = features_dump(exts[k], 2 * B, pick)
+        u, z = mts[k].download_stereo(B)
+        lp = pick[pick < B]                       # left images of the sample: frame f of the batch is pair f's left image
+        write_outputs(a.dump_outputs, {"sample_frames": pick, "counts": counts, "keypoints": kp, "descriptors": de, "sample_pairs": lp,
+                                       "uRight": masked(u[lp, :kp.shape[1]], counts[lp], -1), "depth": masked(z[lp, :kp.shape[1]], counts[lp], -1)})
+    if a.full:
+        # ONE handle pair, every step synchronised: the latency chain of a 64-pair batch (what a caller that waits for each batch's result gets; this is
+        # the "17k pairs/s" figure of tools/bench_configs.py, against the pipelined `value` of three handle pairs)
+        nchain = max(3, a.steps // 2)
+        sync_all()
+        tcs = time.perf_counter()
+        for i in range(nchain):
+            step(0, False)
+            mts[0].sync()
+        chain = (time.perf_counter() - tcs) / nchain
+        # every stage with nothing else on the GPU (HIP events on the library's streams, calls synchronised)
+        ext.set_profiling(True)
+        mt.sync()
+        try:
+            mt.last_timing()
+        except orbx.OrbxError:
+            pass
+        for _ in range(3):
+            step(0, True)
+        alone = dict(ext.last_timing()[1])
+        alone["stereo_match"] = float(mt.last_timing())
+        ext.set_profiling(False)
+    u, z = mts[k].download_stereo(B)     # (the frames of every handle pair are the same: so are their results)
+    cnt = exts[k].download(2 * B)[2]
     t, total, per_rank = grp.aggregate(elapsed, B * a.steps, int(cnt.sum()))
     if grp.rank != 0:
         return None
     K = float(cnt.mean())
     nmatch = float((u >= 0).sum(1).mean())
-    alg = algorithmic_bytes(W, H, K)
-    alg.pop("match")
-    merge_orient(alg, alone)
-    per_image = sum(alg.values())
-    # Frame::ComputeStereoMatches per pair (both descriptor sets once + one result per left keypoint) + the SAD windows of the refined
-    # matches (11x11 left patch, 11 rows x 21 columns right strip, src/Frame.cc:1248-1292) + mvuRight / mvDepth
-    alg_match = 32 * (K + K) + 8 * K + (121 + 231) * nmatch + 8 * K
-    stage_alg = {k: v * 2 * B for k, v in alg.items()}
-    stage_alg["stereo_match"] = alg_match * B
-    dom = max((k for k in alone if stage_alg.get(k, 0) > 0), key=lambda k: alone[k])
-    achieved = stage_alg[dom] / (alone[dom] * 1e-3) / 1e9
-    kern = dict(STAGE_KERNEL, stereo_match="k_stereo_rows + k_stereo_full + k_stereo_cut")
-    whole = (per_image * 2 + alg_match) * total / t / 1e9
-    roof = {"bound": "hbm", "kernel": kern.get(dom, dom), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": pmc_traffic(dom, 2 * B, "latest_stereo_hbm_traffic.json"), "algorithmic_bytes_per_launch": int(stage_alg[dom]), "avg_launch_ms": round(alone[dom], 4),
-            "images_per_launch": 2 * B, "algorithmic_bytes_per_image": int(per_image), "algorithmic_bytes_per_pair": int(per_image * 2 + alg_match),
-            "timing": "HIP events on the library's streams, calls synchronised (no other stream active)",
-            "stage_ms_alone": {k: round(v, 4) for k, v in alone.items()},
-            "stage_frac_of_hbm_peak_alone": {k: round(stage_alg[k] / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for k, v in alone.items() if stage_alg.get(k, 0) > 0 and v > 0},
-            "whole_path": {"achieved": round(whole, 2), "frac": round(whole / HBM_PEAK_GBS, 5)},
-            "rocprof": "profiles/*_stereo_kernel_stats.csv (this workload, pipelined) and *_stereo_alone_kernel_stats.csv (--alone: average durations = stage_ms_alone)"}
     out = {"metric": "stereo pairs/s ORB extract L+R + ComputeStereoMatches (2000 feat, 1241x376)", "value": round(total / t, 1), "unit": "pairs/s",
            "images_per_s": round(2 * total / t, 1),
            "n_gpus": grp.world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(t / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
            "config": {"workload": "BASELINE config 3: batch of %d KITTI-shaped stereo pairs, extract left + right (2000 feat) + L<->R match on the device" % B, "streams": NS,
                       "keypoints_per_image": round(K, 1), "stereo_matches_per_pair": round(nmatch, 1)},
-           "single_handle_synchronised": {"pairs_per_s": round(B / chain, 1), "ms_per_batch": round(chain * 1e3, 3), "sum_of_stages_alone_ms": round(sum(alone.values()), 3),
-                                          "note": "one handle pair, the host waits for every batch: the latency chain (stage sum + launch gaps + the host's issue time); "
-                                                  "`value` overlaps %d such chains on %d stream pairs" % (NS, NS)},
-           "ranks": dict(rank_info, per_rank=[{"pairs": r[0], "seconds": round(r[1], 6)} for r in per_rank]), "roofline": roof}
+           "ranks": dict(rank_info, per_rank=[{"pairs": r[0], "seconds": round(r[1], 6)} for r in per_rank])}
+    if a.full:
+        alg = algorithmic_bytes(W, H, K)
+        alg.pop("match")
+        merge_orient(alg, alone)
+        per_image = sum(alg.values())
+        # Frame::ComputeStereoMatches per pair (both descriptor sets once + one result per left keypoint) + the SAD windows of the refined
+        # matches (11x11 left patch, 11 rows x 21 columns right strip, src/Frame.cc:1248-1292) + mvuRight / mvDepth
+        alg_match = 32 * (K + K) + 8 * K + (121 + 231) * nmatch + 8 * K
+        stage_alg = {k: v * 2 * B for k, v in alg.items()}
+        stage_alg["stereo_match"] = alg_match * B
+        dom = max((k for k in alone if stage_alg.get(k, 0) > 0), key=lambda k: alone[k])
+        achieved = stage_alg[dom] / (alone[dom] * 1e-3) / 1e9
+        kern = dict(STAGE_KERNEL, stereo_match="k_stereo_rows + k_stereo_full + k_stereo_cut")
+        whole = (per_image * 2 + alg_match) * total / t / 1e9
+        roof = {"bound": "hbm", "kernel": kern.get(dom, dom), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "traffic": pmc_traffic(dom, 2 * B, "latest_stereo_hbm_traffic.json"), "algorithmic_bytes_per_launch": int(stage_alg[dom]), "avg_launch_ms": round(alone[dom], 4),
+                "images_per_launch": 2 * B, "algorithmic_bytes_per_image": int(per_image), "algorithmic_bytes_per_pair": int(per_image * 2 + alg_match),
+                "timing": "HIP events on the library's streams, calls synchronised (no other stream active)",
+                "stage_ms_alone": {k: round(v, 4) for k, v in alone.items()},
+                "stage_frac_of_hbm_peak_alone": {k: round(stage_alg[k] / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for k, v in alone.items() if stage_alg.get(k, 0) > 0 and v > 0},
+                "whole_path": {"achieved": round(whole, 2), "frac": round(whole / HBM_PEAK_GBS, 5)},
+                "rocprof": "profiles/*_stereo_kernel_stats.csv (this workload, pipelined) and *_stereo_alone_kernel_stats.csv (--alone: average durations = stage_ms_alone)"}
+        out["single_handle_synchronised"] = {"pairs_per_s": round(B / chain, 1), "ms_per_batch": round(chain * 1e3, 3), "sum_of_stages_alone_ms": round(sum(alone.values()), 3),
+                                             "note": "one handle pair, the host waits for every batch: the latency chain (stage sum + launch gaps + the host's issue time); "
+                                                     "`value` overlaps %d such chains on %d stream pairs" % (NS, NS)}
+        out["roofline"] = roof
     if not a.no_cpu_baseline and grp.world == 1:
         cb = stereo_cpu_baseline(orbx, W, H, nf, bf)
         if cb:
@@ -716,29 +796,33 @@ def bench_lba(a, orbx, torch, grp, dev_t, local, rank_info):
     t0 = time.perf_counter()
     kern = []
     for _ in range(a.steps):
-        opt.LocalBundleAdjustment(w)
+        res = opt.LocalBundleAdjustment(w)
         kern.append(opt.last_timing()[0])
     grp.barrier()
     elapsed = time.perf_counter() - t0
     ms, flops = opt.last_timing()
-    # ---- S windows in flight (outside the timed region of `value`)
-    S = max(1, a.streams)
-    opts = [opt] + [orbx.Optimizer(max_keyframes=64, max_points=6000, max_edges=80000, device=local) for _ in range(S - 1)]
-    ws = [w] + [orbx.lba_synth.make_window(K=50, P=5000, seed=777 + 13 * i + grp.rank) for i in range(S - 1)]
-    _HANDLES.extend(opts)
-    for o, x in zip(opts[1:], ws[1:]):
-        o.LocalBundleAdjustment(x)
+    if a.dump_outputs and grp.rank == 0:
+        write_outputs(a.dump_outputs, {k: res[k] for k in ("poses", "points", "chi2", "outlier")})
+    conc = None
+    if a.full:
+        # ---- S windows in flight (outside the timed region of `value`)
+        S = max(1, a.streams)
+        opts = [opt] + [orbx.Optimizer(max_keyframes=64, max_points=6000, max_edges=80000, device=local) for _ in range(S - 1)]
+        ws = [w] + [orbx.lba_synth.make_window(K=50, P=5000, seed=777 + 13 * i + grp.rank) for i in range(S - 1)]
+        _HANDLES.extend(opts)
+        for o, x in zip(opts[1:], ws[1:]):
+            o.LocalBundleAdjustment(x)
 
-    def work(i):
-        for _ in range(a.steps):
-            opts[i].LocalBundleAdjustment(ws[i])
-    th = [threading.Thread(target=work, args=(i,)) for i in range(S)]
-    tc = time.perf_counter()
-    for x in th:
-        x.start()
-    for x in th:
-        x.join()
-    conc = S * a.steps / (time.perf_counter() - tc)
+        def work(i):
+            for _ in range(a.steps):
+                opts[i].LocalBundleAdjustment(ws[i])
+        th = [threading.Thread(target=work, args=(i,)) for i in range(S)]
+        tc = time.perf_counter()
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        conc = S * a.steps / (time.perf_counter() - tc)
     t, total, per_rank = grp.aggregate(elapsed, a.steps, w["E"])
     if grp.rank != 0:
         return None
@@ -795,7 +879,7 @@ def bench_lba(a, orbx, torch, grp, dev_t, local, rank_info):
             "warmup": a.warmup, "ms_per_step": round(t / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic", "config": {"workload": "BASELINE config 5: LocalBundleAdjustment, %d keyframes, %d points, %d edges; replicas only" % (w["K"], w["P"], w["E"]),
                                             "kernel_ms": round(float(np.mean(kern)), 4), "fp64_gflops": round(flops / (ms * 1e-3) / 1e9, 2) if ms > 0 else None,
-                                            "launches": launches, "concurrent": {"windows_in_flight": S, "windows_per_s": round(conc, 1)}},
+                                            "launches": launches, "concurrent": {"windows_in_flight": S, "windows_per_s": round(conc, 1)} if conc else None},
             "ranks": dict(rank_info, per_rank=[{"windows": r[0], "seconds": round(r[1], 6)} for r in per_rank]), "roofline": roof}
     if cpu:
         out["cpu_baseline"] = cpu
@@ -861,12 +945,20 @@ def main():
     ap.add_argument("--no-match", action="store_true", help="extract only (BASELINE config 2)")
     ap.add_argument("--batches-per-step", type=int, default=8, help="distinct resident batches of --batch frames a step of the default workload passes over "
                     "(8 x 256 x 640x480 = 630 MB of input, more than the 256 MiB Infinity Cache; the timed region of 20 steps is ~0.2 s)")
-    ap.add_argument("--no-workloads", dest="workloads", action="store_false", help="headline metric only: skip the extract-only / stereo / LBA legs measured after it")
+    ap.add_argument("--no-workloads", dest="workloads", action="store_false", help="with --full: skip the extract-only / stereo / LBA legs measured after the headline")
     ap.add_argument("--alone", action="store_true", help="profiling aid: ONE handle pair and a synchronisation after every call, so that a rocprofv3 kernel trace of this "
                     "command holds every kernel's duration with nothing else on the GPU (profiles/*_alone_kernel_stats.csv)")
     ap.add_argument("--streams", type=int, default=3, help="extractor/matcher handle pairs (HIP stream pairs) that take the batches in turn, so that "
                     "the latency-bound stages of one batch overlap the VALU-bound stages of the others")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the other BASELINE configs, the drop-in digest, the "
+                    "host-pointer batch rates, the CPU baselines, and every workload's roofline and extra runs (off: the headline line alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32 / float64, a seeded sample of the frames, %d MiB at most)" % (DUMP_BUDGET >> 20))
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.workloads, a.no_cpu_baseline = False, True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started without a launcher: spawn the N ranks exactly as the contract launches them, one per GPU, and pass the result through
@@ -924,7 +1016,7 @@ def main():
         import copy
         for key, f2, st in (("stereo_1241x376", bench_stereo, max(a.steps, 12)), ("lba_50kf", bench_lba, max(a.steps, 10))):
             a2 = copy.copy(a)
-            a2.steps, a2.warmup, a2.batch = st, max(a.warmup, 2), 256
+            a2.steps, a2.warmup, a2.batch, a2.dump_outputs = st, max(a.warmup, 2), 256, None
             try:
                 r = f2(a2, orbx, torch, grp, dev_t, local, rank_info)
                 for k in ("n_gpus", "higher_is_better", "scaling", "vs_baseline", "data", "ranks", "warmup"):
@@ -956,7 +1048,7 @@ def main():
         try:
             import copy
             a4 = copy.copy(a)
-            a4.workload, a4.workloads, a4.no_cpu_baseline, a4.steps, a4.warmup = "sequence", False, True, max(4, min(a.steps, 10)), 2
+            a4.workload, a4.workloads, a4.no_cpu_baseline, a4.steps, a4.warmup, a4.dump_outputs = "sequence", False, True, max(4, min(a.steps, 10)), 2, None
             r4 = bench_extract_match(a4, orbx, torch, grp, dev_t, local, rank_info)
             dig["sequence_512"] = {"frames_per_s": r4.get("value"), "ms_per_pass": r4.get("ms_per_step")}
         except Exception as e:      # noqa: BLE001

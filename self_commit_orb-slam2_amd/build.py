@@ -33,18 +33,28 @@ def hipcc_path():
     return None
 
 
+def _inputs():
+    srcs = [CSRC / s for s in HIP_SOURCES if (CSRC / s).exists()]
+    common = list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + [ROOT / "include" / "orbx.h"]
+    return srcs, common
+
+
 def build_liborbx(force=False, verbose=True):
     """Several ranks of one node may import the package at the same moment (bench.py --gpus N): the staleness check and the
     compilation run under an exclusive file lock, and the library is linked to a temporary name and renamed into place, so
-    no rank ever dlopens a half-written file."""
+    no rank ever dlopens a half-written file.  A library that is already current is returned without taking the lock, and the
+    lock file is opened read-only: a tree built by another user, or one without write access, loads its library as it is."""
     import fcntl
+    hipcc = hipcc_path()
+    if not force and LIB.exists() and (hipcc is None or (_stamp_matches(hipcc) and _newer(LIB, sum(_inputs(), [])))):
+        return LIB
     LIB.parent.mkdir(parents=True, exist_ok=True)
-    with open(LIB.parent / ".build.lock", "w") as lock:
+    lock = os.open(str(LIB.parent / ".build.lock"), os.O_RDONLY | os.O_CREAT, 0o666)
+    try:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            return _build_liborbx_locked(force, verbose)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
+        return _build_liborbx_locked(force, verbose)
+    finally:
+        os.close(lock)      # (closing the descriptor releases the lock)
 
 
 def _flags_stamp(hipcc):
@@ -65,8 +75,7 @@ def _build_liborbx_locked(force, verbose):
     """One object per source (compiled in parallel, only the stale ones), then one link: a kernel edit costs the compile of its own
     file, not of all eight."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [CSRC / s for s in HIP_SOURCES if (CSRC / s).exists()]
-    common = list(CSRC.glob("*.h")) + list(CSRC.glob("*.inc")) + [ROOT / "include" / "orbx.h"]
+    srcs, common = _inputs()
     hipcc = hipcc_path()
     if hipcc is None:
         if LIB.exists():

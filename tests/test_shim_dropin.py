@@ -24,7 +24,7 @@ def build_shim():
     subprocess.run(["g++", "-std=gnu++11", "-O2", "-fPIC", "-shared", "-pthread", "-I" + str(ROOT / "oracle" / "cvshim"),
                     "-I" + str(ROOT / "self_commit_orb-slam2_amd" / "shim"), "-I" + str(ROOT / "include"), "-o", str(SO)] +
                    [str(s) for s in srcs] + ["-L" + str(ROOT / "self_commit_orb-slam2_amd" / "lib"), "-lorbx",
-                                             "-Wl,-rpath," + str(ROOT / "self_commit_orb-slam2_amd" / "lib")], check=True)
+                                             "-Wl,-rpath,$ORIGIN/../self_commit_orb-slam2_amd/lib"], check=True)   # relative: the tree may be moved after the build
 
 
 def test_shim_compiles_against_the_opencv_surface(orbx):

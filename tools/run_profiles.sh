@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 RAW=/tmp/prof_raw_$TAG
 mkdir -p $OUT/summary $RAW
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --no-cpu-baseline --no-workloads"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-workloads"
 run() {   # run <name> <rocprof args...> -- <command...>
     local name=$1; shift
     timeout 900 rocprofv3 "$@" > $OUT/$name.log 2>&1 || echo "[$name] rc $?" >> $OUT/errors.txt
