@@ -333,6 +333,34 @@ int build_geometry(orbx_extractor *h, int W, int H)
     }
     g.cellsPerFrame = cells; g.slotsPerFrame = slots; g.kpPerFrame = kps; g.outCap = kps;
     g.blurTiles = btiles;
+    // k_pyr_band plan (batches): bands of <= 32 full-width rows of level l plus the blur's 3-row halos, within 48 KB of LDS (640 px: 38 rows of 672
+    // bytes, 25 KB, six 256-thread workgroups per CU; 1241 px: 38 rows of 1280 bytes).  Measured in the headline against the split launches: 64-row
+    // bands with 512 threads (47 KB, three per CU) -1 %, 32 rows +3 %, 16 rows +0.5 %; the 6 halo rows of a band are staged twice.  Level l+1's rows go to the band that holds
+    // their first source row; the second one must lie in its staged rows too, or the batch path keeps the split launches.
+    g.pyrBand = 1;
+    for (int l = 0; l < nl && g.pyrBand; l++) {
+        OrbxLevel &lv = g.lv[l];
+        lv.bandPitch = (int)align_up((size_t)lv.w, 16) + 32;      // pixel 0 at byte 16, >= 12 readable bytes behind every resize window
+        lv.bandH = std::min(32, (int)((48 * 1024) / lv.bandPitch - 6) & ~7);
+        lv.bandOff = 0;
+        if (lv.bandH < 8) { g.pyrBand = 0; break; }
+        if (l + 1 == nl) break;
+        const OrbxLevel &ln = g.lv[l + 1];
+        const int nb = (lv.h + lv.bandH - 1) / lv.bandH;
+        lv.bandOff = (int)h->rsHost.size();
+        int dy = 0;
+        for (int b = 0; b < nb; b++) {
+            const int s0 = b * lv.bandH, s1 = std::min(s0 + lv.bandH, lv.h);
+            h->rsHost.push_back((uint32_t)dy);
+            for (; dy < ln.h; dy++) {
+                const uint32_t t = h->rsHost[(size_t)ln.rsRowOff + 2 * dy];
+                const int y0 = (int)(t & 0xffffu), y1 = (int)(t >> 16);
+                if (y0 >= s1 && b + 1 < nb) break;
+                if (std::min(y0, y1) < s0 - 3 || std::max(y0, y1) > s1 + 2) g.pyrBand = 0;
+            }
+        }
+        h->rsHost.push_back((uint32_t)ln.h);
+    }
     // LDS carve-up of k_fast_cells (one wave per cell): row pitch 16*segments+16 bytes for both tiles
     if (maxWCell > 64 || maxHCell > 63) { orbx_set_error("cell %dx%d larger than the detector supports", maxWCell, maxHCell); return ORBX_ERR_ARG; }
     // window rows: the widest window (aw + 6 rounded up to 16) and the widest pre-test read (16 * segments + 8); score rows: aw + 6
@@ -513,7 +541,14 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
             tiled = true;
         }
     }
-    if (!tiled)
+    // the blur rides in the pyramid chain (k_pyr_band: level l blurred in the launch that resizes level l + 1, the last level's own launch after
+    // them); ORBX_PYR_SPLIT=1 (read per call, A/B switch) keeps the split launches, 7 x k_resize ... k_blur behind the quadtree
+    const char *es = getenv("ORBX_PYR_SPLIT");
+    L.pyrBand = !tiled && h->geom.pyrBand && !(es && es[0] == '1');
+    if (L.pyrBand) {
+        for (int l = 0; l < h->geom.nlevels; l++)
+            if ((rc = orbx_launch_pyr_band(L, l)) != ORBX_OK) return rc;
+    } else if (!tiled)
         for (int l = 1; l < h->geom.nlevels; l++)
             if ((rc = orbx_launch_resize(L, l)) != ORBX_OK) return rc;
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_PYR + 1], h->stream));
@@ -522,8 +557,8 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
     if ((rc = orbx_launch_octree(L)) != ORBX_OK) return rc;
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_OCTREE + 1], h->stream));
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_ORIENT + 1], h->stream));      // (orientation is part of the descriptor kernel: this span is empty)
-    if ((rc = orbx_launch_blur(L)) != ORBX_OK) return rc;
-    if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_BLUR + 1], h->stream));
+    if (!L.pyrBand && (rc = orbx_launch_blur(L)) != ORBX_OK) return rc;
+    if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_BLUR + 1], h->stream));      // (k_pyr_band: empty, the blur is part of the pyramid span)
     if (h->consumerEv[cb]) { ORBX_HIP_CHECK(hipStreamWaitEvent(h->stream, h->consumerEv[cb], 0)); h->consumerEv[cb] = nullptr; }
     if ((rc = orbx_launch_orient_describe(L)) != ORBX_OK) return rc;
     if (prof) { ORBX_HIP_CHECK(hipEventRecord(ev[ST_DESC + 1], h->stream)); h->profCount++; }

@@ -35,6 +35,8 @@ struct OrbxLevel {
     int binOff;             /* offset of this level's x -> initial-node table (u8)        */
     int kpBase, kpCap;      /* slice of the per-frame level-keypoint array                */
     int blurTileBase, blurTilesX, blurTilesY;
+    int bandH, bandPitch;   /* k_pyr_band (batches): rows of this level per band (multiple of 8), LDS row pitch of a staged band row */
+    int bandOff;            /* u32 offset in the resize tables of the bands' first rows of level l+1 (nBands + 1 entries; levels < nlevels-1) */
     double rsScaleX, rsScaleY; /* cv::resize inverse scale from level l-1: 1.0 / ((double)w / w_prev)  */
     int rsColOff, rsRowOff; /* u32 offsets of this level's cv::resize tables (levels >= 1), see build_resize_tables */
     int patchSize;          /* (int)(PATCH_SIZE*scale), src/ORBextractor.cc:1175          */
@@ -49,6 +51,7 @@ struct OrbxGeom {
     int fcPitch, fcScPitch, fcNS;   /* k_fast_cells template arguments: LDS row pitch of the window (48 / 64 / 80) and of the score tile (48 / 80), 16-byte window units per lane (2 / 3 / 4 / 6) */
     int fcInBytes, fcScBytes, fcLdsBytes;   /* LDS carve-up of k_fast_cells: input window, score tile, total */
     size_t pyrBytes;        /* bytes of levels 1.. of one frame */
+    int pyrBand;            /* 1: every level has a k_pyr_band plan (the batch path blurs inside the pyramid chain) */
     uint32_t taps[7];
     int umax[16];
     OrbxLevel lv[ORBX_MAX_LEVELS];
@@ -127,6 +130,7 @@ struct OrbxLaunch {
     int *status;                  /* per frame error bits (scratch of the running batch; [batch] = OR over the batch) */
     int *outStatus;               /* snapshot of `status` in the result buffer (written by k_orient_describe, guarded like the results) */
     int nodeCap;                  /* 256 / 512 / 1024 / 2048 */
+    bool pyrBand = false;         /* batch with k_pyr_band: k_octree sums the output prefix into outBase (cleared by the first band launch) */
     /* graph construction (single-frame call): when `graph` is set, a launcher adds a kernel node that depends on deps[0..ndeps)
      * and returns it in *node instead of launching on `stream` */
     const OrbxCombMember *combTab = nullptr;      /* combined single-frame batches: member table (pinned host memory) */
@@ -142,6 +146,7 @@ struct OrbxLaunch {
 };
 
 int orbx_launch_resize(const OrbxLaunch &L, int level);
+int orbx_launch_pyr_band(const OrbxLaunch &L, int level);   /* batches: blur of `level` + resize of level + 1 */
 int orbx_launch_pyramid_tiles(const OrbxLaunch &L);   /* all levels of a frame in one launch (L.pyrTiles); single frames and small combined batches */
 int orbx_launch_comb_upload(const OrbxLaunch &L, uint8_t *stagingDev);   /* members' pinned frames -> the engine's staging area (L.combTab) */
 int orbx_launch_comb_finish(const OrbxLaunch &L);     /* the engine's results / pyramid / frames -> every member's device and pinned buffers */

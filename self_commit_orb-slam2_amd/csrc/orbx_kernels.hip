@@ -1,7 +1,8 @@
 // orbx_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the ORB extractor.
 //
 // The stages of ORB_SLAM2::ORBextractor::operator() (reference src/ORBextractor.cc:1544-1668) as
-// k_resize (x7), k_fast_cells, k_octree, k_blur, k_orient_describe; every launch covers the whole
+// k_pyr_band (x8: blur of level l + resize of level l+1), k_fast_cells, k_octree, k_orient_describe for batches
+// (ORBX_PYR_SPLIT=1: k_resize x7 ... k_blur behind the quadtree); every launch covers the whole
 // batch (blockIdx.y = frame) and, where the stage has no level-to-level dependency, all pyramid
 // levels at once (blockIdx.x -> (level, tile) through OrbxGeom).  All launches go through emit():
 // onto a stream, or as nodes of the single-frame hipGraph.
@@ -982,7 +983,7 @@ template <int NODECAP>
 __global__ __launch_bounds__(256) void k_octree(const OrbxGeom *__restrict__ g, const int *__restrict__ cellCount, const uint32_t *__restrict__ cellSlots,
                                                 const uint8_t *__restrict__ binTab, uint32_t *__restrict__ ptBuf, uint32_t *__restrict__ labBuf,
                                                 OrbxLevelKp *__restrict__ lvlKp, int *__restrict__ lvlCnt, int *__restrict__ status,
-                                                const OrbxCombMember *__restrict__ comb, const uint8_t *__restrict__ engPyr)
+                                                const OrbxCombMember *__restrict__ comb, const uint8_t *__restrict__ engPyr, int *__restrict__ outBase)
 {
     // (level, frame) through the same XCD bijection as the detector before and the descriptor kernel after this stage: a frame's
     // candidates were written, and its keypoints will be read, by the XCD that owns the frame's range - in the natural order
@@ -996,6 +997,12 @@ __global__ __launch_bounds__(256) void k_octree(const OrbxGeom *__restrict__ g, 
         return;
     }
     octree_body<NODECAP, 256>(g, cellCount, cellSlots, binTab, ptBuf, labBuf, lvlKp, lvlCnt, status, l, f, (int)gridDim.y);
+    // batches with the blur in the pyramid chain (k_pyr_band, which cleared outBase): where each level's keypoints start in the frame's output list
+    // (level 0..n-1 in order, src/ORBextractor.cc:1577-1668) - every level adds its count to the levels behind it; k_orient_describe reads the sums
+    if (outBase && threadIdx.x == 0) {
+        const int n = lvlCnt[f * g->nlevels + l];      // (this thread's own store in octree_body)
+        for (int j = l + 1; j < g->nlevels; j++) atomicAdd(&outBase[f * g->nlevels + j], n);
+    }
 }
 
 // sin/cos of the keypoint angle: glibc's sinf/cosf algorithm in double, restated so the device
@@ -1086,6 +1093,62 @@ __device__ __forceinline__ int reflect101(int p, int len)
     return p;
 }
 
+// The arithmetic of one thread's 4 x 8 output pixels of the 7-tap blur: `win` = the window word that holds pixels x - 4 .. x - 1 of the first of the
+// 14 input rows (the output rows' top halo row), `pitchW` = window row pitch in words.  Shared by blur_body (64 x 32 tiles) and k_pyr_band
+// (full-width bands of a batch level).
+template <bool CLAMP>
+__device__ __forceinline__ void blur_rows8(const OrbxGeom *__restrict__ g, const uint32_t *__restrict__ win, const int pitchW, uint32_t outw[8])
+{
+    const uint32_t k0 = g->taps[0], k1 = g->taps[1], k2 = g->taps[2], k3 = g->taps[3], k4 = g->taps[4], k5 = g->taps[5], k6 = g->taps[6];
+    // ---- horizontal: the 14 rows from `win`; pixel j of the group = bytes 1+j .. 7+j of (w0,w1,w2) ----
+    // The TAPS are shifted, not the data: pixel j's seven taps sit at bytes 1+j .. 7+j of a 12-byte tap vector (uniform: scalar registers), so
+    // a pixel is two or three v_dot4_u32_u8 on the window words as loaded - 10 per row of four pixels, where byte-aligning the window for every
+    // pixel first took 6 v_alignbyte_b32 + 8 v_dot4.
+    const uint32_t A0 = (k0 << 8) | (k1 << 16) | (k2 << 24), A1 = k3 | (k4 << 8) | (k5 << 16) | (k6 << 24);                      // j = 0: w0, w1
+    const uint32_t B0 = (k0 << 16) | (k1 << 24), B1 = k2 | (k3 << 8) | (k4 << 16) | (k5 << 24), B2 = k6;                           // j = 1: w0, w1, w2
+    const uint32_t C0 = k0 << 24, C1 = k1 | (k2 << 8) | (k3 << 16) | (k4 << 24), C2 = k5 | (k6 << 8);                              // j = 2: w0, w1, w2
+    const uint32_t D1 = k0 | (k1 << 8) | (k2 << 16) | (k3 << 24), D2 = k4 | (k5 << 8) | (k6 << 16);                                // j = 3: w1, w2
+    // the 16-bit sums of two vertically adjacent rows (2m, 2m + 1) of a column share a word: exactly the operand pairs of the vertical pass below
+    uint32_t hp[4][7];
+#pragma unroll
+    for (int m = 0; m < 7; m++) {
+        uint32_t o[2][4];
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const uint32_t *pw = win + (2 * m + s) * pitchW;
+            const uint32_t w0 = pw[0], w1 = pw[1], w2 = pw[2];
+            o[s][0] = __builtin_amdgcn_udot4(w1, A1, __builtin_amdgcn_udot4(w0, A0, 0u, false), false);
+            o[s][1] = __builtin_amdgcn_udot4(w2, B2, __builtin_amdgcn_udot4(w1, B1, __builtin_amdgcn_udot4(w0, B0, 0u, false), false), false);
+            o[s][2] = __builtin_amdgcn_udot4(w2, C2, __builtin_amdgcn_udot4(w1, C1, __builtin_amdgcn_udot4(w0, C0, 0u, false), false), false);
+            o[s][3] = __builtin_amdgcn_udot4(w2, D2, __builtin_amdgcn_udot4(w1, D1, 0u, false), false);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) hp[j][m] = o[0][j] | (o[1][j] << 16);
+    }
+    // ---- vertical: output row q = 2t takes rows 2t .. 2t+6 = pairs t .. t+3 with the taps (k0,k1) (k2,k3) (k4,k5) (k6,0); row q = 2t+1 takes rows
+    // 2t+1 .. 2t+7 = the SAME pairs with the taps (0,k0) (k1,k2) (k3,k4) (k5,k6): the taps move (scalar registers), not the data.  (Until round 5 every
+    // output row had its own (h[q+2i], h[q+2i+1]) pairs, cut out of column-paired words by 14 v_perm_b32 per column: 56 of the kernel's ~500 instructions.)
+    const uint32_t E0 = k0 | (k1 << 16), E1 = k2 | (k3 << 16), E2 = k4 | (k5 << 16), E3 = k6;
+    const uint32_t O0 = k0 << 16, O1 = k1 | (k2 << 16), O2 = k3 | (k4 << 16), O3 = k5 | (k6 << 16);
+#pragma unroll
+    for (int q = 0; q < 8; q++) outw[q] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        // (sum + 32768) >> 16 is byte 2 of the sum, and with taps that add up to at most 256 it cannot exceed 255 (65280 * 256 + 32768 <
+        // 2^24): ONE v_perm_b32 drops that byte into byte j of the output word (shift, clamp and shift-or before).  Taps summing to 257
+        // (the configuration allows them) keep the clamp.
+        const uint32_t selo = j == 0 ? 0x03020106u : j == 1 ? 0x03020600u : j == 2 ? 0x03060100u : 0x06020100u;
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int t = q >> 1;
+            const uint32_t sum = (q & 1) ? udot2(hp[j][t + 3], O3, udot2(hp[j][t + 2], O2, udot2(hp[j][t + 1], O1, udot2(hp[j][t], O0, 32768u))))
+                                         : udot2(hp[j][t + 3], E3, udot2(hp[j][t + 2], E2, udot2(hp[j][t + 1], E1, udot2(hp[j][t], E0, 32768u))));
+            if (CLAMP) outw[q] |= min(sum >> 16, 255u) << (8 * j);
+            else outw[q] = __builtin_amdgcn_perm(sum, outw[q], selo);
+        }
+    }
+}
+
 // One 64 x 32 tile of the blurred pyramid by ONE wave: the body shared by k_blur (batches: one single-wave workgroup per tile) and k_octree_blur
 // (combined single-frame calls: four tiles per 256-thread workgroup, next to the quadtree's workgroups).  `in` = the wave's own LDS window,
 // `store` = false for the padding waves of the last workgroup (they run through the same barriers and store nothing).
@@ -1158,58 +1221,11 @@ __device__ __forceinline__ void blur_body(const OrbxGeom *__restrict__ g, const 
         }
     }
     __syncthreads();      // (unconditional: in k_octree_blur four waves with different tiles share the workgroup's barriers)
-    const uint32_t k0 = g->taps[0], k1 = g->taps[1], k2 = g->taps[2], k3 = g->taps[3], k4 = g->taps[4], k5 = g->taps[5], k6 = g->taps[6];
     const int gq = lane & 15, rg = lane >> 4;
     const int x = X0 + 4 * gq;
     if (!store || x >= w || Y0 + 8 * rg >= h) return;
-    // ---- horizontal: rows 8rg .. 8rg+13 of the window; pixel j of the group = bytes 1+j .. 7+j of (w0,w1,w2) ----
-    // The TAPS are shifted, not the data: pixel j's seven taps sit at bytes 1+j .. 7+j of a 12-byte tap vector (uniform: scalar registers), so
-    // a pixel is two or three v_dot4_u32_u8 on the window words as loaded - 10 per row of four pixels, where byte-aligning the window for every
-    // pixel first took 6 v_alignbyte_b32 + 8 v_dot4.
-    const uint32_t A0 = (k0 << 8) | (k1 << 16) | (k2 << 24), A1 = k3 | (k4 << 8) | (k5 << 16) | (k6 << 24);                      // j = 0: w0, w1
-    const uint32_t B0 = (k0 << 16) | (k1 << 24), B1 = k2 | (k3 << 8) | (k4 << 16) | (k5 << 24), B2 = k6;                           // j = 1: w0, w1, w2
-    const uint32_t C0 = k0 << 24, C1 = k1 | (k2 << 8) | (k3 << 16) | (k4 << 24), C2 = k5 | (k6 << 8);                              // j = 2: w0, w1, w2
-    const uint32_t D1 = k0 | (k1 << 8) | (k2 << 16) | (k3 << 24), D2 = k4 | (k5 << 8) | (k6 << 16);                                // j = 3: w1, w2
-    // the 16-bit sums of two vertically adjacent rows (2m, 2m + 1) of a column share a word: exactly the operand pairs of the vertical pass below
-    uint32_t hp[4][7];
-#pragma unroll
-    for (int m = 0; m < 7; m++) {
-        uint32_t o[2][4];
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const uint32_t *pw = in + (8 * rg + 2 * m + s) * (BT_P / 4) + gq + 1;
-            const uint32_t w0 = pw[0], w1 = pw[1], w2 = pw[2];
-            o[s][0] = __builtin_amdgcn_udot4(w1, A1, __builtin_amdgcn_udot4(w0, A0, 0u, false), false);
-            o[s][1] = __builtin_amdgcn_udot4(w2, B2, __builtin_amdgcn_udot4(w1, B1, __builtin_amdgcn_udot4(w0, B0, 0u, false), false), false);
-            o[s][2] = __builtin_amdgcn_udot4(w2, C2, __builtin_amdgcn_udot4(w1, C1, __builtin_amdgcn_udot4(w0, C0, 0u, false), false), false);
-            o[s][3] = __builtin_amdgcn_udot4(w2, D2, __builtin_amdgcn_udot4(w1, D1, 0u, false), false);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) hp[j][m] = o[0][j] | (o[1][j] << 16);
-    }
-    // ---- vertical: output row q = 2t takes rows 2t .. 2t+6 = pairs t .. t+3 with the taps (k0,k1) (k2,k3) (k4,k5) (k6,0); row q = 2t+1 takes rows
-    // 2t+1 .. 2t+7 = the SAME pairs with the taps (0,k0) (k1,k2) (k3,k4) (k5,k6): the taps move (scalar registers), not the data.  (Until round 5 every
-    // output row had its own (h[q+2i], h[q+2i+1]) pairs, cut out of column-paired words by 14 v_perm_b32 per column: 56 of the kernel's ~500 instructions.)
-    const uint32_t E0 = k0 | (k1 << 16), E1 = k2 | (k3 << 16), E2 = k4 | (k5 << 16), E3 = k6;
-    const uint32_t O0 = k0 << 16, O1 = k1 | (k2 << 16), O2 = k3 | (k4 << 16), O3 = k5 | (k6 << 16);
     uint32_t outw[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) outw[q] = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        // (sum + 32768) >> 16 is byte 2 of the sum, and with taps that add up to at most 256 it cannot exceed 255 (65280 * 256 + 32768 <
-        // 2^24): ONE v_perm_b32 drops that byte into byte j of the output word (shift, clamp and shift-or before).  Taps summing to 257
-        // (the configuration allows them) keep the clamp.
-        const uint32_t selo = j == 0 ? 0x03020106u : j == 1 ? 0x03020600u : j == 2 ? 0x03060100u : 0x06020100u;
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int t = q >> 1;
-            const uint32_t sum = (q & 1) ? udot2(hp[j][t + 3], O3, udot2(hp[j][t + 2], O2, udot2(hp[j][t + 1], O1, udot2(hp[j][t], O0, 32768u))))
-                                         : udot2(hp[j][t + 3], E3, udot2(hp[j][t + 2], E2, udot2(hp[j][t + 1], E1, udot2(hp[j][t], E0, 32768u))));
-            if (CLAMP) outw[q] |= min(sum >> 16, 255u) << (8 * j);
-            else outw[q] = __builtin_amdgcn_perm(sum, outw[q], selo);
-        }
-    }
+    blur_rows8<CLAMP>(g, in + 8 * rg * (BT_P / 4) + gq + 1, BT_P / 4, outw);
     uint8_t *dst = blur + (size_t)f * g->pyrBytes + lv.off;
 #pragma unroll
     for (int q = 0; q < 8; q++) {
@@ -1233,6 +1249,158 @@ __global__ __launch_bounds__(64) void k_blur(const OrbxGeom *__restrict__ g, con
         for (int i = 0; i < g->nlevels; i++) { outBase[f * g->nlevels + i] = run; run += lvlCnt[f * g->nlevels + i]; }
     }
     blur_body<CLAMP>(g, img0, img0Stride, img0FramePitch, pyr, blur, bx, f, in, (int)threadIdx.x, true);
+}
+
+// ------------------------------------------------------------------------------------
+// Batches: blur of level l AND cv::resize of level l + 1 in ONE launch per level (l = 0 .. nlevels-1; the last one only blurs).
+// Workgroup = one horizontal band of level l of one frame (host plan: OrbxLevel::band*): its rows, full width, plus the blur's 3-row halo above
+// and below, are staged into LDS once; the blur of the band's rows and the resize rows whose first source row lies in the band (the +1 row is
+// inside the halo) both read that copy.  Full-width rows: no horizontal halo, BORDER_REFLECT_101 in x is six bytes per LDS row, in y the
+// mirrored rows are staged (first and last band of a level).  The blur is blur_body's arithmetic (blur_rows8); the resize computes the
+// horizontal pass of each source row ONCE per column group and 8-row chunk and blends every output row from the two it reads - the same
+// tables, selectors and truncating >>16 blend as k_resize, where every output row fetched and filtered both of its source rows.
+// Replaces 7 x k_resize + k_blur (ORBX_PYR_SPLIT=1 keeps those).
+// ------------------------------------------------------------------------------------
+#define PB_THREADS 256    /* (measured: 512 threads with 64-row bands, 1 % below the split launches in the headline; 256 x 32 rows, 3 % above) */
+#define PB_ORG 16          /* LDS byte of pixel 0 of a band row (pixels -3 .. -1 in front of it) */
+#define PB_STAGE 4         /* 16-byte staging loads per thread in flight */
+template <bool CLAMP>
+__global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restrict__ g, const int l, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                                         const int readable, uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, const uint32_t *__restrict__ rsTab,
+                                                         int *__restrict__ outBase)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t band[];
+    uint8_t *bb = (uint8_t *)band;
+    XCD_REMAP_XY(b, f);
+    const int nl = g->nlevels, tid = (int)threadIdx.x;
+    // the per-level output prefix of the frame is summed up by k_octree's workgroups (atomics): cleared here, the first launch of the batch
+    if (l == 0 && b == 0 && tid < nl && outBase) outBase[f * nl + tid] = 0;
+    const OrbxLevel &lv = g->lv[l];
+    const int w = lv.w, h = lv.h, P = lv.bandPitch;
+    const int s0 = b * lv.bandH, s1 = min(s0 + lv.bandH, h);
+    const int nr = ((s1 - s0 + 7) & ~7) + 6;      // staged rows s0 - 3 ..: the last 8-row group of the blur reads all of them (stores only rows < s1)
+    int sp;
+    const uint8_t *src = level_ptr(g, l, f, img0, img0Stride, img0FramePitch, pyr, sp);
+    // ---- stage: item = (row, 16-byte chunk); rows mirrored (BORDER_REFLECT_101) above and below the level ----
+    {
+        const int nc = (w + 15) >> 4, items = nr * nc;
+        for (int i0 = 0; i0 < items; i0 += PB_THREADS * PB_STAGE) {
+            uint4 v[PB_STAGE];
+            int dOff[PB_STAGE];
+#pragma unroll
+            for (int k = 0; k < PB_STAGE; k++) {
+                const int item = i0 + tid + k * PB_THREADS, it = min(item, items - 1);
+                const int r = it / nc, c = it - r * nc;
+                int y = reflect101(s0 - 3 + r, h);
+                y = min(max(y, 0), h - 1);
+                const uint8_t *row = src + (size_t)y * sp;
+                const int x = 16 * c;
+                if (x + 16 <= readable) __builtin_memcpy(&v[k], row + x, 16);
+                else {      // the tail of an unpadded caller row: bytes up to the last pixel (what lies behind it is never weighted)
+                    uint32_t t[4] = {0u, 0u, 0u, 0u};
+                    for (int j = 0; x + j < w; j++) t[j >> 2] |= (uint32_t)row[x + j] << (8 * (j & 3));
+                    v[k] = make_uint4(t[0], t[1], t[2], t[3]);
+                }
+                dOff[k] = item < items ? r * P + PB_ORG + 16 * c : -1;
+            }
+#pragma unroll
+            for (int k = 0; k < PB_STAGE; k++)
+                if (dOff[k] >= 0) *(uint4 *)(bb + dOff[k]) = v[k];
+        }
+    }
+    __syncthreads();
+    // BORDER_REFLECT_101 in x (blur_body's order): x = -1, -2, -3 <- 1, 2, 3 and x = w, w + 1, w + 2 <- w - 2, w - 3, w - 4
+    for (int r = tid; r < nr; r += PB_THREADS) {
+        uint8_t *rowb = bb + r * P + PB_ORG;
+        rowb[-1] = rowb[1]; rowb[-2] = rowb[2]; rowb[-3] = rowb[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) rowb[w + k] = rowb[w - 2 - k];
+    }
+    __syncthreads();
+    // ---- blur of rows s0 .. s1-1: thread item = 4 columns x 8 rows ----
+    {
+        const int G4 = (w + 3) >> 2, items = G4 * ((s1 - s0 + 7) >> 3), PW = P >> 2;
+        uint8_t *dst = blur + (size_t)f * g->pyrBytes + lv.off;
+        for (int item = tid; item < items; item += PB_THREADS) {
+            const int rgi = item / G4, gx = item - rgi * G4;
+            uint32_t outw[8];
+            blur_rows8<CLAMP>(g, band + 8 * rgi * PW + gx + PB_ORG / 4 - 1, PW, outw);      // word of pixels 4gx - 4 .. 4gx - 1
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int y = s0 + 8 * rgi + q;
+                if (y >= s1) break;
+                *(uint32_t *)(dst + (size_t)y * lv.pitch + 4 * gx) = outw[q];
+            }
+        }
+    }
+    if (l + 1 >= nl) return;
+    // ---- resize into level l + 1: the rows [d0, d1) the plan gave this band, in chunks of 8 rows per column group ----
+    const OrbxLevel &ln = g->lv[l + 1];
+    const int d0 = (int)rsTab[lv.bandOff + b], d1 = (int)rsTab[lv.bandOff + b + 1];
+    const int Gd = (ln.w + 3) >> 2, items = Gd * ((d1 - d0 + 7) >> 3);
+    const uint2 *rt = (const uint2 *)(rsTab + ln.rsRowOff);
+    uint8_t *dstBase = pyr + (size_t)f * g->pyrBytes + ln.off;
+    const uint8_t *lrow0 = bb + PB_ORG - (s0 - 3) * P;       // LDS byte of pixel 0 of image row y: lrow0 + y * P
+    for (int item = tid; item < items; item += PB_THREADS) {
+        const int ch = item / Gd, cg = item - ch * Gd;
+        const uint32_t *ct = rsTab + ln.rsColOff + 12 * cg;
+        const uint4 c0 = *(const uint4 *)ct, c1 = *(const uint4 *)(ct + 4), c2 = *(const uint4 *)(ct + 8);
+        const int sx0 = (int)c0.x, sxa = sx0 & ~3;
+        const uint32_t mis = (uint32_t)(sx0 & 3);
+        const bool wide = (int)c0.y <= 7;      // (LDS rows are readable 12 bytes past every group window)
+        const uint32_t sel[4] = {c0.z, c0.w, c1.x, c1.y}, coef[4] = {c1.z, c1.w, c2.x, c2.y};
+        // horizontal pass of source row y, >> 4: k_resize's r0 / r1 before the blend
+        auto hpass = [&](int y, uint32_t hv[4]) {
+            const uint8_t *row = lrow0 + (size_t)y * P;
+            if (wide) {
+                const uint32_t *p = (const uint32_t *)(row + sxa);
+                const uint32_t a0 = p[0], a1 = p[1], a2 = p[2];
+                const uint32_t v0 = __builtin_amdgcn_alignbyte(a1, a0, mis), v1 = __builtin_amdgcn_alignbyte(a2, a1, mis);
+#pragma unroll
+                for (int k = 0; k < 4; k++) hv[k] = udot2(__builtin_amdgcn_perm(v1, v0, sel[k]), coef[k], 0u) >> 4;
+            } else {
+                const uint8_t *S = row + sx0;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int off = (int)((c2.z >> (8 * k)) & 0xffu), off1 = (int)((c2.w >> (8 * k)) & 0xffu);
+                    hv[k] = udot2((uint32_t)S[off] | ((uint32_t)S[off1] << 16), coef[k], 0u) >> 4;
+                }
+            }
+        };
+        uint32_t ha[4], hb[4];      // horizontal passes of source rows ra, rb (consecutive output rows share a row: computed once)
+        int ra = -1, rb = -1;
+        // the chunk's row-table entries requested together (one memory round trip, not one per output row)
+        const int dA = d0 + 8 * ch, nrow = min(8, d1 - dA);
+        uint2 tr[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) tr[r] = rt[dA + min(r, nrow - 1)];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            if (r >= nrow) break;
+            const int dy = dA + r;
+            const uint2 t = tr[r];
+            const int y0 = (int)(t.x & 0xffffu), y1 = (int)(t.x >> 16);
+            if (y0 != ra) {
+                if (y0 == rb) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) ha[k] = hb[k];
+                } else hpass(y0, ha);
+                ra = y0;
+            }
+            if (y1 != rb) {
+                if (y1 == ra) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) hb[k] = ha[k];
+                } else hpass(y1, hb);
+                rb = y1;
+            }
+            const uint32_t b0 = t.y & 0xffffu, b1 = t.y >> 16;
+            uint32_t out = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) out |= ((((b0 * ha[k]) >> 16) + ((b1 * hb[k]) >> 16) + 2u) >> 2) << (8 * k);      // (<= 255, see k_resize)
+            *(uint32_t *)(dstBase + (size_t)dy * ln.pitch + 4 * cg) = out;
+        }
+    }
 }
 
 // Combined single-frame calls: quadtree, host pyramid copy AND blur in one launch.  The quadtree is eight workgroups of dependent latency
@@ -1679,7 +1847,7 @@ int orbx_launch_octree(const OrbxLaunch &L)
     // (combined single-frame calls: 48 more workgroups per frame carry the host pyramid copy, see the kernel)
     dim3 grid((unsigned)(L.geom->nlevels + (L.combTab ? ORBX_OCTREE_COPY_BLOCKS : 0)), (unsigned)L.batch);
 #define OT_LAUNCH(NC) return emit(L, k_octree<NC>, grid, dim3(256), 0, L.geomDev, L.cellCount, L.cellSlots, L.binTab, L.ptBuf, L.labBuf, L.lvlKp, L.lvlCnt, L.status, L.combTab, \
-                                  (const uint8_t *)L.pyr)
+                                  (const uint8_t *)L.pyr, L.pyrBand ? L.outBase : (int *)nullptr)
     if (L.nodeCap <= 256) OT_LAUNCH(256);   // 1000 features at 640x480: 224 nodes at most; a fraction of the LDS, more resident quadtrees per CU
     if (L.nodeCap <= 512) OT_LAUNCH(512);
     if (L.nodeCap <= 1024) OT_LAUNCH(1024);
@@ -1727,6 +1895,21 @@ int orbx_launch_blur(const OrbxLaunch &L)
     for (int i = 0; i < 7; i++) tapSum += L.geom->taps[i];
     if (tapSum > 256u) return emit(L, k_blur<true>, grid, dim3(64), 0, L.geomDev, L.img0, L.img0Stride, L.img0FramePitch, L.pyr, L.blur, L.lvlCnt, L.outBase);
     return emit(L, k_blur<false>, grid, dim3(64), 0, L.geomDev, L.img0, L.img0Stride, L.img0FramePitch, L.pyr, L.blur, L.lvlCnt, L.outBase);
+}
+
+// batches: blur of level l + resize of level l + 1 (k_pyr_band), one launch per level, l = 0 .. nlevels-1
+int orbx_launch_pyr_band(const OrbxLaunch &L, int l)
+{
+    const OrbxGeom &g = *L.geom;
+    const OrbxLevel &lv = g.lv[l];
+    const dim3 grid((unsigned)((lv.h + lv.bandH - 1) / lv.bandH), (unsigned)L.batch);
+    const size_t lds = (size_t)(lv.bandH + 6) * lv.bandPitch;      // (bandH is a multiple of 8; the plan keeps this within 48 KB)
+    // bytes readable from the start of a source row: pyramid rows have >= 16 spare bytes; the caller's level-0 rows their stride when the frame pitch covers it
+    const int readable = l > 0 ? lv.pitch : (L.img0FramePitch >= (size_t)L.img0Stride * (size_t)lv.h ? L.img0Stride : lv.w);
+    unsigned tapSum = 0;
+    for (int i = 0; i < 7; i++) tapSum += g.taps[i];
+    if (tapSum > 256u) return emit(L, k_pyr_band<true>, grid, dim3(PB_THREADS), lds, L.geomDev, l, L.img0, L.img0Stride, L.img0FramePitch, readable, L.pyr, L.blur, L.rsTab, L.outBase);
+    return emit(L, k_pyr_band<false>, grid, dim3(PB_THREADS), lds, L.geomDev, l, L.img0, L.img0Stride, L.img0FramePitch, readable, L.pyr, L.blur, L.rsTab, L.outBase);
 }
 
 int orbx_launch_orient_describe(const OrbxLaunch &L)
