@@ -714,6 +714,26 @@ int orbx_bundle_adjustment(orbx_lba *h, const orbx_lba_problem *problem, int ite
 /* Kernel milliseconds (HIP events) spent inside the last orbx_lba_solve and FP64 flop count. */
 int orbx_lba_last_timing(orbx_lba *h, float *device_ms, double *flops);
 
+/* Batched LocalBundleAdjustment: ONE handle solves N independent windows (several maps in one process: multi-session or
+ * multi-agent SLAM, independent sequences on one device), and every kernel launch of the chain covers all N windows.
+ * Capacities are PER WINDOW; max_keyframes <= 341 (6 * K <= 2048: every reduced system stays on the LDS paths), else
+ * ORBX_ERR_ARG.  Without a device, create returns ORBX_ERR_NODEVICE after the argument checks, as orbx_lba_create does.
+ * Only the two-stage 5 + 10 iteration form of orbx_lba_solve is batched (global BA windows come one at a time). */
+typedef struct orbx_lba_batch orbx_lba_batch;
+int orbx_lba_batch_create(int device, int max_windows, int max_keyframes, int max_points, int max_edges, orbx_lba_batch **out);
+void orbx_lba_batch_destroy(orbx_lba_batch *h);
+/* Optimizer::LocalBundleAdjustment on num_windows independent windows.  problems[w] / results[w] exactly as for orbx_lba_solve,
+ * and results[w] is BIT-IDENTICAL to what orbx_lba_solve returns for problems[w] alone (poses, points, edge_chi2, edge_outlier,
+ * all 8 stats), whatever the other windows of the batch are and in any order.
+ * stop_flags: NULL, or num_windows pointers (each may be NULL) = each window's pbStopFlag, polled as orbx_lba_solve polls it; a
+ * raised flag affects only its own window.  Bad input in any window (NULL array, edge id out of range, size over capacity,
+ * num_windows outside 1..max_windows) fails the whole call before anything is launched: ORBX_ERR_ARG / ORBX_ERR_CAPACITY, the
+ * window's index in orbx_last_error, no result written. */
+int orbx_lba_solve_batch(orbx_lba_batch *h, int num_windows, const orbx_lba_problem *problems,
+                         const volatile uint8_t *const *stop_flags, orbx_lba_result *results);
+/* Kernel milliseconds (HIP events) of the last orbx_lba_solve_batch (all windows) and its FP64 flop count. */
+int orbx_lba_batch_last_timing(orbx_lba_batch *h, float *device_ms, double *flops);
+
 
 /* ------------------------------------------------------------------------------------
  * Motion-only bundle adjustment  ==  Optimizer::PoseOptimization(Frame *pFrame)

@@ -1176,3 +1176,63 @@ class Optimizer:
         fl = ctypes.c_double()
         _check(self._L.orbx_lba_last_timing(self._h, ctypes.byref(ms), ctypes.byref(fl)))
         return ms.value, fl.value
+
+
+class BatchOptimizer:
+    """Optimizer::LocalBundleAdjustment on many independent windows with ONE handle (orbx_lba_solve_batch): every kernel launch
+    covers all windows of a call, and every window's result is bit-identical to Optimizer().LocalBundleAdjustment(w).
+    Capacities are per window; max_keyframes <= 341."""
+
+    def __init__(self, max_windows, max_keyframes, max_points, max_edges, device=0):
+        self._L = load_library()
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        self._L.orbx_lba_batch_create.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
+        self._L.orbx_lba_batch_destroy.argtypes = [vp]
+        self._L.orbx_lba_batch_destroy.restype = None
+        self._L.orbx_lba_solve_batch.argtypes = [vp, ci, ctypes.POINTER(LbaProblem), vp, ctypes.POINTER(LbaResult)]
+        self._L.orbx_lba_batch_last_timing.argtypes = [vp, vp, vp]
+        self._h = vp()
+        _check(self._L.orbx_lba_batch_create(device, max_windows, max_keyframes, max_points, max_edges, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.orbx_lba_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def LocalBundleAdjustment(self, windows, stop_flags=None):
+        """windows: list of dicts as produced by lba_synth.make_window; stop_flags: None, or one uint8 array (or None) per window.
+        Returns one dict per window, in the form of Optimizer.LocalBundleAdjustment."""
+        n = len(windows)
+        keep, outs = [], []
+        probs = (LbaProblem * max(n, 1))()
+        results = (LbaResult * max(n, 1))()
+        for i, w in enumerate(windows):
+            arrs = {k: np.ascontiguousarray(w[k]) for k in ("poses", "fixed", "intr", "points", "edge_point", "edge_kf", "edge_obs", "edge_inv_sigma2")}
+            keep.append(arrs)
+            probs[i] = LbaProblem(w["K"], arrs["poses"].ctypes.data, arrs["fixed"].ctypes.data, arrs["intr"].ctypes.data, w["P"], arrs["points"].ctypes.data, w["E"],
+                                  arrs["edge_point"].ctypes.data, arrs["edge_kf"].ctypes.data, arrs["edge_obs"].ctypes.data, arrs["edge_inv_sigma2"].ctypes.data)
+            o = dict(poses=np.zeros((w["K"], 16), np.float32), points=np.zeros((w["P"], 3), np.float32), chi2=np.zeros(w["E"], np.float64),
+                     outlier=np.zeros(w["E"], np.uint8))
+            outs.append(o)
+            results[i] = LbaResult(o["poses"].ctypes.data, o["points"].ctypes.data, o["chi2"].ctypes.data, o["outlier"].ctypes.data)
+        stops = None
+        if stop_flags is not None:
+            if len(stop_flags) != n:
+                raise ValueError("stop_flags: one entry per window")
+            stops = (ctypes.c_void_p * max(n, 1))(*[None if f is None else f.ctypes.data for f in stop_flags])
+        _check(self._L.orbx_lba_solve_batch(self._h, n, probs, stops, results))
+        for i, o in enumerate(outs):
+            o["stats"] = np.array(list(results[i].stats))
+        return outs
+
+    def last_timing(self):
+        ms = ctypes.c_float()
+        fl = ctypes.c_double()
+        _check(self._L.orbx_lba_batch_last_timing(self._h, ctypes.byref(ms), ctypes.byref(fl)))
+        return ms.value, fl.value

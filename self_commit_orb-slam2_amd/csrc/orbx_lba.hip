@@ -314,9 +314,54 @@ __device__ __forceinline__ double block_sum256(double v, double *sw /* 4 */)
     return sw[0] + sw[1] + sw[2] + sw[3];
 }
 
+struct LmState {
+    double lambda, ni, currentChi, iniChi, rho, chi0, tempChi;
+    int it, qmax, nBad, ok, done, lastRejected, relin, trials, iters, maxIters;
+    unsigned arrive;      // workgroups of k_errors_decide that have stored their share of chi2 (0 between launches)
+};
+// ---------------------------------------------------------------------------------------------
+// Batched local bundle adjustment (orbx_lba_solve_batch): N independent windows, and every launch of the chain covers all of them.  The
+// window is blockIdx.z (y is taken by k_schur_rows / k_schur_fin); its views, buffers, LM state and partition parameters come from one
+// descriptor per window (LbaWin) in device memory.  Grids are sized by the largest window; the workgroups past a window's own extent return
+// at entry, as the gated launches of a finished stage do.  Every kernel of the chain is a template <bool BATCH>: BATCH = false is the
+// single-window kernel as it always was (its code generation is unchanged: the batch prologue is an `if constexpr`), BATCH = true replaces
+// the arguments by the window's in that prologue and runs the SAME body with the window's own partition (spSplit, the y-splits of the Schur
+// rows, gE / gU, the Cholesky route), so that every window computes the bits orbx_lba_solve computes for it alone.  (The bodies were
+// __device__ functions called by both forms at first: that changed the single-window kernels' code - k_chol_solve<32> went from 100 to
+// 2020 bytes of scratch per lane.)  Only the default forms exist here: fused k_lin_sums, k_errors + k_lm_decide, no speculative factorisation.
+// ---------------------------------------------------------------------------------------------
+struct LbaWin {
+    LbaDev d;
+    Huber hub;
+    int robust;
+    int prep;                 // stage preparation (k_stage_*) runs for this window
+    int run;                  // the window's Levenberg loop runs in this stage
+    int spSplit, nPose, nPt, nP6, ySplit, iters, stamp, nChunk;
+    int *ptStart, *ptEdges, *kfStart, *kfEdges, *kfRowS0, *kfRowN, *ptPi, *csrCnt, *ptTmp, *fillP, *pActF, *lActF, *okFlag, *poseIdx, *ptIdx;
+    uint8_t *fixed, *active, *flag;            // flag: the window's outlier flags (front of its result record)
+    const uint8_t *stageFlags;                 // stage 2: the flags of stage 1; nullptr in stage 1
+    double *Hll, *bl, *Hpp, *bp, *spPart, *Dinv, *Ddb, *S, *L, *bsDev, *ywork, *ysol, *diagInv, *xp, *xl, *ptBak, *partChi, *partL, *bsPart, *red;
+    DPose *poseBak;
+    unsigned long long *Sacc, *scaleBits;
+    LmState *st;
+    double *host;                              // the window's LM record in mapped pinned memory (sequence number at [15])
+    const volatile int *stop;                  // the window's device-visible stop word
+    double *chiOut; DPose *poseOut; double *ptOut;      // final classification (chiOut may be nullptr)
+};
+
+// workgroups of a window in the launches whose grids depend on its sizes (the single-window driver's formulas)
+__device__ __forceinline__ int win_gE(const LbaWin &w) { return (w.d.E + 255) / 256; }
+__device__ __forceinline__ int win_gU(const LbaWin &w) { return (max(w.d.K, 16 * w.d.P) + 255) / 256; }
+
 // partChi[blockIdx.x] = this workgroup's share of activeRobustChi2 (summed in block order by k_lm_begin / k_lm_decide)
-__global__ __launch_bounds__(256) void k_errors(LbaDev d, Huber h, int robust, double *partChi, const int *gate, int want)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_errors(LbaDev d, Huber h, int robust, double *partChi, const int *gate, int want, const LbaWin *W = nullptr, int gated = 0)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run || (int)blockIdx.x >= win_gE(w)) return;
+        d = w.d; h = w.hub; robust = w.robust; partChi = w.partChi; gate = gated ? &w.st->done : nullptr; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     __shared__ double sw[4];
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -511,9 +556,16 @@ __global__ __launch_bounds__(256) void k_sum_poses(LbaDev d, const int *kfStart,
 // kernels read per trial, is still written (by the keyframe side, which visits every active edge of a free keyframe exactly once).
 //   blocks [0, K * SP_SPLIT)     the keyframe sums (k_sum_poses' body; first: they are the longer ones)
 //   the rest                     the landmark sums (k_sum_points' body), 16 lanes per landmark
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_lin_sums(LbaDev d, Huber h, int robust, const int *ptStart, const int *ptEdges, double *Hll, double *bl, const int *kfStart,
-                                                  const int *kfEdges, double *part /* K x SP_SPLIT x 27 */, int spSplit, const int *gate, int want)
+                                                  const int *kfEdges, double *part /* K x SP_SPLIT x 27 */, int spSplit, const int *gate, int want, const LbaWin *W = nullptr, int gated = 0)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run || (int)blockIdx.x >= w.d.K * w.spSplit + (w.d.P + 15) / 16) return;
+        d = w.d; h = w.hub; robust = w.robust; ptStart = w.ptStart; ptEdges = w.ptEdges; Hll = w.Hll; bl = w.bl; kfStart = w.kfStart; kfEdges = w.kfEdges;
+        part = w.spPart; spSplit = w.spSplit; gate = gated ? &w.st->relin : nullptr; want = 1;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     __shared__ double redT[27 * SP_TP];
     __shared__ double part8[27][9];
@@ -596,8 +648,14 @@ __global__ __launch_bounds__(256) void k_lin_sums(LbaDev d, Huber h, int robust,
 #undef LIN_DOT
 // ... and the SP_SPLIT partial results added in order by a second small launch (a "last workgroup adds" inside the first one needs a
 // device-scope release, i.e. a write-back of the L2 - right after k_linearize has left 34 MB of dirty lines there: 28 us instead of 16)
-__global__ __launch_bounds__(256) void k_sum_poses_fin(LbaDev d, const double *__restrict__ part, double *__restrict__ Hpp, double *__restrict__ bp, int spSplit, const int *gate, int want)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_sum_poses_fin(LbaDev d, const double *__restrict__ part, double *__restrict__ Hpp, double *__restrict__ bp, int spSplit, const int *gate, int want, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run || (int)blockIdx.x >= (32 * w.d.K + 255) / 256) return;
+        d = w.d; part = w.spPart; Hpp = w.Hpp; bp = w.bp; spSplit = w.spSplit; gate = nullptr;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     const int idx = blockIdx.x * 256 + threadIdx.x, k = idx >> 5, v = idx & 31;
     if (k >= d.K || v >= 27) return;
@@ -625,11 +683,7 @@ __global__ __launch_bounds__(256) void k_sum_poses_fin(LbaDev d, const double *_
 // The state is mirrored into pinned memory by every decision, the sequence number last; the stop flag (pbStopFlag) is a pinned word that
 // the waiting host keeps equal to the caller's flag.
 // ---------------------------------------------------------------------------------------------
-struct LmState {
-    double lambda, ni, currentChi, iniChi, rho, chi0, tempChi;
-    int it, qmax, nBad, ok, done, lastRejected, relin, trials, iters, maxIters;
-    unsigned arrive;      // workgroups of k_errors_decide that have stored their share of chi2 (0 between launches)
-};
+// (LmState: before the batch descriptor, see the Levenberg-Marquardt section below)
 
 __device__ __forceinline__ double wave_sum(double x)
 {
@@ -648,9 +702,15 @@ __device__ __forceinline__ void lm_mirror(const LmState *st, double *host, doubl
 
 // start of optimize(maxIters): chi2 of the start (k_errors' partial sums, in block order), computeLambdaInit (:166-180: tau = 1e-5 times
 // the largest diagonal entry, from k_diag_max), counters cleared
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_lm_begin(LmState *st, const double *partChi, int nChi, const double *diagMax, int maxIters, const volatile int *stopHost, double *host,
-                                                  double seq, unsigned long long *scaleBits)
+                                                  double seq, unsigned long long *scaleBits, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run) return;
+        st = w.st; partChi = w.partChi; nChi = win_gE(w); diagMax = w.red; maxIters = w.iters; stopHost = w.stop; host = w.host; scaleBits = w.scaleBits;
+    }
     // (measured and not kept, round 6: the maximum of k_diag_max computed here, by these 256 threads - 21.5 us instead of 4.5 + 7.2 for the two launches)
     __shared__ double sw[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -751,10 +811,17 @@ __device__ __forceinline__ void lm_decide_block(LmState *st, const double *partC
     }
 }
 
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_lm_decide(LmState *st, const double *partChi, int nChi, const double *partL, int nL, const double *xp, const double *bp, int nP6,
                                                    const int *okFlag, const volatile int *stopHost, double *host, double seq, LbaDev d, const DPose *poseBak, const double *ptBak,
-                                                   unsigned long long *scaleBits)
+                                                   unsigned long long *scaleBits, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run) return;
+        st = w.st; partChi = w.partChi; nChi = win_gE(w); partL = w.partL; nL = win_gU(w); xp = w.xp; bp = w.bp; nP6 = w.nP6; okFlag = w.nP6 > 0 ? w.okFlag : nullptr;
+        stopHost = w.stop; host = w.host; d = w.d; poseBak = w.poseBak; ptBak = w.ptBak; scaleBits = w.scaleBits;
+    }
     if (st->done) {      // a trial the stage did not need: only the sequence number moves (the host may be waiting for this very launch)
         if (threadIdx.x < 6) scaleBits[threadIdx.x] = 0ull;
         if (threadIdx.x == 0) { __threadfence_system(); __hip_atomic_store(host + 15, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
@@ -818,8 +885,10 @@ struct UnpackSegs {
                                           // way up, and the host does a memcpy instead of a conversion loop); 2: stereo flag of every observation triplet, !(obs[2] < 0)
     int n;
 };
-__global__ __launch_bounds__(256) void k_unpack(const uint8_t *arena, UnpackSegs sg)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_unpack(const uint8_t *arena, UnpackSegs sg, const UnpackSegs *segs = nullptr)
 {
+    if constexpr (BATCH) sg = segs[blockIdx.z];      // (batch: the window's segments)
     const size_t stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
     for (int i = 0; i < sg.n; i++) {
         if (sg.kind[i] == 1) {
@@ -853,8 +922,14 @@ __global__ __launch_bounds__(256) void k_unpack(const uint8_t *arena, UnpackSegs
 //   landmark rows (short): unordered fill with an atomic slot counter, then every edge counts the smaller edge ids of its row.
 // ---------------------------------------------------------------------------------------------
 #define CSR_CHUNK 256
-__global__ __launch_bounds__(256) void k_csr_kf_count(const int *__restrict__ ek, int E, int K, int *__restrict__ chunkCnt)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_csr_kf_count(const int *__restrict__ ek, int E, int K, int *__restrict__ chunkCnt, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if ((int)blockIdx.x >= w.nChunk) return;
+        ek = w.d.ek; E = w.d.E; K = w.d.K; chunkCnt = w.csrCnt;
+    }
     extern __shared__ int csrLds[];
     for (int i = threadIdx.x; i < K; i += 256) csrLds[i] = 0;
     __syncthreads();
@@ -865,8 +940,14 @@ __global__ __launch_bounds__(256) void k_csr_kf_count(const int *__restrict__ ek
 }
 
 // one workgroup per key: exclusive scan of its counts over the chunks, starting at the row start
-__global__ __launch_bounds__(256) void k_csr_kf_scan(const int *__restrict__ kfStart, int K, int nChunk, int *chunkCnt)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_csr_kf_scan(const int *__restrict__ kfStart, int K, int nChunk, int *chunkCnt, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if ((int)blockIdx.x >= w.d.K) return;
+        kfStart = w.kfStart; K = w.d.K; nChunk = w.nChunk; chunkCnt = w.csrCnt;
+    }
     __shared__ int wsum[4];
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int run = kfStart[k];
@@ -888,8 +969,14 @@ __global__ __launch_bounds__(256) void k_csr_kf_scan(const int *__restrict__ kfS
 
 // slot of edge e = first slot of its chunk in its row + the number of earlier edges of the chunk with the same keyframe (counted by
 // walking the chunk's keys in LDS, the same address for every lane)
-__global__ __launch_bounds__(256) void k_csr_kf_fill(const int *__restrict__ ek, int E, int K, const int *__restrict__ chunkBase, int *__restrict__ kfEdges)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_csr_kf_fill(const int *__restrict__ ek, int E, int K, const int *__restrict__ chunkBase, int *__restrict__ kfEdges, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if ((int)blockIdx.x >= w.nChunk) return;
+        ek = w.d.ek; E = w.d.E; K = w.d.K; chunkBase = w.csrCnt; kfEdges = w.kfEdges;
+    }
     __shared__ int keys[CSR_CHUNK];
     const int tid = threadIdx.x, e = blockIdx.x * CSR_CHUNK + tid;
     const int key = e < E ? ek[e] : -1;
@@ -901,16 +988,26 @@ __global__ __launch_bounds__(256) void k_csr_kf_fill(const int *__restrict__ ek,
     if (e < E) kfEdges[chunkBase[(size_t)blockIdx.x * K + key] + rank] = e;
 }
 
-__global__ __launch_bounds__(256) void k_csr_pt_fill(const int *__restrict__ ep, int E, const int *__restrict__ ptStart, int *fill, int *__restrict__ ptTmp)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_csr_pt_fill(const int *__restrict__ ep, int E, const int *__restrict__ ptStart, int *fill, int *__restrict__ ptTmp, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        ep = w.d.ep; E = w.d.E; ptStart = w.ptStart; fill = w.fillP; ptTmp = w.ptTmp;
+    }
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     const int l = ep[e];
     ptTmp[ptStart[l] + atomicAdd(&fill[l], 1)] = e;
 }
 
-__global__ __launch_bounds__(256) void k_csr_pt_rank(const int *__restrict__ ep, int E, const int *__restrict__ ptStart, const int *__restrict__ ptTmp, int *__restrict__ ptEdges)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_csr_pt_rank(const int *__restrict__ ep, int E, const int *__restrict__ ptStart, const int *__restrict__ ptTmp, int *__restrict__ ptEdges, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        ep = w.d.ep; E = w.d.E; ptStart = w.ptStart; ptTmp = w.ptTmp; ptEdges = w.ptEdges;
+    }
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     const int l = ep[e], s0 = ptStart[l], m = ptStart[l + 1] - s0;
@@ -922,18 +1019,29 @@ __global__ __launch_bounds__(256) void k_csr_pt_rank(const int *__restrict__ ep,
 // What k_schur_rows needs per slot of the keyframe lists without chasing five dependent indices (edge -> landmark -> row -> partner edge ->
 // keyframe -> free-pose index, ~1.5 us each on a device that the launch does not fill): the landmark row of every keyframe-list slot
 // (static per call) and, per stage, the free-pose index of the edge in every landmark-list slot (-1: inactive edge or fixed keyframe).
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_csr_rows(int E, const int *__restrict__ ep, const int *__restrict__ kfEdges, const int *__restrict__ ptStart, int *__restrict__ kfRowS0,
-                                                  int *__restrict__ kfRowN)
+                                                  int *__restrict__ kfRowN, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        E = w.d.E; ep = w.d.ep; kfEdges = w.kfEdges; ptStart = w.ptStart; kfRowS0 = w.kfRowS0; kfRowN = w.kfRowN;
+    }
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= E) return;
     const int l = ep[kfEdges[s]], s0 = ptStart[l];
     kfRowS0[s] = s0;
     kfRowN[s] = ptStart[l + 1] - s0;
 }
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_stage_pairs(int E, const int *__restrict__ ek, const int *__restrict__ ptEdges, const uint8_t *__restrict__ active,
-                                                     const int *__restrict__ poseIdx, int *__restrict__ ptPi)
+                                                     const int *__restrict__ poseIdx, int *__restrict__ ptPi, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.prep) return;
+        E = w.d.E; ek = w.d.ek; ptEdges = w.ptEdges; active = w.active; poseIdx = w.poseIdx; ptPi = w.ptPi;
+    }
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= E) return;
     const int e2 = ptEdges[j];
@@ -959,9 +1067,15 @@ __device__ __forceinline__ int block_incl_scan1024(int v, int *wsum /* 17 */, in
     return x + off;
 }
 // (a) wide: active flags, vertex marks (stamped with the stage number, so that nothing has to be cleared between the stages), per-workgroup counts
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_stage_mark(int E, const int *__restrict__ ep, const int *__restrict__ ek, const uint8_t *__restrict__ flag, uint8_t *__restrict__ active,
-                                                    int *pAct, int *lAct, int stamp, int *__restrict__ partCnt)
+                                                    int *pAct, int *lAct, int stamp, int *__restrict__ partCnt, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.prep || (int)blockIdx.x >= win_gE(w)) return;
+        E = w.d.E; ep = w.d.ep; ek = w.d.ek; flag = w.stageFlags; active = w.active; pAct = w.pActF; lAct = w.lActF; stamp = w.stamp; partCnt = w.csrCnt;
+    }
     __shared__ int sw[4];
     const int e = blockIdx.x * 256 + threadIdx.x;
     int a = 0;
@@ -976,9 +1090,16 @@ __global__ __launch_bounds__(256) void k_stage_mark(int E, const int *__restrict
     if (threadIdx.x == 0) partCnt[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
 }
 // (b) one workgroup: numbering of the free keyframes and the active landmarks, the counts to the host
+template <bool BATCH = false>
 __global__ __launch_bounds__(1024) void k_stage_index(int K, int P, const uint8_t *__restrict__ fixed, const int *__restrict__ pAct, const int *__restrict__ lAct, int stamp,
-                                                      int *__restrict__ poseIdx, int *__restrict__ ptIdx, const int *__restrict__ partCnt, int nPart, double *host, double seq)
+                                                      int *__restrict__ poseIdx, int *__restrict__ ptIdx, const int *__restrict__ partCnt, int nPart, double *host, double seq, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.prep) return;
+        K = w.d.K; P = w.d.P; fixed = w.fixed; pAct = w.pActF; lAct = w.lActF; stamp = w.stamp; poseIdx = w.poseIdx; ptIdx = w.ptIdx; partCnt = w.csrCnt;
+        nPart = win_gE(w); host = w.host;
+    }
     __shared__ int wsum[17];
     const int tid = threadIdx.x;
     int nPose = 0, nPt = 0, tot;
@@ -1016,8 +1137,14 @@ __global__ __launch_bounds__(256) void k_restore(LbaDev d, const DPose *poseBak,
 }
 
 // computeLambdaInit (optimization_algorithm_levenberg.cpp:166-180): out[2] = max |diagonal entry| over the pose and landmark blocks
-__global__ __launch_bounds__(1024) void k_diag_max(const double *Hpp, int nPose, const double *Hll, int nPt, double *out)
+template <bool BATCH = false>
+__global__ __launch_bounds__(1024) void k_diag_max(const double *Hpp, int nPose, const double *Hll, int nPt, double *out, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run) return;
+        Hpp = w.Hpp; nPose = w.nPose; Hll = w.Hll; nPt = w.nPt; out = w.red;
+    }
     __shared__ double m[1024];
     double b = 0;
     for (int i = threadIdx.x; i < 6 * nPose; i += 1024) b = fmax(b, fabs(Hpp[(size_t)(i / 6) * 36 + 7 * (i % 6)]));
@@ -1031,8 +1158,14 @@ __global__ __launch_bounds__(1024) void k_diag_max(const double *Hpp, int nPose,
 // S = blockdiag(Hpp) + lambda*I ; bs = bp   (setLambda + "_Hpp->add(_Hschur)", block_solver.hpp:363-365, 564-589)
 // e->chi2() from the stored _error and isDepthPositive() from the CURRENT estimates (src/Optimizer.cc:880-958): flag = outlier
 // poseOut / ptOut (final call): the estimates copied next to the flags, so that ONE device-to-host copy brings everything back
-__global__ __launch_bounds__(256) void k_classify(LbaDev d, uint8_t *flag, double *chiOut, DPose *poseOut, double *ptOut)
+template <bool BATCH = false>
+__global__ __launch_bounds__(256) void k_classify(LbaDev d, uint8_t *flag, double *chiOut, DPose *poseOut, double *ptOut, const LbaWin *W = nullptr, int last = 0)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if ((!last && !w.prep) || (int)blockIdx.x >= (max(w.d.E, max(w.d.K, 3 * w.d.P)) + 255) / 256) return;
+        d = w.d; flag = w.flag; chiOut = last ? w.chiOut : nullptr; poseOut = last ? w.poseOut : nullptr; ptOut = last ? w.ptOut : nullptr;
+    }
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (poseOut && e < d.K) poseOut[e] = d.pose[e];
     if (ptOut && e < 3 * d.P) ptOut[e] = d.pt[e];
@@ -1143,10 +1276,18 @@ __device__ __forceinline__ void schur_poses_part(int block, const LbaDev &d, con
     if (i == j) atomicMax(&scaleBits[i], (unsigned long long)__double_as_longlong(fabs(t)));
 }
 
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_schur_setup(LbaDev d, int nInit, const double *Hpp, const double *bp, int nPose, const int *ptStart, const int *ptEdges,
                                                      const double *Hll, const double *bl, double lambda, double *S, double *bs, double *Dinv, double *Ddb, int *okFlag, const double *lamSrc,
-                                                     unsigned long long *scaleBits, const double *spPart, int spSplit, double *HppOut, double *bpOut, const int *gate, int want)
+                                                     unsigned long long *scaleBits, const double *spPart, int spSplit, double *HppOut, double *bpOut, const int *gate, int want, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        nInit = w.nP6 > 0 ? (32 * w.d.K + 255) / 256 : 0;
+        if (!w.run || (int)blockIdx.x >= nInit + (w.d.P + 3) / 4 + (w.nP6 > 0 ? win_gE(w) : 0)) return;
+        d = w.d; Hpp = w.Hpp; bp = w.bp; nPose = w.nPose; ptStart = w.ptStart; ptEdges = w.ptEdges; Hll = w.Hll; bl = w.bl; lambda = 0.0; S = w.S; bs = w.bsDev; Dinv = w.Dinv;
+        Ddb = w.Ddb; okFlag = w.okFlag; lamSrc = &w.st->lambda; scaleBits = w.scaleBits; spPart = w.spPart; spSplit = w.spSplit; HppOut = w.Hpp; bpOut = w.bp; gate = &w.st->done; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     if (lamSrc) lambda = *lamSrc;      // the stage's lambda lives on the device (LmState, k_lm_decide)
     if (blockIdx.x == 0 && threadIdx.x == 0) *okFlag = 1;      // the factorisation clears it at a failed pivot
@@ -1171,11 +1312,18 @@ __global__ __launch_bounds__(256) void k_schur_setup(LbaDev d, int nInit, const 
 // the same walk with the integer atomics going straight to the global accumulator.
 #define SCHUR_MAGIC 6755399441055744.0          /* 1.5 * 2^52 */
 #define SCHUR_MAGIC_BITS 0x4338000000000000ll
-template <bool GLOBAL>
+template <bool GLOBAL, bool BATCH = false>
 __global__ __launch_bounds__(256, 6) void k_schur_rows(LbaDev d, const int *kfStart, const int *kfEdges, const int *__restrict__ kfRowS0, const int *__restrict__ kfRowN,
                                                     const int *ptEdges, const int *__restrict__ ptPi, int nP6, const double *__restrict__ Ddb, unsigned long long *Sacc,
-                                                    double *bsPart, const unsigned long long *__restrict__ scaleBits, const int *gate, int want)
+                                                    double *bsPart, const unsigned long long *__restrict__ scaleBits, const int *gate, int want, const LbaWin *W = nullptr)
 {
+    unsigned gyB = 0;      // batch: the window's y-splits (gridDim.y is the largest window's)
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run || w.nP6 == 0 || (int)blockIdx.x >= w.d.K || (int)blockIdx.y >= w.ySplit) return;
+        d = w.d; kfStart = w.kfStart; kfEdges = w.kfEdges; kfRowS0 = w.kfRowS0; kfRowN = w.kfRowN; ptEdges = w.ptEdges; ptPi = w.ptPi; nP6 = w.nP6; Ddb = w.Ddb; Sacc = w.Sacc;
+        bsPart = w.bsPart; scaleBits = w.scaleBits; gate = &w.st->done; want = 0; gyB = (unsigned)w.ySplit;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     extern __shared__ __attribute__((aligned(16))) unsigned long long rowLds[];   // [6][nP6] fixed-point sums
     __shared__ double bsRed[16][6];
@@ -1193,7 +1341,7 @@ __global__ __launch_bounds__(256, 6) void k_schur_rows(LbaDev d, const int *kfSt
     for (int i = 0; i < 6; i++) { const int q = __builtin_amdgcn_readfirstlane(schur_q(scaleBits[i])); qa[i] = 24 - q; qb[i] = 25 - q; }
     // a wave works on four edges of the keyframe at once: 16 lanes per edge, one lane per second observation of the
     // landmark (the index lookups are done once per pair, the 6x6 block comes out of 36 registers)
-    const int sub = lane >> 4, a = lane & 15, stride = 16 * gridDim.y;
+    const int sub = lane >> 4, a = lane & 15, stride = 16 * (BATCH ? gyB : gridDim.y);
     double accB = 0.0;      // lane a < 6: row a of this lane group's share of bs[i1]
     for (int s = kfStart[k] + (blockIdx.y * 4 + wv) * 4 + sub; s < kfStart[k + 1]; s += stride) {
         // three dependent round trips instead of eight: slot -> (edge | landmark row) -> (partner edge, its free-pose index) -> its block
@@ -1236,7 +1384,7 @@ __global__ __launch_bounds__(256, 6) void k_schur_rows(LbaDev d, const int *kfSt
         double t = 0.0;
 #pragma unroll
         for (int gq = 0; gq < 16; gq++) t += bsRed[gq][tid];
-        bsPart[((size_t)k * gridDim.y + blockIdx.y) * 6 + tid] = t;
+        bsPart[((size_t)k * (BATCH ? gyB : gridDim.y) + blockIdx.y) * 6 + tid] = t;
     }
     if (GLOBAL) return;
     for (int i = tid; i < 6 * nP6; i += 256) {
@@ -1248,9 +1396,16 @@ __global__ __launch_bounds__(256, 6) void k_schur_rows(LbaDev d, const int *kfSt
 
 // S = blockdiag(Hpp) + lambda I - (fixed-point sums, converted and cleared for the next trial); bs = bp + the workgroups' partial sums in order
 // ("_Hpp->add(_Hschur)", block_solver.hpp:363-365, 564-589).  One launch behind k_schur_rows.
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_schur_fin(LbaDev d, const double *Hpp, const double *bp, int nPose, double lambda, const double *lamSrc, unsigned long long *Sacc,
-                                                   const double *bsPart, int ySplit, const unsigned long long *__restrict__ scaleBits, double *S, double *bs, const int *gate, int want)
+                                                   const double *bsPart, int ySplit, const unsigned long long *__restrict__ scaleBits, double *S, double *bs, const int *gate, int want, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run || w.nP6 == 0 || (int)blockIdx.x >= (w.nP6 + 255) / 256 || (int)blockIdx.y > w.nPose) return;
+        d = w.d; Hpp = w.Hpp; bp = w.bp; nPose = w.nPose; lambda = 0.0; lamSrc = &w.st->lambda; Sacc = w.Sacc; bsPart = w.bsPart; ySplit = w.ySplit; scaleBits = w.scaleBits;
+        S = w.S; bs = w.bsDev; gate = &w.st->done; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     if (lamSrc) lambda = *lamSrc;
     const int n = 6 * nPose;
@@ -1269,7 +1424,7 @@ __global__ __launch_bounds__(256) void k_schur_fin(LbaDev d, const double *Hpp, 
             S[idx] = v;
         }
     }
-    if (blockIdx.y == gridDim.y - 1 && blockIdx.x == 0)      // (one extra block row: the right-hand side)
+    if (blockIdx.y == (BATCH ? (unsigned)nPose : gridDim.y - 1) && blockIdx.x == 0)      // (one extra block row: the right-hand side)
         for (int i = threadIdx.x; i < 6 * d.K; i += 256) {
             const int k = i / 6, r = i - 6 * k, pi = d.poseIdx[k];
             if (pi < 0) continue;
@@ -1295,9 +1450,13 @@ __global__ __launch_bounds__(256) void k_schur_fin(LbaDev d, const double *Hpp, 
 // columns (all rows below the diagonal block) lives in LDS while it is factorised (two LDS barriers per
 // column instead of three global round trips), is written back once, and updates the trailing matrix
 // in one parallel sweep; the substitutions reuse the same panels.  n <= CHOL_MAX_N, NB*n*8 bytes of LDS.
-template <int NB>
-__global__ __launch_bounds__(1024) void k_chol_solve(double *S, const double *bs, int n, double *x, int *okFlag, const int *gate, int want)
+template <int NB, bool BATCH = false>
+__global__ __launch_bounds__(1024) void k_chol_solve(double *S, const double *bs, int n, double *x, int *okFlag, const int *gate, int want, const LbaWin *W = nullptr, const int *list = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z of the list
+        const LbaWin &wl = W[list[blockIdx.z]];
+        S = wl.S; bs = wl.bsDev; n = wl.nP6; x = wl.xp; okFlag = wl.okFlag; gate = &wl.st->done; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     extern __shared__ __attribute__((aligned(16))) double panel[];   // [rows][NB], rows = n - p0
     __shared__ double sx[CHOL_MAX_N];
@@ -1516,10 +1675,19 @@ __device__ __forceinline__ double pivot_rsqrt(double x)
 //   inside the diagonal block, summed over its 8 blocks of four columns: 5 the pivot chain (readlanes, 4 x rsq + Newton, the 4 x 4 part), 6 own entries + publishing the four columns
 //   through LDS, 7 the rank-4 update of the rest of the block.
 #define CH_STAMP(i) do { if (PROF && blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[i] += t_ - tPrev; pcnt[i] += 1; tPrev = __builtin_amdgcn_s_memtime(); } } while (0)
-template <bool PROF>
+template <bool PROF, bool BATCH = false>
 __global__ __launch_bounds__(256) void k_chol_step(double *__restrict__ S, double *__restrict__ L, int n, int p0, int nPW, int T1, double *ywork, double *ysol, int *okFlag,
-                                                   double *__restrict__ diagInv /* 1 / L[i][i], for the substitution kernel */, const int *gate, int want, unsigned long long *prof)
+                                                   double *__restrict__ diagInv /* 1 / L[i][i], for the substitution kernel */, const int *gate, int want, unsigned long long *prof, const LbaWin *W = nullptr, const int *list = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z of the list
+        const LbaWin &wl = W[list[blockIdx.z]];
+        n = wl.nP6;
+        if (p0 >= n) return;      // the panel loop runs to the largest n of the list
+        const int below = n - p0 - min(CNB, n - p0), T1r = p0 > 0 ? (n - p0 + CNB - 1) / CNB - 1 : 0;
+        nPW = max(1, (below + CHOL_RPW - 1) / CHOL_RPW); T1 = max(T1r, 1);
+        if ((int)blockIdx.x >= nPW + T1r * T1r) return;
+        S = wl.S; L = wl.L; ywork = wl.ywork; ysol = wl.ysol; okFlag = wl.okFlag; diagInv = wl.diagInv; gate = &wl.st->done; want = 0;
+    }
     if (gate && *gate != want) return;
     unsigned long long tPrev = PROF ? __builtin_amdgcn_s_memtime() : 0ull, pacc[PROF ? 8 : 1] = {}, pcnt[PROF ? 8 : 1] = {};
     (void)tPrev; (void)pacc; (void)pcnt;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
@@ -1790,9 +1958,13 @@ template <bool XG> struct XVec {
     __device__ double get(int i) const { return XG ? __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : p[i]; }
     __device__ void set(int i, double v) const { if (XG) __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else p[i] = v; }
 };
-template <bool XG>
-__global__ __launch_bounds__(1024) void k_chol_backsub(const double *__restrict__ L, const double *__restrict__ ysol, int n, double *x, const int *gate, int want)
+template <bool XG, bool BATCH = false>
+__global__ __launch_bounds__(1024) void k_chol_backsub(const double *__restrict__ L, const double *__restrict__ ysol, int n, double *x, const int *gate, int want, const LbaWin *W = nullptr, const int *list = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z of the list
+        const LbaWin &wl = W[list[blockIdx.z]];
+        L = wl.L; ysol = wl.ysol; n = wl.nP6; x = wl.xp; gate = &wl.st->done; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     __shared__ double sxLds[XG ? 1 : CHOL_LDS_X];
     __shared__ double part[32][CNB + 1];
@@ -1852,9 +2024,13 @@ __global__ __launch_bounds__(1024) void k_chol_backsub(const double *__restrict_
 // outstanding across its barriers.  Only LDS data is exchanged at these barriers.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int NP>
-__global__ __launch_bounds__(1024) void k_chol_backsub_reg(const double *__restrict__ L, const double *__restrict__ ysol, const double *__restrict__ diagInv, int n, double *x, const int *gate, int want)
+template <int NP, bool BATCH = false>
+__global__ __launch_bounds__(1024) void k_chol_backsub_reg(const double *__restrict__ L, const double *__restrict__ ysol, const double *__restrict__ diagInv, int n, double *x, const int *gate, int want, const LbaWin *W = nullptr, const int *list = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z of the list
+        const LbaWin &wl = W[list[blockIdx.z]];
+        L = wl.L; ysol = wl.ysol; diagInv = wl.diagInv; n = wl.nP6; x = wl.xp; gate = &wl.st->done; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     // columns; row groups of the 1024 threads (3 above 256 columns, else 4); rows per thread and panel (3 x 11, 4 x 8 >= 32).  With four groups a
     // thread keeps 8 instead of 11 prefetched values per panel in flight: no register spill - and a spill reload inside the panel loop is followed by
@@ -1923,9 +2099,16 @@ __global__ __launch_bounds__(1024) void k_chol_backsub_reg(const double *__restr
 // x_l = D^-1 (b_l - B^T x_p)   (block_solver.hpp:459-481)
 // x_l, push() and update(x) in one launch: thread t computes the increment of landmark t (k_backsub), saves the estimates of
 // keyframe t / landmark t (SparseOptimizer::push, sparse_optimizer.cpp:502-506: every vertex) and applies the increments (oplus).
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void k_backsub_update(LbaDev d, const int *ptStart, const int *ptEdges, const int *__restrict__ ptPi, const double *bl, const double *Dinv,
-                                                        const double *xp, double *xl, DPose *poseBak, double *ptBak, double lambda, double *partL, const double *lamSrc, const int *gate, int want)
+                                                        const double *xp, double *xl, DPose *poseBak, double *ptBak, double lambda, double *partL, const double *lamSrc, const int *gate, int want, const LbaWin *W = nullptr)
 {
+    if constexpr (BATCH) {      // window blockIdx.z: its views and partition; workgroups past its extent return
+        const LbaWin &w = W[blockIdx.z];
+        if (!w.run || (int)blockIdx.x >= win_gU(w)) return;
+        d = w.d; ptStart = w.ptStart; ptEdges = w.ptEdges; ptPi = w.ptPi; bl = w.bl; Dinv = w.Dinv; xp = w.xp; xl = w.xl; poseBak = w.poseBak; ptBak = w.ptBak; lambda = 0.0;
+        partL = w.partL; lamSrc = &w.st->lambda; gate = &w.st->done; want = 0;
+    }
     if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
     if (lamSrc) lambda = *lamSrc;      // the stage's lambda lives on the device (LmState, k_lm_decide)
     __shared__ double sw[4];
@@ -2575,6 +2758,75 @@ namespace {
 // developer tap (tools/chol_phases.py; not part of include/orbx.h): a device array of 16 u64 the PROF instantiation of k_chol_step adds its phase cycles / passes to
 static unsigned long long *g_cholProf = nullptr;
 
+// The partition choices of a call that the batch driver (lba_run_batch) must make for every window exactly as this driver makes them for that
+// window alone: the bits of the sums depend on them.  One function each, called by both drivers.
+// workgroups per keyframe in k_lin_sums: ceil(longest keyframe row / 256), 1 .. SP_SPLIT
+int lba_sp_split(int longestRow) { return std::max(1, std::min(SP_SPLIT, (longestRow + 255) / 256)); }
+// y-splits per keyframe of k_schur_rows so that ALL workgroups are resident at once (six per CU at the kernel's 80 registers, fewer where the LDS row is
+// long): a step of the edge loop is three dependent memory round trips, ~5 us, and a second round of workgroups costs a whole one.  k_schur_fin adds
+// the y-splits' shares of bs in y order.
+int lba_schur_ysplit(int nP6, int K, int numCU)
+{
+    const size_t ldsRows = (size_t)(6 * nP6) * sizeof(unsigned long long);
+    const int perCU = std::max(1, std::min(6, (int)(150 * 1024 / std::max<size_t>(ldsRows, 1))));
+    return std::max(4, std::min(32, perCU * numCU / std::max(K, 1)));
+}
+// the factorisation route of a reduced system of n unknowns (RT_MULTI: the panel steps every route from RT_REG4 on starts with)
+enum { RT_SOLVE = 0, RT_MULTI, RT_REG4, RT_REG7, RT_REG8, RT_REG10, RT_LDS, RT_GLOBAL, RT_N };
+int lba_chol_route(int n)
+{
+    if (n < CHOL_MULTI_MIN_N) return RT_SOLVE;
+    if (n <= 128) return RT_REG4;
+    if (n <= 224) return RT_REG7;
+    if (n <= 256) return RT_REG8;
+    if (n <= 320) return RT_REG10;
+    return n <= CHOL_LDS_X ? RT_LDS : RT_GLOBAL;
+}
+
+// The host half of a window's marshalling, the same for both drivers: float boundary -> double state (Converter::toSE3Quat / toVector3d) into the
+// pinned arena at the given offsets, the row lengths of the adjacency lists, the edge ids checked.  -> -1, or the first edge out of range.
+int lba_marshal(const orbx_lba_problem *p, uint8_t *io, size_t oPose, size_t oIntr, size_t oPt, size_t oObs, size_t oInfo, size_t oEp, size_t oEk, size_t oPs, size_t oKs,
+                size_t oFx, int &nPose0, int &nPt0, int &spSplit)
+{
+    const int K = p->num_keyframes, P = p->num_points, E = p->num_edges;
+    DPose *pose = (DPose *)(io + oPose);
+    double *intr = (double *)(io + oIntr), *pt = (double *)(io + oPt);
+    uint8_t *fixedH = io + oFx;
+    int *epH = (int *)(io + oEp), *ekH = (int *)(io + oEk), *ptStart = (int *)(io + oPs), *kfStart = (int *)(io + oKs);
+    for (int k = 0; k < K; k++) {
+        double R[9];
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R[3 * i + j] = p->poses[16 * (size_t)k + 4 * i + j];
+        pose[k].q = quat_from_R(R);
+        quat_normalize_pos(pose[k].q);
+        for (int i = 0; i < 3; i++) pose[k].t[i] = p->poses[16 * (size_t)k + 4 * i + 3];
+        for (int i = 0; i < 5; i++) intr[5 * (size_t)k + i] = p->intrinsics[5 * (size_t)k + i];
+        fixedH[k] = p->fixed[k] ? 1 : 0;
+    }
+    for (int i = 0; i < 3 * P; i++) pt[i] = p->points[i];
+    for (int l = 0; l <= P; l++) ptStart[l] = 0;
+    for (int k = 0; k <= K; k++) kfStart[k] = 0;
+    // the edge arrays travel as they are (float observations / information, int ids): four memcpy; the device converts and derives the stereo flags
+    // (k_unpack).  The host only checks the ids and counts the row lengths of the adjacency lists.
+    memcpy(io + oObs, p->edge_obs, (size_t)3 * E * sizeof(float));
+    memcpy(io + oInfo, p->edge_inv_sigma2, (size_t)E * sizeof(float));
+    memcpy(epH, p->edge_point, (size_t)E * sizeof(int));
+    memcpy(ekH, p->edge_keyframe, (size_t)E * sizeof(int));
+    for (int e = 0; e < E; e++) {
+        const int l = epH[e], k = ekH[e];
+        if (l < 0 || l >= P || k < 0 || k >= K) return e;
+        ptStart[l + 1]++; kfStart[k + 1]++;
+    }
+    nPose0 = nPt0 = 0;
+    for (int l = 0; l < P; l++) { nPt0 += ptStart[l + 1] > 0; ptStart[l + 1] += ptStart[l]; }                       // row starts; vertices with an edge
+    {
+        int longest = 0;
+        for (int k = 0; k < K; k++) longest = std::max(longest, kfStart[k + 1]);
+        spSplit = lba_sp_split(longest);
+    }
+    for (int k = 0; k < K; k++) { nPose0 += kfStart[k + 1] > 0 && !fixedH[k]; kfStart[k + 1] += kfStart[k]; }
+    return -1;
+}
+
 struct Ctx {
     orbx_lba *h;
     LbaDev d;
@@ -2709,10 +2961,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
         }
         if (nP6 > 0) {
             const size_t ldsRows = (size_t)(6 * nP6) * sizeof(unsigned long long);
-            // y-splits per keyframe so that ALL workgroups are resident at once (six per CU at the kernel's 80 registers, fewer where the LDS row is
-            // long): a step of the edge loop is three dependent memory round trips, ~5 us, and a second round of workgroups costs a whole one
-            const int perCU = std::max(1, std::min(6, (int)(150 * 1024 / std::max<size_t>(ldsRows, 1))));
-            const int ySplit = std::max(4, std::min(32, perCU * h->numCU / std::max(K, 1)));
+            const int ySplit = lba_schur_ysplit(nP6, K, h->numCU);
             int ys = ySplit;
             if (ldsRows > 150 * 1024) {      // > ~530 free keyframes: the block row no longer fits into LDS
                 ys = 16;
@@ -2744,12 +2993,14 @@ int optimize(Ctx &c, int iterations, double stats[4])
                     else hipLaunchKernelGGL(k_chol_step<false>, dim3((unsigned)(nPW + T1 * T1)), dim3(256), 0, h->stream, h->S.p, h->Lmat.p, n, p0, nPW, std::max(T1, 1), h->ywork.p,
                                             h->ysol.p, h->okFlag.p, h->diagInv.p, gDone, 0, (unsigned long long *)nullptr);
                 }
-                if (n <= 128) hipLaunchKernelGGL(k_chol_backsub_reg<4>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0);
-                else if (n <= 224) hipLaunchKernelGGL(k_chol_backsub_reg<7>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0);
-                else if (n <= 256) hipLaunchKernelGGL(k_chol_backsub_reg<8>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0);
-                else if (n <= 320) hipLaunchKernelGGL(k_chol_backsub_reg<10>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0);
-                else if (n <= CHOL_LDS_X) hipLaunchKernelGGL(k_chol_backsub<false>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, n, h->xp.p, gDone, 0);
-                else hipLaunchKernelGGL(k_chol_backsub<true>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, n, h->xp.p, gDone, 0);
+                switch (lba_chol_route(n)) {
+                case RT_REG4: hipLaunchKernelGGL(k_chol_backsub_reg<4>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0); break;
+                case RT_REG7: hipLaunchKernelGGL(k_chol_backsub_reg<7>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0); break;
+                case RT_REG8: hipLaunchKernelGGL(k_chol_backsub_reg<8>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0); break;
+                case RT_REG10: hipLaunchKernelGGL(k_chol_backsub_reg<10>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, h->diagInv.p, n, h->xp.p, gDone, 0); break;
+                case RT_LDS: hipLaunchKernelGGL(k_chol_backsub<false>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, n, h->xp.p, gDone, 0); break;
+                default: hipLaunchKernelGGL(k_chol_backsub<true>, dim3(1), dim3(1024), 0, h->stream, h->Lmat.p, h->ysol.p, n, h->xp.p, gDone, 0); break;
+                }
             } else {   // widest panel whose n x NB doubles fit next to the solution vector in LDS
                 const size_t budget = 120 * 1024;
                 if ((size_t)nP6 * 32 * 8 <= budget) {
@@ -2869,42 +3120,12 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
     // kernel distributes it, and the adjacency lists and the index mapping of the stages are made on the device.  Nothing waits for
     // the copy: the results come back into the front of the same buffer long after the device has consumed it.
     uint8_t *io = h->hostIO;
-    DPose *pose = (DPose *)(io + oPose);
-    double *intr = (double *)(io + oIntr), *pt = (double *)(io + oPt);
-    uint8_t *fixedH = io + oFx;
-    int *epH = (int *)(io + oEp), *ekH = (int *)(io + oEk), *ptStart = (int *)(io + oPs), *kfStart = (int *)(io + oKs);
-    for (int k = 0; k < K; k++) {
-        double R[9];
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R[3 * i + j] = p->poses[16 * (size_t)k + 4 * i + j];
-        pose[k].q = quat_from_R(R);
-        quat_normalize_pos(pose[k].q);
-        for (int i = 0; i < 3; i++) pose[k].t[i] = p->poses[16 * (size_t)k + 4 * i + 3];
-        for (int i = 0; i < 5; i++) intr[5 * (size_t)k + i] = p->intrinsics[5 * (size_t)k + i];
-        fixedH[k] = p->fixed[k] ? 1 : 0;
-    }
-    for (int i = 0; i < 3 * P; i++) pt[i] = p->points[i];
-    for (int l = 0; l <= P; l++) ptStart[l] = 0;
-    for (int k = 0; k <= K; k++) kfStart[k] = 0;
-    // the edge arrays travel as they are (float observations / information, int ids): four memcpy; the device converts and derives the stereo flags
-    // (k_unpack).  The host only checks the ids and counts the row lengths of the adjacency lists.
-    memcpy(io + oObs, p->edge_obs, (size_t)3 * E * sizeof(float));
-    memcpy(io + oInfo, p->edge_inv_sigma2, (size_t)E * sizeof(float));
-    memcpy(epH, p->edge_point, (size_t)E * sizeof(int));
-    memcpy(ekH, p->edge_keyframe, (size_t)E * sizeof(int));
-    for (int e = 0; e < E; e++) {
-        const int l = epH[e], k = ekH[e];
-        if (l < 0 || l >= P || k < 0 || k >= K) { orbx_set_error("edge %d references a vertex out of range", e); return ORBX_ERR_ARG; }
-        ptStart[l + 1]++; kfStart[k + 1]++;
-    }
     Ctx c;
     c.h = h; c.stop = stop;
-    for (int l = 0; l < P; l++) { c.nPt0 += ptStart[l + 1] > 0; ptStart[l + 1] += ptStart[l]; }                       // row starts; vertices with an edge
     {
-        int longest = 0;
-        for (int k = 0; k < K; k++) longest = std::max(longest, kfStart[k + 1]);
-        c.spSplit = std::max(1, std::min(SP_SPLIT, (longest + 255) / 256));
+        const int bad = lba_marshal(p, io, oPose, oIntr, oPt, oObs, oInfo, oEp, oEk, oPs, oKs, oFx, c.nPose0, c.nPt0, c.spSplit);
+        if (bad >= 0) { orbx_set_error("edge %d references a vertex out of range", bad); return ORBX_ERR_ARG; }
     }
-    for (int k = 0; k < K; k++) { c.nPose0 += kfStart[k + 1] > 0 && !fixedH[k]; kfStart[k + 1] += kfStart[k]; }
     hipStream_t s = h->stream;
     ORBX_HIP_CHECK(hipEventRecord(h->ev0, s));
     {
@@ -2923,7 +3144,7 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
         LCHECK();
         // adjacency lists
         if (csrLds > 48 * 1024) {
-            ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_csr_kf_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)csrLds));
+            ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_csr_kf_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)csrLds));
         }
         const unsigned gE = (unsigned)((E + 255) / 256);
         hipLaunchKernelGGL(k_csr_kf_count, dim3((unsigned)nChunk), dim3(256), csrLds, s, (const int *)h->ek.p, E, K, h->csrCnt.p);
@@ -2969,7 +3190,8 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     memcpy(res->edge_outlier, io + dFlag, (size_t)E);
     if (res->edge_chi2) memcpy(res->edge_chi2, io + dChi, (size_t)E * 8);
-    pose = (DPose *)(io + dPose); pt = (double *)(io + dPt);                  // final estimates (pinned read-back)
+    const DPose *pose = (const DPose *)(io + dPose);
+    const double *pt = (const double *)(io + dPt);                  // final estimates (pinned read-back)
     for (int k = 0; k < K; k++) {                                             // Converter::toCvMat(SE3Quat)
         double R[9];
         quat_to_R(pose[k].q, R);
@@ -3094,3 +3316,518 @@ extern "C" int orbx_lba_last_timing(orbx_lba *h, float *device_ms, double *flops
     if (flops) *flops = h->flops;
     return ORBX_OK;
 }
+// ---- batched LocalBundleAdjustment: N independent windows, one launch chain ----
+struct orbx_lba_batch {
+    int device = 0, maxW = 0, maxK = 0, maxP = 0, maxE = 0;
+    int numCU = 256;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+    double flops = 0, seq = 0;
+    int launches = 0;                    // kernel launches of the last call (tools/lba_batch_rate.py)
+    // per-window regions of the handle's capacities (maxK / maxP / maxE), window w at w times the region
+    OrbxDevBuf<DPose> pose, poseBak;
+    OrbxDevBuf<double> pt, ptBak, intr, obs, info, err, rchi, edgeBlk, Hpp, bp, Hll, bl, Dinv, Ddb, bs, xp, xl, red, ywork, ysol, diagInv, spPart, partChi, partL, bsPart;
+    OrbxDevBuf<int> ep, ek, ptStart, ptEdges, kfStart, kfEdges, poseIdx, ptIdx, okFlag, ptTmp, fillP, pActF, lActF, kfRowS0, kfRowN, ptPi;
+    OrbxDevBuf<uint8_t> stereo, active, fixedDev;
+    OrbxDevBuf<unsigned long long> scaleBits;
+    OrbxDevBuf<LmState> lm;
+    // sized per call
+    OrbxDevBuf<double> S, Lmat;
+    OrbxDevBuf<unsigned long long> Sacc;
+    OrbxDevBuf<int> csrCnt;
+    OrbxDevBuf<uint8_t> inArena, outArena, descDev;      // descDev: LbaWin[2][maxW] | UnpackSegs[maxW] | route lists [2][7][maxW]
+    uint8_t *hostIO = nullptr; size_t hostIOBytes = 0;    // pinned: the marshalled inputs on their way up, the results on their way down
+    uint8_t *hostDesc = nullptr;                          // pinned staging of descDev
+    double *rec = nullptr, *recDev = nullptr;             // mapped: 16 doubles per window, the LM record of k_stage_index / k_lm_begin / k_lm_decide
+    int *stopW = nullptr, *stopWDev = nullptr;            // mapped: the windows' stop words as the device sees them (16 ints apart)
+};
+
+namespace {
+const LbaDev D0 = {};      // the by-value views of a batch launch's arguments: unused, the window's come from its descriptor
+size_t batch_desc_bytes(int maxW) { return (size_t)2 * maxW * sizeof(LbaWin) + (size_t)maxW * sizeof(UnpackSegs) + (size_t)2 * RT_N * maxW * sizeof(int); }
+}
+
+extern "C" void orbx_lba_batch_destroy(orbx_lba_batch *h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->pose.release(); h->poseBak.release();
+    h->pt.release(); h->ptBak.release(); h->intr.release(); h->obs.release(); h->info.release(); h->err.release(); h->rchi.release(); h->edgeBlk.release(); h->Hpp.release(); h->bp.release();
+    h->Hll.release(); h->bl.release(); h->Dinv.release(); h->Ddb.release(); h->bs.release(); h->xp.release(); h->xl.release(); h->red.release(); h->ywork.release(); h->ysol.release();
+    h->diagInv.release(); h->spPart.release(); h->partChi.release(); h->partL.release(); h->bsPart.release();
+    h->ep.release(); h->ek.release(); h->ptStart.release(); h->ptEdges.release(); h->kfStart.release(); h->kfEdges.release(); h->poseIdx.release(); h->ptIdx.release(); h->okFlag.release();
+    h->ptTmp.release(); h->fillP.release(); h->pActF.release(); h->lActF.release(); h->kfRowS0.release(); h->kfRowN.release(); h->ptPi.release();
+    h->stereo.release(); h->active.release(); h->fixedDev.release(); h->scaleBits.release(); h->lm.release();
+    h->S.release(); h->Lmat.release(); h->Sacc.release(); h->csrCnt.release(); h->inArena.release(); h->outArena.release(); h->descDev.release();
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->hostIO) (void)hipHostFree(h->hostIO);
+    if (h->hostDesc) (void)hipHostFree(h->hostDesc);
+    if (h->rec) (void)hipHostFree(h->rec);
+    if (h->stopW) (void)hipHostFree(h->stopW);
+    delete h;
+}
+
+extern "C" int orbx_lba_batch_create(int device, int max_windows, int max_keyframes, int max_points, int max_edges, orbx_lba_batch **out)
+{
+    if (!out || max_windows < 1 || max_keyframes < 1 || max_points < 1 || max_edges < 1) { orbx_set_error("bad LBA batch sizes"); return ORBX_ERR_ARG; }
+    *out = nullptr;
+    // 6 K <= CHOL_LDS_X: the reduced system of every window stays on the LDS paths (Schur rows, back-substitution)
+    if (6 * max_keyframes > CHOL_LDS_X) { orbx_set_error("max_keyframes %d exceeds the batch limit %d", max_keyframes, CHOL_LDS_X / 6); return ORBX_ERR_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
+    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
+    ORBX_HIP_CHECK(hipSetDevice(device));
+    orbx_lba_batch *h = new orbx_lba_batch();
+    h->device = device; h->maxW = max_windows; h->maxK = max_keyframes; h->maxP = max_points; h->maxE = max_edges;
+    { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
+    (void)hipEventCreate(&h->ev0);
+    (void)hipEventCreate(&h->ev1);
+    const size_t W = (size_t)max_windows;
+    if (hipHostMalloc((void **)&h->rec, W * 16 * sizeof(double), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->recDev, h->rec, 0) != hipSuccess ||
+        hipHostMalloc((void **)&h->stopW, W * 16 * sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->stopWDev, h->stopW, 0) != hipSuccess ||
+        hipHostMalloc((void **)&h->hostDesc, batch_desc_bytes(max_windows), hipHostMallocDefault) != hipSuccess) {
+        orbx_lba_batch_destroy(h); orbx_set_error("hipHostMalloc failed"); return ORBX_ERR_HIP;
+    }
+    for (size_t i = 0; i < W * 16; i++) { h->rec[i] = 0; h->stopW[i] = 0; }
+    const size_t K = (size_t)max_keyframes, P = (size_t)max_points, E = (size_t)max_edges, n6 = 6 * K;
+    int rc = 0;
+    rc = rc ? rc : h->pose.ensure(W * K); rc = rc ? rc : h->poseBak.ensure(W * K); rc = rc ? rc : h->pt.ensure(W * 3 * P); rc = rc ? rc : h->ptBak.ensure(W * 3 * P);
+    rc = rc ? rc : h->intr.ensure(W * 5 * K); rc = rc ? rc : h->obs.ensure(W * 3 * E); rc = rc ? rc : h->info.ensure(W * E); rc = rc ? rc : h->err.ensure(W * 3 * E);
+    rc = rc ? rc : h->rchi.ensure(W * E); rc = rc ? rc : h->edgeBlk.ensure(W * 36 * E);      // Hpl | BD (the fused form writes no eb_rest)
+    rc = rc ? rc : h->Hpp.ensure(W * 36 * K); rc = rc ? rc : h->bp.ensure(W * n6); rc = rc ? rc : h->Hll.ensure(W * 9 * P); rc = rc ? rc : h->bl.ensure(W * 3 * P);
+    rc = rc ? rc : h->Dinv.ensure(W * 9 * P); rc = rc ? rc : h->Ddb.ensure(W * 3 * P); rc = rc ? rc : h->bs.ensure(W * n6); rc = rc ? rc : h->xp.ensure(W * n6);
+    rc = rc ? rc : h->xl.ensure(W * 3 * P); rc = rc ? rc : h->red.ensure(W * 16); rc = rc ? rc : h->ywork.ensure(W * n6); rc = rc ? rc : h->ysol.ensure(W * n6);
+    rc = rc ? rc : h->diagInv.ensure(W * (n6 + CNB)); rc = rc ? rc : h->spPart.ensure(W * K * SP_SPLIT * 27);
+    rc = rc ? rc : h->partChi.ensure(W * ((E + 255) / 256)); rc = rc ? rc : h->partL.ensure(W * ((std::max(K, 16 * P) + 255) / 256)); rc = rc ? rc : h->bsPart.ensure(W * K * 32 * 6);
+    rc = rc ? rc : h->ep.ensure(W * E); rc = rc ? rc : h->ek.ensure(W * E); rc = rc ? rc : h->ptStart.ensure(W * (P + 1)); rc = rc ? rc : h->ptEdges.ensure(W * E);
+    rc = rc ? rc : h->kfStart.ensure(W * (K + 1)); rc = rc ? rc : h->kfEdges.ensure(W * E); rc = rc ? rc : h->poseIdx.ensure(W * K); rc = rc ? rc : h->ptIdx.ensure(W * P);
+    rc = rc ? rc : h->okFlag.ensure(W * 16); rc = rc ? rc : h->ptTmp.ensure(W * E); rc = rc ? rc : h->fillP.ensure(W * P); rc = rc ? rc : h->pActF.ensure(W * K);
+    rc = rc ? rc : h->lActF.ensure(W * P); rc = rc ? rc : h->kfRowS0.ensure(W * E); rc = rc ? rc : h->kfRowN.ensure(W * E); rc = rc ? rc : h->ptPi.ensure(W * E);
+    rc = rc ? rc : h->stereo.ensure(W * E); rc = rc ? rc : h->active.ensure(W * E); rc = rc ? rc : h->fixedDev.ensure(W * K); rc = rc ? rc : h->scaleBits.ensure(W * 8);
+    rc = rc ? rc : h->lm.ensure(W); rc = rc ? rc : h->descDev.ensure(batch_desc_bytes(max_windows));
+    if (rc) { orbx_lba_batch_destroy(h); return rc; }
+    *out = h;
+    return ORBX_OK;
+}
+
+namespace {
+
+// host-side facts of one window of a batch call
+struct BatchWinHost {
+    int K, P, E, nChunk, spSplit, nPose0, nPt0;
+    bool stage1, stage2, run1, run2;
+    int nPose2, nPt2, nAct2;
+    size_t in, oPose, oIntr, oPt, oObs, oInfo, oEp, oEk, oPs, oKs, oFx;      // input layout (absolute offsets in the arena)
+    size_t out, dFlag, dChi, dPose, dPt;                                          // result layout (absolute offsets)
+};
+
+// Waits until the LM record of every listed window has reached `seq`, mirroring the windows' stop flags into their device-visible words
+int batch_wait(orbx_lba_batch *h, const std::vector<int> &wins, double seq, const volatile uint8_t *const *stops)
+{
+    for (unsigned spins = 1;; spins++) {
+        bool all = true;
+        for (int w : wins) {
+            if (*(volatile double *)(h->rec + 16 * (size_t)w + 15) < seq) all = false;
+            const volatile uint8_t *s = stops ? stops[w] : nullptr;
+            if (s && *s && !h->stopW[16 * (size_t)w]) { h->stopW[16 * (size_t)w] = 1; std::atomic_thread_fence(std::memory_order_release); }
+        }
+        if (all) break;
+        if ((spins & 0x3fff) == 0) {
+            const hipError_t q = hipStreamQuery(h->stream);
+            if (q == hipSuccess) {
+                bool done = true;
+                for (int w : wins) done = done && *(volatile double *)(h->rec + 16 * (size_t)w + 15) >= seq;
+                if (done) break;
+                orbx_set_error("LBA batch: the stream drained without the trial results");
+                return ORBX_ERR_HIP;
+            }
+            if (q != hipErrorNotReady) { orbx_set_error("LBA batch: %s", hipGetErrorString(q)); return ORBX_ERR_HIP; }
+        }
+        if (spins > 4096 && (spins & 63) == 0) std::this_thread::yield();
+        __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return ORBX_OK;
+}
+
+#define BLAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); h->launches++; } while (0)
+
+// SparseOptimizer::optimize(iters) of every window with run = 1 in the descriptors `Wd` (optimize() of the single-window driver, from the
+// start of the stage on): the windows advance trial by trial together; the host waits for the decision of every window that is not done yet.
+int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<LbaWin> &hw, const int *lists /* device [RT_N][maxW] */, const int (&nList)[RT_N],
+                int maxP0, int maxK0, int maxE0, const volatile uint8_t *const *stops, double *stats /* 4 per window */)
+{
+    hipStream_t s = h->stream;
+    std::vector<int> live;
+    int maxN = 0, maxY = 0, maxNP6 = 0, maxPose = 0, maxLin = 0, maxSetup = 0;
+    for (int w = 0; w < N; w++) {
+        if (!hw[w].run) continue;
+        live.push_back(w);
+        h->stopW[16 * (size_t)w] = 0;
+        const LbaWin &x = hw[w];
+        if (x.nP6 >= CHOL_MULTI_MIN_N) maxN = std::max(maxN, x.nP6);
+        maxY = std::max(maxY, x.ySplit); maxNP6 = std::max(maxNP6, x.nP6); maxPose = std::max(maxPose, x.nPose);
+        maxLin = std::max(maxLin, x.d.K * x.spSplit + (x.d.P + 15) / 16);
+        maxSetup = std::max(maxSetup, (x.nP6 > 0 ? (32 * x.d.K + 255) / 256 : 0) + (x.d.P + 3) / 4 + (x.nP6 > 0 ? (x.d.E + 255) / 256 : 0));
+    }
+    if (live.empty()) return ORBX_OK;
+    std::atomic_thread_fence(std::memory_order_seq_cst);
+    const unsigned Nz = (unsigned)N, gE = (unsigned)((maxE0 + 255) / 256), gU = (unsigned)((std::max(maxK0, 16 * maxP0) + 255) / 256);
+    // ---- start of the stage
+    BLAUNCH(k_errors<true>, dim3(gE, 1, Nz), dim3(256), 0, s, D0, Huber{}, 0, nullptr, nullptr, 0, Wd, 0);
+    BLAUNCH(k_lin_sums<true>, dim3((unsigned)maxLin, 1, Nz), dim3(256), 0, s, D0, Huber{}, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, Wd, 0);
+    BLAUNCH(k_sum_poses_fin<true>, dim3((unsigned)((32 * maxK0 + 255) / 256), 1, Nz), dim3(256), 0, s, D0, nullptr, nullptr, nullptr, 0, nullptr, 0, Wd);
+    BLAUNCH(k_diag_max<true>, dim3(1, 1, Nz), dim3(1024), 0, s, nullptr, 0, nullptr, 0, nullptr, Wd);
+    BLAUNCH(k_lm_begin<true>, dim3(1, 1, Nz), dim3(256), 0, s, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, (h->seq += 1.0), nullptr, Wd);
+    LCHECK();
+    const size_t ldsRows = (size_t)(6 * maxNP6) * sizeof(unsigned long long);
+    if (ldsRows > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_schur_rows<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsRows));
+    auto trialSchur = [&]() -> int {
+        BLAUNCH(k_schur_setup<true>, dim3((unsigned)maxSetup, 1, Nz), dim3(256), 0, s, D0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, Wd);
+        if (maxNP6 > 0) {
+            BLAUNCH((k_schur_rows<false, true>), dim3((unsigned)maxK0, (unsigned)maxY, Nz), dim3(256), ldsRows, s, D0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, 0, Wd);
+            BLAUNCH(k_schur_fin<true>, dim3((unsigned)((maxNP6 + 255) / 256), (unsigned)(maxPose + 1), Nz), dim3(256), 0, s, D0, nullptr, nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0, nullptr,
+                    nullptr, nullptr, nullptr, 0, Wd);
+        }
+        LCHECK();
+        return ORBX_OK;
+    };
+    auto trialChol = [&]() -> int {
+        const int *L = lists;
+        const int mw = h->maxW;
+        if (nList[RT_SOLVE]) {
+            int n = 0;
+            for (int w : live) if (hw[w].nP6 > 0 && hw[w].nP6 < CHOL_MULTI_MIN_N) n = std::max(n, hw[w].nP6);
+            BLAUNCH((k_chol_solve<32, true>), dim3(1, 1, (unsigned)nList[RT_SOLVE]), dim3(1024), (size_t)n * 32 * 8, s, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, Wd, L + RT_SOLVE * mw);
+        }
+        if (nList[RT_MULTI]) {
+            for (int p0 = 0; p0 < maxN; p0 += CNB) {
+                int g = 1;
+                for (int w : live) {
+                    const int n = hw[w].nP6;
+                    if (n < CHOL_MULTI_MIN_N || p0 >= n) continue;
+                    const int nb = std::min(CNB, n - p0), below = n - p0 - nb, nPW = std::max(1, (below + CHOL_RPW - 1) / CHOL_RPW);
+                    const int T1 = p0 > 0 ? (n - p0 + CNB - 1) / CNB - 1 : 0;
+                    g = std::max(g, nPW + T1 * T1);
+                }
+                BLAUNCH((k_chol_step<false, true>), dim3((unsigned)g, 1, (unsigned)nList[RT_MULTI]), dim3(256), 0, s, nullptr, nullptr, 0, p0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                        nullptr, Wd, L + RT_MULTI * mw);
+            }
+            if (nList[RT_REG4]) BLAUNCH((k_chol_backsub_reg<4, true>), dim3(1, 1, (unsigned)nList[RT_REG4]), dim3(1024), 0, s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_REG4 * mw);
+            if (nList[RT_REG7]) BLAUNCH((k_chol_backsub_reg<7, true>), dim3(1, 1, (unsigned)nList[RT_REG7]), dim3(1024), 0, s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_REG7 * mw);
+            if (nList[RT_REG8]) BLAUNCH((k_chol_backsub_reg<8, true>), dim3(1, 1, (unsigned)nList[RT_REG8]), dim3(1024), 0, s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_REG8 * mw);
+            if (nList[RT_REG10]) BLAUNCH((k_chol_backsub_reg<10, true>), dim3(1, 1, (unsigned)nList[RT_REG10]), dim3(1024), 0, s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_REG10 * mw);
+            if (nList[RT_LDS]) BLAUNCH((k_chol_backsub<false, true>), dim3(1, 1, (unsigned)nList[RT_LDS]), dim3(1024), 0, s, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_LDS * mw);
+        }
+        LCHECK();
+        return ORBX_OK;
+    };
+    auto trialRest = [&](double *seqOut) -> int {
+        BLAUNCH(k_backsub_update<true>, dim3(gU, 1, Nz), dim3(256), 0, s, D0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, nullptr, nullptr, 0, Wd);
+        BLAUNCH(k_errors<true>, dim3(gE, 1, Nz), dim3(256), 0, s, D0, Huber{}, 0, nullptr, nullptr, 0, Wd, 1);
+        const double seq = (h->seq += 1.0);
+        BLAUNCH(k_lm_decide<true>, dim3(1, 1, Nz), dim3(256), 0, s, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, seq, D0, nullptr, nullptr, nullptr, Wd);
+        BLAUNCH(k_lin_sums<true>, dim3((unsigned)maxLin, 1, Nz), dim3(256), 0, s, D0, Huber{}, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, Wd, 1);
+        LCHECK();
+        for (int w : live) h->flops += 650.0 * hw[w].d.E + (double)hw[w].nP6 * hw[w].nP6 * hw[w].nP6 / 3.0;
+        *seqOut = seq;
+        return ORBX_OK;
+    };
+    int rc = trialSchur();
+    if (rc) return rc;
+    int maxIters = 0;
+    for (int w : live) maxIters = std::max(maxIters, hw[w].iters);
+    for (int t = 0;; t++) {
+        double seqT = 0;
+        if ((rc = trialChol()) != ORBX_OK) return rc;
+        if ((rc = trialRest(&seqT)) != ORBX_OK) return rc;
+        if ((rc = trialSchur()) != ORBX_OK) return rc;      // of trial t + 1, speculatively
+        if ((rc = batch_wait(h, live, seqT, stops)) != ORBX_OK) return rc;
+        std::vector<int> still;
+        for (int w : live) if (h->rec[16 * (size_t)w + 13] == 0.0) still.push_back(w);
+        live.swap(still);
+        if (live.empty()) break;
+        if (t >= 10 * maxIters + 10) { orbx_set_error("LBA batch: the Levenberg loop did not terminate"); return ORBX_ERR_STATE; }
+    }
+    for (int w = 0; w < N; w++) {
+        if (!hw[w].run) continue;
+        const double *r = h->rec + 16 * (size_t)w;
+        stats[4 * w] = r[7]; stats[4 * w + 1] = r[9]; stats[4 * w + 2] = r[6]; stats[4 * w + 3] = r[1];
+    }
+    return ORBX_OK;
+}
+
+}  // namespace
+
+static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs, const volatile uint8_t *const *stops, orbx_lba_result *res)
+{
+    if (!h || !probs || !res) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    if (N < 1 || N > h->maxW) { orbx_set_error("%d windows outside the handle's capacity 1..%d", N, h->maxW); return ORBX_ERR_CAPACITY; }
+    // ---- every window checked (and marshalled) before anything is launched or any result written
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    std::vector<BatchWinHost> wh(N);
+    size_t inBytes = 0, outBytes = 0;
+    for (int w = 0; w < N; w++) {
+        const orbx_lba_problem *p = probs + w;
+        const orbx_lba_result *r = res + w;
+        if (!r->poses || !r->points || !r->edge_outlier) { orbx_set_error("window %d: NULL result array", w); return ORBX_ERR_ARG; }
+        const int K = p->num_keyframes, P = p->num_points, E = p->num_edges;
+        if (K < 1 || P < 1 || E < 1 || K > h->maxK || P > h->maxP || E > h->maxE) {
+            orbx_set_error("window %d: problem size %d/%d/%d outside the handle's capacity %d/%d/%d", w, K, P, E, h->maxK, h->maxP, h->maxE);
+            return ORBX_ERR_CAPACITY;
+        }
+        if (!p->poses || !p->fixed || !p->intrinsics || !p->points || !p->edge_point || !p->edge_keyframe || !p->edge_obs || !p->edge_inv_sigma2) {
+            orbx_set_error("window %d: NULL problem array", w);
+            return ORBX_ERR_ARG;
+        }
+        BatchWinHost &x = wh[w];
+        x.K = K; x.P = P; x.E = E; x.nChunk = (E + CSR_CHUNK - 1) / CSR_CHUNK;
+        x.in = inBytes;
+        x.oPose = x.in; x.oIntr = x.oPose + pad((size_t)K * sizeof(DPose)); x.oPt = x.oIntr + pad((size_t)5 * K * 8); x.oObs = x.oPt + pad((size_t)3 * P * 8);
+        x.oInfo = x.oObs + pad((size_t)3 * E * 4); x.oEp = x.oInfo + pad((size_t)E * 4); x.oEk = x.oEp + pad((size_t)E * 4); x.oPs = x.oEk + pad((size_t)E * 4);
+        x.oKs = x.oPs + pad(((size_t)P + 1) * 4); x.oFx = x.oKs + pad(((size_t)K + 1) * 4);
+        inBytes = x.oFx + pad((size_t)K);
+        x.out = outBytes;
+        x.dFlag = x.out; x.dChi = x.dFlag + pad((size_t)E); x.dPose = x.dChi + pad((size_t)E * 8); x.dPt = x.dPose + pad((size_t)K * sizeof(DPose));
+        outBytes = x.dPt + pad((size_t)3 * P * 8);
+    }
+    ORBX_HIP_CHECK(hipSetDevice(h->device));
+    {
+        const size_t need = std::max(inBytes, outBytes);
+        if (need > h->hostIOBytes) {
+            ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if (h->hostIO) (void)hipHostFree(h->hostIO);
+            h->hostIO = nullptr; h->hostIOBytes = 0;
+            ORBX_HIP_CHECK(hipHostMalloc((void **)&h->hostIO, need, hipHostMallocDefault));
+            h->hostIOBytes = need;
+        }
+    }
+    uint8_t *io = h->hostIO;
+    for (int w = 0; w < N; w++) {      // float boundary -> double state, row lengths of the adjacency lists, edge ids checked (lba_run's marshalling)
+        BatchWinHost &x = wh[w];
+        const int bad = lba_marshal(probs + w, io, x.oPose, x.oIntr, x.oPt, x.oObs, x.oInfo, x.oEp, x.oEk, x.oPs, x.oKs, x.oFx, x.nPose0, x.nPt0, x.spSplit);
+        if (bad >= 0) { orbx_set_error("window %d: edge %d references a vertex out of range", w, bad); return ORBX_ERR_ARG; }
+    }
+    // ---- from here on nothing fails for a reason of the input
+    for (int w = 0; w < N; w++) for (int i = 0; i < 8; i++) res[w].stats[i] = 0;
+    h->flops = 0; h->launches = 0;
+    const int mw = h->maxW;
+    size_t nnStride = 1, cntStride = 1;
+    int maxK0 = 1, maxP0 = 1, maxE0 = 1, maxChunk = 1;
+    for (int w = 0; w < N; w++) {
+        const BatchWinHost &x = wh[w];
+        nnStride = std::max(nnStride, (size_t)(6 * x.nPose0) * (size_t)(6 * x.nPose0));      // stage 2 has at most the free keyframes of stage 1
+        cntStride = std::max(cntStride, (size_t)x.nChunk * (size_t)x.K);
+        maxK0 = std::max(maxK0, x.K); maxP0 = std::max(maxP0, x.P); maxE0 = std::max(maxE0, x.E); maxChunk = std::max(maxChunk, x.nChunk);
+    }
+    {
+        int rc = h->S.ensure((size_t)N * nnStride);
+        rc = rc ? rc : h->Lmat.ensure((size_t)N * nnStride);
+        rc = rc ? rc : h->Sacc.ensure((size_t)N * nnStride);
+        rc = rc ? rc : h->csrCnt.ensure((size_t)N * cntStride);
+        rc = rc ? rc : h->inArena.ensure(inBytes);
+        rc = rc ? rc : h->outArena.ensure(outBytes);
+        if (rc) return rc;
+    }
+    // ---- descriptors
+    LbaWin *hD1 = (LbaWin *)h->hostDesc, *hD2 = hD1 + mw;
+    UnpackSegs *hSeg = (UnpackSegs *)(hD2 + mw);
+    int *hL1 = (int *)(hSeg + mw), *hL2 = hL1 + RT_N * mw;
+    LbaWin *dD1 = (LbaWin *)h->descDev.p, *dD2 = dD1 + mw;
+    UnpackSegs *dSeg = (UnpackSegs *)(dD2 + mw);
+    int *dL1 = (int *)(dSeg + mw), *dL2 = dL1 + RT_N * mw;
+    std::vector<LbaWin> hw1(N), hw2(N);
+    const float thMono = (float)sqrt(5.991), thStereo = (float)sqrt(7.815);
+    Huber hub;
+    hub.dMono = thMono; hub.dStereo = thStereo;
+    hub.dsqrMono = (double)(float)((double)thMono * (double)thMono);
+    hub.dsqrStereo = (double)(float)((double)thStereo * (double)thStereo);
+    const size_t K = (size_t)h->maxK, P = (size_t)h->maxP, E = (size_t)h->maxE, n6 = 6 * K;
+    uint8_t *oa = h->outArena.p;
+    for (int w = 0; w < N; w++) {
+        const BatchWinHost &x = wh[w];
+        const size_t W = (size_t)w;
+        LbaWin v;
+        memset(&v, 0, sizeof v);
+        LbaDev &d = v.d;
+        d.K = x.K; d.P = x.P; d.E = x.E;
+        d.pose = h->pose.p + W * K; d.pt = h->pt.p + W * 3 * P; d.intr = h->intr.p + W * 5 * K; d.ep = h->ep.p + W * E; d.ek = h->ek.p + W * E;
+        d.obs = h->obs.p + W * 3 * E; d.stereo = h->stereo.p + W * E; d.info = h->info.p + W * E; d.active = h->active.p + W * E;
+        d.poseIdx = h->poseIdx.p + W * K; d.ptIdx = h->ptIdx.p + W * P; d.err = h->err.p + W * 3 * E; d.rchi = h->rchi.p + W * E; d.edgeBlk = h->edgeBlk.p + W * 36 * E;
+        v.hub = hub; v.robust = 1;
+        v.spSplit = x.spSplit; v.nChunk = x.nChunk; v.iters = 5; v.stamp = 1;
+        v.ptStart = h->ptStart.p + W * (P + 1); v.ptEdges = h->ptEdges.p + W * E; v.kfStart = h->kfStart.p + W * (K + 1); v.kfEdges = h->kfEdges.p + W * E;
+        v.kfRowS0 = h->kfRowS0.p + W * E; v.kfRowN = h->kfRowN.p + W * E; v.ptPi = h->ptPi.p + W * E; v.csrCnt = h->csrCnt.p + W * cntStride;
+        v.ptTmp = h->ptTmp.p + W * E; v.fillP = h->fillP.p + W * P; v.pActF = h->pActF.p + W * K; v.lActF = h->lActF.p + W * P; v.okFlag = h->okFlag.p + W * 16;
+        v.poseIdx = h->poseIdx.p + W * K; v.ptIdx = h->ptIdx.p + W * P;
+        v.fixed = h->fixedDev.p + W * K; v.active = h->active.p + W * E; v.flag = oa + x.dFlag; v.stageFlags = nullptr;
+        v.Hll = h->Hll.p + W * 9 * P; v.bl = h->bl.p + W * 3 * P; v.Hpp = h->Hpp.p + W * 36 * K; v.bp = h->bp.p + W * n6; v.spPart = h->spPart.p + W * K * SP_SPLIT * 27;
+        v.Dinv = h->Dinv.p + W * 9 * P; v.Ddb = h->Ddb.p + W * 3 * P; v.S = h->S.p + W * nnStride; v.L = h->Lmat.p + W * nnStride;
+        v.ywork = h->ywork.p + W * n6; v.ysol = h->ysol.p + W * n6; v.diagInv = h->diagInv.p + W * (n6 + CNB); v.xp = h->xp.p + W * n6; v.xl = h->xl.p + W * 3 * P;
+        v.ptBak = h->ptBak.p + W * 3 * P; v.partChi = h->partChi.p + W * ((E + 255) / 256); v.partL = h->partL.p + W * ((std::max(K, 16 * P) + 255) / 256);
+        v.bsPart = h->bsPart.p + W * K * 32 * 6; v.red = h->red.p + W * 16; v.poseBak = h->poseBak.p + W * K;
+        v.Sacc = h->Sacc.p + W * nnStride; v.scaleBits = h->scaleBits.p + W * 8; v.st = h->lm.p + W;
+        v.host = h->recDev + 16 * W; v.stop = (const volatile int *)(h->stopWDev + 16 * W);
+        v.chiOut = res[w].edge_chi2 ? (double *)(oa + x.dChi) : nullptr; v.poseOut = (DPose *)(oa + x.dPose); v.ptOut = (double *)(oa + x.dPt);
+        // stage 1: no flags, the vertex counts are the host's
+        const volatile uint8_t *sf = stops ? stops[w] : nullptr;
+        wh[w].stage1 = !(sf && *sf);
+        v.prep = wh[w].stage1 ? 1 : 0;
+        v.nPose = x.nPose0; v.nPt = x.nPt0; v.nP6 = 6 * x.nPose0;
+        wh[w].run1 = wh[w].stage1 && x.nPose0 + x.nPt0 > 0;
+        v.run = wh[w].run1 ? 1 : 0;
+        v.bsDev = v.nP6 >= CHOL_MULTI_MIN_N ? v.ywork : h->bs.p + W * n6;
+        {
+            v.ySplit = lba_schur_ysplit(v.nP6, x.K, h->numCU);
+        }
+        hw1[w] = v;
+        // segments of k_unpack (lba_run's list)
+        UnpackSegs &sg = hSeg[w];
+        int ns = 0;
+        auto seg = [&](size_t off, void *dst, size_t bytes, int kind = 0) { sg.src[ns] = off; sg.dst[ns] = dst; sg.bytes[ns] = bytes; sg.kind[ns] = kind; ns++; };
+        seg(x.oPose, d.pose, (size_t)x.K * sizeof(DPose)); seg(x.oPt, d.pt, (size_t)3 * x.P * 8); seg(x.oIntr, (void *)d.intr, (size_t)5 * x.K * 8);
+        seg(x.oObs, (void *)d.obs, (size_t)3 * x.E, 1); seg(x.oInfo, (void *)d.info, (size_t)x.E, 1); seg(x.oObs, (void *)d.stereo, (size_t)x.E, 2);
+        seg(x.oEp, (void *)d.ep, (size_t)x.E * 4); seg(x.oEk, (void *)d.ek, (size_t)x.E * 4);
+        seg(x.oPs, v.ptStart, ((size_t)x.P + 1) * 4); seg(x.oKs, v.kfStart, ((size_t)x.K + 1) * 4); seg(x.oFx, v.fixed, (size_t)x.K);
+        seg(~(size_t)0, d.err, (size_t)x.E * 3 * 8);
+        seg(~(size_t)0, v.fillP, (size_t)x.P * 4); seg(~(size_t)0, v.pActF, (size_t)x.K * 4); seg(~(size_t)0, v.lActF, (size_t)x.P * 4);
+        sg.n = ns;
+    }
+    // route lists of a stage: windows whose LM runs, by the route of their n
+    auto buildLists = [&](const std::vector<LbaWin> &hw, int *hl, int (&cnt)[RT_N]) {
+        for (int r = 0; r < RT_N; r++) cnt[r] = 0;
+        for (int w = 0; w < N; w++) {
+            if (!hw[w].run || hw[w].nP6 == 0) continue;
+            const int r = lba_chol_route(hw[w].nP6);
+            hl[r * mw + cnt[r]++] = w;
+            if (r != RT_SOLVE) hl[RT_MULTI * mw + cnt[RT_MULTI]++] = w;
+        }
+    };
+    int cnt1[RT_N], cnt2[RT_N];
+    buildLists(hw1, hL1, cnt1);
+    for (int w = 0; w < N; w++) hD1[w] = hw1[w];
+    hipStream_t s = h->stream;
+    ORBX_HIP_CHECK(hipEventRecord(h->ev0, s));
+    ORBX_HIP_CHECK(hipMemcpyAsync(h->inArena.p, io, inBytes, hipMemcpyHostToDevice, s));
+    ORBX_HIP_CHECK(hipMemcpyAsync(h->descDev.p, h->hostDesc, batch_desc_bytes(mw), hipMemcpyHostToDevice, s));
+    const unsigned Nz = (unsigned)N, gE = (unsigned)((maxE0 + 255) / 256);
+    BLAUNCH(k_unpack<true>, dim3(128, 1, Nz), dim3(256), 0, s, (const uint8_t *)h->inArena.p, UnpackSegs{}, (const UnpackSegs *)dSeg);
+    {
+        const size_t csrLds = (size_t)maxK0 * sizeof(int);
+        if (csrLds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_csr_kf_count<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)csrLds));
+        BLAUNCH(k_csr_kf_count<true>, dim3((unsigned)maxChunk, 1, Nz), dim3(256), csrLds, s, nullptr, 0, 0, nullptr, dD1);
+        BLAUNCH(k_csr_kf_scan<true>, dim3((unsigned)maxK0, 1, Nz), dim3(256), 0, s, nullptr, 0, 0, nullptr, dD1);
+        BLAUNCH(k_csr_kf_fill<true>, dim3((unsigned)maxChunk, 1, Nz), dim3(256), 0, s, nullptr, 0, 0, nullptr, nullptr, dD1);
+        BLAUNCH(k_csr_pt_fill<true>, dim3(gE, 1, Nz), dim3(256), 0, s, nullptr, 0, nullptr, nullptr, nullptr, dD1);
+        BLAUNCH(k_csr_pt_rank<true>, dim3(gE, 1, Nz), dim3(256), 0, s, nullptr, 0, nullptr, nullptr, nullptr, dD1);
+        BLAUNCH(k_csr_rows<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dD1);
+        LCHECK();
+    }
+    std::vector<double> st1(4 * (size_t)N, 0.0), st2(4 * (size_t)N, 0.0);
+    // ---- stage 1 (:863-864): initializeOptimization, then 5 robust iterations
+    bool any1 = false;
+    for (int w = 0; w < N; w++) any1 = any1 || wh[w].stage1;
+    if (any1) {
+        BLAUNCH(k_stage_mark<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dD1);
+        BLAUNCH(k_stage_index<true>, dim3(1, 1, Nz), dim3(1024), 0, s, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, (h->seq += 1.0), dD1);
+        BLAUNCH(k_stage_pairs<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dD1);
+        LCHECK();
+        ORBX_HIP_CHECK(hipMemsetAsync(h->Sacc.p, 0, (size_t)N * nnStride * sizeof(unsigned long long), s));
+        int rc = batch_stage(h, N, dD1, hw1, dL1, cnt1, maxP0, maxK0, maxE0, stops, st1.data());
+        if (rc) return rc;
+    }
+    // ---- stage 2 (:880-917): outliers classified on the device, 10 iterations without kernels on the inliers
+    bool any2 = false;
+    for (int w = 0; w < N; w++) {
+        const volatile uint8_t *sf = stops ? stops[w] : nullptr;
+        wh[w].stage2 = wh[w].stage1 && !(sf && *sf);
+        any2 = any2 || wh[w].stage2;
+        LbaWin v = hw1[w];
+        v.prep = wh[w].stage2 ? 1 : 0; v.run = 0;
+        v.stageFlags = v.flag; v.stamp = 2; v.robust = 0; v.iters = 10;
+        hw2[w] = v;
+        hD2[w] = v;
+    }
+    if (any2) {
+        ORBX_HIP_CHECK(hipMemcpyAsync(dD2, hD2, (size_t)N * sizeof(LbaWin), hipMemcpyHostToDevice, s));
+        BLAUNCH(k_classify<true>, dim3((unsigned)((std::max(maxE0, std::max(maxK0, 3 * maxP0)) + 255) / 256), 1, Nz), dim3(256), 0, s, D0, nullptr, nullptr, nullptr, nullptr, dD2, 0);
+        BLAUNCH(k_stage_mark<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dD2);
+        const double seq = (h->seq += 1.0);
+        BLAUNCH(k_stage_index<true>, dim3(1, 1, Nz), dim3(1024), 0, s, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, seq, dD2);
+        BLAUNCH(k_stage_pairs<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dD2);
+        LCHECK();
+        std::vector<int> in2;
+        for (int w = 0; w < N; w++) if (wh[w].stage2) in2.push_back(w);
+        int rc = batch_wait(h, in2, seq, stops);      // the stage's vertex counts, once for the whole batch
+        if (rc) return rc;
+        for (int w : in2) {
+            const double *r = h->rec + 16 * (size_t)w;
+            const int nPose = (int)r[10], nPt = (int)r[11], nAct = (int)r[12];
+            const volatile uint8_t *sf = stops ? stops[w] : nullptr;
+            LbaWin &v = hw2[w];
+            v.nPose = nPose; v.nPt = nPt; v.nP6 = 6 * nPose;
+            v.run = (nAct > 0 && nPose + nPt > 0 && !(sf && *sf)) ? 1 : 0;
+            v.bsDev = v.nP6 >= CHOL_MULTI_MIN_N ? v.ywork : h->bs.p + (size_t)w * n6;
+            v.ySplit = lba_schur_ysplit(v.nP6, v.d.K, h->numCU);
+            hD2[w] = v;
+        }
+        buildLists(hw2, hL2, cnt2);
+        ORBX_HIP_CHECK(hipMemcpyAsync(dD2, hD2, (size_t)N * sizeof(LbaWin), hipMemcpyHostToDevice, s));
+        ORBX_HIP_CHECK(hipMemcpyAsync(dL2, hL2, (size_t)RT_N * mw * sizeof(int), hipMemcpyHostToDevice, s));
+        ORBX_HIP_CHECK(hipMemsetAsync(h->Sacc.p, 0, (size_t)N * nnStride * sizeof(unsigned long long), s));
+        rc = batch_stage(h, N, dD2, hw2, dL2, cnt2, maxP0, maxK0, maxE0, stops, st2.data());
+        if (rc) return rc;
+    }
+    ORBX_HIP_CHECK(hipEventRecord(h->ev1, s));
+    h->timed = true;
+    // :921-958: final classification, chi2 and estimates of every window in one launch, one copy back
+    BLAUNCH(k_classify<true>, dim3((unsigned)((std::max(maxE0, std::max(maxK0, 3 * maxP0)) + 255) / 256), 1, Nz), dim3(256), 0, s, D0, nullptr, nullptr, nullptr, nullptr, dD1, 1);
+    LCHECK();
+    ORBX_HIP_CHECK(hipMemcpyAsync(io, oa, outBytes, hipMemcpyDeviceToHost, s));
+    ORBX_HIP_CHECK(hipStreamSynchronize(s));
+    for (int w = 0; w < N; w++) {
+        const BatchWinHost &x = wh[w];
+        orbx_lba_result *r = res + w;
+        for (int i = 0; i < 4; i++) { r->stats[i] = st1[4 * w + i]; r->stats[4 + i] = st2[4 * w + i]; }
+        memcpy(r->edge_outlier, io + x.dFlag, (size_t)x.E);
+        if (r->edge_chi2) memcpy(r->edge_chi2, io + x.dChi, (size_t)x.E * 8);
+        const DPose *pose = (const DPose *)(io + x.dPose);
+        const double *pt = (const double *)(io + x.dPt);
+        for (int k = 0; k < x.K; k++) {
+            double R[9];
+            quat_to_R(pose[k].q, R);
+            float *o = r->poses + 16 * (size_t)k;
+            for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) o[4 * i + j] = (float)R[3 * i + j]; o[4 * i + 3] = (float)pose[k].t[i]; }
+            o[12] = o[13] = o[14] = 0.f; o[15] = 1.f;
+        }
+        for (int i = 0; i < 3 * x.P; i++) r->points[i] = (float)pt[i];
+    }
+    return ORBX_OK;
+}
+#undef BLAUNCH
+
+extern "C" int orbx_lba_solve_batch(orbx_lba_batch *h, int num_windows, const orbx_lba_problem *problems, const volatile uint8_t *const *stop_flags, orbx_lba_result *results)
+{
+    return lba_run_batch(h, num_windows, problems, stop_flags, results);
+}
+
+extern "C" int orbx_lba_batch_last_timing(orbx_lba_batch *h, float *device_ms, double *flops)
+{
+    if (!h) { orbx_set_error("NULL handle"); return ORBX_ERR_ARG; }
+    if (!h->timed) { orbx_set_error("no solve yet"); return ORBX_ERR_STATE; }
+    ORBX_HIP_CHECK(hipSetDevice(h->device));
+    ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
+    if (device_ms) ORBX_HIP_CHECK(hipEventElapsedTime(device_ms, h->ev0, h->ev1));
+    if (flops) *flops = h->flops;
+    return ORBX_OK;
+}
+
+// developer tap (tools/lba_batch_rate.py; not part of include/orbx.h): kernel launches of the handle's last batch call
+extern "C" int orbx_debug_lba_batch_launches(orbx_lba_batch *h) { return h ? h->launches : -1; }
