@@ -119,6 +119,8 @@ struct orbx_vocabulary {
     OrbxDevBuf<double> weight[2];
     int cur = 0, lastBatch = 0, lastCap = 0;
     OrbxCallBox box;   // host-array form: descriptors in, word / node / weight out through mapped pinned memory
+    OrbxDevBuf<int32_t> hostWord, hostNode;   // host-array _sorted form: the device copy k_bow_ranks reads - its own, never the device form's word[] / node[] (a
+                                              // host call between two device calls must leave the last batch's results, and the pointers handed out, alone)
 };
 
 extern "C" int orbx_vocabulary_create(int device, int k, int L, int num_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *descriptors,
@@ -172,7 +174,7 @@ extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v)
     if (!v) return;
     (void)hipSetDevice(v->device);
     if (v->stream) { (void)hipStreamSynchronize(v->stream); (void)hipStreamDestroy(v->stream); }
-    v->nodes.release(); v->childList.release(); v->childDesc.release(); v->nodeWeight.release(); v->box.release();
+    v->nodes.release(); v->childList.release(); v->childDesc.release(); v->nodeWeight.release(); v->box.release(); v->hostWord.release(); v->hostNode.release();
     for (int b = 0; b < 2; b++) { v->word[b].release(); v->node[b].release(); v->weight[b].release(); }
     delete v;
 }
@@ -248,12 +250,12 @@ static int bow_transform_host(orbx_vocabulary *v, const uint8_t *descriptors, in
     if (rc != ORBX_OK) return rc;
     const uint8_t *dDesc = bx.put(descriptors, N * 32);
     const unsigned long long seq = bx.arm();
-    if (sorted && ((rc = v->word[0].ensure(N)) || (rc = v->node[0].ensure(N)))) return rc;
+    if (sorted && ((rc = v->hostWord.ensure(N)) || (rc = v->hostNode.ensure(N)))) return rc;
     hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((n + 255) / 256), 1u), dim3(256), 0, v->stream, v->nodes.p, v->childList.p, v->childDesc.p, v->nodeWeight.p, v->L - levelsup,
-                       dDesc, (const int32_t *)nullptr, n, bx.outDev<int32_t>(0), bx.outDev<int32_t>(offNode), bx.outDev<double>(offW), sorted ? v->word[0].p : (int32_t *)nullptr,
-                       sorted ? v->node[0].p : (int32_t *)nullptr, bx.counter, sorted ? (unsigned long long *)nullptr : bx.flagDev, seq);
+                       dDesc, (const int32_t *)nullptr, n, bx.outDev<int32_t>(0), bx.outDev<int32_t>(offNode), bx.outDev<double>(offW), sorted ? v->hostWord.p : (int32_t *)nullptr,
+                       sorted ? v->hostNode.p : (int32_t *)nullptr, bx.counter, sorted ? (unsigned long long *)nullptr : bx.flagDev, seq);
     if (sorted)
-        hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, v->stream, (const int32_t *)v->word[0].p, (const int32_t *)v->node[0].p, n, bx.outDev<int32_t>(offBW),
+        hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, v->stream, (const int32_t *)v->hostWord.p, (const int32_t *)v->hostNode.p, n, bx.outDev<int32_t>(offBW),
                            bx.outDev<int32_t>(offBN), bx.outDev<int32_t>(offF), bx.counter, bx.flagDev, seq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
