@@ -344,6 +344,15 @@ int build_geometry(orbx_extractor *h, int W, int H)
         lv.bandH = std::min(32, (int)((48 * 1024) / lv.bandPitch - 6) & ~7);
         lv.bandOff = 0;
         if (lv.bandH < 8) { g.pyrBand = 0; break; }
+        // the kernel's three item loops divide by these with orbx_band_div's multiply-shift, exact below ORBX_BAND_MAX_ITEMS items: staging =
+        // (bandH + 6) rows x nc chunks, blur = bandH / 8 row groups x G4 column groups, resize (below) = 8-row chunks x the next level's groups
+        const int nc = (lv.w + 15) >> 4, G4 = (lv.w + 3) >> 2;
+        lv.bandDivNc = orbx_band_div(nc);
+        lv.bandDivG4 = orbx_band_div(G4);
+        if ((lv.bandH + 6) * nc > ORBX_BAND_MAX_ITEMS || (lv.bandH >> 3) * G4 > ORBX_BAND_MAX_ITEMS) {
+            orbx_set_error("level %d (%dx%d): a pyramid band of %d rows has more than %d work items", l, lv.w, lv.h, lv.bandH, ORBX_BAND_MAX_ITEMS);
+            return ORBX_ERR_ARG;
+        }
         if (l + 1 == nl) break;
         const OrbxLevel &ln = g.lv[l + 1];
         const int nb = (lv.h + lv.bandH - 1) / lv.bandH;
@@ -358,9 +367,16 @@ int build_geometry(orbx_extractor *h, int W, int H)
                 if (y0 >= s1 && b + 1 < nb) break;
                 if (std::min(y0, y1) < s0 - 3 || std::max(y0, y1) > s1 + 2) g.pyrBand = 0;
             }
+            if (((ln.w + 3) >> 2) * ((dy - (int)h->rsHost[(size_t)lv.bandOff + b] + 7) >> 3) > ORBX_BAND_MAX_ITEMS) {
+                orbx_set_error("level %d (%dx%d): a pyramid band resizes more than %d work items of level %d", l, lv.w, lv.h, ORBX_BAND_MAX_ITEMS, l + 1);
+                return ORBX_ERR_ARG;
+            }
         }
         h->rsHost.push_back((uint32_t)ln.h);
     }
+    // k_pyr_band requests the eight row-table entries of a chunk unclamped: the last chunk of a level reads up to seven entries (14 words) behind its
+    // table and uses none of them - whatever table ends the array, they lie inside it
+    h->rsHost.insert(h->rsHost.end(), 16, 0u);
     // LDS carve-up of k_fast_cells (one wave per cell): row pitch 16*segments+16 bytes for both tiles
     if (maxWCell > 64 || maxHCell > 63) { orbx_set_error("cell %dx%d larger than the detector supports", maxWCell, maxHCell); return ORBX_ERR_ARG; }
     // window rows: the widest window (aw + 6 rounded up to 16) and the widest pre-test read (16 * segments + 8); score rows: aw + 6

@@ -37,6 +37,7 @@ struct OrbxLevel {
     int blurTileBase, blurTilesX, blurTilesY;
     int bandH, bandPitch;   /* k_pyr_band (batches): rows of this level per band (multiple of 8), LDS row pitch of a staged band row */
     int bandOff;            /* u32 offset in the resize tables of the bands' first rows of level l+1 (nBands + 1 entries; levels < nlevels-1) */
+    uint32_t bandDivNc, bandDivG4; /* k_pyr_band: orbx_band_div() of the level's 16-byte chunks per row, (w + 15) / 16, and of its 4-pixel column groups, (w + 3) / 4 */
     double rsScaleX, rsScaleY; /* cv::resize inverse scale from level l-1: 1.0 / ((double)w / w_prev)  */
     int rsColOff, rsRowOff; /* u32 offsets of this level's cv::resize tables (levels >= 1), see build_resize_tables */
     int patchSize;          /* (int)(PATCH_SIZE*scale), src/ORBextractor.cc:1175          */
@@ -56,6 +57,20 @@ struct OrbxGeom {
     int umax[16];
     OrbxLevel lv[ORBX_MAX_LEVELS];
 };
+
+/* Division of k_pyr_band's item indices by a per-level constant n (chunks or column groups per row) without a division in the kernel:
+ *   item / n == (item * m) >> S   with S = 14 + ceil(log2 n), m = ceil(2^S / n), packed as m | S << 20.
+ * Exact for every item < ORBX_BAND_MAX_ITEMS = 2^14 and every n in 1 .. 2^14: with e = m * n - 2^S (0 <= e < n) the quotient is exact while
+ * item * e < 2^S, and item * e < 2^14 * n <= 2^S; the product item * m <= (2^14 - 1) * (2^14 + 1) stays below 2^32 and m <= 2^14 + 1 below 2^20.
+ * build_geometry refuses a geometry whose bands would form more items (tests/test_pyr_band_plan.py checks every item of every level). */
+#define ORBX_BAND_MAX_ITEMS (1 << 14)
+static inline uint32_t orbx_band_div(int n)
+{
+    uint32_t S = 14;
+    while ((1u << (S - 14)) < (uint32_t)n) S++;
+    const uint32_t m = (uint32_t)((((uint64_t)1 << S) + (uint64_t)n - 1) / (uint64_t)n);
+    return m | (S << 20);
+}
 
 /* Everything k_fast_cells needs to know about one 30-px cell (src/ORBextractor.cc:1089-1123), built with the geometry: one 32-byte scalar load per
  * cell instead of a chain of dependent loads through OrbxGeom and three integer divisions. */

@@ -1264,6 +1264,46 @@ __global__ __launch_bounds__(64) void k_blur(const OrbxGeom *__restrict__ g, con
 #define PB_THREADS 256    /* (measured: 512 threads with 64-row bands, 1 % below the split launches in the headline; 256 x 32 rows, 3 % above) */
 #define PB_ORG 16          /* LDS byte of pixel 0 of a band row (pixels -3 .. -1 in front of it) */
 #define PB_STAGE 4         /* 16-byte staging loads per thread in flight */
+// item / n of the three item loops with the host's constant (orbx_band_div: exact for item < ORBX_BAND_MAX_ITEMS): one 24-bit multiply and a shift by a
+// scalar where the runtime division cost every item a dozen instructions (v_rcp_iflag_f32 hoisted, v_mul_hi_u32 + v_mul_lo_u32 + the quotient's fix-up not)
+__device__ __forceinline__ int pb_div(int item, uint32_t dv) { return (int)(__umul24((uint32_t)item, dv & 0xfffffu) >> (dv >> 20)); }
+// bits 32 .. 47 of the product of two values below 2^24: v_mul_hi_u32_u24 where the compiler sees the callers' masks, v_mul_hi_u32 where it does not
+// (behind the row-reuse copies of the resize loop) - the same result and the same measured issue cost (profiles/pyr_band_valu_issue.txt)
+__device__ __forceinline__ uint32_t pb_mulhi24(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+// staging of a band's rows; EDGE = some of them lie above or below the level and are mirrored (first and last band of a level: uniform in the workgroup)
+template <bool EDGE>
+__device__ __forceinline__ void pb_stage(uint8_t *__restrict__ bb, const uint8_t *__restrict__ src, const int sp, const int readable, const int w, const int h, const int P,
+                                         const int s0, const int nr, const uint32_t divNc, const int tid)
+{
+    const int nc = (w + 15) >> 4, items = nr * nc;
+    for (int i0 = 0; i0 < items; i0 += PB_THREADS * PB_STAGE) {
+        uint4 v[PB_STAGE];
+        int dOff[PB_STAGE];
+#pragma unroll
+        for (int k = 0; k < PB_STAGE; k++) {
+            const int item = i0 + tid + k * PB_THREADS, it = min(item, items - 1);
+            const int r = pb_div(it, divNc), c = it - (int)__umul24((uint32_t)r, (uint32_t)nc);
+            int y = s0 - 3 + r;
+            if (EDGE) {
+                y = reflect101(y, h);
+                y = min(max(y, 0), h - 1);
+            }
+            const uint8_t *row = src + (size_t)y * sp;
+            const int x = 16 * c;
+            if (x + 16 <= readable) __builtin_memcpy(&v[k], row + x, 16);
+            else {      // the tail of an unpadded caller row: bytes up to the last pixel (what lies behind it is never weighted)
+                uint32_t t[4] = {0u, 0u, 0u, 0u};
+                for (int j = 0; x + j < w; j++) t[j >> 2] |= (uint32_t)row[x + j] << (8 * (j & 3));
+                v[k] = make_uint4(t[0], t[1], t[2], t[3]);
+            }
+            dOff[k] = item < items ? (int)__umul24((uint32_t)r, (uint32_t)P) + PB_ORG + x : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < PB_STAGE; k++)
+            if (dOff[k] >= 0) *(uint4 *)(bb + dOff[k]) = v[k];
+    }
+}
+
 template <bool CLAMP>
 __global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restrict__ g, const int l, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
                                                          const int readable, uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, const uint32_t *__restrict__ rsTab,
@@ -1282,32 +1322,8 @@ __global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restr
     int sp;
     const uint8_t *src = level_ptr(g, l, f, img0, img0Stride, img0FramePitch, pyr, sp);
     // ---- stage: item = (row, 16-byte chunk); rows mirrored (BORDER_REFLECT_101) above and below the level ----
-    {
-        const int nc = (w + 15) >> 4, items = nr * nc;
-        for (int i0 = 0; i0 < items; i0 += PB_THREADS * PB_STAGE) {
-            uint4 v[PB_STAGE];
-            int dOff[PB_STAGE];
-#pragma unroll
-            for (int k = 0; k < PB_STAGE; k++) {
-                const int item = i0 + tid + k * PB_THREADS, it = min(item, items - 1);
-                const int r = it / nc, c = it - r * nc;
-                int y = reflect101(s0 - 3 + r, h);
-                y = min(max(y, 0), h - 1);
-                const uint8_t *row = src + (size_t)y * sp;
-                const int x = 16 * c;
-                if (x + 16 <= readable) __builtin_memcpy(&v[k], row + x, 16);
-                else {      // the tail of an unpadded caller row: bytes up to the last pixel (what lies behind it is never weighted)
-                    uint32_t t[4] = {0u, 0u, 0u, 0u};
-                    for (int j = 0; x + j < w; j++) t[j >> 2] |= (uint32_t)row[x + j] << (8 * (j & 3));
-                    v[k] = make_uint4(t[0], t[1], t[2], t[3]);
-                }
-                dOff[k] = item < items ? r * P + PB_ORG + 16 * c : -1;
-            }
-#pragma unroll
-            for (int k = 0; k < PB_STAGE; k++)
-                if (dOff[k] >= 0) *(uint4 *)(bb + dOff[k]) = v[k];
-        }
-    }
+    if (s0 >= 3 && s0 - 3 + nr <= h) pb_stage<false>(bb, src, sp, readable, w, h, P, s0, nr, lv.bandDivNc, tid);
+    else pb_stage<true>(bb, src, sp, readable, w, h, P, s0, nr, lv.bandDivNc, tid);
     __syncthreads();
     // BORDER_REFLECT_101 in x (blur_body's order): x = -1, -2, -3 <- 1, 2, 3 and x = w, w + 1, w + 2 <- w - 2, w - 3, w - 4
     for (int r = tid; r < nr; r += PB_THREADS) {
@@ -1320,16 +1336,23 @@ __global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restr
     // ---- blur of rows s0 .. s1-1: thread item = 4 columns x 8 rows ----
     {
         const int G4 = (w + 3) >> 2, items = G4 * ((s1 - s0 + 7) >> 3), PW = P >> 2;
-        uint8_t *dst = blur + (size_t)f * g->pyrBytes + lv.off;
+        const uint32_t pitch = (uint32_t)lv.pitch;
+        const bool full = ((s1 - s0) & 7) == 0;      // (uniform: only the last band of a level ends inside an 8-row group)
+        uint8_t *dst = blur + (size_t)f * g->pyrBytes + lv.off;      // uniform base + 32-bit byte offsets (a level is far smaller than 4 GB)
         for (int item = tid; item < items; item += PB_THREADS) {
-            const int rgi = item / G4, gx = item - rgi * G4;
+            const int rgi = pb_div(item, lv.bandDivG4), gx = item - (int)__umul24((uint32_t)rgi, (uint32_t)G4);
             uint32_t outw[8];
-            blur_rows8<CLAMP>(g, band + 8 * rgi * PW + gx + PB_ORG / 4 - 1, PW, outw);      // word of pixels 4gx - 4 .. 4gx - 1
+            blur_rows8<CLAMP>(g, band + (int)__umul24((uint32_t)(8 * rgi), (uint32_t)PW) + gx + PB_ORG / 4 - 1, PW, outw);      // word of pixels 4gx - 4 .. 4gx - 1
+            uint32_t o = (uint32_t)(s0 + 8 * rgi) * pitch + 4u * (uint32_t)gx;
+            if (full) {
 #pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const int y = s0 + 8 * rgi + q;
-                if (y >= s1) break;
-                *(uint32_t *)(dst + (size_t)y * lv.pitch + 4 * gx) = outw[q];
+                for (int q = 0; q < 8; q++, o += pitch) *(uint32_t *)(dst + o) = outw[q];
+            } else {
+#pragma unroll
+                for (int q = 0; q < 8; q++, o += pitch) {
+                    if (s0 + 8 * rgi + q >= s1) break;
+                    *(uint32_t *)(dst + o) = outw[q];
+                }
             }
         }
     }
@@ -1338,46 +1361,51 @@ __global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restr
     const OrbxLevel &ln = g->lv[l + 1];
     const int d0 = (int)rsTab[lv.bandOff + b], d1 = (int)rsTab[lv.bandOff + b + 1];
     const int Gd = (ln.w + 3) >> 2, items = Gd * ((d1 - d0 + 7) >> 3);
+    const uint32_t dpitch = (uint32_t)ln.pitch;
     const uint2 *rt = (const uint2 *)(rsTab + ln.rsRowOff);
+    const uint32_t *ctab = rsTab + ln.rsColOff;
     uint8_t *dstBase = pyr + (size_t)f * g->pyrBytes + ln.off;
     const uint8_t *lrow0 = bb + PB_ORG - (s0 - 3) * P;       // LDS byte of pixel 0 of image row y: lrow0 + y * P
     for (int item = tid; item < items; item += PB_THREADS) {
-        const int ch = item / Gd, cg = item - ch * Gd;
-        const uint32_t *ct = rsTab + ln.rsColOff + 12 * cg;
+        const int ch = pb_div(item, ln.bandDivG4), cg = item - (int)__umul24((uint32_t)ch, (uint32_t)Gd);
+        const uint32_t *ct = ctab + 12u * (uint32_t)cg;
         const uint4 c0 = *(const uint4 *)ct, c1 = *(const uint4 *)(ct + 4), c2 = *(const uint4 *)(ct + 8);
         const int sx0 = (int)c0.x, sxa = sx0 & ~3;
         const uint32_t mis = (uint32_t)(sx0 & 3);
         const bool wide = (int)c0.y <= 7;      // (LDS rows are readable 12 bytes past every group window)
         const uint32_t sel[4] = {c0.z, c0.w, c1.x, c1.y}, coef[4] = {c1.z, c1.w, c2.x, c2.y};
-        // horizontal pass of source row y, >> 4: k_resize's r0 / r1 before the blend
+        // horizontal pass of source row y: k_resize's r0 / r1 before the blend, (dot >> 4) << 4.  The dot product of two 8-bit pixels with 11-bit
+        // coefficients that add up to 2048 (+-1) is below 2^20, so the mask keeps every bit above the four that k_resize shifts out
         auto hpass = [&](int y, uint32_t hv[4]) {
-            const uint8_t *row = lrow0 + (size_t)y * P;
+            const uint8_t *row = lrow0 + (int)__umul24((uint32_t)y, (uint32_t)P);
             if (wide) {
                 const uint32_t *p = (const uint32_t *)(row + sxa);
                 const uint32_t a0 = p[0], a1 = p[1], a2 = p[2];
                 const uint32_t v0 = __builtin_amdgcn_alignbyte(a1, a0, mis), v1 = __builtin_amdgcn_alignbyte(a2, a1, mis);
 #pragma unroll
-                for (int k = 0; k < 4; k++) hv[k] = udot2(__builtin_amdgcn_perm(v1, v0, sel[k]), coef[k], 0u) >> 4;
+                for (int k = 0; k < 4; k++) hv[k] = udot2(__builtin_amdgcn_perm(v1, v0, sel[k]), coef[k], 0u) & 0x00fffff0u;
             } else {
                 const uint8_t *S = row + sx0;
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int off = (int)((c2.z >> (8 * k)) & 0xffu), off1 = (int)((c2.w >> (8 * k)) & 0xffu);
-                    hv[k] = udot2((uint32_t)S[off] | ((uint32_t)S[off1] << 16), coef[k], 0u) >> 4;
+                    hv[k] = udot2((uint32_t)S[off] | ((uint32_t)S[off1] << 16), coef[k], 0u) & 0x00fffff0u;
                 }
             }
         };
         uint32_t ha[4], hb[4];      // horizontal passes of source rows ra, rb (consecutive output rows share a row: computed once)
         int ra = -1, rb = -1;
-        // the chunk's row-table entries requested together (one memory round trip, not one per output row)
+        // the chunk's row-table entries requested together (one memory round trip, not one per output row) and unclamped: one address, eight
+        // offsets; the entries behind row d1 - 1 are not used (the host pads the tables' array for the last chunk of the last level)
         const int dA = d0 + 8 * ch, nrow = min(8, d1 - dA);
+        const uint2 *rtc = rt + (uint32_t)dA;
         uint2 tr[8];
 #pragma unroll
-        for (int r = 0; r < 8; r++) tr[r] = rt[dA + min(r, nrow - 1)];
+        for (int r = 0; r < 8; r++) tr[r] = rtc[r];
+        uint32_t o = (uint32_t)dA * dpitch + 4u * (uint32_t)cg;
 #pragma unroll
-        for (int r = 0; r < 8; r++) {
+        for (int r = 0; r < 8; r++, o += dpitch) {
             if (r >= nrow) break;
-            const int dy = dA + r;
             const uint2 t = tr[r];
             const int y0 = (int)(t.x & 0xffffu), y1 = (int)(t.x >> 16);
             if (y0 != ra) {
@@ -1394,11 +1422,15 @@ __global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restr
                 } else hpass(y1, hb);
                 rb = y1;
             }
-            const uint32_t b0 = t.y & 0xffffu, b1 = t.y >> 16;
+            // k_resize's truncating blend ((b0 * h0) >> 16) + ((b1 * h1) >> 16) with ONE multiply per term: the row weights (0 .. 2048) shifted
+            // left by 12 (< 2^24) times the horizontal value still shifted left by 4 (< 2^24) is b * h * 2^16, and the high multiply returns bits
+            // 32 .. 47 of that 48-bit product = (b * h) >> 16 exactly (tests/test_pyr_band_plan.py runs every pair); it issues at the cost of
+            // v_mul_lo_u32 (tools/ubench_valu.hip), so the two v_lshrrev_b32 per pixel are simply gone
+            const uint32_t b0 = (t.y << 12) & 0x00fff000u, b1 = (t.y >> 4) & 0x00fff000u;      // (weights are 0 .. 2048: twelve bits)
             uint32_t out = 0;
 #pragma unroll
-            for (int k = 0; k < 4; k++) out |= ((((b0 * ha[k]) >> 16) + ((b1 * hb[k]) >> 16) + 2u) >> 2) << (8 * k);      // (<= 255, see k_resize)
-            *(uint32_t *)(dstBase + (size_t)dy * ln.pitch + 4 * cg) = out;
+            for (int k = 0; k < 4; k++) out |= ((pb_mulhi24(b0, ha[k]) + pb_mulhi24(b1, hb[k]) + 2u) >> 2) << (8 * k);      // (<= 255, see k_resize)
+            *(uint32_t *)(dstBase + o) = out;
         }
     }
 }

@@ -21,7 +21,7 @@ __device__ __forceinline__ unsigned udot2(unsigned a, unsigned b, unsigned c) { 
 enum { OP_BCNT = 0, OP_XOR, OP_ADD, OP_MIN3, OP_PKMIN, OP_PERM, OP_ALIGN, OP_DOT4, OP_DOT2, OP_SAD, OP_LSHLOR, OP_MAD24, OP_FADD, OP_FFMA, OP_PKFMA,
        OP_AND, OP_LSHL, OP_MIN, OP_MED3, OP_BFE, OP_ADD3, OP_LSHLADD, OP_ANDOR, OP_PKSUB, OP_PKMAX, OP_MULLO, OP_SUB,
        OP_FMIN, OP_FMAX, OP_PKMINH, OP_PKMAXH, OP_PKADDU16, OP_PKADDH, OP_OR, OP_MOV, OP_LSHR, OP_MAXU, OP_MINH, OP_MINU16, OP_NOT, OP_CVTUB, OP_FMUL, OP_PKFMAH, OP_MAX3F, OP_ALIGNBIT,
-       OP_MIN3U16, OP_MAX3U16, OP_MED3U16, OP_MAXU16, OP_MAXI16, OP_SUBU16, OP_ADDU16, OP_MADU16, OP_LSHLB16, OP_CNDMASK, OP_ADDC, OP_BFI, OP_MINI32, OP_MINU16SDWA, OP_ADDSDWA, OP_MULU16, OP_MIN3F16, OP_CMPCND, OP_COUNT };
+       OP_MIN3U16, OP_MAX3U16, OP_MED3U16, OP_MAXU16, OP_MAXI16, OP_SUBU16, OP_ADDU16, OP_MADU16, OP_LSHLB16, OP_CNDMASK, OP_ADDC, OP_BFI, OP_MINI32, OP_MINU16SDWA, OP_ADDSDWA, OP_MULU16, OP_MIN3F16, OP_CMPCND, OP_MULHI24, OP_MUL24, OP_MULHI, OP_COUNT };
 static const char *kNames[OP_COUNT] = {"v_bcnt_u32_b32", "v_xor_b32", "v_add_u32", "v_min3_u32", "v_pk_min_u16", "v_perm_b32", "v_alignbyte_b32", "v_dot4_u32_u8", "v_dot2_u32_u16",
                                        "v_sad_u8", "v_lshl_or_b32", "v_mad_u32_u24", "v_add_f32", "v_fma_f32", "v_pk_fma_f32",
                                        "v_and_b32", "v_lshlrev_b32", "v_min_u32", "v_med3_i32", "v_bfe_u32", "v_add3_u32", "v_lshl_add_u32", "v_and_or_b32", "v_pk_sub_i16", "v_pk_max_i16",
@@ -29,7 +29,8 @@ static const char *kNames[OP_COUNT] = {"v_bcnt_u32_b32", "v_xor_b32", "v_add_u32
                                        "v_min_f32", "v_max_f32", "v_pk_min_f16", "v_pk_max_f16", "v_pk_add_u16", "v_pk_add_f16", "v_or_b32", "v_mov_b32", "v_lshrrev_b32", "v_max_u32",
                                        "v_min_f16", "v_min_u16", "v_not_b32", "v_cvt_f32_ubyte0", "v_mul_f32", "v_pk_fma_f16", "v_max3_f32", "v_alignbit_b32",
                                        "v_min3_u16", "v_max3_u16", "v_med3_u16", "v_max_u16", "v_max_i16", "v_sub_u16", "v_add_u16", "v_mad_u16", "v_lshlrev_b16", "v_cndmask_b32", "v_addc_co_u32",
-                                       "v_bfi_b32", "v_min_i32", "v_min_u16_sdwa(bytes)", "v_add_u32_sdwa(bytes)", "v_mul_lo_u16", "v_min3_f16", "v_cmp_gt_u16+v_cndmask"};
+                                       "v_bfi_b32", "v_min_i32", "v_min_u16_sdwa(bytes)", "v_add_u32_sdwa(bytes)", "v_mul_lo_u16", "v_min3_f16", "v_cmp_gt_u16+v_cndmask",
+                                       "v_mul_hi_u32_u24", "v_mul_u32_u24", "v_mul_hi_u32"};
 
 // every class is ONE named instruction (inline asm: the optimiser neither folds the chains nor picks another opcode)
 #define ASM2(NAME) { unsigned r; asm volatile(NAME " %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -97,6 +98,9 @@ template <int OP> __device__ __forceinline__ unsigned op(unsigned a, unsigned b,
     if (OP == OP_MULU16) ASM2("v_mul_lo_u16")
     if (OP == OP_MIN3F16) ASM3("v_min3_f16")
     if (OP == OP_CMPCND) { unsigned r; asm volatile("v_cmp_gt_u16 vcc, %1, %2\n\tv_cndmask_b32 %0, %1, %2, vcc" : "=v"(r) : "v"(a), "v"(b) : "vcc"); return r; }
+    if (OP == OP_MULHI24) ASM2("v_mul_hi_u32_u24")
+    if (OP == OP_MUL24) ASM2("v_mul_u32_u24")
+    if (OP == OP_MULHI) ASM2("v_mul_hi_u32")
     if (OP == OP_ALIGNBIT) { unsigned r; asm volatile("v_alignbit_b32 %0, %1, %2, 1" : "=v"(r) : "v"(a), "v"(b)); return r; }
     return a;
 }
@@ -194,5 +198,6 @@ int main()
     run<OP_SUBU16>(out, stamps, host); run<OP_ADDU16>(out, stamps, host); run<OP_MADU16>(out, stamps, host); run<OP_LSHLB16>(out, stamps, host); run<OP_CNDMASK>(out, stamps, host);
     run<OP_ADDC>(out, stamps, host); run<OP_BFI>(out, stamps, host); run<OP_MINI32>(out, stamps, host); run<OP_MINU16SDWA>(out, stamps, host); run<OP_ADDSDWA>(out, stamps, host);
     run<OP_MULU16>(out, stamps, host); run<OP_MIN3F16>(out, stamps, host); run<OP_CMPCND>(out, stamps, host);
+    run<OP_MULHI24>(out, stamps, host); run<OP_MUL24>(out, stamps, host); run<OP_MULHI>(out, stamps, host);      // (the resize blend of k_pyr_band: is (b * h) >> 16 as ONE 24-bit high multiply worth it?)
     return 0;
 }
