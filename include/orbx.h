@@ -660,6 +660,67 @@ int orbx_frame_download(orbx_frame_ops *h, orbx_extractor *ext, int batch, orbx_
 int orbx_frame_finish_begin(orbx_frame_ops *h, orbx_extractor *ext, const orbx_frame_grid *grid);
 int orbx_frame_finish_end(orbx_frame_ops *h, const orbx_keypoint **kp_un, const int32_t **grid_offsets, const int32_t **grid_indices, int *n);
 
+/* ------------------------------------------------------------------------------------
+ * The RGB-D Frame constructor  ==  Frame::Frame(imGray, imDepth, ...) (reference src/Frame.cc:238-348): the frame-finish work above plus
+ * Frame::ComputeStereoFromRGBD (:1423-1461), fused into the same launch, and what the tracker derives from mvDepth on every RGB-D frame.
+ * Per feature i of a frame, with (u, v) = mvKeys[i].pt converted float -> int by truncation (imDepth.at<float>(v, u), :1444):
+ *     d = depth(v, u);   d > 0 (false for NaN):  mvDepth[i] = d,  mvuRight[i] = mvKeysUn[i].pt.x - bf / d;   otherwise both -1      (:1451-1458)
+ *     xyz_cam[3i..] = ((uUn - cx) * d) * invfx, ((vUn - cy) * d) * invfy, d  with invfx = 1.0f / fx  (Frame::UnprojectStereo, :1478-1491,
+ *                     before mRwc * x + mOw, which stays with the caller);  0 0 0 where mvDepth[i] <= 0
+ * and per frame
+ *     order[0 .. n_valid)  the features with mvDepth > 0, ascending by (mvDepth, i): the sorted vector<pair<float,int>> of
+ *                          Tracking::UpdateLastFrame / CreateNewKeyFrame (src/Tracking.cc); order[n_valid .. n) = -1
+ *     n_close              features with 0 < mvDepth < th_depth (Tracking::NeedNewKeyFrame)
+ * All of it float32, one correctly rounded operation at a time (no contraction).  A keypoint outside the depth image (the extractor never
+ * produces one) has no depth.
+ * Depth formats: ORBX_DEPTH_F32 = the CV_32F image the constructor takes, used as is (`factor` is ignored);  ORBX_DEPTH_U16 = the raw 16-bit
+ * image Tracking::GrabImageRGBD receives, d = (float)raw * factor with factor = mDepthMapFactor = 1 / DepthMapFactor (src/Tracking.cc:212-216,
+ * 334-338: imDepth.convertTo(CV_32F, mDepthMapFactor)) - only the looked-up pixels are converted.
+ * ---------------------------------------------------------------------------------- */
+#define ORBX_DEPTH_F32 0
+#define ORBX_DEPTH_U16 1
+typedef struct orbx_depth_desc {
+    const void *data;  /* batch form: DEVICE memory, frame f at data + f * stride_bytes * rows;  latency form: HOST memory, one image */
+    int format;        /* ORBX_DEPTH_F32 | ORBX_DEPTH_U16                                                                          */
+    int cols, rows;    /* must equal the size of the frames the extractor ran on                                                    */
+    int stride_bytes;  /* bytes between rows: a multiple of the pixel size, >= cols * pixel size                                    */
+    float factor;      /* ORBX_DEPTH_U16: mDepthMapFactor                                                                            */
+} orbx_depth_desc;
+typedef struct orbx_rgbd_params {
+    float bf;       /* mbf                                                                     */
+    float th_depth; /* mThDepth = mbf * ThDepth / fx (src/Tracking.cc:205)                     */
+} orbx_rgbd_params;
+
+/* Host depth images (one per frame, same size and format) into a handle-owned device area laid out as orbx_depth_desc asks for the batch
+ * form; *depth_dev receives the descriptor to pass on.  Valid until the next orbx_upload_depth on `h`. */
+int orbx_upload_depth(orbx_frame_ops *h, const void *const *images, int batch, int format, int cols, int rows, int stride_bytes, float factor,
+                      orbx_depth_desc *depth_dev);
+/* orbx_frame_finish_device + the RGB-D step for every frame of the extractor's LAST batch, in the same launch on the extractor's stream.
+ * Results stay on the device next to those of orbx_frame_results_device: depth / u_right / order [f*capacity + i], xyz_cam[(f*capacity + i)*3],
+ * n_valid[f], n_close[f]; entries at and behind a frame's keypoint count are undefined. */
+int orbx_frame_rgbd_device(orbx_frame_ops *h, orbx_extractor *ext, const orbx_frame_grid *grid, const orbx_depth_desc *depth_dev,
+                           const orbx_rgbd_params *params);
+int orbx_frame_rgbd_results_device(orbx_frame_ops *h, const float **depth_dev, const float **u_right_dev, const int32_t **order_dev,
+                                   const int32_t **n_valid_dev, const int32_t **n_close_dev, const float **xyz_cam_dev, int *capacity);
+/* Waits for the extractor's stream; any pointer may be NULL.  Arrays as above with `batch` frames; orbx_frame_download brings the rest. */
+int orbx_frame_rgbd_download(orbx_frame_ops *h, orbx_extractor *ext, int batch, float *depth, float *u_right, int32_t *order, int32_t *n_valid,
+                             int32_t *n_close, float *xyz_cam);
+/* Latency form for ONE frame, as orbx_frame_finish_begin / _end (same kernel, same pinned result area, `ext` must not be called in between):
+ * `depth` is the caller's HOST image (pageable: the cv::Mat of the constructor).  _begin looks the n depth values up on the host - the
+ * extractor's keypoints are in its pinned result arena already - and hands the kernel n floats; ORBX_RGBD_STAGE_IMAGE=1 in the environment
+ * copies the whole image to pinned memory and lets the kernel gather instead (same bits; the two are compared in profiles/rgbd_latency.txt).  _end waits and hands
+ * out pointers into the handle's pinned memory, valid until the next call on the handle. */
+typedef struct orbx_rgbd_frame {
+    const float *depth, *u_right; /* mvDepth, mvuRight [n]               */
+    const int32_t *order;         /* [n], see above                      */
+    const float *xyz_cam;         /* [3n]                                */
+    int n_valid, n_close;
+} orbx_rgbd_frame;
+int orbx_frame_rgbd_begin(orbx_frame_ops *h, orbx_extractor *ext, const orbx_frame_grid *grid, const orbx_depth_desc *depth_host,
+                          const orbx_rgbd_params *params);
+int orbx_frame_rgbd_end(orbx_frame_ops *h, const orbx_keypoint **kp_un, const int32_t **grid_offsets, const int32_t **grid_indices, int *n,
+                        orbx_rgbd_frame *rgbd);
+
 
 /* ------------------------------------------------------------------------------------
  * Local bundle adjustment  ==  the numerical core of Optimizer::LocalBundleAdjustment

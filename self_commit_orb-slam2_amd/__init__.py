@@ -949,6 +949,32 @@ class FrameGrid(ctypes.Structure):
                    float(np.float32(FRAME_GRID_ROWS) / np.float32(b[3] - b[2])))
 
 
+DEPTH_F32, DEPTH_U16 = 0, 1
+
+
+class DepthDesc(ctypes.Structure):
+    """orbx_depth_desc: a depth image (latency form, host) or B of them (batch form, device)."""
+    _fields_ = [("data", ctypes.c_void_p), ("format", ctypes.c_int), ("cols", ctypes.c_int), ("rows", ctypes.c_int),
+                ("stride_bytes", ctypes.c_int), ("factor", ctypes.c_float)]
+
+    @classmethod
+    def of(cls, image, factor=1.0):
+        """descriptor of a host image (float32 or uint16, rows may be strided); the caller keeps `image` alive"""
+        assert image.ndim == 2 and image.strides[1] == image.itemsize and image.dtype in (np.float32, np.uint16)
+        return cls(image.ctypes.data, DEPTH_F32 if image.dtype == np.float32 else DEPTH_U16, image.shape[1], image.shape[0], image.strides[0], factor)
+
+
+class RgbdParams(ctypes.Structure):
+    """orbx_rgbd_params: mbf, mThDepth."""
+    _fields_ = [("bf", ctypes.c_float), ("th_depth", ctypes.c_float)]
+
+
+class RgbdFrame(ctypes.Structure):
+    """orbx_rgbd_frame: what orbx_frame_rgbd_end hands out."""
+    _fields_ = [("depth", ctypes.c_void_p), ("u_right", ctypes.c_void_p), ("order", ctypes.c_void_p), ("xyz_cam", ctypes.c_void_p),
+                ("n_valid", ctypes.c_int), ("n_close", ctypes.c_int)]
+
+
 class FrameOps:
     """Frame::UndistortKeyPoints, ComputeImageBounds and AssignFeaturesToGrid on the device
     (reference src/Frame.cc:899-1004, 460-491) for one camera (mK, mDistCoef)."""
@@ -966,6 +992,12 @@ class FrameOps:
         L.orbx_frame_finish_device.argtypes = [vp, vp, vp]
         L.orbx_frame_results_device.argtypes = [vp, vp, vp, vp, vp]
         L.orbx_frame_download.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.orbx_upload_depth.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, vp]
+        L.orbx_frame_rgbd_device.argtypes = [vp, vp, vp, vp, vp]
+        L.orbx_frame_rgbd_results_device.argtypes = [vp] * 7 + [vp]
+        L.orbx_frame_rgbd_download.argtypes = [vp, vp, ci] + [vp] * 6
+        L.orbx_frame_rgbd_begin.argtypes = [vp, vp, vp, vp, vp]
+        L.orbx_frame_rgbd_end.argtypes = [vp, vp, vp, vp, vp, vp]
         cam = Camera(fx, fy, cx, cy)
         dist = [float(d) for d in dist]
         for i, d in enumerate(dist[:5]):
@@ -1025,6 +1057,54 @@ class FrameOps:
         o = np.ctypeslib.as_array(ctypes.cast(off, ctypes.POINTER(ctypes.c_int32)), shape=(FRAME_GRID_COLS * FRAME_GRID_ROWS + 1,)).copy() if off.value else None
         i = np.ctypeslib.as_array(ctypes.cast(idx, ctypes.POINTER(ctypes.c_int32)), shape=(max(n, 1),))[:int(o[-1])].copy() if (idx.value and o is not None) else None
         return kun, o, i, n
+
+    # --- the RGB-D constructor: frame finish + Frame::ComputeStereoFromRGBD (src/Frame.cc:1423-1461) in one launch ---
+    def upload_depth(self, images, factor=1.0):
+        """B host depth images (float32 or uint16, same shape) -> DepthDesc of their device copy (orbx_upload_depth)"""
+        B = len(images)
+        d0 = DepthDesc.of(images[0], factor)
+        arr = (ctypes.c_void_p * B)(*[im.ctypes.data for im in images])
+        assert all(im.shape == images[0].shape and im.dtype == images[0].dtype and im.strides == images[0].strides for im in images)
+        out = DepthDesc()
+        _check(self._L.orbx_upload_depth(self._h, arr, B, d0.format, d0.cols, d0.rows, d0.stride_bytes, factor, ctypes.byref(out)))
+        return out
+
+    def rgbd_device(self, extractor, grid, depth_dev, bf, th_depth):
+        """finish_device + the RGB-D step on the extractor's last batch (device resident)"""
+        prm = RgbdParams(bf, th_depth)
+        _check(self._L.orbx_frame_rgbd_device(self._h, extractor._h, ctypes.byref(grid), ctypes.byref(depth_dev), ctypes.byref(prm)))
+
+    def rgbd_download(self, extractor, batch):
+        """-> dict(depth, u_right, order [B, cap], n_valid, n_close [B], xyz_cam [B, cap, 3]); entries behind a frame's keypoint count are undefined"""
+        cap = ctypes.c_int()
+        _check(self._L.orbx_frame_rgbd_results_device(self._h, None, None, None, None, None, None, ctypes.byref(cap)))
+        cap = cap.value
+        r = dict(depth=np.zeros((batch, cap), np.float32), u_right=np.zeros((batch, cap), np.float32), order=np.zeros((batch, cap), np.int32),
+                 n_valid=np.zeros(batch, np.int32), n_close=np.zeros(batch, np.int32), xyz_cam=np.zeros((batch, cap, 3), np.float32))
+        _check(self._L.orbx_frame_rgbd_download(self._h, extractor._h, batch, _ptr(r["depth"]), _ptr(r["u_right"]), _ptr(r["order"]), _ptr(r["n_valid"]),
+                                                _ptr(r["n_close"]), _ptr(r["xyz_cam"])))
+        return r
+
+    def rgbd_frame(self, extractor, grid, depth, bf, th_depth, factor=1.0):
+        """Latency form for ONE frame (orbx_frame_rgbd_begin + _end) with the host image `depth` (float32, or uint16 with `factor`).
+        -> (mvKeysUn or None, offsets, indices, n, dict(depth, u_right, order, xyz_cam, n_valid, n_close)); copies of the pinned views."""
+        L = self._L
+        vp = ctypes.c_void_p
+        dd, prm = DepthDesc.of(depth, factor), RgbdParams(bf, th_depth)
+        _check(L.orbx_frame_rgbd_begin(self._h, extractor._h, ctypes.byref(grid) if grid is not None else None, ctypes.byref(dd), ctypes.byref(prm)))
+        un, off, idx, n, rf = vp(), vp(), vp(), ctypes.c_int(), RgbdFrame()
+        _check(L.orbx_frame_rgbd_end(self._h, ctypes.byref(un), ctypes.byref(off), ctypes.byref(idx), ctypes.byref(n), ctypes.byref(rf)))
+        n = n.value
+        kun = np.ctypeslib.as_array(ctypes.cast(un, ctypes.POINTER(ctypes.c_uint8)), shape=(max(n, 1) * KEYPOINT_DTYPE.itemsize,)).view(KEYPOINT_DTYPE)[:n].copy() if un.value else None
+        o = np.ctypeslib.as_array(ctypes.cast(off, ctypes.POINTER(ctypes.c_int32)), shape=(FRAME_GRID_COLS * FRAME_GRID_ROWS + 1,)).copy() if off.value else None
+        i = np.ctypeslib.as_array(ctypes.cast(idx, ctypes.POINTER(ctypes.c_int32)), shape=(max(n, 1),))[:int(o[-1])].copy() if (idx.value and o is not None) else None
+
+        def view(p, ct, dt, m):
+            return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ct)), shape=(max(m, 1),))[:m].astype(dt, copy=True)
+        r = dict(depth=view(rf.depth, ctypes.c_float, np.float32, n), u_right=view(rf.u_right, ctypes.c_float, np.float32, n),
+                 order=view(rf.order, ctypes.c_int32, np.int32, n), xyz_cam=view(rf.xyz_cam, ctypes.c_float, np.float32, 3 * n).reshape(n, 3),
+                 n_valid=rf.n_valid, n_close=rf.n_close)
+        return kun, o, i, n, r
 
     def keypoints_un_device(self):
         kp, cap = ctypes.c_void_p(), ctypes.c_int()
