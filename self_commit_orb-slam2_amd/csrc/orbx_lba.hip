@@ -20,7 +20,7 @@
 //   k_lm_begin / k_lm_decide   the Levenberg-Marquardt state machine of optimization_algorithm_levenberg.cpp:61-164 ON THE DEVICE: lambda, rho,
 //                 accept / reject, the iteration's and the stage's termination tests; state mirrored into pinned memory, sequence number
 //                 last (the host polls it once per optimize(n), not once per trial); every launch of a trial that is not needed returns at once
-//   k_restore, k_classify   pop() of a rejected trial (gated by the decision); outlier flags / chi2 / estimates of the result
+//   k_classify    outlier flags / chi2 / estimates of the result (pop() of a rejected trial happens inside k_lm_decide)
 // The stop flag (g2o's forceStopFlag) is a pinned word the waiting host keeps current.  This path is latency bound (~45 MFLOP per iteration): the deliverable
 // is parity (<= 1e-5 vs the reference's own Optimizer.cc + g2o, tests/test_optimizer_ref.py, tests/golden/lba) plus every O(E)
 // stage on the device and as few dependent latencies as possible (DESIGN.md section 7 has the measured history).
@@ -317,7 +317,8 @@ __device__ __forceinline__ double block_sum256(double v, double *sw /* 4 */)
 struct LmState {
     double lambda, ni, currentChi, iniChi, rho, chi0, tempChi;
     int it, qmax, nBad, ok, done, lastRejected, relin, trials, iters, maxIters;
-    unsigned arrive;      // workgroups of k_errors_decide that have stored their share of chi2 (0 between launches)
+    unsigned arrive;      // unused (the arrival counter of a removed one-launch errors + decision kernel): it and its clearing in k_lm_begin stay until that
+                          // kernel is next changed, so that the kernels come out of a host-side refactor byte for byte
 };
 // ---------------------------------------------------------------------------------------------
 // Batched local bundle adjustment (orbx_lba_solve_batch): N independent windows, and every launch of the chain covers all of them.  The
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(256) void k_sum_poses_fin(LbaDev d, const double *_
 // Levenberg-Marquardt ON THE DEVICE (g2o: optimization_algorithm_levenberg.cpp:61-164, sparse_optimizer.cpp:350-424).  lambda, the
 // Nielsen factor, the chi2 bookkeeping and the accept / restore decision of every trial live in LmState; the kernels of a trial take
 // lambda from there, k_lm_decide ends a trial (the three sums, rho, accept or reject, the iteration's and the stage's termination tests),
-// k_restore runs only behind a rejected trial, and every launch of a trial the stage turns out not to need returns at once (the `gate`
+// and takes a rejected update back, and every launch of a trial the stage turns out not to need returns at once (the `gate`
 // argument of the kernels).  The host therefore enqueues a whole optimize(n) - n trials, one per iteration, which is what a bundle
 // adjustment near its optimum takes - WITHOUT waiting for any of them, then reads the state once; only when a trial was rejected somewhere
 // does it add trials one by one.  (Before: one host round trip per trial, ~10-20 us of idle device each, 9 per window.)
@@ -828,50 +829,6 @@ __global__ __launch_bounds__(256) void k_lm_decide(LmState *st, const double *pa
         return;
     }
     lm_decide_block(st, partChi, nChi, partL, nL, xp, bp, nP6, okFlag, stopHost, host, seq, d, poseBak, ptBak, scaleBits);
-}
-
-// k_errors and k_lm_decide of a trial as ONE launch: every workgroup stores its share of activeRobustChi2 (partChi[blockIdx.x], as k_errors does) and
-// counts itself in; the workgroup that arrives last takes the decision - it adds the shares in BLOCK order, so the sums do not depend on who arrives
-// when - and takes a rejected update back.  One launch and one kernel boundary (~6 us) less per trial.
-__global__ __launch_bounds__(256) void k_errors_decide(LbaDev d, Huber h, int robust, double *partChi, LmState *st, const double *partL, int nL, const double *xp, const double *bp,
-                                                       int nP6, const int *okFlag, const volatile int *stopHost, double *host, double seq, const DPose *poseBak, const double *ptBak,
-                                                       unsigned long long *scaleBits)
-{
-    __shared__ double swE[4];
-    __shared__ int sLast;
-    if (st->done) {      // a trial the stage did not need: only the sequence number moves (the host may be waiting for this very launch)
-        if (blockIdx.x == 0) {
-            if (threadIdx.x < 6) scaleBits[threadIdx.x] = 0ull;
-            if (threadIdx.x == 0) { __threadfence_system(); __hip_atomic_store(host + 15, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-        }
-        return;
-    }
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    double r0 = 0;
-    if (e < d.E) {
-        if (!d.active[e]) d.rchi[e] = 0;   // _error of inactive edges stays as last computed
-        else {
-            double r[3];
-            edge_error(d, e, r, nullptr);
-            d.err[3 * (size_t)e] = r[0]; d.err[3 * (size_t)e + 1] = r[1]; d.err[3 * (size_t)e + 2] = r[2];
-            const double chi = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) * d.info[e];
-            double r1 = 1;
-            r0 = chi;
-            if (robust) huber_rho(h, d.stereo[e] != 0, chi, r0, r1);
-            d.rchi[e] = r0;
-        }
-    }
-    const double t = block_sum256(r0, swE);
-    if (threadIdx.x == 0) {
-        partChi[blockIdx.x] = t;
-        __threadfence();      // the share (and this workgroup's _error / chi2 stores) before the arrival
-        sLast = atomicAdd(&st->arrive, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!sLast) return;
-    __threadfence();          // (acquire side: everybody's shares)
-    if (threadIdx.x == 0) st->arrive = 0;
-    lm_decide_block(st, partChi, (int)gridDim.x, partL, nL, xp, bp, nP6, okFlag, stopHost, host, seq, d, poseBak, ptBak, scaleBits);
 }
 
 // The marshalled inputs of a call arrive as ONE host-to-device copy of the pinned staging buffer; this kernel distributes the segments
@@ -1125,15 +1082,6 @@ __global__ __launch_bounds__(1024) void k_stage_index(int K, int P, const uint8_
         __threadfence_system();
         __hip_atomic_store(host + 15, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-}
-
-// pop() of a rejected trial: the estimates saved by k_backsub_update come back (one launch instead of two copies)
-__global__ __launch_bounds__(256) void k_restore(LbaDev d, const DPose *poseBak, const double *ptBak, const int *gate, int want)
-{
-    if (gate && *gate != want) return;      // device-side LM: this launch belongs to a trial the stage no longer needs (or to a branch not taken)
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g < d.K) d.pose[g] = poseBak[g];
-    if (g < 3 * d.P) d.pt[g] = ptBak[g];
 }
 
 // computeLambdaInit (optimization_algorithm_levenberg.cpp:166-180): out[2] = max |diagonal entry| over the pose and landmark blocks
@@ -2652,75 +2600,291 @@ __global__ __launch_bounds__(256) void k_pose_opt(PoseOptDev P, Huber hub)
 
 }  // namespace
 
-struct orbx_lba {
-    int device = 0, maxK = 0, maxP = 0, maxE = 0;
+// ---------------------------------------------------------------------------------------------
+// Host plumbing shared by the single-window handle (orbx_lba: orbx_lba_solve, orbx_bundle_adjustment) and the batch handle
+// (orbx_lba_batch: orbx_lba_solve_batch).  The two drivers differ in how they pass a window to the kernels (by-value arguments / one
+// descriptor per window) and keep their own stage loops; everything else a window needs on the host is here, once.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// The device buffers of `windows` windows of the handle's capacities, window w at w times the per-window size.
+struct LbaBuffers {
+    OrbxDevBuf<DPose> pose, poseBak;
+    OrbxDevBuf<double> pt, ptBak, intr, obs, info, err, rchi, edgeBlk, Hpp, bp, Hll, bl, Dinv, Ddb, bs, xp, xl, red;
+    OrbxDevBuf<double> ywork, ysol, diagInv;   // multi-workgroup Cholesky: the two halves of the right-hand side, 1 / diagonal
+    OrbxDevBuf<double> spPart;                 // k_lin_sums: SP_SPLIT partial results per keyframe
+    OrbxDevBuf<double> partChi, partL;         // per-workgroup partial sums of k_errors / k_backsub_update
+    OrbxDevBuf<double> bsPart;                 // K x 32 x 6: the workgroups' shares of the reduced right-hand side
+    OrbxDevBuf<int> ep, ek, ptStart, ptEdges, kfStart, kfEdges, poseIdx, ptIdx, okFlag;
+    OrbxDevBuf<int> ptTmp, fillP, pActF, lActF, kfRowS0, kfRowN, ptPi;   // adjacency-list builder and stage preparation (device side)
+    OrbxDevBuf<uint8_t> stereo, active, fixedDev;
+    OrbxDevBuf<unsigned long long> scaleBits;  // max |Hpp[r][r]| over the free poses as bit patterns, r = 0..5: the fixed-point scale (k_schur_setup)
+    OrbxDevBuf<LmState> lm;                    // Levenberg-Marquardt state of the running stage (device side)
+    // sized by the call (grow-only): the reduced system, its factor and its fixed-point sums (all zero between trials) by the FREE keyframes,
+    // the chunk counters of the adjacency-list builder, the device images of the input and result layouts (LbaLayout)
+    OrbxDevBuf<double> S, Lmat;
+    OrbxDevBuf<unsigned long long> Sacc;
+    OrbxDevBuf<int> csrCnt;
+    OrbxDevBuf<uint8_t> inArena, outArena;
+    size_t capK = 0, capP = 0, capE = 0, ebPerEdge = 0, okStride = 0;      // per-window strides (ensure)
+
+    // splitForm: room for eb_rest, which only the launch-per-stage form (ORBX_LBA_SPLIT=1) writes; okStride: ints between the windows' okFlag
+    int ensure(size_t windows, size_t K, size_t P, size_t E, bool splitForm, size_t okFlagStride)
+    {
+        const size_t n6 = 6 * K;
+        capK = K; capP = P; capE = E; ebPerEdge = splitForm ? EB_SIZE : 36; okStride = okFlagStride;
+        int rc = 0;
+#define LBA_ENSURE(buf, perWindow) rc = rc ? rc : buf.ensure(windows * (perWindow))
+        LBA_ENSURE(pose, K); LBA_ENSURE(poseBak, K); LBA_ENSURE(pt, 3 * P); LBA_ENSURE(ptBak, 3 * P); LBA_ENSURE(intr, 5 * K); LBA_ENSURE(obs, 3 * E); LBA_ENSURE(info, E);
+        LBA_ENSURE(err, 3 * E); LBA_ENSURE(rchi, E); LBA_ENSURE(edgeBlk, ebPerEdge * E); LBA_ENSURE(Hpp, 36 * K); LBA_ENSURE(bp, n6); LBA_ENSURE(Hll, 9 * P); LBA_ENSURE(bl, 3 * P);
+        LBA_ENSURE(Dinv, 9 * P); LBA_ENSURE(Ddb, 3 * P); LBA_ENSURE(bs, n6); LBA_ENSURE(xp, n6); LBA_ENSURE(xl, 3 * P); LBA_ENSURE(red, 16);
+        LBA_ENSURE(ywork, n6); LBA_ENSURE(ysol, n6); LBA_ENSURE(diagInv, n6 + CNB); LBA_ENSURE(spPart, K * SP_SPLIT * 27);
+        LBA_ENSURE(partChi, (E + 255) / 256); LBA_ENSURE(partL, (std::max(K, 16 * P) + 255) / 256); LBA_ENSURE(bsPart, K * 32 * 6);
+        LBA_ENSURE(ep, E); LBA_ENSURE(ek, E); LBA_ENSURE(ptStart, P + 1); LBA_ENSURE(ptEdges, E); LBA_ENSURE(kfStart, K + 1); LBA_ENSURE(kfEdges, E); LBA_ENSURE(poseIdx, K);
+        LBA_ENSURE(ptIdx, P); LBA_ENSURE(okFlag, okStride); LBA_ENSURE(ptTmp, E); LBA_ENSURE(fillP, P); LBA_ENSURE(pActF, K); LBA_ENSURE(lActF, P);
+        LBA_ENSURE(kfRowS0, E); LBA_ENSURE(kfRowN, E); LBA_ENSURE(ptPi, E); LBA_ENSURE(stereo, E); LBA_ENSURE(active, E); LBA_ENSURE(fixedDev, K);
+        LBA_ENSURE(scaleBits, 8); LBA_ENSURE(lm, 1);
+#undef LBA_ENSURE
+        return rc;
+    }
+    void release()
+    {
+        pose.release(); poseBak.release(); pt.release(); ptBak.release(); intr.release(); obs.release(); info.release(); err.release(); rchi.release(); edgeBlk.release();
+        Hpp.release(); bp.release(); Hll.release(); bl.release(); Dinv.release(); Ddb.release(); bs.release(); xp.release(); xl.release(); red.release();
+        ywork.release(); ysol.release(); diagInv.release(); spPart.release(); partChi.release(); partL.release(); bsPart.release();
+        ep.release(); ek.release(); ptStart.release(); ptEdges.release(); kfStart.release(); kfEdges.release(); poseIdx.release(); ptIdx.release(); okFlag.release();
+        ptTmp.release(); fillP.release(); pActF.release(); lActF.release(); kfRowS0.release(); kfRowN.release(); ptPi.release();
+        stereo.release(); active.release(); fixedDev.release(); scaleBits.release(); lm.release();
+        S.release(); Lmat.release(); Sacc.release(); csrCnt.release(); inArena.release(); outArena.release();
+    }
+    // the by-value views of window w, for a problem of K keyframes, P points and E edges
+    LbaDev views(size_t w, int K, int P, int E) const
+    {
+        LbaDev d;
+        d.K = K; d.P = P; d.E = E;
+        d.pose = pose.p + w * capK; d.pt = pt.p + w * 3 * capP; d.intr = intr.p + w * 5 * capK; d.ep = ep.p + w * capE; d.ek = ek.p + w * capE;
+        d.obs = obs.p + w * 3 * capE; d.stereo = stereo.p + w * capE; d.info = info.p + w * capE; d.active = active.p + w * capE;
+        d.poseIdx = poseIdx.p + w * capK; d.ptIdx = ptIdx.p + w * capP; d.err = err.p + w * 3 * capE; d.rchi = rchi.p + w * capE; d.edgeBlk = edgeBlk.p + w * ebPerEdge * capE;
+        return d;
+    }
+};
+
+// What both handles are made of: the buffers, the stream and its timing events, the pinned I/O buffer of a call and, per window, the
+// mapped record the device mirrors the LM state into and the mapped stop word it reads.
+struct LbaCore : LbaBuffers {
+    int device = 0, maxW = 1, maxK = 0, maxP = 0, maxE = 0;
+    int numCU = 256;                     // compute units of the device (residency of k_schur_rows)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     double flops = 0;
-    OrbxDevBuf<DPose> pose, poseBak;
-    OrbxDevBuf<double> pt, ptBak, intr, obs, info, err, rchi, edgeBlk, Hpp, bp, Hll, bl, Dinv, Ddb, S, bs, xp, xl, red;
-    OrbxDevBuf<double> Lmat, ywork, ysol, diagInv;   // multi-workgroup Cholesky: the factor and the two halves of the right-hand side
-    int numCU = 256;                                 // compute units of the device (residency of k_schur_rows)
-    bool linSplit = false;                           // ORBX_LBA_SPLIT=1 (measurement switch): k_linearize, k_sum_points, k_sum_poses as separate launches
-    OrbxDevBuf<int> ep, ek, ptStart, ptEdges, kfStart, kfEdges, poseIdx, ptIdx, okFlag;
-    OrbxDevBuf<uint8_t> stereo, active;
-    uint8_t *hostIO = nullptr;   // pinned: the marshalled inputs of a call on their way up, flags / chi2 / estimates on their way down
-    size_t hostIOBytes = 0;
-    OrbxDevBuf<uint8_t> flagDev, inArena, fixedDev;
-    OrbxDevBuf<double> spPart;           // k_sum_poses: SP_SPLIT partial results per keyframe
-    OrbxDevBuf<int> csrCnt, ptTmp, fillP, pActF, lActF, kfRowS0, kfRowN, ptPi;   // adjacency-list builder and stage preparation (device side)
-    OrbxDevBuf<double> partChi, partL;   // per-workgroup partial sums of k_errors / k_backsub_update
-    OrbxDevBuf<unsigned long long> Sacc; // fixed-point sums of the Schur complement (k_schur_rows -> k_schur_fin), all zero between trials
-    OrbxDevBuf<double> bsPart;           // K x 32 x 6: the workgroups' shares of the reduced right-hand side
-    OrbxDevBuf<unsigned long long> scaleBits;   // max |Hpp[r][r]| over the free poses as bit patterns, r = 0..5: the fixed-point scale (k_schur_setup)
-    OrbxDevBuf<LmState> lm;              // Levenberg-Marquardt state of the running stage (device side)
-    int *hostStop = nullptr, *hostStopDev = nullptr;   // pinned: the caller's stop flag as the device sees it (the waiting host keeps it current)
-    double *hostRedDev = nullptr;        // device view of hostRed
     double seq = 0;                      // last sequence number handed out (k_stage_index, k_lm_begin, k_lm_decide)
+    uint8_t *hostIO = nullptr;           // pinned: the marshalled inputs of a call on their way up, flags / chi2 / estimates on their way down
+    size_t hostIOBytes = 0;
+    // mapped, 16 doubles per window: {chi, -, diag max, -, scale_p, scale_l, okFlag (as int), ...} of a trial and the vertex counts of a stage,
+    // the sequence number at [15] stored last, so that ONE poll reads them back
+    double *rec = nullptr, *recDev = nullptr;
+    int *stopW = nullptr, *stopWDev = nullptr;      // mapped, 16 ints apart: the callers' stop flags as the device sees them (the waiting host keeps them current)
+};
+
+// device check, stream, events, CU count, the mapped words; lba_close() undoes whatever part of it was reached
+int lba_open(LbaCore *h, int device, int maxW, int maxK, int maxP, int maxE)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
+    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
+    ORBX_HIP_CHECK(hipSetDevice(device));
+    h->device = device; h->maxW = maxW; h->maxK = maxK; h->maxP = maxP; h->maxE = maxE;
+    { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
+    (void)hipEventCreate(&h->ev0);
+    (void)hipEventCreate(&h->ev1);
+    const size_t W = (size_t)maxW;
+    if (hipHostMalloc((void **)&h->rec, W * 16 * sizeof(double), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->recDev, h->rec, 0) != hipSuccess ||
+        hipHostMalloc((void **)&h->stopW, W * 16 * sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->stopWDev, h->stopW, 0) != hipSuccess) {
+        orbx_set_error("hipHostMalloc (mapped) failed");
+        return ORBX_ERR_HIP;
+    }
+    for (size_t i = 0; i < W * 16; i++) { h->rec[i] = 0; h->stopW[i] = 0; }
+    return ORBX_OK;
+}
+
+void lba_close(LbaCore *h)
+{
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->release();
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->hostIO) (void)hipHostFree(h->hostIO);
+    if (h->rec) (void)hipHostFree(h->rec);
+    if (h->stopW) (void)hipHostFree(h->stopW);
+}
+
+int lba_last_timing(LbaCore *h, float *device_ms, double *flops)
+{
+    if (!h) { orbx_set_error("NULL handle"); return ORBX_ERR_ARG; }
+    if (!h->timed) { orbx_set_error("no solve yet"); return ORBX_ERR_STATE; }
+    ORBX_HIP_CHECK(hipSetDevice(h->device));
+    ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
+    if (device_ms) ORBX_HIP_CHECK(hipEventElapsedTime(device_ms, h->ev0, h->ev1));
+    if (flops) *flops = h->flops;
+    return ORBX_OK;
+}
+
+// the pinned I/O buffer holds the larger of a call's inputs and results (grow-only; nothing of an earlier call is in flight when it moves)
+int lba_grow_pinned(LbaCore *h, size_t need)
+{
+    if (need <= h->hostIOBytes) return ORBX_OK;
+    ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (h->hostIO) (void)hipHostFree(h->hostIO);
+    h->hostIO = nullptr; h->hostIOBytes = 0;
+    ORBX_HIP_CHECK(hipHostMalloc((void **)&h->hostIO, need, hipHostMallocDefault));
+    h->hostIOBytes = need;
+    return ORBX_OK;
+}
+
+// The arguments of one window checked against the handle's capacities; win >= 0: the window's number in a batch, named in the message.
+int lba_check_problem(const LbaCore *h, const orbx_lba_problem *p, const orbx_lba_result *r, int win = -1)
+{
+    char pre[32] = "";
+    if (win >= 0) snprintf(pre, sizeof pre, "window %d: ", win);
+    if (!r->poses || !r->points || !r->edge_outlier) { orbx_set_error(win >= 0 ? "%sNULL result array" : "%sNULL argument", pre); return ORBX_ERR_ARG; }
+    const int K = p->num_keyframes, P = p->num_points, E = p->num_edges;
+    if (K < 1 || P < 1 || E < 1 || K > h->maxK || P > h->maxP || E > h->maxE) {
+        orbx_set_error("%sproblem size %d/%d/%d outside the handle's capacity %d/%d/%d", pre, K, P, E, h->maxK, h->maxP, h->maxE);
+        return ORBX_ERR_CAPACITY;
+    }
+    if (!p->poses || !p->fixed || !p->intrinsics || !p->points || !p->edge_point || !p->edge_keyframe || !p->edge_obs || !p->edge_inv_sigma2) {
+        orbx_set_error("%sNULL problem array", pre);
+        return ORBX_ERR_ARG;
+    }
+    return ORBX_OK;
+}
+
+// Where a window's marshalled inputs lie in the pinned arena (and in its device image), and where its results come back: byte offsets,
+// every array padded to 256 bytes.  A batch lays its windows out one after the other: inBase / outBase = the previous window's ends.
+struct LbaLayout {
+    size_t oPose, oIntr, oPt, oObs, oInfo, oEp, oEk, oPs, oKs, oFx, inEnd;      // observations / information as floats
+    size_t dFlag, dChi, dPose, dPt, outEnd;
+};
+LbaLayout lba_layout(int K_, int P_, int E_, size_t inBase, size_t outBase)
+{
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t K = (size_t)K_, P = (size_t)P_, E = (size_t)E_;
+    LbaLayout l;
+    l.oPose = inBase; l.oIntr = l.oPose + pad(K * sizeof(DPose)); l.oPt = l.oIntr + pad(5 * K * 8); l.oObs = l.oPt + pad(3 * P * 8);
+    l.oInfo = l.oObs + pad(3 * E * 4); l.oEp = l.oInfo + pad(E * 4); l.oEk = l.oEp + pad(E * 4); l.oPs = l.oEk + pad(E * 4);
+    l.oKs = l.oPs + pad((P + 1) * 4); l.oFx = l.oKs + pad((K + 1) * 4); l.inEnd = l.oFx + pad(K);
+    l.dFlag = outBase; l.dChi = l.dFlag + pad(E); l.dPose = l.dChi + pad(E * 8); l.dPt = l.dPose + pad(K * sizeof(DPose)); l.outEnd = l.dPt + pad(3 * P * 8);
+    return l;
+}
+
+// the segments k_unpack distributes a window's inputs by (and the arrays it clears): d = the window's views, the rest its other arrays
+void lba_unpack_segs(const LbaLayout &l, const LbaDev &d, int *ptStart, int *kfStart, uint8_t *fixed, int *fillP, int *pActF, int *lActF, UnpackSegs &sg)
+{
+    const size_t K = (size_t)d.K, P = (size_t)d.P, E = (size_t)d.E;
+    int ns = 0;
+    auto seg = [&](size_t off, const void *dst, size_t bytes, int kind = 0) { sg.src[ns] = off; sg.dst[ns] = const_cast<void *>(dst); sg.bytes[ns] = bytes; sg.kind[ns] = kind; ns++; };
+    seg(l.oPose, d.pose, K * sizeof(DPose)); seg(l.oPt, d.pt, 3 * P * 8); seg(l.oIntr, d.intr, 5 * K * 8);
+    seg(l.oObs, d.obs, 3 * E, 1); seg(l.oInfo, d.info, E, 1); seg(l.oObs, d.stereo, E, 2);
+    seg(l.oEp, d.ep, E * 4); seg(l.oEk, d.ek, E * 4);
+    seg(l.oPs, ptStart, (P + 1) * 4); seg(l.oKs, kfStart, (K + 1) * 4); seg(l.oFx, fixed, K);
+    seg(~(size_t)0, d.err, E * 3 * 8);
+    seg(~(size_t)0, fillP, P * 4); seg(~(size_t)0, pActF, K * 4); seg(~(size_t)0, lActF, P * 4);
+    sg.n = ns;
+}
+
+// float deltas of the Huber kernels: sqrt(chi2Mono) and sqrt(7.815); LocalBundleAdjustment uses 5.991 (src/Optimizer.cc:764-765),
+// BundleAdjustment 5.99 (:141-142)
+Huber lba_huber(double chi2Mono)
+{
+    const float thMono = (float)sqrt(chi2Mono), thStereo = (float)sqrt(7.815);
+    Huber hub;
+    hub.dMono = thMono; hub.dStereo = thStereo;
+    hub.dsqrMono = (double)(float)((double)thMono * (double)thMono);        // `float dsqr` member (robust_kernel_impl.h:84)
+    hub.dsqrStereo = (double)(float)((double)thStereo * (double)thStereo);
+    return hub;
+}
+
+// a window's results from the pinned read-back: flags, chi2, Converter::toCvMat(SE3Quat) of the poses, the points
+void lba_write_result(const uint8_t *io, const LbaLayout &l, int K, int P, int E, orbx_lba_result *res)
+{
+    memcpy(res->edge_outlier, io + l.dFlag, (size_t)E);
+    if (res->edge_chi2) memcpy(res->edge_chi2, io + l.dChi, (size_t)E * 8);
+    const DPose *pose = (const DPose *)(io + l.dPose);
+    const double *pt = (const double *)(io + l.dPt);
+    for (int k = 0; k < K; k++) {
+        double R[9];
+        quat_to_R(pose[k].q, R);
+        float *o = res->poses + 16 * (size_t)k;
+        for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) o[4 * i + j] = (float)R[3 * i + j]; o[4 * i + 3] = (float)pose[k].t[i]; }
+        o[12] = o[13] = o[14] = 0.f; o[15] = 1.f;
+    }
+    for (int i = 0; i < 3 * P; i++) res->points[i] = (float)pt[i];
+}
+
+// grid of k_chol_step for the panel at column p0 of an n x n system: nPW workgroups of panel rows, then T1 x T1 tiles
+void lba_chol_panel_grid(int n, int p0, int &nPW, int &T1)
+{
+    const int nb = std::min(CNB, n - p0), below = n - p0 - nb;
+    nPW = std::max(1, (below + CHOL_RPW - 1) / CHOL_RPW);
+    T1 = p0 > 0 ? (n - p0 + CNB - 1) / CNB - 1 : 0;        // tile rows / columns beyond block column p that still await the previous panel's update
+}
+
+// Waits until the record of every listed window has reached `seq` (k_stage_index, k_lm_begin and k_lm_decide store theirs after their
+// results; the numbers only grow).  The words are polled; meanwhile the callers' stop flags (stops[w], or none) are copied into the
+// mapped words the device reads, and the stream is queried now and then so that a failed launch surfaces as an error instead of a hang.
+int lba_wait(LbaCore *h, const char *who, const int *wins, int nWins, double seq, const volatile uint8_t *const *stops)
+{
+    auto reached = [&]() {
+        bool all = true;
+        for (int i = 0; i < nWins; i++) all = all && *(volatile double *)(h->rec + 16 * (size_t)wins[i] + 15) >= seq;
+        return all;
+    };
+    for (unsigned spins = 1;; spins++) {
+        const bool all = reached();
+        for (int i = 0; i < nWins; i++) {
+            const size_t w = (size_t)wins[i];
+            const volatile uint8_t *s = stops ? stops[w] : nullptr;
+            if (s && *s && !h->stopW[16 * w]) { h->stopW[16 * w] = 1; std::atomic_thread_fence(std::memory_order_release); }
+        }
+        if (all) break;
+        if ((spins & 0x3fff) == 0) {
+            const hipError_t q = hipStreamQuery(h->stream);
+            if (q == hipSuccess) {
+                if (reached()) break;
+                orbx_set_error("%s: the stream drained without the trial results", who);
+                return ORBX_ERR_HIP;
+            }
+            if (q != hipErrorNotReady) { orbx_set_error("%s: %s", who, hipGetErrorString(q)); return ORBX_ERR_HIP; }
+        }
+        if (spins > 4096 && (spins & 63) == 0) std::this_thread::yield();      // a result normally arrives within ~300 us; do not starve other threads of an oversubscribed host
+        __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return ORBX_OK;
+}
+
+}  // namespace
+
+struct orbx_lba : LbaCore {
+    bool linSplit = false;               // ORBX_LBA_SPLIT=1 (measurement switch): k_linearize, k_sum_points, k_sum_poses as separate launches
     // test hook (ORBX_LBA_TEST_STOP_AFTER_DECISIONS=k, read per call): the CALLER's stop flag is raised - as another thread of the caller would -
     // when the host has seen the k-th trial decision of the call; from there on the library's own mirroring has to carry it to the device
     int dbgStopAfter = 0, dbgDecisions = 0;
-    double *hostRed = nullptr;   // pinned: {chi, -, diag max, -, scale_p, scale_l, okFlag (as int)} of a trial, read back with ONE synchronisation
 };
 
 extern "C" int orbx_lba_create(int device, int max_keyframes, int max_points, int max_edges, orbx_lba **out)
 {
     if (!out || max_keyframes < 1 || max_points < 1 || max_edges < 1) { orbx_set_error("bad LBA sizes"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
     orbx_lba *h = new orbx_lba();
-    h->device = device; h->maxK = max_keyframes; h->maxP = max_points; h->maxE = max_edges;
     { const char *e = getenv("ORBX_LBA_SPLIT"); h->linSplit = e && e[0] == '1'; }
-    { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev0);
-    (void)hipEventCreate(&h->ev1);
-    if (hipHostMalloc((void **)&h->hostRed, 16 * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&h->hostRedDev, h->hostRed, 0) != hipSuccess) { orbx_lba_destroy(h); orbx_set_error("hipHostMalloc (mapped) failed"); return ORBX_ERR_HIP; }
-    for (int i = 0; i < 16; i++) h->hostRed[i] = 0;
-    if (hipHostMalloc((void **)&h->hostStop, 64, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&h->hostStopDev, h->hostStop, 0) != hipSuccess) { orbx_lba_destroy(h); orbx_set_error("hipHostMalloc (mapped) failed"); return ORBX_ERR_HIP; }
-    h->hostStop[0] = 0;
-    const size_t K = (size_t)max_keyframes, P = (size_t)max_points, E = (size_t)max_edges, n6 = 6 * K;
-    int rc = 0;
-    rc = rc ? rc : h->pose.ensure(K); rc = rc ? rc : h->poseBak.ensure(K); rc = rc ? rc : h->pt.ensure(3 * P); rc = rc ? rc : h->ptBak.ensure(3 * P);
-    rc = rc ? rc : h->intr.ensure(5 * K); rc = rc ? rc : h->obs.ensure(3 * E); rc = rc ? rc : h->info.ensure(E); rc = rc ? rc : h->err.ensure(3 * E);
-    rc = rc ? rc : h->rchi.ensure(E); rc = rc ? rc : h->edgeBlk.ensure(E * EB_SIZE); rc = rc ? rc : h->Hpp.ensure(36 * K); rc = rc ? rc : h->bp.ensure(n6);
-    rc = rc ? rc : h->Hll.ensure(9 * P); rc = rc ? rc : h->bl.ensure(3 * P); rc = rc ? rc : h->Dinv.ensure(9 * P); rc = rc ? rc : h->Ddb.ensure(3 * P); rc = rc ? rc : h->ywork.ensure(n6); rc = rc ? rc : h->ysol.ensure(n6); rc = rc ? rc : h->diagInv.ensure(n6 + CNB);
-    rc = rc ? rc : h->bs.ensure(n6); rc = rc ? rc : h->xp.ensure(n6); rc = rc ? rc : h->xl.ensure(3 * P); rc = rc ? rc : h->red.ensure(16);
-    rc = rc ? rc : h->ep.ensure(E); rc = rc ? rc : h->ek.ensure(E); rc = rc ? rc : h->ptStart.ensure(P + 1); rc = rc ? rc : h->ptEdges.ensure(E);
-    rc = rc ? rc : h->kfStart.ensure(K + 1); rc = rc ? rc : h->kfEdges.ensure(E); rc = rc ? rc : h->poseIdx.ensure(K); rc = rc ? rc : h->ptIdx.ensure(P);
-    rc = rc ? rc : h->okFlag.ensure(1); rc = rc ? rc : h->stereo.ensure(E); rc = rc ? rc : h->active.ensure(E);
-    rc = rc ? rc : h->spPart.ensure(K * SP_SPLIT * 27);
-    rc = rc ? rc : h->kfRowS0.ensure(E); rc = rc ? rc : h->kfRowN.ensure(E); rc = rc ? rc : h->ptPi.ensure(E);
-    rc = rc ? rc : h->fixedDev.ensure(K); rc = rc ? rc : h->ptTmp.ensure(E); rc = rc ? rc : h->fillP.ensure(P); rc = rc ? rc : h->pActF.ensure(K); rc = rc ? rc : h->lActF.ensure(P);
-    rc = rc ? rc : h->lm.ensure(1);
-    rc = rc ? rc : h->bsPart.ensure(K * 32 * 6); rc = rc ? rc : h->scaleBits.ensure(8);
-    rc = rc ? rc : h->partChi.ensure((E + 255) / 256); rc = rc ? rc : h->partL.ensure((std::max(K, 16 * P) + 255) / 256);
+    int rc = lba_open(h, device, 1, max_keyframes, max_points, max_edges);
+    // (room for eb_rest whichever form runs; one window: nothing shares the cache line of okFlag)
+    rc = rc ? rc : h->ensure(1, (size_t)max_keyframes, (size_t)max_points, (size_t)max_edges, true, 1);
     if (rc) { orbx_lba_destroy(h); return rc; }
     *out = h;
     return ORBX_OK;
@@ -2729,21 +2893,7 @@ extern "C" int orbx_lba_create(int device, int max_keyframes, int max_points, in
 extern "C" void orbx_lba_destroy(orbx_lba *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->pose.release(); h->poseBak.release(); h->pt.release(); h->ptBak.release(); h->intr.release(); h->obs.release(); h->info.release(); h->err.release();
-    h->rchi.release(); h->edgeBlk.release(); h->Hpp.release(); h->bp.release(); h->Hll.release(); h->bl.release(); h->Dinv.release(); h->Ddb.release(); h->S.release(); h->Lmat.release(); h->ywork.release(); h->ysol.release(); h->diagInv.release();
-    h->bs.release(); h->xp.release(); h->xl.release(); h->red.release(); h->ep.release(); h->ek.release(); h->ptStart.release(); h->ptEdges.release();
-    h->kfStart.release(); h->kfEdges.release(); h->poseIdx.release(); h->ptIdx.release(); h->okFlag.release(); h->stereo.release(); h->active.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->hostRed) (void)hipHostFree(h->hostRed);
-    if (h->hostStop) (void)hipHostFree(h->hostStop);
-    h->lm.release();
-    if (h->hostIO) (void)hipHostFree(h->hostIO);
-    h->flagDev.release(); h->partChi.release(); h->partL.release(); h->inArena.release(); h->fixedDev.release(); h->csrCnt.release(); h->ptTmp.release(); h->fillP.release(); h->pActF.release(); h->lActF.release(); h->kfRowS0.release(); h->kfRowN.release(); h->ptPi.release(); h->spPart.release();
-    h->Sacc.release(); h->bsPart.release(); h->scaleBits.release();
+    lba_close(h);
     delete h;
 }
 
@@ -2784,15 +2934,14 @@ int lba_chol_route(int n)
 }
 
 // The host half of a window's marshalling, the same for both drivers: float boundary -> double state (Converter::toSE3Quat / toVector3d) into the
-// pinned arena at the given offsets, the row lengths of the adjacency lists, the edge ids checked.  -> -1, or the first edge out of range.
-int lba_marshal(const orbx_lba_problem *p, uint8_t *io, size_t oPose, size_t oIntr, size_t oPt, size_t oObs, size_t oInfo, size_t oEp, size_t oEk, size_t oPs, size_t oKs,
-                size_t oFx, int &nPose0, int &nPt0, int &spSplit)
+// pinned arena at the window's layout, the row lengths of the adjacency lists, the edge ids checked.  -> -1, or the first edge out of range.
+int lba_marshal(const orbx_lba_problem *p, uint8_t *io, const LbaLayout &l, int &nPose0, int &nPt0, int &spSplit)
 {
     const int K = p->num_keyframes, P = p->num_points, E = p->num_edges;
-    DPose *pose = (DPose *)(io + oPose);
-    double *intr = (double *)(io + oIntr), *pt = (double *)(io + oPt);
-    uint8_t *fixedH = io + oFx;
-    int *epH = (int *)(io + oEp), *ekH = (int *)(io + oEk), *ptStart = (int *)(io + oPs), *kfStart = (int *)(io + oKs);
+    DPose *pose = (DPose *)(io + l.oPose);
+    double *intr = (double *)(io + l.oIntr), *pt = (double *)(io + l.oPt);
+    uint8_t *fixedH = io + l.oFx;
+    int *epH = (int *)(io + l.oEp), *ekH = (int *)(io + l.oEk), *ptStart = (int *)(io + l.oPs), *kfStart = (int *)(io + l.oKs);
     for (int k = 0; k < K; k++) {
         double R[9];
         for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R[3 * i + j] = p->poses[16 * (size_t)k + 4 * i + j];
@@ -2807,8 +2956,8 @@ int lba_marshal(const orbx_lba_problem *p, uint8_t *io, size_t oPose, size_t oIn
     for (int k = 0; k <= K; k++) kfStart[k] = 0;
     // the edge arrays travel as they are (float observations / information, int ids): four memcpy; the device converts and derives the stereo flags
     // (k_unpack).  The host only checks the ids and counts the row lengths of the adjacency lists.
-    memcpy(io + oObs, p->edge_obs, (size_t)3 * E * sizeof(float));
-    memcpy(io + oInfo, p->edge_inv_sigma2, (size_t)E * sizeof(float));
+    memcpy(io + l.oObs, p->edge_obs, (size_t)3 * E * sizeof(float));
+    memcpy(io + l.oInfo, p->edge_inv_sigma2, (size_t)E * sizeof(float));
     memcpy(epH, p->edge_point, (size_t)E * sizeof(int));
     memcpy(ekH, p->edge_keyframe, (size_t)E * sizeof(int));
     for (int e = 0; e < E; e++) {
@@ -2839,29 +2988,11 @@ struct Ctx {
     int spSplit = 4;                       // workgroups per keyframe in k_lin_sums: ceil(longest keyframe row / 256), 1 .. SP_SPLIT
 };
 
-// Waits until the sequence number in pinned memory has reached `seq` (k_stage_index, k_lm_begin and k_lm_decide store theirs after their
-// results; the numbers only grow).  The word is polled; meanwhile the caller's stop flag is copied into the pinned word the device reads,
-// and the stream is queried now and then so that a failed launch surfaces as an error instead of a hang.
+// the one-window case of lba_wait
 int wait_seq(orbx_lba *h, double seq, const volatile uint8_t *stop = nullptr)
 {
-    volatile double *flag = h->hostRed + 15;
-    for (unsigned spins = 1;; spins++) {
-        if (*flag >= seq) break;
-        if (stop && *stop && !h->hostStop[0]) { h->hostStop[0] = 1; std::atomic_thread_fence(std::memory_order_release); }
-        if ((spins & 0x3fff) == 0) {
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipSuccess) {
-                if (*flag >= seq) break;
-                orbx_set_error("LBA: the stream drained without the trial results");
-                return ORBX_ERR_HIP;
-            }
-            if (q != hipErrorNotReady) { orbx_set_error("LBA: %s", hipGetErrorString(q)); return ORBX_ERR_HIP; }
-        }
-        if (spins > 4096 && (spins & 63) == 0) std::this_thread::yield();      // a result normally arrives within ~300 us; do not starve other threads of an oversubscribed host
-        __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return ORBX_OK;
+    const int w0 = 0;
+    return lba_wait(h, "LBA", &w0, 1, seq, &stop);
 }
 
 // SparseOptimizer::optimize(iterations) on the edges of level 0 (see oracle/lba_oracle.cc for the CPU twin)
@@ -2879,7 +3010,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
         hipLaunchKernelGGL(k_stage_mark, dim3(gM), dim3(256), 0, h->stream, E, (const int *)h->ep.p, (const int *)h->ek.p, c.stageFlags, h->active.p, h->pActF.p, h->lActF.p, stamp,
                            h->csrCnt.p);      // (the chunk counters of the adjacency-list builder are free again: >= E / 256 entries)
         hipLaunchKernelGGL(k_stage_index, dim3(1), dim3(1024), 0, h->stream, K, P, (const uint8_t *)h->fixedDev.p, (const int *)h->pActF.p, (const int *)h->lActF.p, stamp,
-                           h->poseIdx.p, h->ptIdx.p, (const int *)h->csrCnt.p, (int)gM, h->hostRedDev, seq);
+                           h->poseIdx.p, h->ptIdx.p, (const int *)h->csrCnt.p, (int)gM, h->recDev, seq);
         hipLaunchKernelGGL(k_stage_pairs, dim3(gM), dim3(256), 0, h->stream, E, (const int *)h->ek.p, (const int *)h->ptEdges.p, (const uint8_t *)h->active.p, (const int *)h->poseIdx.p,
                            h->ptPi.p);
         LCHECK();
@@ -2887,7 +3018,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
         else {
             int rcw = wait_seq(h, seq, c.stop);
             if (rcw) return rcw;
-            nPose = (int)h->hostRed[10]; nPt = (int)h->hostRed[11]; nAct = (int)h->hostRed[12];
+            nPose = (int)h->rec[10]; nPt = (int)h->rec[11]; nAct = (int)h->rec[12];
         }
     }
     if (nAct == 0 || nPose + nPt == 0) return ORBX_OK;
@@ -2927,7 +3058,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
         return ORBX_OK;
     };
     // ---- start of the stage: errors and chi2 of the start, H and b, computeLambdaInit, the LM state (nothing is waited for)
-    h->hostStop[0] = 0;
+    h->stopW[0] = 0;
     {
         // (the state's `done` of the previous stage is still set: the first launches are not gated)
         hipLaunchKernelGGL(k_errors, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->partChi.p, (const int *)nullptr, 0);
@@ -2943,8 +3074,8 @@ int optimize(Ctx &c, int iterations, double stats[4])
         hipLaunchKernelGGL(k_sum_poses_fin, dim3((unsigned)((32 * K + 255) / 256)), dim3(256), 0, h->stream, c.d, (const double *)h->spPart.p, h->Hpp.p, h->bp.p, c.spSplit, (const int *)nullptr, 0);
         hipLaunchKernelGGL(k_diag_max, dim3(1), dim3(1024), 0, h->stream, h->Hpp.p, nPose, h->Hll.p, nPt, h->red.p);
         const double seq = (h->seq += 1.0);
-        hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(256), 0, h->stream, st, (const double *)h->partChi.p, (int)gE, (const double *)h->red.p, iterations, (const volatile int *)h->hostStopDev,
-                           h->hostRedDev, seq, h->scaleBits.p);
+        hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(256), 0, h->stream, st, (const double *)h->partChi.p, (int)gE, (const double *)h->red.p, iterations, (const volatile int *)h->stopWDev,
+                           h->recDev, seq, h->scaleBits.p);
         LCHECK();
     }
     // ---- one Levenberg trial in two halves
@@ -2985,9 +3116,8 @@ int optimize(Ctx &c, int iterations, double stats[4])
             if (nP6 >= CHOL_MULTI_MIN_N) {
                 const int n = nP6;
                 for (int p0 = 0; p0 < n; p0 += CNB) {
-                    const int nb = std::min(CNB, n - p0), below = n - p0 - nb;
-                    const int nPW = std::max(1, (below + CHOL_RPW - 1) / CHOL_RPW);
-                    const int T1 = p0 > 0 ? (n - p0 + CNB - 1) / CNB - 1 : 0;        // tile rows / columns beyond block column p that still await the previous panel's update
+                    int nPW, T1;
+                    lba_chol_panel_grid(n, p0, nPW, T1);
                     if (g_cholProf) hipLaunchKernelGGL(k_chol_step<true>, dim3((unsigned)(nPW + T1 * T1)), dim3(256), 0, h->stream, h->S.p, h->Lmat.p, n, p0, nPW, std::max(T1, 1), h->ywork.p,
                                                        h->ysol.p, h->okFlag.p, h->diagInv.p, gDone, 0, g_cholProf);
                     else hipLaunchKernelGGL(k_chol_step<false>, dim3((unsigned)(nPW + T1 * T1)), dim3(256), 0, h->stream, h->S.p, h->Lmat.p, n, p0, nPW, std::max(T1, 1), h->ywork.p,
@@ -3028,22 +3158,12 @@ int optimize(Ctx &c, int iterations, double stats[4])
                            h->Dinv.p, h->xp.p, h->xl.p, h->poseBak.p, h->ptBak.p, 0.0, h->partL.p, lam, gDone, 0);
         LCHECK();
         const double seq = (h->seq += 1.0);
-        // ORBX_LBA_MERGE_DECIDE=1 (measured, round 6: profiles/r06_lba_merge_decide.txt): one launch instead of two, nine launches less per window - and 14.7 us per
-        // trial instead of 4.9 + 6.4 + a kernel boundary: the last arriver's fences cost what the boundary did.  Not the default.
-        static const bool mergeDecide = getenv("ORBX_LBA_MERGE_DECIDE") && getenv("ORBX_LBA_MERGE_DECIDE")[0] == '1';
-        if (mergeDecide) {
-            hipLaunchKernelGGL(k_errors_decide, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->partChi.p, st, (const double *)h->partL.p, (int)gU, (const double *)h->xp.p,
-                               (const double *)h->bp.p, nP6, nP6 > 0 ? (const int *)h->okFlag.p : (const int *)nullptr, (const volatile int *)h->hostStopDev, h->hostRedDev, seq,
-                               (const DPose *)h->poseBak.p, (const double *)h->ptBak.p, h->scaleBits.p);
-            LCHECK();
-        } else {
-            hipLaunchKernelGGL(k_errors, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->partChi.p, gDone, 0);
-            LCHECK();
-            hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), 0, h->stream, st, (const double *)h->partChi.p, (int)gE, (const double *)h->partL.p, (int)gU, (const double *)h->xp.p,
-                               (const double *)h->bp.p, nP6, nP6 > 0 ? (const int *)h->okFlag.p : (const int *)nullptr, (const volatile int *)h->hostStopDev, h->hostRedDev, seq, c.d,
-                               (const DPose *)h->poseBak.p, (const double *)h->ptBak.p, h->scaleBits.p);
-            LCHECK();
-        }
+        hipLaunchKernelGGL(k_errors, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->partChi.p, gDone, 0);
+        LCHECK();
+        hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), 0, h->stream, st, (const double *)h->partChi.p, (int)gE, (const double *)h->partL.p, (int)gU, (const double *)h->xp.p,
+                           (const double *)h->bp.p, nP6, nP6 > 0 ? (const int *)h->okFlag.p : (const int *)nullptr, (const volatile int *)h->stopWDev, h->recDev, seq, c.d,
+                           (const DPose *)h->poseBak.p, (const double *)h->ptBak.p, h->scaleBits.p);
+        LCHECK();
         // (a rejected update is taken back inside k_lm_decide); H and b at the new estimates behind an accepted trial
         int rcl = linearize();
         if (rcl) return rcl;
@@ -3055,25 +3175,20 @@ int optimize(Ctx &c, int iterations, double stats[4])
     // the Schur half of trial t + 1 (~40 us of device work) when it starts to wait for that decision, and queues the solve half of t + 1 while
     // those run.  A stage that ends leaves those seven launches to fall through (~4 us each); a whole trial enqueued in advance would cost
     // twenty (measured: every trial of both stages up front, 15 per window where 9 are needed: 2.08 ms per window instead of 1.87).
-    // ORBX_LBA_SPEC_CHOL=1 (measured): the factorisation of trial t + 1 is queued speculatively too, so that the device never waits for
-    // the host's nine panel launches behind a decision; a stage that ends then lets nine more gated launches fall through.
-    static const bool specChol = getenv("ORBX_LBA_SPEC_CHOL") && getenv("ORBX_LBA_SPEC_CHOL")[0] == '1';
     int rct = trialSchur();
     if (rct) return rct;
-    if (specChol && (rct = trialChol()) != ORBX_OK) return rct;
     for (int t = 0;; t++) {
         double seqT = 0;
-        if (!specChol && (rct = trialChol()) != ORBX_OK) return rct;
+        if ((rct = trialChol()) != ORBX_OK) return rct;
         if ((rct = trialRest(&seqT)) != ORBX_OK) return rct;
         if ((rct = trialSchur()) != ORBX_OK) return rct;      // of trial t + 1, speculatively
-        if (specChol && (rct = trialChol()) != ORBX_OK) return rct;
         int rcw = wait_seq(h, seqT, c.stop);
         if (rcw) return rcw;
         if (h->dbgStopAfter > 0 && c.stop && ++h->dbgDecisions == h->dbgStopAfter) *const_cast<volatile uint8_t *>(c.stop) = 1;      // (test hook, see the handle)
-        if (h->hostRed[13] != 0.0) break;      // done
+        if (h->rec[13] != 0.0) break;      // done
         if (t >= 10 * iterations + 10) { orbx_set_error("LBA: the Levenberg loop did not terminate"); return ORBX_ERR_STATE; }
     }
-    stats[0] = h->hostRed[7]; stats[1] = h->hostRed[9]; stats[2] = h->hostRed[6]; stats[3] = h->hostRed[1];
+    stats[0] = h->rec[7]; stats[1] = h->rec[9]; stats[2] = h->rec[6]; stats[3] = h->rec[1];
     return ORBX_OK;
 }
 
@@ -3083,39 +3198,25 @@ int optimize(Ctx &c, int iterations, double stats[4])
 // classification + 10 iterations without kernels on the inliers)
 static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_t *stop, orbx_lba_result *res, int iters1, bool robust1, bool secondStage)
 {
-    if (!h || !p || !res || !res->poses || !res->points || !res->edge_outlier) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    if (!h || !p || !res) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    int rc = lba_check_problem(h, p, res);
+    if (rc) return rc;
     const int K = p->num_keyframes, P = p->num_points, E = p->num_edges;
-    if (K < 1 || P < 1 || E < 1 || K > h->maxK || P > h->maxP || E > h->maxE) { orbx_set_error("problem size %d/%d/%d outside the handle's capacity %d/%d/%d", K, P, E, h->maxK, h->maxP, h->maxE); return ORBX_ERR_CAPACITY; }
-    if (!p->poses || !p->fixed || !p->intrinsics || !p->points || !p->edge_point || !p->edge_keyframe || !p->edge_obs || !p->edge_inv_sigma2) { orbx_set_error("NULL problem array"); return ORBX_ERR_ARG; }
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     for (int i = 0; i < 8; i++) res->stats[i] = 0;
     h->flops = 0;
     { const char *e = getenv("ORBX_LBA_TEST_STOP_AFTER_DECISIONS"); h->dbgStopAfter = e && *e ? atoi(e) : 0; h->dbgDecisions = 0; }
     // ---- host marshalling: float boundary -> double state (Converter::toSE3Quat / toVector3d), written straight into ONE pinned
     // buffer (copies from pageable vectors are staged and synchronous: a dozen of them cost 0.3 ms of a 5 ms call) ----
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t oPose = 0, oIntr = oPose + pad((size_t)K * sizeof(DPose)), oPt = oIntr + pad((size_t)5 * K * 8), oObs = oPt + pad((size_t)3 * P * 8),
-                 oInfo = oObs + pad((size_t)3 * E * 4), oEp = oInfo + pad((size_t)E * 4), oEk = oEp + pad((size_t)E * 4),      // observations / information as floats
-                 oPs = oEk + pad((size_t)E * 4), oKs = oPs + pad(((size_t)P + 1) * 4), oFx = oKs + pad(((size_t)K + 1) * 4), inBytes = oFx + pad((size_t)K);
-    const size_t dFlag = 0, dChi = dFlag + pad((size_t)E), dPose = dChi + pad((size_t)E * 8), dPt = dPose + pad((size_t)K * sizeof(DPose)),
-                 outBytes = dPt + pad((size_t)3 * P * 8);
+    const LbaLayout L = lba_layout(K, P, E, 0, 0);
     const int nChunk = (E + CSR_CHUNK - 1) / CSR_CHUNK;
     const size_t csrLds = (size_t)K * sizeof(int);
     if (csrLds > 150 * 1024) { orbx_set_error("%d keyframes exceed the adjacency-list builder's limit %d", K, 150 * 1024 / 4); return ORBX_ERR_CAPACITY; }
-    {
-        const size_t need = std::max(inBytes, outBytes);
-        if (need > h->hostIOBytes) {
-            ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
-            if (h->hostIO) (void)hipHostFree(h->hostIO);
-            h->hostIO = nullptr; h->hostIOBytes = 0;
-            ORBX_HIP_CHECK(hipHostMalloc((void **)&h->hostIO, need, hipHostMallocDefault));
-            h->hostIOBytes = need;
-        }
-        int rcb = h->flagDev.ensure(outBytes);
-        rcb = rcb ? rcb : h->inArena.ensure(inBytes);
-        rcb = rcb ? rcb : h->csrCnt.ensure((size_t)nChunk * (size_t)K);
-        if (rcb) return rcb;
-    }
+    rc = lba_grow_pinned(h, std::max(L.inEnd, L.outEnd));
+    rc = rc ? rc : h->outArena.ensure(L.outEnd);
+    rc = rc ? rc : h->inArena.ensure(L.inEnd);
+    rc = rc ? rc : h->csrCnt.ensure((size_t)nChunk * (size_t)K);
+    if (rc) return rc;
     // The host only converts (float boundary -> double state) and counts; everything goes up in ONE copy of the pinned buffer, one
     // kernel distributes it, and the adjacency lists and the index mapping of the stages are made on the device.  Nothing waits for
     // the copy: the results come back into the front of the same buffer long after the device has consumed it.
@@ -3123,23 +3224,16 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
     Ctx c;
     c.h = h; c.stop = stop;
     {
-        const int bad = lba_marshal(p, io, oPose, oIntr, oPt, oObs, oInfo, oEp, oEk, oPs, oKs, oFx, c.nPose0, c.nPt0, c.spSplit);
+        const int bad = lba_marshal(p, io, L, c.nPose0, c.nPt0, c.spSplit);
         if (bad >= 0) { orbx_set_error("edge %d references a vertex out of range", bad); return ORBX_ERR_ARG; }
     }
+    c.d = h->views(0, K, P, E);
     hipStream_t s = h->stream;
     ORBX_HIP_CHECK(hipEventRecord(h->ev0, s));
     {
-        ORBX_HIP_CHECK(hipMemcpyAsync(h->inArena.p, io, inBytes, hipMemcpyHostToDevice, s));
+        ORBX_HIP_CHECK(hipMemcpyAsync(h->inArena.p, io, L.inEnd, hipMemcpyHostToDevice, s));
         UnpackSegs sg;
-        int ns = 0;
-        auto seg = [&](size_t off, void *dst, size_t bytes, int kind = 0) { sg.src[ns] = off; sg.dst[ns] = dst; sg.bytes[ns] = bytes; sg.kind[ns] = kind; ns++; };
-        seg(oPose, h->pose.p, (size_t)K * sizeof(DPose)); seg(oPt, h->pt.p, (size_t)3 * P * 8); seg(oIntr, h->intr.p, (size_t)5 * K * 8);
-        seg(oObs, h->obs.p, (size_t)3 * E, 1); seg(oInfo, h->info.p, (size_t)E, 1); seg(oObs, h->stereo.p, (size_t)E, 2);
-        seg(oEp, h->ep.p, (size_t)E * 4); seg(oEk, h->ek.p, (size_t)E * 4);
-        seg(oPs, h->ptStart.p, ((size_t)P + 1) * 4); seg(oKs, h->kfStart.p, ((size_t)K + 1) * 4); seg(oFx, h->fixedDev.p, (size_t)K);
-        seg(~(size_t)0, h->err.p, (size_t)E * 3 * 8);
-        seg(~(size_t)0, h->fillP.p, (size_t)P * 4); seg(~(size_t)0, h->pActF.p, (size_t)K * 4); seg(~(size_t)0, h->lActF.p, (size_t)P * 4);
-        sg.n = ns;
+        lba_unpack_segs(L, c.d, h->ptStart.p, h->kfStart.p, h->fixedDev.p, h->fillP.p, h->pActF.p, h->lActF.p, sg);
         hipLaunchKernelGGL(k_unpack, dim3(256), dim3(256), 0, s, (const uint8_t *)h->inArena.p, sg);
         LCHECK();
         // adjacency lists
@@ -3155,27 +3249,18 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
         hipLaunchKernelGGL(k_csr_rows, dim3(gE), dim3(256), 0, s, E, (const int *)h->ep.p, (const int *)h->kfEdges.p, (const int *)h->ptStart.p, h->kfRowS0.p, h->kfRowN.p);
         LCHECK();
     }
-    LbaDev &d = c.d;
-    d.K = K; d.P = P; d.E = E; d.pose = h->pose.p; d.pt = h->pt.p; d.intr = h->intr.p; d.ep = h->ep.p; d.ek = h->ek.p; d.obs = h->obs.p;
-    d.stereo = h->stereo.p; d.info = h->info.p; d.active = h->active.p; d.poseIdx = h->poseIdx.p; d.ptIdx = h->ptIdx.p; d.err = h->err.p;
-    d.rchi = h->rchi.p; d.edgeBlk = h->edgeBlk.p;
-    // float deltas; LocalBundleAdjustment uses sqrt(5.991) (src/Optimizer.cc:764-765), BundleAdjustment sqrt(5.99) (:141-142)
-    const float thMono = (float)sqrt(secondStage ? 5.991 : 5.99), thStereo = (float)sqrt(7.815);
-    c.hub.dMono = thMono; c.hub.dStereo = thStereo;
-    c.hub.dsqrMono = (double)(float)((double)thMono * (double)thMono);        // `float dsqr` member (robust_kernel_impl.h:84)
-    c.hub.dsqrStereo = (double)(float)((double)thStereo * (double)thStereo);
+    c.hub = lba_huber(secondStage ? 5.991 : 5.99);
     // classification on the device (k_classify); only the flags come back between the stages, the rest with the final results
     const unsigned gEc = (unsigned)((std::max(E, std::max(K, 3 * P)) + 255) / 256);
-    uint8_t *oa = h->flagDev.p;     // device image of the result layout dFlag | dChi | dPose | dPt
-    int rc = ORBX_OK;
+    uint8_t *oa = h->outArena.p;     // device image of the result layout dFlag | dChi | dPose | dPt
     if (!(stop && *stop)) {
         c.robust = robust1 ? 1 : 0;
         if ((rc = optimize(c, iters1, res->stats)) != ORBX_OK) return rc;       // :863-864 (LBA), :247 (BundleAdjustment)
         if (secondStage && !(stop && *stop)) {
             // :880-912: the outlier flags stay on the device, the second stage starts from them (k_stage_prep)
-            hipLaunchKernelGGL(k_classify, dim3(gEc), dim3(256), 0, h->stream, c.d, oa + dFlag, (double *)nullptr, (DPose *)nullptr, (double *)nullptr);
+            hipLaunchKernelGGL(k_classify, dim3(gEc), dim3(256), 0, h->stream, c.d, oa + L.dFlag, (double *)nullptr, (DPose *)nullptr, (double *)nullptr);
             LCHECK();
-            c.stageFlags = oa + dFlag;
+            c.stageFlags = oa + L.dFlag;
             c.robust = 0;
             if ((rc = optimize(c, 10, res->stats + 4)) != ORBX_OK) return rc;   // :916-917
         }
@@ -3183,23 +3268,12 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
     ORBX_HIP_CHECK(hipEventRecord(h->ev1, s));
     h->timed = true;
     // :921-958: final classification, chi2 and estimates in one kernel and one copy
-    hipLaunchKernelGGL(k_classify, dim3(gEc), dim3(256), 0, h->stream, c.d, oa + dFlag, res->edge_chi2 ? (double *)(oa + dChi) : (double *)nullptr, (DPose *)(oa + dPose),
-                       (double *)(oa + dPt));
+    hipLaunchKernelGGL(k_classify, dim3(gEc), dim3(256), 0, h->stream, c.d, oa + L.dFlag, res->edge_chi2 ? (double *)(oa + L.dChi) : (double *)nullptr, (DPose *)(oa + L.dPose),
+                       (double *)(oa + L.dPt));
     LCHECK();
-    ORBX_HIP_CHECK(hipMemcpyAsync(io, oa, outBytes, hipMemcpyDeviceToHost, h->stream));
+    ORBX_HIP_CHECK(hipMemcpyAsync(io, oa, L.outEnd, hipMemcpyDeviceToHost, h->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
-    memcpy(res->edge_outlier, io + dFlag, (size_t)E);
-    if (res->edge_chi2) memcpy(res->edge_chi2, io + dChi, (size_t)E * 8);
-    const DPose *pose = (const DPose *)(io + dPose);
-    const double *pt = (const double *)(io + dPt);                  // final estimates (pinned read-back)
-    for (int k = 0; k < K; k++) {                                             // Converter::toCvMat(SE3Quat)
-        double R[9];
-        quat_to_R(pose[k].q, R);
-        float *o = res->poses + 16 * (size_t)k;
-        for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) o[4 * i + j] = (float)R[3 * i + j]; o[4 * i + 3] = (float)pose[k].t[i]; }
-        o[12] = o[13] = o[14] = 0.f; o[15] = 1.f;
-    }
-    for (int i = 0; i < 3 * P; i++) res->points[i] = (float)pt[i];
+    lba_write_result(io, L, K, P, E, res);
     return ORBX_OK;
 }
 
@@ -3306,41 +3380,13 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
     return ORBX_OK;
 }
 
-extern "C" int orbx_lba_last_timing(orbx_lba *h, float *device_ms, double *flops)
-{
-    if (!h) { orbx_set_error("NULL handle"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no solve yet"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
-    if (device_ms) ORBX_HIP_CHECK(hipEventElapsedTime(device_ms, h->ev0, h->ev1));
-    if (flops) *flops = h->flops;
-    return ORBX_OK;
-}
+extern "C" int orbx_lba_last_timing(orbx_lba *h, float *device_ms, double *flops) { return lba_last_timing(h, device_ms, flops); }
+
 // ---- batched LocalBundleAdjustment: N independent windows, one launch chain ----
-struct orbx_lba_batch {
-    int device = 0, maxW = 0, maxK = 0, maxP = 0, maxE = 0;
-    int numCU = 256;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    double flops = 0, seq = 0;
+struct orbx_lba_batch : LbaCore {
     int launches = 0;                    // kernel launches of the last call (tools/lba_batch_rate.py)
-    // per-window regions of the handle's capacities (maxK / maxP / maxE), window w at w times the region
-    OrbxDevBuf<DPose> pose, poseBak;
-    OrbxDevBuf<double> pt, ptBak, intr, obs, info, err, rchi, edgeBlk, Hpp, bp, Hll, bl, Dinv, Ddb, bs, xp, xl, red, ywork, ysol, diagInv, spPart, partChi, partL, bsPart;
-    OrbxDevBuf<int> ep, ek, ptStart, ptEdges, kfStart, kfEdges, poseIdx, ptIdx, okFlag, ptTmp, fillP, pActF, lActF, kfRowS0, kfRowN, ptPi;
-    OrbxDevBuf<uint8_t> stereo, active, fixedDev;
-    OrbxDevBuf<unsigned long long> scaleBits;
-    OrbxDevBuf<LmState> lm;
-    // sized per call
-    OrbxDevBuf<double> S, Lmat;
-    OrbxDevBuf<unsigned long long> Sacc;
-    OrbxDevBuf<int> csrCnt;
-    OrbxDevBuf<uint8_t> inArena, outArena, descDev;      // descDev: LbaWin[2][maxW] | UnpackSegs[maxW] | route lists [2][7][maxW]
-    uint8_t *hostIO = nullptr; size_t hostIOBytes = 0;    // pinned: the marshalled inputs on their way up, the results on their way down
-    uint8_t *hostDesc = nullptr;                          // pinned staging of descDev
-    double *rec = nullptr, *recDev = nullptr;             // mapped: 16 doubles per window, the LM record of k_stage_index / k_lm_begin / k_lm_decide
-    int *stopW = nullptr, *stopWDev = nullptr;            // mapped: the windows' stop words as the device sees them (16 ints apart)
+    OrbxDevBuf<uint8_t> descDev;         // LbaWin[2][maxW] | UnpackSegs[maxW] | route lists [2][7][maxW]
+    uint8_t *hostDesc = nullptr;         // pinned staging of descDev
 };
 
 namespace {
@@ -3351,23 +3397,9 @@ size_t batch_desc_bytes(int maxW) { return (size_t)2 * maxW * sizeof(LbaWin) + (
 extern "C" void orbx_lba_batch_destroy(orbx_lba_batch *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->pose.release(); h->poseBak.release();
-    h->pt.release(); h->ptBak.release(); h->intr.release(); h->obs.release(); h->info.release(); h->err.release(); h->rchi.release(); h->edgeBlk.release(); h->Hpp.release(); h->bp.release();
-    h->Hll.release(); h->bl.release(); h->Dinv.release(); h->Ddb.release(); h->bs.release(); h->xp.release(); h->xl.release(); h->red.release(); h->ywork.release(); h->ysol.release();
-    h->diagInv.release(); h->spPart.release(); h->partChi.release(); h->partL.release(); h->bsPart.release();
-    h->ep.release(); h->ek.release(); h->ptStart.release(); h->ptEdges.release(); h->kfStart.release(); h->kfEdges.release(); h->poseIdx.release(); h->ptIdx.release(); h->okFlag.release();
-    h->ptTmp.release(); h->fillP.release(); h->pActF.release(); h->lActF.release(); h->kfRowS0.release(); h->kfRowN.release(); h->ptPi.release();
-    h->stereo.release(); h->active.release(); h->fixedDev.release(); h->scaleBits.release(); h->lm.release();
-    h->S.release(); h->Lmat.release(); h->Sacc.release(); h->csrCnt.release(); h->inArena.release(); h->outArena.release(); h->descDev.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->hostIO) (void)hipHostFree(h->hostIO);
+    lba_close(h);
+    h->descDev.release();
     if (h->hostDesc) (void)hipHostFree(h->hostDesc);
-    if (h->rec) (void)hipHostFree(h->rec);
-    if (h->stopW) (void)hipHostFree(h->stopW);
     delete h;
 }
 
@@ -3377,39 +3409,12 @@ extern "C" int orbx_lba_batch_create(int device, int max_windows, int max_keyfra
     *out = nullptr;
     // 6 K <= CHOL_LDS_X: the reduced system of every window stays on the LDS paths (Schur rows, back-substitution)
     if (6 * max_keyframes > CHOL_LDS_X) { orbx_set_error("max_keyframes %d exceeds the batch limit %d", max_keyframes, CHOL_LDS_X / 6); return ORBX_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
     orbx_lba_batch *h = new orbx_lba_batch();
-    h->device = device; h->maxW = max_windows; h->maxK = max_keyframes; h->maxP = max_points; h->maxE = max_edges;
-    { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev0);
-    (void)hipEventCreate(&h->ev1);
-    const size_t W = (size_t)max_windows;
-    if (hipHostMalloc((void **)&h->rec, W * 16 * sizeof(double), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->recDev, h->rec, 0) != hipSuccess ||
-        hipHostMalloc((void **)&h->stopW, W * 16 * sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->stopWDev, h->stopW, 0) != hipSuccess ||
-        hipHostMalloc((void **)&h->hostDesc, batch_desc_bytes(max_windows), hipHostMallocDefault) != hipSuccess) {
-        orbx_lba_batch_destroy(h); orbx_set_error("hipHostMalloc failed"); return ORBX_ERR_HIP;
-    }
-    for (size_t i = 0; i < W * 16; i++) { h->rec[i] = 0; h->stopW[i] = 0; }
-    const size_t K = (size_t)max_keyframes, P = (size_t)max_points, E = (size_t)max_edges, n6 = 6 * K;
-    int rc = 0;
-    rc = rc ? rc : h->pose.ensure(W * K); rc = rc ? rc : h->poseBak.ensure(W * K); rc = rc ? rc : h->pt.ensure(W * 3 * P); rc = rc ? rc : h->ptBak.ensure(W * 3 * P);
-    rc = rc ? rc : h->intr.ensure(W * 5 * K); rc = rc ? rc : h->obs.ensure(W * 3 * E); rc = rc ? rc : h->info.ensure(W * E); rc = rc ? rc : h->err.ensure(W * 3 * E);
-    rc = rc ? rc : h->rchi.ensure(W * E); rc = rc ? rc : h->edgeBlk.ensure(W * 36 * E);      // Hpl | BD (the fused form writes no eb_rest)
-    rc = rc ? rc : h->Hpp.ensure(W * 36 * K); rc = rc ? rc : h->bp.ensure(W * n6); rc = rc ? rc : h->Hll.ensure(W * 9 * P); rc = rc ? rc : h->bl.ensure(W * 3 * P);
-    rc = rc ? rc : h->Dinv.ensure(W * 9 * P); rc = rc ? rc : h->Ddb.ensure(W * 3 * P); rc = rc ? rc : h->bs.ensure(W * n6); rc = rc ? rc : h->xp.ensure(W * n6);
-    rc = rc ? rc : h->xl.ensure(W * 3 * P); rc = rc ? rc : h->red.ensure(W * 16); rc = rc ? rc : h->ywork.ensure(W * n6); rc = rc ? rc : h->ysol.ensure(W * n6);
-    rc = rc ? rc : h->diagInv.ensure(W * (n6 + CNB)); rc = rc ? rc : h->spPart.ensure(W * K * SP_SPLIT * 27);
-    rc = rc ? rc : h->partChi.ensure(W * ((E + 255) / 256)); rc = rc ? rc : h->partL.ensure(W * ((std::max(K, 16 * P) + 255) / 256)); rc = rc ? rc : h->bsPart.ensure(W * K * 32 * 6);
-    rc = rc ? rc : h->ep.ensure(W * E); rc = rc ? rc : h->ek.ensure(W * E); rc = rc ? rc : h->ptStart.ensure(W * (P + 1)); rc = rc ? rc : h->ptEdges.ensure(W * E);
-    rc = rc ? rc : h->kfStart.ensure(W * (K + 1)); rc = rc ? rc : h->kfEdges.ensure(W * E); rc = rc ? rc : h->poseIdx.ensure(W * K); rc = rc ? rc : h->ptIdx.ensure(W * P);
-    rc = rc ? rc : h->okFlag.ensure(W * 16); rc = rc ? rc : h->ptTmp.ensure(W * E); rc = rc ? rc : h->fillP.ensure(W * P); rc = rc ? rc : h->pActF.ensure(W * K);
-    rc = rc ? rc : h->lActF.ensure(W * P); rc = rc ? rc : h->kfRowS0.ensure(W * E); rc = rc ? rc : h->kfRowN.ensure(W * E); rc = rc ? rc : h->ptPi.ensure(W * E);
-    rc = rc ? rc : h->stereo.ensure(W * E); rc = rc ? rc : h->active.ensure(W * E); rc = rc ? rc : h->fixedDev.ensure(W * K); rc = rc ? rc : h->scaleBits.ensure(W * 8);
-    rc = rc ? rc : h->lm.ensure(W); rc = rc ? rc : h->descDev.ensure(batch_desc_bytes(max_windows));
+    int rc = lba_open(h, device, max_windows, max_keyframes, max_points, max_edges);
+    if (!rc && hipHostMalloc((void **)&h->hostDesc, batch_desc_bytes(max_windows), hipHostMallocDefault) != hipSuccess) { orbx_set_error("hipHostMalloc failed"); rc = ORBX_ERR_HIP; }
+    // (the fused form writes no eb_rest: Hpl | BD; the windows' okFlag a cache line apart)
+    rc = rc ? rc : h->ensure((size_t)max_windows, (size_t)max_keyframes, (size_t)max_points, (size_t)max_edges, false, 16);
+    rc = rc ? rc : h->descDev.ensure(batch_desc_bytes(max_windows));
     if (rc) { orbx_lba_batch_destroy(h); return rc; }
     *out = h;
     return ORBX_OK;
@@ -3422,38 +3427,8 @@ struct BatchWinHost {
     int K, P, E, nChunk, spSplit, nPose0, nPt0;
     bool stage1, stage2, run1, run2;
     int nPose2, nPt2, nAct2;
-    size_t in, oPose, oIntr, oPt, oObs, oInfo, oEp, oEk, oPs, oKs, oFx;      // input layout (absolute offsets in the arena)
-    size_t out, dFlag, dChi, dPose, dPt;                                          // result layout (absolute offsets)
+    LbaLayout L;      // absolute offsets in the arenas of the batch
 };
-
-// Waits until the LM record of every listed window has reached `seq`, mirroring the windows' stop flags into their device-visible words
-int batch_wait(orbx_lba_batch *h, const std::vector<int> &wins, double seq, const volatile uint8_t *const *stops)
-{
-    for (unsigned spins = 1;; spins++) {
-        bool all = true;
-        for (int w : wins) {
-            if (*(volatile double *)(h->rec + 16 * (size_t)w + 15) < seq) all = false;
-            const volatile uint8_t *s = stops ? stops[w] : nullptr;
-            if (s && *s && !h->stopW[16 * (size_t)w]) { h->stopW[16 * (size_t)w] = 1; std::atomic_thread_fence(std::memory_order_release); }
-        }
-        if (all) break;
-        if ((spins & 0x3fff) == 0) {
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipSuccess) {
-                bool done = true;
-                for (int w : wins) done = done && *(volatile double *)(h->rec + 16 * (size_t)w + 15) >= seq;
-                if (done) break;
-                orbx_set_error("LBA batch: the stream drained without the trial results");
-                return ORBX_ERR_HIP;
-            }
-            if (q != hipErrorNotReady) { orbx_set_error("LBA batch: %s", hipGetErrorString(q)); return ORBX_ERR_HIP; }
-        }
-        if (spins > 4096 && (spins & 63) == 0) std::this_thread::yield();
-        __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return ORBX_OK;
-}
 
 #define BLAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); h->launches++; } while (0)
 
@@ -3513,8 +3488,8 @@ int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<Lb
                 for (int w : live) {
                     const int n = hw[w].nP6;
                     if (n < CHOL_MULTI_MIN_N || p0 >= n) continue;
-                    const int nb = std::min(CNB, n - p0), below = n - p0 - nb, nPW = std::max(1, (below + CHOL_RPW - 1) / CHOL_RPW);
-                    const int T1 = p0 > 0 ? (n - p0 + CNB - 1) / CNB - 1 : 0;
+                    int nPW, T1;
+                    lba_chol_panel_grid(n, p0, nPW, T1);
                     g = std::max(g, nPW + T1 * T1);
                 }
                 BLAUNCH((k_chol_step<false, true>), dim3((unsigned)g, 1, (unsigned)nList[RT_MULTI]), dim3(256), 0, s, nullptr, nullptr, 0, p0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
@@ -3549,7 +3524,7 @@ int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<Lb
         if ((rc = trialChol()) != ORBX_OK) return rc;
         if ((rc = trialRest(&seqT)) != ORBX_OK) return rc;
         if ((rc = trialSchur()) != ORBX_OK) return rc;      // of trial t + 1, speculatively
-        if ((rc = batch_wait(h, live, seqT, stops)) != ORBX_OK) return rc;
+        if ((rc = lba_wait(h, "LBA batch", live.data(), (int)live.size(), seqT, stops)) != ORBX_OK) return rc;
         std::vector<int> still;
         for (int w : live) if (h->rec[16 * (size_t)w + 13] == 0.0) still.push_back(w);
         live.swap(still);
@@ -3571,48 +3546,25 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
     if (!h || !probs || !res) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
     if (N < 1 || N > h->maxW) { orbx_set_error("%d windows outside the handle's capacity 1..%d", N, h->maxW); return ORBX_ERR_CAPACITY; }
     // ---- every window checked (and marshalled) before anything is launched or any result written
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     std::vector<BatchWinHost> wh(N);
     size_t inBytes = 0, outBytes = 0;
     for (int w = 0; w < N; w++) {
-        const orbx_lba_problem *p = probs + w;
-        const orbx_lba_result *r = res + w;
-        if (!r->poses || !r->points || !r->edge_outlier) { orbx_set_error("window %d: NULL result array", w); return ORBX_ERR_ARG; }
-        const int K = p->num_keyframes, P = p->num_points, E = p->num_edges;
-        if (K < 1 || P < 1 || E < 1 || K > h->maxK || P > h->maxP || E > h->maxE) {
-            orbx_set_error("window %d: problem size %d/%d/%d outside the handle's capacity %d/%d/%d", w, K, P, E, h->maxK, h->maxP, h->maxE);
-            return ORBX_ERR_CAPACITY;
-        }
-        if (!p->poses || !p->fixed || !p->intrinsics || !p->points || !p->edge_point || !p->edge_keyframe || !p->edge_obs || !p->edge_inv_sigma2) {
-            orbx_set_error("window %d: NULL problem array", w);
-            return ORBX_ERR_ARG;
-        }
+        int rc = lba_check_problem(h, probs + w, res + w, w);
+        if (rc) return rc;
         BatchWinHost &x = wh[w];
-        x.K = K; x.P = P; x.E = E; x.nChunk = (E + CSR_CHUNK - 1) / CSR_CHUNK;
-        x.in = inBytes;
-        x.oPose = x.in; x.oIntr = x.oPose + pad((size_t)K * sizeof(DPose)); x.oPt = x.oIntr + pad((size_t)5 * K * 8); x.oObs = x.oPt + pad((size_t)3 * P * 8);
-        x.oInfo = x.oObs + pad((size_t)3 * E * 4); x.oEp = x.oInfo + pad((size_t)E * 4); x.oEk = x.oEp + pad((size_t)E * 4); x.oPs = x.oEk + pad((size_t)E * 4);
-        x.oKs = x.oPs + pad(((size_t)P + 1) * 4); x.oFx = x.oKs + pad(((size_t)K + 1) * 4);
-        inBytes = x.oFx + pad((size_t)K);
-        x.out = outBytes;
-        x.dFlag = x.out; x.dChi = x.dFlag + pad((size_t)E); x.dPose = x.dChi + pad((size_t)E * 8); x.dPt = x.dPose + pad((size_t)K * sizeof(DPose));
-        outBytes = x.dPt + pad((size_t)3 * P * 8);
+        x.K = probs[w].num_keyframes; x.P = probs[w].num_points; x.E = probs[w].num_edges; x.nChunk = (x.E + CSR_CHUNK - 1) / CSR_CHUNK;
+        x.L = lba_layout(x.K, x.P, x.E, inBytes, outBytes);
+        inBytes = x.L.inEnd; outBytes = x.L.outEnd;
     }
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     {
-        const size_t need = std::max(inBytes, outBytes);
-        if (need > h->hostIOBytes) {
-            ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
-            if (h->hostIO) (void)hipHostFree(h->hostIO);
-            h->hostIO = nullptr; h->hostIOBytes = 0;
-            ORBX_HIP_CHECK(hipHostMalloc((void **)&h->hostIO, need, hipHostMallocDefault));
-            h->hostIOBytes = need;
-        }
+        int rc = lba_grow_pinned(h, std::max(inBytes, outBytes));
+        if (rc) return rc;
     }
     uint8_t *io = h->hostIO;
-    for (int w = 0; w < N; w++) {      // float boundary -> double state, row lengths of the adjacency lists, edge ids checked (lba_run's marshalling)
+    for (int w = 0; w < N; w++) {      // float boundary -> double state, row lengths of the adjacency lists, edge ids checked
         BatchWinHost &x = wh[w];
-        const int bad = lba_marshal(probs + w, io, x.oPose, x.oIntr, x.oPt, x.oObs, x.oInfo, x.oEp, x.oEk, x.oPs, x.oKs, x.oFx, x.nPose0, x.nPt0, x.spSplit);
+        const int bad = lba_marshal(probs + w, io, x.L, x.nPose0, x.nPt0, x.spSplit);
         if (bad >= 0) { orbx_set_error("window %d: edge %d references a vertex out of range", w, bad); return ORBX_ERR_ARG; }
     }
     // ---- from here on nothing fails for a reason of the input
@@ -3644,11 +3596,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
     UnpackSegs *dSeg = (UnpackSegs *)(dD2 + mw);
     int *dL1 = (int *)(dSeg + mw), *dL2 = dL1 + RT_N * mw;
     std::vector<LbaWin> hw1(N), hw2(N);
-    const float thMono = (float)sqrt(5.991), thStereo = (float)sqrt(7.815);
-    Huber hub;
-    hub.dMono = thMono; hub.dStereo = thStereo;
-    hub.dsqrMono = (double)(float)((double)thMono * (double)thMono);
-    hub.dsqrStereo = (double)(float)((double)thStereo * (double)thStereo);
+    const Huber hub = lba_huber(5.991);
     const size_t K = (size_t)h->maxK, P = (size_t)h->maxP, E = (size_t)h->maxE, n6 = 6 * K;
     uint8_t *oa = h->outArena.p;
     for (int w = 0; w < N; w++) {
@@ -3656,18 +3604,14 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         const size_t W = (size_t)w;
         LbaWin v;
         memset(&v, 0, sizeof v);
-        LbaDev &d = v.d;
-        d.K = x.K; d.P = x.P; d.E = x.E;
-        d.pose = h->pose.p + W * K; d.pt = h->pt.p + W * 3 * P; d.intr = h->intr.p + W * 5 * K; d.ep = h->ep.p + W * E; d.ek = h->ek.p + W * E;
-        d.obs = h->obs.p + W * 3 * E; d.stereo = h->stereo.p + W * E; d.info = h->info.p + W * E; d.active = h->active.p + W * E;
-        d.poseIdx = h->poseIdx.p + W * K; d.ptIdx = h->ptIdx.p + W * P; d.err = h->err.p + W * 3 * E; d.rchi = h->rchi.p + W * E; d.edgeBlk = h->edgeBlk.p + W * 36 * E;
+        v.d = h->views(W, x.K, x.P, x.E);
         v.hub = hub; v.robust = 1;
         v.spSplit = x.spSplit; v.nChunk = x.nChunk; v.iters = 5; v.stamp = 1;
         v.ptStart = h->ptStart.p + W * (P + 1); v.ptEdges = h->ptEdges.p + W * E; v.kfStart = h->kfStart.p + W * (K + 1); v.kfEdges = h->kfEdges.p + W * E;
         v.kfRowS0 = h->kfRowS0.p + W * E; v.kfRowN = h->kfRowN.p + W * E; v.ptPi = h->ptPi.p + W * E; v.csrCnt = h->csrCnt.p + W * cntStride;
         v.ptTmp = h->ptTmp.p + W * E; v.fillP = h->fillP.p + W * P; v.pActF = h->pActF.p + W * K; v.lActF = h->lActF.p + W * P; v.okFlag = h->okFlag.p + W * 16;
         v.poseIdx = h->poseIdx.p + W * K; v.ptIdx = h->ptIdx.p + W * P;
-        v.fixed = h->fixedDev.p + W * K; v.active = h->active.p + W * E; v.flag = oa + x.dFlag; v.stageFlags = nullptr;
+        v.fixed = h->fixedDev.p + W * K; v.active = h->active.p + W * E; v.flag = oa + x.L.dFlag; v.stageFlags = nullptr;
         v.Hll = h->Hll.p + W * 9 * P; v.bl = h->bl.p + W * 3 * P; v.Hpp = h->Hpp.p + W * 36 * K; v.bp = h->bp.p + W * n6; v.spPart = h->spPart.p + W * K * SP_SPLIT * 27;
         v.Dinv = h->Dinv.p + W * 9 * P; v.Ddb = h->Ddb.p + W * 3 * P; v.S = h->S.p + W * nnStride; v.L = h->Lmat.p + W * nnStride;
         v.ywork = h->ywork.p + W * n6; v.ysol = h->ysol.p + W * n6; v.diagInv = h->diagInv.p + W * (n6 + CNB); v.xp = h->xp.p + W * n6; v.xl = h->xl.p + W * 3 * P;
@@ -3675,7 +3619,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         v.bsPart = h->bsPart.p + W * K * 32 * 6; v.red = h->red.p + W * 16; v.poseBak = h->poseBak.p + W * K;
         v.Sacc = h->Sacc.p + W * nnStride; v.scaleBits = h->scaleBits.p + W * 8; v.st = h->lm.p + W;
         v.host = h->recDev + 16 * W; v.stop = (const volatile int *)(h->stopWDev + 16 * W);
-        v.chiOut = res[w].edge_chi2 ? (double *)(oa + x.dChi) : nullptr; v.poseOut = (DPose *)(oa + x.dPose); v.ptOut = (double *)(oa + x.dPt);
+        v.chiOut = res[w].edge_chi2 ? (double *)(oa + x.L.dChi) : nullptr; v.poseOut = (DPose *)(oa + x.L.dPose); v.ptOut = (double *)(oa + x.L.dPt);
         // stage 1: no flags, the vertex counts are the host's
         const volatile uint8_t *sf = stops ? stops[w] : nullptr;
         wh[w].stage1 = !(sf && *sf);
@@ -3684,21 +3628,9 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         wh[w].run1 = wh[w].stage1 && x.nPose0 + x.nPt0 > 0;
         v.run = wh[w].run1 ? 1 : 0;
         v.bsDev = v.nP6 >= CHOL_MULTI_MIN_N ? v.ywork : h->bs.p + W * n6;
-        {
-            v.ySplit = lba_schur_ysplit(v.nP6, x.K, h->numCU);
-        }
+        v.ySplit = lba_schur_ysplit(v.nP6, x.K, h->numCU);
         hw1[w] = v;
-        // segments of k_unpack (lba_run's list)
-        UnpackSegs &sg = hSeg[w];
-        int ns = 0;
-        auto seg = [&](size_t off, void *dst, size_t bytes, int kind = 0) { sg.src[ns] = off; sg.dst[ns] = dst; sg.bytes[ns] = bytes; sg.kind[ns] = kind; ns++; };
-        seg(x.oPose, d.pose, (size_t)x.K * sizeof(DPose)); seg(x.oPt, d.pt, (size_t)3 * x.P * 8); seg(x.oIntr, (void *)d.intr, (size_t)5 * x.K * 8);
-        seg(x.oObs, (void *)d.obs, (size_t)3 * x.E, 1); seg(x.oInfo, (void *)d.info, (size_t)x.E, 1); seg(x.oObs, (void *)d.stereo, (size_t)x.E, 2);
-        seg(x.oEp, (void *)d.ep, (size_t)x.E * 4); seg(x.oEk, (void *)d.ek, (size_t)x.E * 4);
-        seg(x.oPs, v.ptStart, ((size_t)x.P + 1) * 4); seg(x.oKs, v.kfStart, ((size_t)x.K + 1) * 4); seg(x.oFx, v.fixed, (size_t)x.K);
-        seg(~(size_t)0, d.err, (size_t)x.E * 3 * 8);
-        seg(~(size_t)0, v.fillP, (size_t)x.P * 4); seg(~(size_t)0, v.pActF, (size_t)x.K * 4); seg(~(size_t)0, v.lActF, (size_t)x.P * 4);
-        sg.n = ns;
+        lba_unpack_segs(x.L, v.d, v.ptStart, v.kfStart, v.fixed, v.fillP, v.pActF, v.lActF, hSeg[w]);
     }
     // route lists of a stage: windows whose LM runs, by the route of their n
     auto buildLists = [&](const std::vector<LbaWin> &hw, int *hl, int (&cnt)[RT_N]) {
@@ -3765,7 +3697,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         LCHECK();
         std::vector<int> in2;
         for (int w = 0; w < N; w++) if (wh[w].stage2) in2.push_back(w);
-        int rc = batch_wait(h, in2, seq, stops);      // the stage's vertex counts, once for the whole batch
+        int rc = lba_wait(h, "LBA batch", in2.data(), (int)in2.size(), seq, stops);      // the stage's vertex counts, once for the whole batch
         if (rc) return rc;
         for (int w : in2) {
             const double *r = h->rec + 16 * (size_t)w;
@@ -3796,18 +3728,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         const BatchWinHost &x = wh[w];
         orbx_lba_result *r = res + w;
         for (int i = 0; i < 4; i++) { r->stats[i] = st1[4 * w + i]; r->stats[4 + i] = st2[4 * w + i]; }
-        memcpy(r->edge_outlier, io + x.dFlag, (size_t)x.E);
-        if (r->edge_chi2) memcpy(r->edge_chi2, io + x.dChi, (size_t)x.E * 8);
-        const DPose *pose = (const DPose *)(io + x.dPose);
-        const double *pt = (const double *)(io + x.dPt);
-        for (int k = 0; k < x.K; k++) {
-            double R[9];
-            quat_to_R(pose[k].q, R);
-            float *o = r->poses + 16 * (size_t)k;
-            for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) o[4 * i + j] = (float)R[3 * i + j]; o[4 * i + 3] = (float)pose[k].t[i]; }
-            o[12] = o[13] = o[14] = 0.f; o[15] = 1.f;
-        }
-        for (int i = 0; i < 3 * x.P; i++) r->points[i] = (float)pt[i];
+        lba_write_result(io, x.L, x.K, x.P, x.E, r);
     }
     return ORBX_OK;
 }
@@ -3818,16 +3739,7 @@ extern "C" int orbx_lba_solve_batch(orbx_lba_batch *h, int num_windows, const or
     return lba_run_batch(h, num_windows, problems, stop_flags, results);
 }
 
-extern "C" int orbx_lba_batch_last_timing(orbx_lba_batch *h, float *device_ms, double *flops)
-{
-    if (!h) { orbx_set_error("NULL handle"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no solve yet"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
-    if (device_ms) ORBX_HIP_CHECK(hipEventElapsedTime(device_ms, h->ev0, h->ev1));
-    if (flops) *flops = h->flops;
-    return ORBX_OK;
-}
+extern "C" int orbx_lba_batch_last_timing(orbx_lba_batch *h, float *device_ms, double *flops) { return lba_last_timing(h, device_ms, flops); }
 
 // developer tap (tools/lba_batch_rate.py; not part of include/orbx.h): kernel launches of the handle's last batch call
 extern "C" int orbx_debug_lba_batch_launches(orbx_lba_batch *h) { return h ? h->launches : -1; }
