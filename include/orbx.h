@@ -823,6 +823,49 @@ void orbx_pose_optimizer_destroy(orbx_pose_optimizer *h);
 int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_problem *problem, float *poses_out, uint8_t *outlier,
                            int32_t *inliers, double *stats);
 
+
+/* ------------------------------------------------------------------------------------
+ * MapPoint refresh  ==  MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth
+ * (reference src/MapPoint.cc:359-439, 477-521; the loops of LocalMapping::ProcessNewKeyFrame /
+ * CreateNewMapPoints / SearchInNeighbors, Tracking::CreateNewKeyFrame, the bundle adjustments and
+ * loop correction) for M points with ragged observation lists, in one launch chain.
+ * Observations are CSR: those of point p at obs_offset[p] .. obs_offset[p+1], in the CALLER's
+ * order (the order of std::map<KeyFrame*, size_t>, which the reference iterates); it is never
+ * reordered.  desc_valid[t] == 0 marks an observer whose keyframe isBad(): skipped for the
+ * descriptor choice (:384), still counted for the normal, as in the reference.
+ *   best_obs / best_median: with N valid descriptors in list order and row i = the Hamming
+ *     distances of descriptor i to all N (self-distance included), the median of a row is its
+ *     element at sorted position (N-1)/2; best_obs = the position IN THE POINT'S FULL LIST of the
+ *     lowest i with the smallest median, best_median that median (0..256).  N == 0: -1, INT_MAX
+ *     (the caller keeps the old descriptor).
+ *   normal / max_dist / min_dist: the reference's float / double steps on the project's OpenCV
+ *     stand-in, bit for bit, the float sum of the unit vectors taken sequentially in list order.
+ *     Stock OpenCV's Mat / double multiplies by a float reciprocal instead of dividing in double:
+ *     parity unpinned for the quotient.
+ *   updated[p] = 0 for a point without observations (the reference returns early: nothing of it
+ *     is to be written back; its other outputs are unspecified), 1 otherwise.
+ * At most 65535 observations per point (ORBX_ERR_CAPACITY beyond).  Synchronous: results are in
+ * the caller's arrays on return. */
+typedef struct orbx_mappoint_ops orbx_mappoint_ops;
+typedef struct orbx_mappoint_batch {      /* host memory */
+    int num_points, num_obs;
+    const int32_t *obs_offset;            /* [M+1], obs_offset[0] == 0, non-decreasing, obs_offset[M] == num_obs */
+    const uint8_t *desc, *desc_valid;     /* [T*32] pKF->mDescriptors.row(idx); [T] !pKF->isBad(), NULL = all valid */
+    const float *cam_center;              /* [T*3] pKF->GetCameraCenter()                                         */
+    const float *pos, *ref_center;        /* [M*3] mWorldPos; mpRefKF->GetCameraCenter()                          */
+    const float *ref_scale, *top_scale;   /* [M]   mpRefKF->mvScaleFactors[level of the observation]; [nLevels-1] */
+} orbx_mappoint_batch;
+typedef struct orbx_mappoint_result {     /* any may be NULL */
+    int32_t *best_obs, *best_median;      /* [M] */
+    float *normal, *max_dist, *min_dist;  /* [M*3], [M], [M] */
+    uint8_t *updated;                     /* [M] */
+} orbx_mappoint_result;
+int orbx_mappoint_ops_create(int device, int max_points, int max_obs_total, orbx_mappoint_ops **out);
+void orbx_mappoint_ops_destroy(orbx_mappoint_ops *h);
+int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_batch *b, const orbx_mappoint_result *r);
+/* device time of the last call's kernels and how many were launched (one per non-empty size class) */
+int orbx_mappoint_last_timing(orbx_mappoint_ops *h, float *kernel_ms, int *launches);
+
 #ifdef __cplusplus
 }
 #endif

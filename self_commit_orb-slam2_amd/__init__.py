@@ -1316,3 +1316,69 @@ class BatchOptimizer:
         fl = ctypes.c_double()
         _check(self._L.orbx_lba_batch_last_timing(self._h, ctypes.byref(ms), ctypes.byref(fl)))
         return ms.value, fl.value
+
+
+class MapPointBatch(ctypes.Structure):
+    _fields_ = [("num_points", ctypes.c_int), ("num_obs", ctypes.c_int), ("obs_offset", ctypes.c_void_p), ("desc", ctypes.c_void_p), ("desc_valid", ctypes.c_void_p),
+                ("cam_center", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("ref_center", ctypes.c_void_p), ("ref_scale", ctypes.c_void_p), ("top_scale", ctypes.c_void_p)]
+
+
+class MapPointResult(ctypes.Structure):
+    _fields_ = [("best_obs", ctypes.c_void_p), ("best_median", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("max_dist", ctypes.c_void_p), ("min_dist", ctypes.c_void_p),
+                ("updated", ctypes.c_void_p)]
+
+
+class MapPointOps:
+    """MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:359-439, 477-521) for a batch of
+    points with ragged observation lists (orbx_mappoint_refresh): one launch chain, the observations of a point in the caller's order."""
+
+    def __init__(self, max_points, max_obs_total, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_mappoint_ops_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_mappoint_ops_destroy.argtypes = [vp]
+        L.orbx_mappoint_ops_destroy.restype = None
+        L.orbx_mappoint_refresh.argtypes = [vp, ctypes.POINTER(MapPointBatch), ctypes.POINTER(MapPointResult)]
+        L.orbx_mappoint_last_timing.argtypes = [vp, vp, vp]
+        self._h = vp()
+        _check(L.orbx_mappoint_ops_create(device, max_points, max_obs_total, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_mappoint_ops_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def refresh(self, obs_offset, desc, cam_center, pos, ref_center, ref_scale, top_scale, desc_valid=None):
+        """obs_offset (M+1) int32; desc (T,32) uint8; cam_center (T,3); pos, ref_center (M,3); ref_scale, top_scale (M); desc_valid (T) uint8 or
+        None (all valid).  Returns dict(best_obs, best_median (M) int32; normal (M,3), max_dist, min_dist (M) float32; updated (M) uint8)."""
+        off = np.ascontiguousarray(obs_offset, np.int32)
+        M = len(off) - 1
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        T = len(d)
+        cam = np.ascontiguousarray(cam_center, np.float32).reshape(-1, 3)
+        ps, rc = np.ascontiguousarray(pos, np.float32).reshape(-1, 3), np.ascontiguousarray(ref_center, np.float32).reshape(-1, 3)
+        rs, ts = np.ascontiguousarray(ref_scale, np.float32).reshape(-1), np.ascontiguousarray(top_scale, np.float32).reshape(-1)
+        dv = None if desc_valid is None else np.ascontiguousarray(desc_valid, np.uint8).reshape(-1)
+        if M < 0 or len(cam) != T or (dv is not None and len(dv) != T) or any(len(a) != M for a in (ps, rc, rs, ts)):
+            raise ValueError("MapPointOps.refresh: array sizes do not agree")
+        B = MapPointBatch(M, T, off.ctypes.data, d.ctypes.data, None if dv is None else dv.ctypes.data, cam.ctypes.data, ps.ctypes.data, rc.ctypes.data,
+                          rs.ctypes.data, ts.ctypes.data)
+        o = dict(best_obs=np.zeros(M, np.int32), best_median=np.zeros(M, np.int32), normal=np.zeros((M, 3), np.float32), max_dist=np.zeros(M, np.float32),
+                 min_dist=np.zeros(M, np.float32), updated=np.zeros(M, np.uint8))
+        R = MapPointResult(*[o[k].ctypes.data for k in ("best_obs", "best_median", "normal", "max_dist", "min_dist", "updated")])
+        _check(self._L.orbx_mappoint_refresh(self._h, ctypes.byref(B), ctypes.byref(R)))
+        return o
+
+    def last_timing(self):
+        """(device ms of the last call's kernels, kernel launches)"""
+        ms = ctypes.c_float()
+        n = ctypes.c_int()
+        _check(self._L.orbx_mappoint_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
