@@ -111,6 +111,7 @@ struct orbx_extractor {
     int allocBatch = 0;
     // last run
     int lastBatch = 0;
+    bool lastPyrFast = false;         // the last batch ran the detector inside the pyramid band launches (k_pyr_band_fast); read by the tests' developer tap
     bool lastChunked = false;         // the last call was a host batch pipelined in chunks: the device holds its LAST chunk only, lastBatch = 0 (no device-side view)
     const uint8_t *lastImg0 = nullptr;
     int lastStride = 0;
@@ -407,6 +408,9 @@ int build_geometry(orbx_extractor *h, int W, int H)
     g.fcInBytes = g.fcPitch * (maxHCell + 6);
     g.fcScBytes = g.fcScPitch * (maxHCell + 2);
     g.fcLdsBytes = g.fcInBytes + g.fcScBytes + (int)align_up((size_t)maxWCell * maxHCell * 2, 16);
+    // k_pyr_band_fast plan (batches): the band launch of level l carries the level's detector cells, four waves per workgroup with an LDS region each;
+    // a launch's dynamic LDS is the larger of the two roles' (orbx_pyr_fast_lds), within the 48 KB that need no attribute
+    g.pyrFast = g.pyrBand && (size_t)ORBX_PF_WAVES * (size_t)g.fcLdsBytes <= 48 * 1024 ? 1 : 0;
     // the detector's cell table (ComputeKeyPointsOctTree's cell loop, src/ORBextractor.cc:1089-1123)
     h->fcHost.assign((size_t)cells, OrbxFcCell{});
     for (int l = 0; l < nl; l++) {
@@ -561,15 +565,22 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
     // them); ORBX_PYR_SPLIT=1 (read per call, A/B switch) keeps the split launches, 7 x k_resize ... k_blur behind the quadtree
     const char *es = getenv("ORBX_PYR_SPLIT");
     L.pyrBand = !tiled && h->geom.pyrBand && !(es && es[0] == '1');
+    // the detector of the first levels rides in their band launches (k_pyr_band_fast: launch l also runs level l's FAST cells, which need the unblurred level l alone);
+    // ORBX_FAST_SPLIT=1 (read per call, A/B switch), the parity taps and the profiling instantiation keep its own launch behind the pyramid
+    const char *ef = getenv("ORBX_FAST_SPLIT");
+    const bool pyrFast = L.pyrBand && orbx_pyr_fast_applies(L) && !(ef && ef[0] == '1');
+    const int nJoin = pyrFast ? std::min(ORBX_PF_JOIN_LEVELS, h->geom.nlevels) : 0;      // band launches that carry their level's detector cells
     if (L.pyrBand) {
         for (int l = 0; l < h->geom.nlevels; l++)
-            if ((rc = orbx_launch_pyr_band(L, l)) != ORBX_OK) return rc;
+            if ((rc = l < nJoin ? orbx_launch_pyr_band_fast(L, l) : orbx_launch_pyr_band(L, l)) != ORBX_OK) return rc;
     } else if (!tiled)
         for (int l = 1; l < h->geom.nlevels; l++)
             if ((rc = orbx_launch_resize(L, l)) != ORBX_OK) return rc;
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_PYR + 1], h->stream));
-    if ((rc = orbx_launch_fast_cells(L)) != ORBX_OK) return rc;   // FAST score + cell NMS fused; score map only for the parity taps
-    if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_FAST + 1], h->stream));
+    // FAST score + cell NMS fused; score map only for the parity taps.  The cells of the levels whose band launches carried the detector are done
+    L.fcCellFirst = nJoin < h->geom.nlevels ? h->geom.lv[nJoin].cellBase : h->geom.cellsPerFrame;
+    if (L.fcCellFirst < h->geom.cellsPerFrame && (rc = orbx_launch_fast_cells(L)) != ORBX_OK) return rc;
+    if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_FAST + 1], h->stream));      // (k_pyr_band_fast: the cells of the first levels are part of the pyramid span)
     if ((rc = orbx_launch_octree(L)) != ORBX_OK) return rc;
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_OCTREE + 1], h->stream));
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_ORIENT + 1], h->stream));      // (orientation is part of the descriptor kernel: this span is empty)
@@ -579,9 +590,12 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
     if ((rc = orbx_launch_orient_describe(L)) != ORBX_OK) return rc;
     if (prof) { ORBX_HIP_CHECK(hipEventRecord(ev[ST_DESC + 1], h->stream)); h->profCount++; }
     h->lastBatch = batch; h->lastImg0 = img0Dev; h->lastStride = stride; h->lastFramePitch = framePitch;
-    h->lastCombined = false; h->hostSynced = false; h->lastChunked = false;
+    h->lastCombined = false; h->hostSynced = false; h->lastChunked = false; h->lastPyrFast = pyrFast;
     return ORBX_OK;
 }
+
+// developer tap (tests/test_pyr_fast.py; not part of include/orbx.h): 1 when the handle's last batch ran the joint band + detector launches
+extern "C" int orbx_debug_last_batch_pyr_fast(orbx_extractor *h) { return h && h->lastPyrFast ? 1 : 0; }
 
 // host-side copies of a batch entry point (frames into pinned staging, results out of the pinned arena) on a few threads
 static int host_copy_threads()

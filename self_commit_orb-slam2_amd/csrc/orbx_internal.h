@@ -53,6 +53,7 @@ struct OrbxGeom {
     int fcInBytes, fcScBytes, fcLdsBytes;   /* LDS carve-up of k_fast_cells: input window, score tile, total */
     size_t pyrBytes;        /* bytes of levels 1.. of one frame */
     int pyrBand;            /* 1: every level has a k_pyr_band plan (the batch path blurs inside the pyramid chain) */
+    int pyrFast;            /* 1: the band launches carry the detector too (k_pyr_band_fast): pyrBand and four detector waves' LDS within 48 KB */
     uint32_t taps[7];
     int umax[16];
     OrbxLevel lv[ORBX_MAX_LEVELS];
@@ -70,6 +71,20 @@ static inline uint32_t orbx_band_div(int n)
     while ((1u << (S - 14)) < (uint32_t)n) S++;
     const uint32_t m = (uint32_t)((((uint64_t)1 << S) + (uint64_t)n - 1) / (uint64_t)n);
     return m | (S << 20);
+}
+
+/* k_pyr_band_fast (batches): launch l = the bands of level l + the detector blocks of level l, for the levels l < ORBX_PF_JOIN_LEVELS (58 % of the
+ * cells at 640x480; the small levels' launches are shorter than a detector wave's life and would wait for it - measured, profiles/pyr_fast_ab.json);
+ * the cells of the levels behind them keep the detector's own launch.  A detector block is ORBX_PF_WAVES waves of K cells
+ * each: wave w of block j takes cells cellBase + (ORBX_PF_WAVES j + w) K .. of level l, cut at the level's last cell; the launch's dynamic LDS is the
+ * larger of a band's rows and the detector waves' regions (tests/test_pyr_fast_plan.py restates both). */
+#define ORBX_PF_WAVES 4
+#define ORBX_PF_JOIN_LEVELS 2
+static inline int orbx_fast_blocks(int cells, int K) { return (cells + ORBX_PF_WAVES * K - 1) / (ORBX_PF_WAVES * K); }
+static inline size_t orbx_pyr_fast_lds(const OrbxGeom &g, int l)
+{
+    const size_t band = (size_t)(g.lv[l].bandH + 6) * (size_t)g.lv[l].bandPitch, fast = (size_t)ORBX_PF_WAVES * (size_t)g.fcLdsBytes;
+    return band > fast ? band : fast;
 }
 
 /* Everything k_fast_cells needs to know about one 30-px cell (src/ORBextractor.cc:1089-1123), built with the geometry: one 32-byte scalar load per
@@ -133,6 +148,7 @@ struct OrbxLaunch {
     const uint8_t *binTab;
     const uint32_t *rsTab;        /* cv::resize index / coefficient tables of all levels */
     const OrbxFcCell *fcCells;    /* k_fast_cells: one entry per cell of a frame */
+    int fcCellFirst = 0;          /* k_fast_cells: first cell of a frame its launch takes (batches: the cells in front ran in the band launches) */
     int *cellCount;
     uint32_t *cellSlots;
     uint32_t *ptBuf, *labBuf;     /* quadtree: candidates of a level in list order and their node labels; slotsPerFrame u32 per frame each */
@@ -162,6 +178,8 @@ struct OrbxLaunch {
 
 int orbx_launch_resize(const OrbxLaunch &L, int level);
 int orbx_launch_pyr_band(const OrbxLaunch &L, int level);   /* batches: blur of `level` + resize of level + 1 */
+bool orbx_pyr_fast_applies(const OrbxLaunch &L);   /* batches: the band launches can carry the detector (plan exists, no parity taps, no profiling instantiation) */
+int orbx_launch_pyr_band_fast(const OrbxLaunch &L, int level);   /* ... blur of `level` + resize of level + 1 + FAST cells of `level` */
 int orbx_launch_pyramid_tiles(const OrbxLaunch &L);   /* all levels of a frame in one launch (L.pyrTiles); single frames and small combined batches */
 int orbx_launch_comb_upload(const OrbxLaunch &L, uint8_t *stagingDev);   /* members' pinned frames -> the engine's staging area (L.combTab) */
 int orbx_launch_comb_finish(const OrbxLaunch &L);     /* the engine's results / pyramid / frames -> every member's device and pinned buffers */

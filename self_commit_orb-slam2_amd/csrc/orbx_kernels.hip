@@ -1,8 +1,9 @@
 // orbx_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the ORB extractor.
 //
 // The stages of ORB_SLAM2::ORBextractor::operator() (reference src/ORBextractor.cc:1544-1668) as
-// k_pyr_band (x8: blur of level l + resize of level l+1), k_fast_cells, k_octree, k_orient_describe for batches
-// (ORBX_PYR_SPLIT=1: k_resize x7 ... k_blur behind the quadtree); every launch covers the whole
+// k_pyr_band (x8: blur of level l + resize of level l+1; the first two as k_pyr_band_fast, with the level's FAST cells beside the bands),
+// k_fast_cells (the other levels' cells), k_octree, k_orient_describe for batches
+// (ORBX_PYR_SPLIT=1: k_resize x7 ... k_blur behind the quadtree; ORBX_FAST_SPLIT=1: every cell in k_fast_cells); every launch covers the whole
 // batch (blockIdx.y = frame) and, where the stage has no level-to-level dependency, all pyramid
 // levels at once (blockIdx.x -> (level, tile) through OrbxGeom).  All launches go through emit():
 // onto a stream, or as nodes of the single-frame hipGraph.
@@ -414,21 +415,33 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v)
 // entry (OrbxFcCell, built with the geometry: the v1 prologue - a chain of ~12 dependent scalar loads through OrbxGeom and three integer divisions - was
 // 28 % of a wave's lifetime, profiles/r05_fast_phases.txt), and the window of cell k+1 is requested before the phases of cell k run and stored into LDS
 // after them (v1: three dependent load -> store round trips per cell, 18 % of the lifetime).
-template <int P, int SP, int NS, bool PROF = false, bool DBG = false>      // DBG: the parity tap (score map of a single minThFAST pass); the product instantiation carries none of it
-__global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict__ cells, int K, int cellsPerFrame, int slotsPerFrame, size_t pyrBytes, int iniTh, int minTh,
-                                                   int inBytes, int scBytes, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
-                                                   const uint8_t *__restrict__ pyr, uint8_t *__restrict__ scoreDbg, int *__restrict__ cellCount,
-                                                   uint32_t *__restrict__ cellSlots, unsigned long long *__restrict__ prof)
+//
+// The body is a device function of ONE WAVE: its cells [cFirst, cEnd) of frame f, its own LDS region `lds` (fcLdsBytes) and its lane index.  k_fast_cells
+// wraps it in a single-wave workgroup; k_pyr_band_fast (batches) runs four of them per 256-thread workgroup beside the pyramid bands, each wave with
+// cells and a trip count of its own - so the points where the wave's lanes hand LDS data to each other are ordered by fc_wave_sync, never by s_barrier.
+// ------------------------------------------------------------------------------------
+// Orders the LDS accesses of the lanes of ONE wave: the wave's outstanding LDS operations complete (the workgroup-scope release / acquire pair: a wait
+// on the wave's own LGKM counter - the global prefetch of the next cell stays in flight) and neither the compiler nor the wave moves an access across
+// the point (wave barrier).  A wave's LDS instructions execute in order, so this is all a single wave needs; it involves no other wave, which is what
+// lets waves of one workgroup run different cells with different trip counts (in the single-wave wrapper the compiler lowered s_barrier to the same).
+__device__ __forceinline__ void fc_wave_sync()
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int P, int SP, int NS, bool PROF, bool DBG>      // DBG: the parity tap (score map of a single minThFAST pass); the product instantiation carries none of it
+__device__ __forceinline__ void fast_cells_body(const OrbxFcCell *__restrict__ cells, const int cFirst, const int cEnd, const int f, uint8_t *__restrict__ lds, const int lane,
+                                                int cellsPerFrame, int slotsPerFrame, size_t pyrBytes, int iniTh, int minTh,
+                                                int inBytes, int scBytes, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                                const uint8_t *__restrict__ pyr, uint8_t *__restrict__ scoreDbg, int *__restrict__ cellCount,
+                                                uint32_t *__restrict__ cellSlots, unsigned long long *__restrict__ prof, unsigned long long tStart)
+{
     uint8_t *inT = lds;                                   // (ah+6) x P: input window, tile (0,0) = pixel (x0-3, y0-3)
     uint8_t *scT = lds + inBytes;                         // (ah+2) x SP: scores, area pixel (c, r) at byte (r+1)*SP + c+4
     unsigned short *cand = (unsigned short *)(scT + scBytes);
-    unsigned long long pacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tPrev = 0;
-    if (PROF) tPrev = __builtin_amdgcn_s_memtime();
-    XCD_REMAP_XY(bx, f);
-    const int lane = threadIdx.x;
-    const int cFirst = bx * K, cEnd = min(cFirst + K, cellsPerFrame);
+    unsigned long long pacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tPrev = tStart;
     const uint8_t *frame0 = img0 + (size_t)f * img0FramePitch, *frameP = pyr + (size_t)f * pyrBytes;
     // window of a cell: rows y0-3 .. y1+2, bytes x0-3 .. in units of 16 (the last unit spills up to 15 bytes past x1+2: x1+18 <= w-1 stays inside the
     // row); unit u = (row u / nu, column u % nu), all of a lane's units requested back to back.  (Skipped cells carry a 1 x 1 area: their loads are
@@ -477,7 +490,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
         if (lane == 0) *cnt = 0;
         continue;
     }
-    __syncthreads();
+    fc_wave_sync();
     FC_STAMP(1);
     uint8_t *dbg = DBG && scoreDbg ? scoreDbg + (size_t)f * pyrBytes + loff : nullptr;
     if (dbg)   // parity tap: pixels that fail the pre-test have score 0
@@ -542,7 +555,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
         nc += __builtin_amdgcn_readlane(incl, 63);
         FC_STAMP(th == iniTh || dbg ? 3 : 7);
     }
-    __syncthreads();
+    fc_wave_sync();
     if (PROF) { if (th == iniTh || dbg) pNc1 = nc; else { pNc2 = nc; pRetry = 1; } }
 
     // ---- phase B: full FAST score of the surviving pixels ----
@@ -573,7 +586,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
         scT[(r + 1) * SP + c + 4] = (uint8_t)sco;
         if (dbg) dbg[(size_t)(y0 + r) * lpitch + (x0 + c)] = (uint8_t)sco;
     }
-    __syncthreads();
+    fc_wave_sync();
     FC_STAMP(th == iniTh || dbg ? 4 : 8);
 
     // ---- phase C: strict 3x3 maxima, threshold choice, ordered emission ----
@@ -613,7 +626,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
     FC_STAMP(th == iniTh || dbg ? 5 : 9);
     if (anyIni || th == minTh) break;
     th = minTh;           // :1132-1136: nothing at iniThFAST -> the whole cell again at minThFAST (its phase B rewrites every score of the first pass)
-    __syncthreads();      // (single wave: orders the LDS list / score tile reuse)
+    fc_wave_sync();        // (orders the LDS list / score tile reuse)
     }
     if (dbg) {
         const int keepBit = anyIni ? 0x2000 : 0x1000;   // iniThFAST keypoints exist -> the minThFAST retry is skipped (:1132)
@@ -634,7 +647,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
         }
     }
     if (lane == 0) *cnt = min(base, cellCap);
-    __syncthreads();      // (the next cell's window and zeros overwrite the tiles)
+    fc_wave_sync();      // (the next cell's window and zeros overwrite the tiles)
     FC_STAMP(10);
     if (PROF && lane == 0) {      // one 16-word record per cell, no atomics (208k waves adding to the same words stall the loads of the waves behind them)
         unsigned long long *rec = prof + 32 + ((size_t)f * cellsPerFrame + ci) * 16;
@@ -645,6 +658,21 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
 }
 #undef FC_STAMP
 #undef FC_REQUEST
+
+template <int P, int SP, int NS, bool PROF = false, bool DBG = false>
+__global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict__ cells, int cell0, int K, int cellsPerFrame, int slotsPerFrame, size_t pyrBytes, int iniTh, int minTh,
+                                                   int inBytes, int scBytes, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                                   const uint8_t *__restrict__ pyr, uint8_t *__restrict__ scoreDbg, int *__restrict__ cellCount,
+                                                   uint32_t *__restrict__ cellSlots, unsigned long long *__restrict__ prof)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    unsigned long long tStart = 0;
+    if (PROF) tStart = __builtin_amdgcn_s_memtime();
+    XCD_REMAP_XY(bx, f);
+    const int cFirst = cell0 + bx * K;      // (cell0 > 0: the cells in front of it ran inside the pyramid's band launches, k_pyr_band_fast)
+    fast_cells_body<P, SP, NS, PROF, DBG>(cells, cFirst, min(cFirst + K, cellsPerFrame), f, lds, (int)threadIdx.x, cellsPerFrame, slotsPerFrame, pyrBytes, iniTh, minTh, inBytes, scBytes,
+                                          img0, img0Stride, img0FramePitch, pyr, scoreDbg, cellCount, cellSlots, prof, tStart);
+}
 
 // ------------------------------------------------------------------------------------
 // Quadtree distribution (DistributeOctTree + DivideNode, src/ORBextractor.cc:635-703,
@@ -1304,14 +1332,14 @@ __device__ __forceinline__ void pb_stage(uint8_t *__restrict__ bb, const uint8_t
     }
 }
 
+// One band: the body shared by k_pyr_band and k_pyr_band_fast (the same launch with level l's FAST cells beside the bands).  All PB_THREADS threads of
+// the workgroup call it with the workgroup's band b of frame f and its LDS (`band`: (bandH + 6) x bandPitch bytes).
 template <bool CLAMP>
-__global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restrict__ g, const int l, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
-                                                         const int readable, uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, const uint32_t *__restrict__ rsTab,
-                                                         int *__restrict__ outBase)
+__device__ __forceinline__ void pyr_band_body(const OrbxGeom *__restrict__ g, const int l, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                              const int readable, uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, const uint32_t *__restrict__ rsTab,
+                                              int *__restrict__ outBase, const int b, const int f, uint32_t *__restrict__ band)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t band[];
     uint8_t *bb = (uint8_t *)band;
-    XCD_REMAP_XY(b, f);
     const int nl = g->nlevels, tid = (int)threadIdx.x;
     // the per-level output prefix of the frame is summed up by k_octree's workgroups (atomics): cleared here, the first launch of the batch
     if (l == 0 && b == 0 && tid < nl && outBase) outBase[f * nl + tid] = 0;
@@ -1433,6 +1461,50 @@ __global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restr
             *(uint32_t *)(dstBase + o) = out;
         }
     }
+}
+
+template <bool CLAMP>
+__global__ __launch_bounds__(PB_THREADS) void k_pyr_band(const OrbxGeom *__restrict__ g, const int l, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                                         const int readable, uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, const uint32_t *__restrict__ rsTab,
+                                                         int *__restrict__ outBase)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t band[];
+    XCD_REMAP_XY(b, f);
+    pyr_band_body<CLAMP>(g, l, img0, img0Stride, img0FramePitch, readable, pyr, blur, rsTab, outBase, b, f, band);
+}
+
+// ------------------------------------------------------------------------------------
+// Batches: level l's FAST cells INSIDE level l's band launch.  The detector of level l reads the unblurred level l only - the caller's image, or what
+// band launch l - 1 wrote - so nothing makes it wait behind all eight band launches; as a launch of its own it was a full link of every batch's
+// dependent chain.  Here launch l = blur(l) + resize(l + 1) + detect(l), for the first ORBX_PF_JOIN_LEVELS levels (k_fast_cells takes the cells of the
+// levels behind them, OrbxLaunch::fcCellFirst): block x < nBands is a band (pyr_band_body), the blocks behind them run four
+// detector waves each (fast_cells_body; wave w of block j takes the K cells from cellLo + (4 j + w) K, cells of level l only, waves past the level's last
+// cell leave), each wave in its own fcLds bytes of the workgroup's LDS.  The detector waves have no barriers and do not depend on each other: they
+// issue while band workgroups wait in their staging loads and barriers, and fill the part-empty last round of the band grid.  The XCD bijection runs
+// over the combined grid, so a frame's bands and detector blocks stay on the XCD whose L2 holds the frame.
+// Measured (profiles/pyr_fast_ab.json): joined at levels 0 - 1 the headline gains 2 %; joined at every level it LOSES 3 % - a detector wave's four cells
+// are ~35 us of dependent latency, which every small level's launch (9 - 30 us alone) then waits for; all band blocks in front of all detector blocks
+// (the frames' locality in the XCDs' L2 given up) loses 12 %.
+// Host plan: OrbxGeom::pyrFast (build_geometry); orbx_launch_pyr_band_fast.
+// ------------------------------------------------------------------------------------
+template <bool CLAMP, int P, int SP, int NS>
+__global__ __launch_bounds__(PB_THREADS) void k_pyr_band_fast(const OrbxGeom *__restrict__ g, const int l, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                                              const int readable, uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, const uint32_t *__restrict__ rsTab,
+                                                              int *__restrict__ outBase, const int nBands, const OrbxFcCell *__restrict__ cells, const int K, const int cellLo,
+                                                              const int cellHi, int cellsPerFrame, int slotsPerFrame, size_t pyrBytes, int iniTh, int minTh, int inBytes, int scBytes,
+                                                              const int fcLds, int *__restrict__ cellCount, uint32_t *__restrict__ cellSlots)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t band[];
+    XCD_REMAP_XY(bx, f);
+    if (bx < nBands) {
+        pyr_band_body<CLAMP>(g, l, img0, img0Stride, img0FramePitch, readable, pyr, blur, rsTab, outBase, bx, f, band);
+        return;
+    }
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (uniform in the wave: scalar bookkeeping)
+    const int cFirst = cellLo + (((bx - nBands) * (PB_THREADS / 64) + wv) * K);
+    if (cFirst >= cellHi) return;
+    fast_cells_body<P, SP, NS, false, false>(cells, cFirst, min(cFirst + K, cellHi), f, (uint8_t *)band + wv * fcLds, (int)(threadIdx.x & 63), cellsPerFrame, slotsPerFrame, pyrBytes, iniTh,
+                                             minTh, inBytes, scBytes, img0, img0Stride, img0FramePitch, pyr, nullptr, cellCount, cellSlots, nullptr, 0ull);
 }
 
 // Combined single-frame calls: quadtree, host pyramid copy AND blur in one launch.  The quadtree is eight workgroups of dependent latency
@@ -1849,16 +1921,22 @@ int orbx_launch_comb_finish(const OrbxLaunch &L)
 static unsigned long long *g_fcProf = nullptr;
 extern "C" void orbx_debug_fast_cells_profile(unsigned long long *dev32) { g_fcProf = dev32; }
 
-int orbx_launch_fast_cells(const OrbxLaunch &L)
+// cells per detector wave
+static int fc_cells_per_wave(int batch)
 {
-    const OrbxGeom &g = *L.geom;
     static const int kEnv = getenv("ORBX_FC_CELLS_PER_WAVE") ? atoi(getenv("ORBX_FC_CELLS_PER_WAVE")) : 0;      // (developer knob)
     // batches: four cells per wave (the next cell's window is fetched under the current cell's phases); single frames and the combiner's small launch
     // sets: one - 815 waves per 640x480 frame do not fill the device, and four cells in a row are four times a cell's latency (111 vs 100 us per call)
-    const int K = kEnv > 0 ? kEnv : (L.batch >= 32 ? ORBX_FC_CELLS_PER_WAVE : 1);
-    dim3 grid((unsigned)((g.cellsPerFrame + K - 1) / K), (unsigned)L.batch);
+    return kEnv > 0 ? kEnv : (batch >= 32 ? ORBX_FC_CELLS_PER_WAVE : 1);
+}
+
+int orbx_launch_fast_cells(const OrbxLaunch &L)
+{
+    const OrbxGeom &g = *L.geom;
+    const int K = fc_cells_per_wave(L.batch);
+    dim3 grid((unsigned)((g.cellsPerFrame - L.fcCellFirst + K - 1) / K), (unsigned)L.batch);
     const size_t ldsBytes = (size_t)g.fcLdsBytes;
-#define FC_ARGS L.fcCells, K, g.cellsPerFrame, g.slotsPerFrame, g.pyrBytes, g.iniTh, g.minTh, g.fcInBytes, g.fcScBytes, L.img0, L.img0Stride, L.img0FramePitch, L.pyr, L.score, L.cellCount, L.cellSlots
+#define FC_ARGS L.fcCells, L.fcCellFirst, K, g.cellsPerFrame, g.slotsPerFrame, g.pyrBytes, g.iniTh, g.minTh, g.fcInBytes, g.fcScBytes, L.img0, L.img0Stride, L.img0FramePitch, L.pyr, L.score, L.cellCount, L.cellSlots
 #define FC_LAUNCH(PP, SS, NN) do { if (L.score) return emit(L, k_fast_cells<PP, SS, NN, false, true>, grid, dim3(64), ldsBytes, FC_ARGS, (unsigned long long *)nullptr); \
     if (g_fcProf) return emit(L, k_fast_cells<PP, SS, NN, true, false>, grid, dim3(64), ldsBytes, FC_ARGS, g_fcProf); \
     return emit(L, k_fast_cells<PP, SS, NN, false, false>, grid, dim3(64), ldsBytes, FC_ARGS, (unsigned long long *)nullptr); } while (0)
@@ -1942,6 +2020,36 @@ int orbx_launch_pyr_band(const OrbxLaunch &L, int l)
     for (int i = 0; i < 7; i++) tapSum += g.taps[i];
     if (tapSum > 256u) return emit(L, k_pyr_band<true>, grid, dim3(PB_THREADS), lds, L.geomDev, l, L.img0, L.img0Stride, L.img0FramePitch, readable, L.pyr, L.blur, L.rsTab, L.outBase);
     return emit(L, k_pyr_band<false>, grid, dim3(PB_THREADS), lds, L.geomDev, l, L.img0, L.img0Stride, L.img0FramePitch, readable, L.pyr, L.blur, L.rsTab, L.outBase);
+}
+
+// batches: launch l of the joint form = blur(l) + resize(l + 1) + detect(l) (k_pyr_band_fast; plan: OrbxGeom::pyrFast)
+bool orbx_pyr_fast_applies(const OrbxLaunch &L) { return L.geom->pyrBand && L.geom->pyrFast && !L.score && !g_fcProf; }
+
+int orbx_launch_pyr_band_fast(const OrbxLaunch &L, int l)
+{
+    const OrbxGeom &g = *L.geom;
+    const OrbxLevel &lv = g.lv[l];
+    const int K = fc_cells_per_wave(L.batch), ncell = lv.nCols * lv.nRows;
+    const int nBands = (lv.h + lv.bandH - 1) / lv.bandH;
+    const dim3 grid((unsigned)(nBands + orbx_fast_blocks(ncell, K)), (unsigned)L.batch);
+    const size_t lds = orbx_pyr_fast_lds(g, l);      // (the plan keeps this within 48 KB)
+    const int readable = l > 0 ? lv.pitch : (L.img0FramePitch >= (size_t)L.img0Stride * (size_t)lv.h ? L.img0Stride : lv.w);      // (see orbx_launch_pyr_band)
+    unsigned tapSum = 0;
+    for (int i = 0; i < 7; i++) tapSum += g.taps[i];
+#define PF_ARGS L.geomDev, l, L.img0, L.img0Stride, L.img0FramePitch, readable, L.pyr, L.blur, L.rsTab, L.outBase, nBands, L.fcCells, K, lv.cellBase, lv.cellBase + ncell, g.cellsPerFrame, \
+                g.slotsPerFrame, g.pyrBytes, g.iniTh, g.minTh, g.fcInBytes, g.fcScBytes, g.fcLdsBytes, L.cellCount, L.cellSlots
+#define PF_LAUNCH(PP, SS, NN) do { if (tapSum > 256u) return emit(L, k_pyr_band_fast<true, PP, SS, NN>, grid, dim3(PB_THREADS), lds, PF_ARGS); \
+    return emit(L, k_pyr_band_fast<false, PP, SS, NN>, grid, dim3(PB_THREADS), lds, PF_ARGS); } while (0)
+#define PF_LAUNCH_P(PP, SS) switch (g.fcNS) { case 2: PF_LAUNCH(PP, SS, 2); case 3: PF_LAUNCH(PP, SS, 3); case 4: PF_LAUNCH(PP, SS, 4); default: PF_LAUNCH(PP, SS, 6); }
+    // (the detector's instantiations: see orbx_launch_fast_cells)
+    if (g.fcPitch == 48 && g.fcScPitch == 48) PF_LAUNCH_P(48, 48)
+    if (g.fcPitch == 64 && g.fcScPitch == 48) PF_LAUNCH_P(64, 48)
+    if (g.fcPitch == 80 && g.fcScPitch == 48) PF_LAUNCH_P(80, 48)
+    if (g.fcPitch != 80 || g.fcScPitch != 80) { orbx_set_error("detector LDS pitches %d / %d have no kernel instantiation", g.fcPitch, g.fcScPitch); return ORBX_ERR_STATE; }
+    PF_LAUNCH_P(80, 80)
+#undef PF_LAUNCH_P
+#undef PF_LAUNCH
+#undef PF_ARGS
 }
 
 int orbx_launch_orient_describe(const OrbxLaunch &L)
