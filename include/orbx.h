@@ -866,6 +866,113 @@ int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_batch *b, co
 /* device time of the last call's kernels and how many were launched (one per non-empty size class) */
 int orbx_mappoint_last_timing(orbx_mappoint_ops *h, float *kernel_ms, int *launches);
 
+/* ------------------------------------------------------------------------------------
+ * New map points  ==  the per-match geometry of LocalMapping::CreateNewMapPoints
+ * (src/LocalMapping.cc:423-596) and the chain over the neighbour keyframes around it (:350-624).
+ *
+ * Per match (KF1 feature idx1, KF2 feature idx2), in the reference's operation order: ray
+ * parallax, stereo parallax, the three-way choice (linear triangulation / UnprojectStereo of
+ * KF1 / of KF2), the two depth tests, the two chi2 reprojection tests, the scale test.  The
+ * status byte says which `continue` was taken or which path accepted the point.
+ *   float where the reference computes in float; double where the project's OpenCV stand-in
+ *   does: Mat::dot and cv::norm accumulate in double, 1.0/z is a double quotient narrowed to
+ *   float, the 3-term matrix products go left to right in float.
+ *   The null vector of the 4x4 A comes from a one-sided Jacobi SVD in FP64 (the reference:
+ *   cv::SVD in float), atan2f / cosf from the device library: PARITY UNPINNED AT THE OPENCV
+ *   LEVEL for the SVD and the transcendental functions.  Contract: status equals the numpy
+ *   restatement (tests/triangulate_ref.py) on every match that does not sit on a threshold;
+ *   x3d of the stereo paths bit-equal; x3d of the triangulation path within a float32 SVD's
+ *   own error of the float64 SVD's result.
+ *   UnprojectStereo reads the RAW keypoint (mvKeys), not mvKeysUn (src/KeyFrame.cc:816), and the
+ *   second keyframe's stereo reprojection uses the CURRENT keyframe's mbf (:562): kept.
+ * ---------------------------------------------------------------------------------- */
+#define ORBX_NP_NONE 0           /* the slot holds no match                                   */
+#define ORBX_NP_TRIANGULATED 1   /* accepted, x3D from the SVD (:470-489)                     */
+#define ORBX_NP_STEREO1 2        /* accepted, pKF1->UnprojectStereo (:490-493)                */
+#define ORBX_NP_STEREO2 3        /* accepted, pKF2->UnprojectStereo (:494-497)                */
+#define ORBX_NP_LOW_PARALLAX 4   /* no stereo and very low parallax (:499)                    */
+#define ORBX_NP_W_ZERO 5         /* x3D.at<float>(3) == 0 (:485)                              */
+#define ORBX_NP_DEPTH_INVALID 6  /* UnprojectStereo on mvDepth <= 0 (src/KeyFrame.cc:808)      */
+#define ORBX_NP_BEHIND1 7        /* z1 <= 0 (:507)                                            */
+#define ORBX_NP_BEHIND2 8        /* z2 <= 0 (:511)                                            */
+#define ORBX_NP_REPROJ1 9        /* chi2 test in KF1 (:528 / :540)                            */
+#define ORBX_NP_REPROJ2 10       /* chi2 test in KF2 (:556 / :568)                            */
+#define ORBX_NP_DIST_ZERO 11     /* dist1 == 0 || dist2 == 0 (:582)                           */
+#define ORBX_NP_SCALE 12         /* the two-sided ratio test (:595)                           */
+
+typedef struct orbx_keyframe_geom {   /* host memory: pose and calibration of one KeyFrame */
+    float tcw[12];              /* Rcw | tcw, 3x4 row-major (GetRotation / GetTranslation)     */
+    float center[3];            /* GetCameraCenter() = Ow = Twc.col(3)                         */
+    float fx, fy, cx, cy, invfx, invfy;
+    float mb, mbf;
+    float scale_factor;         /* mfScaleFactor (read of KF1 only: ratioFactor = 1.5f * it)   */
+    const float *scale_factors; /* mvScaleFactors[nlevels]                                     */
+    const float *level_sigma2;  /* mvLevelSigma2[nlevels]                                      */
+    int nlevels;                /* 1..12                                                       */
+} orbx_keyframe_geom;
+
+typedef struct orbx_keyframe_obs {    /* host memory: the per-feature arrays of one KeyFrame */
+    const orbx_keypoint *keys_un;     /* mvKeysUn[count]: x, y, octave are read                  */
+    const float *keys_raw;            /* mvKeys[i].pt as x, y pairs [2*count]; NULL = identical  */
+    const float *u_right, *depth;     /* mvuRight / mvDepth [count]; NULL = monocular            */
+    int count;
+} orbx_keyframe_obs;
+
+/* The geometry alone, on K pairs of keyframes with explicit match lists (CSR over the pairs):
+ * matches match_offset[p] .. match_offset[p+1] belong to pair p, match j is (idx1[j], idx2[j]).
+ * status[j] and x3d[3*j..] per match (x3d is 0 where no point was computed).  No mask is kept:
+ * the caller supplied the matches.  One launch per pair, one synchronisation. */
+typedef struct orbx_triangulate_pairs {
+    int npairs;
+    const int32_t *match_offset;                 /* [npairs+1], match_offset[0] == 0, non-decreasing */
+    const int32_t *idx1, *idx2;                  /* [match_offset[npairs]]                           */
+    const orbx_keyframe_geom *geom1, *geom2;     /* [npairs]                                         */
+    const orbx_keyframe_obs *obs1, *obs2;        /* [npairs]                                         */
+} orbx_triangulate_pairs;
+int orbx_triangulate_matches(orbx_matcher *m, const orbx_triangulate_pairs *pairs, uint8_t *status, float *x3d);
+
+/* The chain: for neighbour k = 0..K-1 in order, SearchForTriangulation(KF1, neighbour k, bOnlyStereo = false) on
+ * the CURRENT eligibility mask of KF1, the geometry above on its matches, and the mask bytes of the accepted KF1
+ * features cleared (the reference: they now hold a MapPoint, src/ORBmatcher.cc:845-855) - all on the matcher's
+ * stream without a host synchronisation between the neighbours; then the accepted slots of all neighbours are
+ * compacted into the `created` list in the order the reference creates the points (neighbour ascending, then
+ * KF1 feature ascending), and the host waits once.
+ *   kf1_host: one frame (nframes = 1); `valid` initialises the mask (1 = the feature has no MapPoint).
+ *   neighbours_host: one feature set, nframes = K, neighbour k at k*capacity; only the neighbours that passed the
+ *     caller's baseline / median-depth gate (:358-384).  F12 and the epipole per neighbour come from the caller.
+ *   stop_flag: NULL or CheckNewKeyFrames() as a byte, never written through; read before neighbour k > 0 is
+ *     enqueued (:353); *pairs_done = how many neighbours ran (their results are complete).
+ * Capacities and LDS sizes are checked before the first launch. */
+typedef struct orbx_new_points_params {   /* host memory */
+    const orbx_keyframe_geom *geom1;      /* KF1                                                       */
+    const orbx_keyframe_geom *geom2;      /* [K]                                                       */
+    const float *f12, *epipole;           /* [9*K], [2*K] as in orbx_triangulation_params              */
+    const float *keys_raw1, *u_right1, *depth1;   /* KF1: [2*n1], [n1], [n1]; NULL as in orbx_keyframe_obs   */
+    const float *keys_raw2, *u_right2, *depth2;   /* neighbours, laid out like the feature set: [2*K*capacity], [K*capacity] x 2 */
+    int check_orientation;                /* mbCheckOrientation (false in CreateNewMapPoints, :323)    */
+    int profile_kernels;                  /* 1: time every k_triangulate launch with events of its own */
+} orbx_new_points_params;
+typedef struct orbx_new_point {
+    int32_t neighbour, idx1, idx2, path;  /* path = ORBX_NP_TRIANGULATED / _STEREO1 / _STEREO2 */
+    float x, y, z;
+} orbx_new_point;
+typedef struct orbx_new_points_result {
+    orbx_new_point *created;              /* [created_capacity]; a KF1 feature is created at most once: n1 suffices */
+    int created_capacity;
+    int32_t *count;                       /* entries written to `created`                               */
+    int32_t *nmatches;                    /* [K] return value of each search (0 for neighbours not run) */
+    int32_t *pairs_done;
+    uint8_t *status;                      /* optional [K*kf1->capacity], slot k*capacity + idx1         */
+    int32_t *matches;                     /* optional, same layout: the KF2 feature or -1               */
+    float *x3d;                           /* optional [3*K*kf1->capacity]                               */
+} orbx_new_points_result;
+int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_set *kf1_host, const orbx_feature_set *neighbours_host,
+                               const orbx_new_points_params *params, const volatile uint8_t *stop_flag,
+                               const orbx_new_points_result *result);
+/* device time of the last chain (first search to k_collect), its kernel launches, and the time inside k_triangulate
+ * (0 unless the chain ran with profile_kernels) */
+int orbx_new_points_last_timing(orbx_matcher *m, float *device_ms, int *launches, float *triangulate_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -486,6 +486,61 @@ def predict_scale_thresholds(log_scale_factor, nlevels):
     return out[:nlevels - 1]
 
 
+class KeyFrameGeom(ctypes.Structure):
+    """orbx_keyframe_geom: pose and calibration of one KeyFrame (host)."""
+    _fields_ = [("tcw", ctypes.c_float * 12), ("center", ctypes.c_float * 3), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("invfx", ctypes.c_float), ("invfy", ctypes.c_float), ("mb", ctypes.c_float), ("mbf", ctypes.c_float), ("scale_factor", ctypes.c_float),
+                ("scale_factors", ctypes.c_void_p), ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
+
+
+class KeyFrameObs(ctypes.Structure):
+    _fields_ = [("keys_un", ctypes.c_void_p), ("keys_raw", ctypes.c_void_p), ("u_right", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("count", ctypes.c_int)]
+
+
+class TriangulatePairs(ctypes.Structure):
+    _fields_ = [("npairs", ctypes.c_int), ("match_offset", ctypes.c_void_p), ("idx1", ctypes.c_void_p), ("idx2", ctypes.c_void_p), ("geom1", ctypes.c_void_p),
+                ("geom2", ctypes.c_void_p), ("obs1", ctypes.c_void_p), ("obs2", ctypes.c_void_p)]
+
+
+class NewPointsParams(ctypes.Structure):
+    _fields_ = [("geom1", ctypes.c_void_p), ("geom2", ctypes.c_void_p), ("f12", ctypes.c_void_p), ("epipole", ctypes.c_void_p), ("keys_raw1", ctypes.c_void_p),
+                ("u_right1", ctypes.c_void_p), ("depth1", ctypes.c_void_p), ("keys_raw2", ctypes.c_void_p), ("u_right2", ctypes.c_void_p), ("depth2", ctypes.c_void_p),
+                ("check_orientation", ctypes.c_int), ("profile_kernels", ctypes.c_int)]
+
+
+class NewPointsResult(ctypes.Structure):
+    _fields_ = [("created", ctypes.c_void_p), ("created_capacity", ctypes.c_int), ("count", ctypes.c_void_p), ("nmatches", ctypes.c_void_p), ("pairs_done", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("matches", ctypes.c_void_p), ("x3d", ctypes.c_void_p)]
+
+
+NEW_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("path", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+assert NEW_POINT_DTYPE.itemsize == 28
+
+
+def _geom(g, keep):
+    """dict(tcw (3,4), center, fx, fy, cx, cy, invfx, invfy, mb, mbf, scale_factor, scale_factors, level_sigma2) -> KeyFrameGeom"""
+    sf, s2 = np.ascontiguousarray(g["scale_factors"], np.float32), np.ascontiguousarray(g["level_sigma2"], np.float32)
+    keep += [sf, s2]
+    out = KeyFrameGeom()
+    out.tcw[:] = [float(x) for x in np.asarray(g["tcw"], np.float32).reshape(-1)[:12]]
+    out.center[:] = [float(x) for x in np.asarray(g["center"], np.float32).reshape(3)]
+    for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf", "scale_factor"):
+        setattr(out, k, float(np.float32(g[k])))
+    out.scale_factors, out.level_sigma2, out.nlevels = sf.ctypes.data, s2.ctypes.data, min(len(sf), len(s2))
+    return out
+
+
+def _obs(o, keep):
+    """dict(kps (mvKeysUn), raw (n,2) or None, u_right, depth (None = monocular)) -> KeyFrameObs"""
+    k = np.ascontiguousarray(o["kps"], KEYPOINT_DTYPE)
+    arrs = [k]
+    for name, shape in (("raw", (-1, 2)), ("u_right", (-1,)), ("depth", (-1,))):
+        a = o.get(name)
+        arrs.append(None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape)))
+    keep += arrs
+    return KeyFrameObs(*[a.ctypes.data if a is not None else None for a in arrs], len(k))
+
+
 class TriangulationParams(ctypes.Structure):
     _fields_ = [("f12", ctypes.c_void_p), ("epipole", ctypes.c_void_p), ("stereo_a", ctypes.c_void_p), ("stereo_b", ctypes.c_void_p),
                 ("scale_factors", ctypes.c_void_p), ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int), ("check_orientation", ctypes.c_int)]
@@ -553,6 +608,103 @@ class ORBmatcher:
         nm = ctypes.c_int32()
         _check(self._L.orbx_search_for_triangulation(self._h, ctypes.byref(sets[0]), ctypes.byref(sets[1]), ctypes.byref(prm), _ptr(out), ctypes.byref(nm)))
         return nm.value, out[:n1]
+
+    def TriangulateMatches(self, pairs):
+        """The per-match geometry of LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:423-596) on explicit match lists.
+        pairs: list of dict(g1, g2 (keyframe geometry, see _geom), o1, o2 (observations, see _obs), idx1, idx2).  Returns dict(status (M) uint8,
+        x3d (M,3) float32, offset (K+1)) over the concatenated matches."""
+        L = self._L
+        L.orbx_triangulate_matches.argtypes = [ctypes.c_void_p, ctypes.POINTER(TriangulatePairs), ctypes.c_void_p, ctypes.c_void_p]
+        K = len(pairs)
+        keep = []
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(p["idx1"]) for p in pairs])
+        M = int(off[K])
+        i1 = np.ascontiguousarray(np.concatenate([np.asarray(p["idx1"], np.int32) for p in pairs] + [np.zeros(0, np.int32)]), np.int32)
+        i2 = np.ascontiguousarray(np.concatenate([np.asarray(p["idx2"], np.int32) for p in pairs] + [np.zeros(0, np.int32)]), np.int32)
+        G1, G2 = (KeyFrameGeom * max(K, 1))(), (KeyFrameGeom * max(K, 1))()
+        O1, O2 = (KeyFrameObs * max(K, 1))(), (KeyFrameObs * max(K, 1))()
+        for k, p in enumerate(pairs):
+            G1[k], G2[k], O1[k], O2[k] = _geom(p["g1"], keep), _geom(p["g2"], keep), _obs(p["o1"], keep), _obs(p["o2"], keep)
+        tp = TriangulatePairs(K, off.ctypes.data, i1.ctypes.data, i2.ctypes.data, ctypes.addressof(G1), ctypes.addressof(G2), ctypes.addressof(O1), ctypes.addressof(O2))
+        status, x3d = np.zeros(max(M, 1), np.uint8), np.zeros((max(M, 1), 3), np.float32)
+        _check(L.orbx_triangulate_matches(self._h, ctypes.byref(tp), _ptr(status), _ptr(x3d)))
+        return dict(status=status[:M], x3d=x3d[:M], offset=off)
+
+    def CreateNewMapPoints(self, kf1, neighbours, stop_flag=None, capacity2=None, full=True, profile_kernels=False, created_capacity=None, capacity1=None):
+        """The neighbour loop of LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:350-624) as one call: per neighbour in order
+        SearchForTriangulation on KF1's current eligibility mask, the geometry of its matches, the mask update; the created points in the
+        reference's creation order.  kf1: dict(kps, desc, groups, has_mp, g (geometry)[, raw, u_right, depth]); neighbours: list of the same
+        plus F12, epipole.  stop_flag: None or a uint8 array of one element (CheckNewKeyFrames()).  Returns dict(created (structured),
+        count, nmatches (K), pairs_done[, status (K,n1), matches (K,n1), x3d (K,n1,3)])."""
+        return self.new_points_prepare(kf1, neighbours, stop_flag, capacity2, full, profile_kernels, created_capacity, capacity1)()
+
+    def new_points_prepare(self, kf1, neighbours, stop_flag=None, capacity2=None, full=True, profile_kernels=False, created_capacity=None, capacity1=None):
+        """CreateNewMapPoints in two steps: the arrays marshalled once, and a function that makes the C call on them and returns the result dict;
+        its attribute `raw` makes the C call alone and returns the status code (what tools/latency_new_points.py times).  capacity1 / capacity2:
+        capacity of KF1's / the neighbours' feature set when it is to exceed the feature count (the per-slot arrays are laid out by it)."""
+        L = self._L
+        L.orbx_create_new_map_points.argtypes = [ctypes.c_void_p, ctypes.POINTER(FeatureSet), ctypes.POINTER(FeatureSet), ctypes.POINTER(NewPointsParams), ctypes.c_void_p,
+                                                 ctypes.POINTER(NewPointsResult)]
+        K = len(neighbours)
+        keep = []
+        n1 = len(kf1["kps"])
+        fs1, k1 = _host_set(kf1["kps"], kf1["desc"], kf1.get("groups"), (np.asarray(kf1["has_mp"], np.uint8) == 0).astype(np.uint8))
+        keep.append(k1)
+        if capacity1:
+            fs1.capacity = capacity1
+        cap2 = capacity2 or max([len(nb["kps"]) for nb in neighbours] + [1])
+        kp2, d2 = np.zeros((max(K, 1), cap2), KEYPOINT_DTYPE), np.zeros((max(K, 1), cap2, 32), np.uint8)
+        cnt2, gr2, va2 = np.zeros(max(K, 1), np.int32), np.full((max(K, 1), cap2), -1, np.int32), np.zeros((max(K, 1), cap2), np.uint8)
+        stereo2 = any(nb.get("u_right") is not None for nb in neighbours)
+        raw2, ur2, dp2 = np.zeros((max(K, 1), cap2, 2), np.float32), np.full((max(K, 1), cap2), -1, np.float32), np.full((max(K, 1), cap2), -1, np.float32)
+        G2 = (KeyFrameGeom * max(K, 1))()
+        f12, epi = np.zeros((max(K, 1), 9), np.float32), np.zeros((max(K, 1), 2), np.float32)
+        for k, nb in enumerate(neighbours):
+            m = len(nb["kps"])
+            cnt2[k] = m
+            kp2[k, :m], d2[k, :m], va2[k, :m] = nb["kps"], nb["desc"], np.asarray(nb["has_mp"], np.uint8) == 0
+            gr2[k, :m] = nb["groups"] if nb.get("groups") is not None else 0
+            raw2[k, :m] = nb["raw"] if nb.get("raw") is not None else np.stack([nb["kps"]["x"], nb["kps"]["y"]], 1)
+            if nb.get("u_right") is not None:
+                ur2[k, :m], dp2[k, :m] = nb["u_right"], nb["depth"]
+            G2[k] = _geom(nb["g"], keep)
+            f12[k], epi[k] = np.asarray(nb["F12"], np.float32).reshape(9), np.asarray(nb["epipole"], np.float32).reshape(2)
+        fs2 = FeatureSet(kp2.ctypes.data, d2.ctypes.data, cnt2.ctypes.data, gr2.ctypes.data, va2.ctypes.data, cap2, K)
+        G1 = _geom(kf1["g"], keep)
+        o1 = _obs(kf1, keep)
+        prm = NewPointsParams(ctypes.addressof(G1), ctypes.addressof(G2), f12.ctypes.data, epi.ctypes.data, o1.keys_raw, o1.u_right, o1.depth,
+                              raw2.ctypes.data, ur2.ctypes.data if stereo2 else None, dp2.ctypes.data if stereo2 else None, 1 if self.checkOri else 0, 1 if profile_kernels else 0)
+        ccap = n1 if created_capacity is None else created_capacity
+        created = np.zeros(max(ccap, 1), NEW_POINT_DTYPE)
+        count, done, nm = ctypes.c_int32(), ctypes.c_int32(), np.zeros(max(K, 1), np.int32)
+        c1 = capacity1 or max(n1, 1)
+        status = np.zeros((max(K, 1), c1), np.uint8) if full else None
+        matches = np.full((max(K, 1), c1), -1, np.int32) if full else None
+        x3d = np.zeros((max(K, 1), c1, 3), np.float32) if full else None
+        res = NewPointsResult(created.ctypes.data, ccap, ctypes.addressof(count), nm.ctypes.data, ctypes.addressof(done),
+                              status.ctypes.data if full else None, matches.ctypes.data if full else None, x3d.ctypes.data if full else None)
+        sf = None if stop_flag is None else np.ascontiguousarray(stop_flag, np.uint8)
+        keep += [fs1, fs2, G1, G2, o1, f12, epi, kp2, d2, cnt2, gr2, va2, raw2, ur2, dp2, prm, res, sf]
+
+        def raw():
+            return L.orbx_create_new_map_points(self._h, ctypes.byref(fs1), ctypes.byref(fs2), ctypes.byref(prm), None if sf is None else sf.ctypes.data, ctypes.byref(res))
+
+        def call():
+            _check(raw())
+            out = dict(created=created[:count.value].copy(), count=count.value, nmatches=nm[:K].copy(), pairs_done=done.value)
+            if full:
+                out.update(status=status[:K, :n1].copy(), matches=matches[:K, :n1].copy(), x3d=x3d[:K, :n1].copy())
+            return out
+        call.keep, call.raw = keep, raw
+        return call
+
+    def new_points_last_timing(self):
+        """(device ms of the last chain, kernel launches, ms inside k_triangulate - 0 unless profile_kernels)"""
+        ms, tri, n = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+        self._L.orbx_new_points_last_timing.argtypes = [ctypes.c_void_p] * 4
+        _check(self._L.orbx_new_points_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(tri)))
+        return ms.value, n.value, tri.value
 
     def FuseSearch(self, kf, points, chi2_gate=True):
         """Steps 2-3 of ORBmatcher::Fuse (reference src/ORBmatcher.cc:1093-1146 / 1258-1276): per map point the KeyFrame

@@ -4,6 +4,7 @@
 #define ORBX_MATCH_INTERNAL_H
 
 #include "orbx_internal.h"
+#include <vector>
 
 #define TH_HIGH 100       /* src/ORBmatcher.cc:49 */
 #define TH_LOW 50         /* :50 */
@@ -118,7 +119,19 @@ struct orbx_matcher {
     size_t frCount = 0;
     int lastPairs = 0, lastStride = 0;
     OrbxDevBuf<int> producerStatus;   // OR of the capacity words of the extractors this handle's calls were chained behind
+    // new map points (orbx_triangulate.hip): KF1 + the K neighbours staged once (pinned buffer, one copy), per-slot results of every neighbour
+    OrbxHostStage npStage;
+    OrbxDevBuf<uint8_t> npStatus;     // [K * npStride]
+    OrbxDevBuf<float> npX3d;          // [K * npStride * 3]
+    OrbxDevBuf<int32_t> npMatches;    // [K * npStride]: the matches of each search (m->matches is overwritten by the next one)
+    OrbxDevBuf<int32_t> npNm;         // [K]
+    hipEvent_t npEv[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> npTriEv;  // profile_kernels: one pair per neighbour
+    int npTriTimed = 0, npLaunches = 0;
+    bool npTimed = false;
 };
+
+namespace orbx_tri { void release(orbx_matcher *m); }   // orbx_triangulate.hip: called by orbx_matcher_destroy
 
 #define MLAUNCH_CHECK()                                                                                              \
     do {                                                                                                             \
