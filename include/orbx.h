@@ -973,6 +973,113 @@ int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_set *kf1_host
  * (0 unless the chain ran with profile_kernels) */
 int orbx_new_points_last_timing(orbx_matcher *m, float *device_ms, int *launches, float *triangulate_ms);
 
+/* ----------------------------------------------------------------------------------
+ * Monocular initialisation: Initializer::Initialize (reference src/Initializer.cc:68-230) and
+ * everything below it - FindHomography / FindFundamental over the caller's RANSAC sets, the
+ * choice between the two models, DecomposeE / ReconstructH's eight motions, CheckRT of all
+ * twelve and the selection - in one chain of six launches on the handle's own stream; the
+ * host waits once.  Inputs go through mapped pinned memory, the last kernel writes the
+ * results into mapped pinned memory and raises a sequence word.
+ *
+ *   Host side of a call: vMatches12 is compacted in i1 order and Normalize (:1501-1575) runs
+ *   over both frames' keypoints - sequential float sums, as the reference has them.
+ *   Device side: k_init_models (one wave per hypothesis and model: the 16x9 / 8x9 system,
+ *   its null vector by a one-sided Jacobi in FP64 with the columns in LDS, rank 2 for F,
+ *   denormalisation, then CheckHomography / CheckFundamental over all matches with the
+ *   score summed in match order), k_init_decompose (first argmax of the scores, the four
+ *   motions of DecomposeE and the eight of ReconstructH - both families always),
+ *   k_init_check_rt (12 x N triangulations), k_init_rank (nGood and the cosine at sorted
+ *   index min(50, nGood-1) by rank counting), k_init_decide (ReconstructF's / ReconstructH's
+ *   selection, the result block).
+ *
+ *   Arithmetic: float in the reference's operation order; 1.0/x a double quotient narrowed to
+ *   float; Mat::dot / cv::norm in double; 3-term products left to right.  PARITY UNPINNED AT
+ *   THE OPENCV LEVEL: cv::SVD in float (here: Jacobi in FP64, narrowed), Mat::inv (here:
+ *   cofactors in FP64), cv::determinant (here: cofactors in FP64), the SIGN of null vectors and
+ *   singular vectors and with it the ORDER of the motion hypotheses inside each family, and
+ *   acos (the host's acosf turns the selected cosine into degrees; the device compares
+ *   cosines against a bound the host derived from the same acosf).  ReconstructH's motions
+ *   are declared invalid (hyp_valid = 0) when d1/d2 < 1.00001 || d2/d3 < 1.00001 (:1185) or
+ *   when one of the quotients is not finite.
+ *   Hypothesis order: 0..3 = (R1,t) (R2,t) (R1,-t) (R2,-t) of ReconstructF (:1050-1060),
+ *   4..7 = the d' = d2 family, 8..11 = the d' = -d2 family of ReconstructH (:1230-1345).
+ * ---------------------------------------------------------------------------------- */
+#define ORBX_INIT_NOT_INLIER 0          /* !vbMatchesInliers[i] (:1652)                                */
+#define ORBX_INIT_NONFINITE 1           /* the triangulated point is not finite (:1668)               */
+#define ORBX_INIT_BEHIND1 2             /* z1 <= 0 && cosParallax < 0.99998 (:1697)                   */
+#define ORBX_INIT_BEHIND2 3             /* z2 <= 0 && cosParallax < 0.99998 (:1707)                   */
+#define ORBX_INIT_REPROJ1 4             /* squareError1 > th2 (:1722)                                 */
+#define ORBX_INIT_REPROJ2 5             /* squareError2 > th2 (:1737)                                 */
+#define ORBX_INIT_GOOD 6                /* counted, vbGood = true                                     */
+#define ORBX_INIT_GOOD_LOW_PARALLAX 7   /* counted (nGood, vP3D, the cosine list), vbGood stays false */
+#define ORBX_INIT_HYPOTHESES 12
+#define ORBX_INIT_MAX_MATCHES 16000     /* k_init_rank keeps a hypothesis' cosines in LDS (64 KB)     */
+
+typedef struct orbx_initializer orbx_initializer;
+/* ORBX_ERR_ARG: max_matches outside 8..ORBX_INIT_MAX_MATCHES, max_iterations < 1; then ORBX_ERR_NODEVICE without a device */
+int orbx_initializer_create(int device, int max_matches, int max_iterations, orbx_initializer **out);
+void orbx_initializer_destroy(orbx_initializer *h);
+
+typedef struct orbx_init_matches {     /* host memory */
+    const float *keys1_xy, *keys2_xy;  /* mvKeysUn[i].pt of the reference / the current frame: [n1][2], [n2][2] */
+    int n1, n2;
+    const int32_t *matches12;          /* [n1]: index into frame 2 or -1, the reference's vMatches12            */
+} orbx_init_matches;
+
+typedef struct orbx_init_problem {     /* host memory */
+    const float *keys1_xy, *keys2_xy;
+    int n1, n2;
+    const int32_t *matches12;
+    const int32_t *sets;               /* [iterations][8]: mvSets, indices into the COMPACTED match list (:139-168) */
+    int iterations;
+    float sigma;
+    float fx, fy, cx, cy;
+    float min_parallax;                /* degrees; the reference passes 1.0 */
+    int min_triangulated;              /* the reference passes 50           */
+} orbx_init_problem;
+
+typedef struct orbx_init_result {      /* host memory; every pointer may be NULL.  N = number of matches, it = iterations */
+    int32_t *success, *model;          /* model: 0 = H, 1 = F (the branch taken on RH, also when it fails)  */
+    int32_t *hyp;                      /* the selected hypothesis 0..11, -1 on failure                       */
+    float *r21, *t21;                  /* [9], [3]; zeros on failure                                         */
+    float *p3d;                        /* [n1][3] vP3D, zeros where nothing was stored                       */
+    uint8_t *triangulated;             /* [n1] vbTriangulated                                                */
+    /* diagnostics (copies of their own behind the call) */
+    int32_t *n_matches;
+    float *t1, *t2;                    /* [9] each: Normalize's T of frame 1 / 2                             */
+    float *hn, *fpre, *fn;             /* [it][9]: unit null vectors of H and of F before / after the rank-2 step */
+    float *h21, *h12, *f21;            /* [it][9] denormalised                                               */
+    float *score_h, *score_f;          /* [it]                                                               */
+    int32_t *best_h, *best_f;
+    float *sh, *sf, *rh;
+    uint8_t *inliers_h, *inliers_f;    /* [N] of the best iteration                                          */
+    float *hyp_r, *hyp_t;              /* [12][9], [12][3]                                                   */
+    uint8_t *hyp_valid;                /* [12]                                                               */
+    int32_t *hyp_good;                 /* [12] nGood                                                         */
+    float *hyp_cos_parallax;           /* [12] the cosine at sorted index min(50, nGood-1); 1.0 when nGood = 0 */
+    float *hyp_parallax_deg;           /* [12] acos of it in degrees (host)                                  */
+    uint8_t *hyp_status;               /* [12][N] ORBX_INIT_*                                                */
+    float *hyp_p3d;                    /* [12][N][3] the triangulated point per MATCH (0 where none was computed) */
+    float *hyp_cos;                    /* [12][N] cosParallax per MATCH (0 where none was computed)            */
+} orbx_init_result;
+/* ORBX_ERR_ARG: fewer than 8 matches, iterations < 1, a set index outside [0, N), a match outside [0, n2);
+ * ORBX_ERR_CAPACITY: more matches or iterations than the handle was created for. */
+int orbx_initialize(orbx_initializer *h, const orbx_init_problem *problem, const orbx_init_result *result);
+
+/* CheckHomography (:616-810, kind 0; H12 = H21^-1 is computed inside as in FindHomography) or CheckFundamental
+ * (:813-953, kind 1) of m explicit 3x3 models (m <= 2 * max_iterations) with the chain's kernel:
+ * scores[m], inliers[m][N]. */
+int orbx_init_score_models(orbx_initializer *h, const orbx_init_matches *matches, const float *models, int m, int kind, float sigma,
+                           float *scores, uint8_t *inliers);
+/* CheckRT (:1578-1797) of m <= 12 explicit motions r[m][9], t[m][3] over the matches whose inliers[N] byte is set, with the chain's
+ * kernels: good[m], vb_good[m][n1], p3d[m][n1][3] (vP3D), cos_parallax[m], status[m][N].  Output pointers may be NULL. */
+int orbx_init_check_rt(orbx_initializer *h, const orbx_init_matches *matches, const uint8_t *inliers, const float *r, const float *t, int m,
+                       float fx, float fy, float cx, float cy, float th2, int32_t *good, uint8_t *vb_good, float *p3d, float *cos_parallax,
+                       uint8_t *status);
+/* device time of the last orbx_initialize chain (first to last kernel) and its kernel launches */
+int orbx_initializer_last_timing(orbx_initializer *h, float *device_ms, int *launches);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -1534,3 +1534,163 @@ class MapPointOps:
         n = ctypes.c_int()
         _check(self._L.orbx_mappoint_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+class InitMatches(ctypes.Structure):
+    _fields_ = [("keys1_xy", ctypes.c_void_p), ("keys2_xy", ctypes.c_void_p), ("n1", ctypes.c_int), ("n2", ctypes.c_int), ("matches12", ctypes.c_void_p)]
+
+
+class InitProblem(ctypes.Structure):
+    _fields_ = [("keys1_xy", ctypes.c_void_p), ("keys2_xy", ctypes.c_void_p), ("n1", ctypes.c_int), ("n2", ctypes.c_int), ("matches12", ctypes.c_void_p),
+                ("sets", ctypes.c_void_p), ("iterations", ctypes.c_int), ("sigma", ctypes.c_float), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
+                ("cy", ctypes.c_float), ("min_parallax", ctypes.c_float), ("min_triangulated", ctypes.c_int)]
+
+
+_INIT_RESULT_FIELDS = ("success", "model", "hyp", "r21", "t21", "p3d", "triangulated", "n_matches", "t1", "t2", "hn", "fpre", "fn", "h21", "h12", "f21", "score_h", "score_f",
+                       "best_h", "best_f", "sh", "sf", "rh", "inliers_h", "inliers_f", "hyp_r", "hyp_t", "hyp_valid", "hyp_good", "hyp_cos_parallax", "hyp_parallax_deg",
+                       "hyp_status", "hyp_p3d", "hyp_cos")
+
+
+class InitResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _INIT_RESULT_FIELDS]
+
+
+INIT_STATUS_NAMES = ("NOT_INLIER", "NONFINITE", "BEHIND1", "BEHIND2", "REPROJ1", "REPROJ2", "GOOD", "GOOD_LOW_PARALLAX")      # ORBX_INIT_*
+
+
+def initializer_sets(n, iterations, randint):
+    """mvSets of Initializer::Initialize (reference src/Initializer.cc:139-168): `iterations` sets of 8 distinct indices into n matches, each drawn
+    as randint(0, len(available) - 1) (both bounds inclusive, like DUtils::Random::RandomInt) from the list of indices still available; the drawn
+    slot is overwritten with the list's back and the back is popped.  -> (iterations, 8) int32"""
+    if n < 8:
+        raise ValueError("initializer_sets: %d matches, a set needs 8" % n)
+    out = np.zeros((iterations, 8), np.int32)
+    for it in range(iterations):
+        avail = list(range(n))
+        for j in range(8):
+            r = int(randint(0, len(avail) - 1))
+            out[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return out
+
+
+class Initializer:
+    """Initializer (reference include/Initializer.h, src/Initializer.cc) on the device: Initialize as one launch chain (orbx_initialize), and its
+    two inner loops on explicit inputs (ScoreModels = CheckHomography / CheckFundamental, CheckRT)."""
+
+    def __init__(self, sigma=1.0, iterations=200, max_matches=4096, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.orbx_initializer_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_initializer_destroy.argtypes = [vp]
+        L.orbx_initializer_destroy.restype = None
+        L.orbx_initialize.argtypes = [vp, ctypes.POINTER(InitProblem), ctypes.POINTER(InitResult)]
+        L.orbx_init_score_models.argtypes = [vp, ctypes.POINTER(InitMatches), vp, ci, ci, cf, vp, vp]
+        L.orbx_init_check_rt.argtypes = [vp, ctypes.POINTER(InitMatches), vp, vp, vp, ci, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]
+        L.orbx_initializer_last_timing.argtypes = [vp, vp, vp]
+        self.sigma, self.iterations, self.max_matches = float(sigma), int(iterations), int(max_matches)
+        self._h = vp()
+        _check(L.orbx_initializer_create(device, self.max_matches, self.iterations, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_initializer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _matches(keys1, keys2, matches12):
+        k1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+        if len(m) != len(k1):
+            raise ValueError("Initializer: matches12 holds %d entries for %d keypoints of frame 1" % (len(m), len(k1)))
+        return k1, k2, m, InitMatches(k1.ctypes.data, k2.ctypes.data, len(k1), len(k2), m.ctypes.data)
+
+    def Initialize(self, keys1, keys2, matches12, K, sets=None, rng=None, full=False, min_parallax=1.0, min_triangulated=50):
+        """keys1 (n1,2), keys2 (n2,2): mvKeysUn[i].pt of the reference / current frame; matches12 (n1): index into frame 2 or -1; K = (fx, fy, cx, cy);
+        sets (iterations,8) int32 or None = drawn by initializer_sets from rng (numpy Generator; default seed 0).
+        -> dict(success, model (0 = H, 1 = F), hyp, r21 (3,3), t21 (3), p3d (n1,3), triangulated (n1) bool); full=True adds every diagnostic of
+        orbx_init_result."""
+        k1, k2, m, _ = self._matches(keys1, keys2, matches12)
+        n1, N = len(k1), int((m >= 0).sum())
+        if sets is None:
+            g = np.random.default_rng(0) if rng is None else rng
+            sets = initializer_sets(N, self.iterations, lambda lo, hi: g.integers(lo, hi + 1))
+        s = np.ascontiguousarray(sets, np.int32).reshape(-1, 8)
+        it = len(s)
+        fx, fy, cx, cy = [float(v) for v in K]
+        P = InitProblem(k1.ctypes.data, k2.ctypes.data, n1, len(k2), m.ctypes.data, s.ctypes.data, it, self.sigma, fx, fy, cx, cy, float(min_parallax), int(min_triangulated))
+        f4, i4, u1 = np.float32, np.int32, np.uint8
+        o = dict(success=np.zeros(1, i4), model=np.zeros(1, i4), hyp=np.zeros(1, i4), r21=np.zeros((3, 3), f4), t21=np.zeros(3, f4), p3d=np.zeros((n1, 3), f4),
+                 triangulated=np.zeros(n1, u1))
+        if full:
+            Nn, itn = max(N, 1), max(it, 1)
+            o.update(n_matches=np.zeros(1, i4), t1=np.zeros((3, 3), f4), t2=np.zeros((3, 3), f4), hn=np.zeros((itn, 3, 3), f4), fpre=np.zeros((itn, 3, 3), f4),
+                     fn=np.zeros((itn, 3, 3), f4), h21=np.zeros((itn, 3, 3), f4), h12=np.zeros((itn, 3, 3), f4), f21=np.zeros((itn, 3, 3), f4), score_h=np.zeros(itn, f4),
+                     score_f=np.zeros(itn, f4), best_h=np.zeros(1, i4), best_f=np.zeros(1, i4), sh=np.zeros(1, f4), sf=np.zeros(1, f4), rh=np.zeros(1, f4),
+                     inliers_h=np.zeros(Nn, u1), inliers_f=np.zeros(Nn, u1), hyp_r=np.zeros((12, 3, 3), f4), hyp_t=np.zeros((12, 3), f4), hyp_valid=np.zeros(12, u1),
+                     hyp_good=np.zeros(12, i4), hyp_cos_parallax=np.zeros(12, f4), hyp_parallax_deg=np.zeros(12, f4), hyp_status=np.zeros((12, Nn), u1),
+                     hyp_p3d=np.zeros((12, Nn, 3), f4), hyp_cos=np.zeros((12, Nn), f4))
+        R = InitResult(*[o[k].ctypes.data if k in o else None for k in _INIT_RESULT_FIELDS])
+        _check(self._L.orbx_initialize(self._h, ctypes.byref(P), ctypes.byref(R)))
+        out = {k: (v.reshape(-1)[0].item() if k in ("success", "model", "hyp", "n_matches", "best_h", "best_f") else v) for k, v in o.items()}
+        for k in ("sh", "sf", "rh"):
+            if k in out:
+                out[k] = out[k][0]
+        out["success"] = bool(out["success"])
+        out["triangulated"] = out["triangulated"].astype(bool)
+        for k in ("inliers_h", "inliers_f"):
+            if k in out:
+                out[k] = out[k][:N].astype(bool)
+        if full:
+            out["hyp_status"], out["hyp_p3d"], out["hyp_cos"] = out["hyp_status"][:, :N], out["hyp_p3d"][:, :N], out["hyp_cos"][:, :N]
+        out["sets"] = s
+        return out
+
+    def ScoreModels(self, keys1, keys2, matches12, models, kind, sigma=None):
+        """CheckHomography (kind 0 / "H") or CheckFundamental (kind 1 / "F") of models (M,3,3) -> (scores (M) float32, inliers (M,N) bool)"""
+        k1, k2, m, Mt = self._matches(keys1, keys2, matches12)
+        mod = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+        kind = {"H": 0, "F": 1}.get(kind, kind)
+        N, M = int((m >= 0).sum()), len(mod)
+        scores, inl = np.zeros(max(M, 1), np.float32), np.zeros((max(M, 1), max(N, 1)), np.uint8)
+        _check(self._L.orbx_init_score_models(self._h, ctypes.byref(Mt), mod.ctypes.data, M, int(kind), self.sigma if sigma is None else float(sigma), scores.ctypes.data,
+                                              inl.ctypes.data))
+        return scores[:M], inl.reshape(-1)[:M * N].reshape(M, N).astype(bool)
+
+    def CheckRT(self, keys1, keys2, matches12, inliers, R, t, K, th2=None):
+        """CheckRT of the motions R (M,3,3), t (M,3), M <= 12, over the matches whose `inliers` (N) entry is set; th2 defaults to 4 sigma^2.
+        -> dict(good (M) int32, vb_good (M,n1) bool, p3d (M,n1,3), cos_parallax (M), parallax_deg (M), status (M,N) uint8)"""
+        k1, k2, m, Mt = self._matches(keys1, keys2, matches12)
+        Rm, tm = np.ascontiguousarray(R, np.float32).reshape(-1, 9), np.ascontiguousarray(t, np.float32).reshape(-1, 3)
+        N, M, n1 = int((m >= 0).sum()), len(Rm), len(k1)
+        inl = np.ascontiguousarray(np.asarray(inliers).astype(np.uint8)).reshape(-1)
+        if len(inl) != N or len(tm) != M:
+            raise ValueError("Initializer.CheckRT: array sizes do not agree")
+        fx, fy, cx, cy = [float(v) for v in K]
+        if th2 is None:
+            th2 = np.float32(4.0 * np.float64(np.float32(self.sigma) * np.float32(self.sigma)))
+        o = dict(good=np.zeros(max(M, 1), np.int32), vb_good=np.zeros((max(M, 1), n1), np.uint8), p3d=np.zeros((max(M, 1), n1, 3), np.float32),
+                 cos_parallax=np.zeros(max(M, 1), np.float32), status=np.zeros(max(M, 1) * max(N, 1), np.uint8))
+        _check(self._L.orbx_init_check_rt(self._h, ctypes.byref(Mt), inl.ctypes.data, Rm.ctypes.data, tm.ctypes.data, M, fx, fy, cx, cy, float(th2), o["good"].ctypes.data,
+                                          o["vb_good"].ctypes.data, o["p3d"].ctypes.data, o["cos_parallax"].ctypes.data, o["status"].ctypes.data))
+        o["status"] = o["status"][:M * N].reshape(M, N)
+        o["vb_good"] = o["vb_good"].astype(bool)
+        c = o["cos_parallax"]
+        o["parallax_deg"] = ((np.arccos(c).astype(np.float32) * np.float32(180)).astype(np.float64) / np.pi).astype(np.float32)
+        return o
+
+    def last_timing(self):
+        """(device ms of the last Initialize chain, kernel launches)"""
+        ms = ctypes.c_float()
+        n = ctypes.c_int()
+        _check(self._L.orbx_initializer_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value

@@ -16,14 +16,6 @@
 
 #include "orbx_match_internal.h"
 
-// Sweeps of the one-sided Jacobi.  Chosen on the CPU with the same Jacobi restated in numpy float64 (tests/triangulate_ref.py::jacobi_null) over
-// the test scenes (sideways 0.4 / forward 0.6 / sideways 0.05 baselines, depth 3-10, mono / mixed / stereo) and near-degenerate ones (parallax
-// at the 0.9998 bound, motion along the optical axis, points 100 baselines away): against the float64 SVD the triangulated x3D was off by up to
-// 1e-2 of its distance after 2 sweeps, 9.3e-8 after 3, and equal in every float32 bit after 4, 5, 6 and 8 (cyclic Jacobi converges
-// quadratically; a 4x4 has six pairs).  The count after which nothing changes is 4; + 2 = 6.
-// tests/test_new_map_points.py::test_jacobi_sweeps_settled asserts that 4 and 6 sweeps give the same bits on all of those scenes.
-#define TRI_JACOBI_SWEEPS 6
-
 struct TriCam {
     float tcw[12], ow[3];
     float fx, fy, cx, cy, invfx, invfy, mb, mbf;
@@ -47,58 +39,6 @@ __device__ __forceinline__ double dot3d(float a0, float a1, float a2, float b0, 
     return s;
 }
 __device__ __forceinline__ double norm3d(float a0, float a1, float a2) { return sqrt(dot3d(a0, a1, a2, a0, a1, a2)); }
-
-// Null vector of the 4x4 float matrix A (rows r0..r3): one-sided (Hestenes) Jacobi in FP64 on the columns of A, V accumulated alongside;
-// the column of V under the smallest column norm is vt.row(3).  Everything is indexed by compile-time constants: registers, no scratch.
-__device__ __forceinline__ void jacobi_null(const float (&r0)[4], const float (&r1)[4], const float (&r2)[4], const float (&r3)[4], double (&nv)[4])
-{
-    double a[4][4], v[4][4];      // [column][row]
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        a[c][0] = (double)r0[c]; a[c][1] = (double)r1[c]; a[c][2] = (double)r2[c]; a[c][3] = (double)r3[c];
-#pragma unroll
-        for (int r = 0; r < 4; r++) v[c][r] = r == c ? 1.0 : 0.0;
-    }
-#pragma unroll 1
-    for (int sweep = 0; sweep < TRI_JACOBI_SWEEPS; sweep++) {
-#pragma unroll
-        for (int p = 0; p < 3; p++) {
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) {
-                double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-                for (int r = 0; r < 4; r++) { alpha = alpha + a[p][r] * a[p][r]; beta = beta + a[q][r] * a[q][r]; gamma = gamma + a[p][r] * a[q][r]; }
-                double c = 1.0, s = 0.0;
-                if (gamma != 0.0) {
-                    const double zeta = (beta - alpha) / (2.0 * gamma);
-                    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    c = 1.0 / sqrt(1.0 + t * t);
-                    s = c * t;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const double ap = a[p][r], aq = a[q][r];
-                    a[p][r] = c * ap - s * aq;
-                    a[q][r] = s * ap + c * aq;
-                    const double vp = v[p][r], vq = v[q][r];
-                    v[p][r] = c * vp - s * vq;
-                    v[q][r] = s * vp + c * vq;
-                }
-            }
-        }
-    }
-    double best = 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        double n2 = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; r++) n2 = n2 + a[c][r] * a[c][r];
-        const bool take = c == 0 || n2 < best;      // the first of equal norms
-        best = take ? n2 : best;
-#pragma unroll
-        for (int r = 0; r < 4; r++) nv[r] = take ? v[c][r] : nv[r];
-    }
-}
 
 // chi2 reprojection test of one keyframe (:516-542 / :546-570); mbf is ALWAYS the current keyframe's (:534, :562)
 __device__ __forceinline__ bool reproj_fails(const TriCam &C, float x, float y, float invz, float kx, float ky, float ur, bool stereo, float sigma2, float mbf1)
