@@ -1079,6 +1079,107 @@ int orbx_init_check_rt(orbx_initializer *h, const orbx_init_matches *matches, co
 /* device time of the last orbx_initialize chain (first to last kernel) and its kernel launches */
 int orbx_initializer_last_timing(orbx_initializer *h, float *device_ms, int *launches);
 
+/* ----------------------------------------------------------------------------------
+ * Sim3Solver (reference include/Sim3Solver.h, src/Sim3Solver.cc): Horn 1987 on RANSAC triples, for ALL loop candidates
+ * of LoopClosing::ComputeSim3 (src/LoopClosing.cc:300-560) in one launch chain with one wait.
+ *
+ *   The host (the shim) walks the pointers: vpMatched12 compacted in i1 order, pairs with a missing or bad point or an
+ *   index < 0 skipped; per kept pair the two world positions, the two mvLevelSigma2[octave] and mvnIndices1.  The device
+ *   does the rest, every iteration of every candidate: iterations do not depend on the solver's state once the sets are
+ *   drawn, so the running best of iterate (:199-285) is a scan over the per-iteration inlier counts.
+ *     k_sim3_prepare  the constructor (:48-140): X3Dc = Rcw * Xw + tcw, FromCameraToImage (:526-545), the two error limits;
+ *                     reads the call's inputs in mapped pinned memory once and leaves everything later kernels read
+ *                     many times in device memory.
+ *     k_sim3_models   one lane per (candidate, iteration): ComputeSim3 (:309-448).
+ *     k_sim3_check    one wave per (candidate, iteration): CheckInliers / Project (:451-523), the ballot of 64 matches is
+ *                     the mask word, its population count the count.  All masks stay on the device.
+ *     k_sim3_decide   one workgroup per candidate: the running best (count >= best updates it), the RETURN EVENTS (an
+ *                     update with count > min_inliers), the first event and its mask, the result block, the sequence word.
+ *
+ *   Arithmetic, in the reference's operation order (float where it is float; the library is built with -ffp-contract=off):
+ *     constructor   X3Dc = (R[0]*x + R[1]*y) + R[2]*z, then + t; invz = 1 / z as a FLOAT quotient; fx * (x * invz) + cx;
+ *                   the limits are std::vector<size_t> (Sim3Solver.h:156-157): 9.210 * sigma2 as a double product,
+ *                   truncated to an unsigned integer, compared as that integer converted to float.
+ *     centroids     the sum of the three columns in order, then Mat / int: a double quotient narrowed to float
+ *     M             Pr2 * Pr1^T, 3-term float products left to right
+ *     N             the ten entries as float sums left to right, widened to double, narrowed to float again
+ *     eigenvector   of the largest eigenvalue (the first of equal ones): cyclic two-sided Jacobi in FP64 on the float N,
+ *                   ORBX_SIM3_JACOBI_SWEEPS sweeps, narrowed to float.  q and -q give the same rotation.
+ *     angle-axis    ang = atan2(norm(vec), q0) in double, norm accumulates in double; vec = float(((2 * ang) / norm) * vec)
+ *     cv::Rodrigues in double on the float vec (theta = norm; R = c I + (1 - c) r r^T + s [r]x), narrowed to float
+ *     scale         P3 = R * Pr2; nom = Pr1.dot(P3) accumulated in double, row-major; den = the double sum of the FLOAT
+ *                   squares of P3, row-major; s = float(nom / den); 1.0f with fix_scale
+ *     t, T12, T21   sR = float products s * R; t = O1 - sR * O2; sRinv = float((1.0 / s) * R^T) with the quotient and the
+ *                   products in double; tinv = (-sRinv) * t
+ *     CheckInliers  P = R * X + t of the 4x4's upper rows, invz = 1 / z as a float quotient, fx * (x * invz) + cx; the error
+ *                   is Mat::dot: the two squares summed in double, narrowed to float; no depth test, z <= 0 and non-finite
+ *                   values are not special-cased, a NaN error fails the <.  inlier = err1 < max1 && err2 < max2.
+ *   PARITY UNPINNED AT THE OPENCV LEVEL: cv::eigen in float (here: Jacobi in FP64, narrowed), cv::Rodrigues, the
+ *   accumulation inside cv::gemm (here: 3-term float products, scalar factors applied to the matrix first) and Mat / int.
+ *   The device library's atan2, sin and cos are not pinned either.
+ *
+ *   RANSAC sets are the caller's, [iterations][3] indices into the compacted list, distinct inside a set, each drawn by
+ *   the reference's draw, overwrite-with-back, pop scheme (:228-249).  The reference draws lazily, three numbers per
+ *   iteration, interleaved between the candidates of the round-robin loop; a batched call has to draw ahead, so a caller's
+ *   rand() sequence is consumed in ANOTHER ORDER than the reference's.  This is not a parity claim.
+ *
+ *   n < min_inliers (:206-210): no iterations are run whatever `iterations` says, no_more = 1.
+ * ---------------------------------------------------------------------------------- */
+/* Sweeps of the 4x4 Jacobi.  Chosen on the CPU with the same iteration restated in numpy float64 (tests/sim3_ref.py::jacobi_eig4) over the
+ * 1843 RANSAC sets of the test scenes: no float32 bit of the eigenvector changes after 5 sweeps (after 4 on all but 3 sets); 8 are run, and
+ * tests/test_sim3_solver.py::test_jacobi_sweeps_settled asserts that 6, 8 and 10 give the same bits. */
+#define ORBX_SIM3_JACOBI_SWEEPS 8
+#define ORBX_SIM3_MAX_MATCHES 65536
+
+typedef struct orbx_sim3_solver orbx_sim3_solver;
+/* ORBX_ERR_ARG: max_candidates < 1, max_matches outside 3..ORBX_SIM3_MAX_MATCHES, max_iterations < 1 (the three are PER
+ * CANDIDATE limits except the first); then ORBX_ERR_NODEVICE without a device */
+int orbx_sim3_solver_create(int device, int max_candidates, int max_matches, int max_iterations, orbx_sim3_solver **out);
+void orbx_sim3_solver_destroy(orbx_sim3_solver *h);
+
+typedef struct orbx_sim3_problem {     /* host memory: one candidate */
+    float rcw1[9], tcw1[3], rcw2[9], tcw2[3];   /* GetRotation / GetTranslation of pKF1, pKF2                       */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    int n;                                      /* kept pairs                                                       */
+    const float *world1, *world2;               /* [n][3] GetWorldPos of pMP1 / pMP2                                */
+    const float *sigma2_1, *sigma2_2;           /* [n] mvLevelSigma2[octave]                                        */
+    const int32_t *sets;                        /* [iterations][3]                                                  */
+    int iterations;                             /* mRansacMaxIts (orbx_sim3_ransac_iterations)                      */
+    int min_inliers;
+    int fix_scale;
+} orbx_sim3_problem;
+
+typedef struct orbx_sim3_result {      /* host memory: one candidate; every pointer may be NULL.  it = iterations run */
+    int32_t *count;                    /* [it] mnInliersi                                                            */
+    float *r12, *t12, *s12;            /* [it][9], [it][3], [it]                                                     */
+    uint8_t *is_event;                 /* [it] the iteration updates the best and count > min_inliers                */
+    int32_t *first_event;              /* the first such iteration, -1 = none                                        */
+    int32_t *best_iteration;           /* the last iteration that updated the best (mBest* after all), -1 = none run */
+    int32_t *no_more;                  /* n < min_inliers, or no event in any iteration                              */
+    uint8_t *inliers_first;            /* [n] mvbInliersi of the first event, COMPACTED indices; zeros without one   */
+    /* diagnostics (copies of their own behind the call) */
+    float *x3dc1, *x3dc2;              /* [n][3]                                                                     */
+    float *p1im1, *p2im2;              /* [n][2]                                                                     */
+    float *max_err1, *max_err2;        /* [n] the truncated limits as floats                                         */
+    float *nmat, *quat;                /* [it][16], [it][4]                                                          */
+    float *t12m, *t21m;                /* [it][16]                                                                   */
+} orbx_sim3_result;
+/* ORBX_ERR_ARG: ncandidates < 1, a NULL problem / array, n < 0, iterations < 0, n < 3 with iterations to run, a set index
+ * outside [0, n), repeated indices inside a set; ORBX_ERR_CAPACITY: more candidates, matches or iterations than the handle
+ * was created for.  Nothing is launched on an error and the handle stays usable. */
+int orbx_sim3_solve(orbx_sim3_solver *h, const orbx_sim3_problem *problems, int ncandidates, const orbx_sim3_result *results);
+/* mvbInliersi [n] of any iteration of any candidate of the last orbx_sim3_solve: one row of the device's masks, copied on
+ * demand (a caller's second and later return events).  ORBX_ERR_STATE before a solve, ORBX_ERR_ARG outside it. */
+int orbx_sim3_inliers(orbx_sim3_solver *h, int candidate, int iteration, uint8_t *inliers);
+/* CheckInliers of m <= max_iterations explicit transformations t12[m][16], t21[m][16] (row-major 4x4) over the problem's
+ * pairs with the chain's kernels: count[m], inliers[m][n] (may be NULL).  sets / iterations / min_inliers are not read. */
+int orbx_sim3_check_models(orbx_sim3_solver *h, const orbx_sim3_problem *problem, const float *t12, const float *t21, int m,
+                           int32_t *count, uint8_t *inliers);
+/* mRansacMaxIts of SetRansacParameters (:143-196) with the reference's libm calls; n = number of kept pairs.  No device. */
+int orbx_sim3_ransac_iterations(double probability, int min_inliers, int max_iterations, int n);
+/* device time of the last orbx_sim3_solve chain (first to last kernel) and its kernel launches */
+int orbx_sim3_last_timing(orbx_sim3_solver *h, float *device_ms, int *launches);
+
 
 #ifdef __cplusplus
 }

@@ -1694,3 +1694,212 @@ class Initializer:
         n = ctypes.c_int()
         _check(self._L.orbx_initializer_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+class Sim3Problem(ctypes.Structure):
+    _fields_ = [("rcw1", ctypes.c_float * 9), ("tcw1", ctypes.c_float * 3), ("rcw2", ctypes.c_float * 9), ("tcw2", ctypes.c_float * 3),
+                ("fx1", ctypes.c_float), ("fy1", ctypes.c_float), ("cx1", ctypes.c_float), ("cy1", ctypes.c_float),
+                ("fx2", ctypes.c_float), ("fy2", ctypes.c_float), ("cx2", ctypes.c_float), ("cy2", ctypes.c_float),
+                ("n", ctypes.c_int), ("world1", ctypes.c_void_p), ("world2", ctypes.c_void_p), ("sigma2_1", ctypes.c_void_p), ("sigma2_2", ctypes.c_void_p),
+                ("sets", ctypes.c_void_p), ("iterations", ctypes.c_int), ("min_inliers", ctypes.c_int), ("fix_scale", ctypes.c_int)]
+
+
+_SIM3_RESULT_FIELDS = ("count", "r12", "t12", "s12", "is_event", "first_event", "best_iteration", "no_more", "inliers_first", "x3dc1", "x3dc2", "p1im1", "p2im2",
+                       "max_err1", "max_err2", "nmat", "quat", "t12m", "t21m")
+
+
+class Sim3Result(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _SIM3_RESULT_FIELDS]
+
+
+def sim3_sets(n, iterations, randint):
+    """The minimal sets of Sim3Solver::iterate (reference src/Sim3Solver.cc:228-249): `iterations` sets of 3 distinct indices into n kept pairs, each
+    drawn as randint(0, len(available) - 1) (both bounds inclusive, like DUtils::Random::RandomInt) from the list of indices still available; the
+    drawn slot is overwritten with the list's back and the back is popped.  -> (iterations, 3) int32"""
+    if n < 3 and iterations > 0:
+        raise ValueError("sim3_sets: %d matches, a set needs 3" % n)
+    out = np.zeros((iterations, 3), np.int32)
+    for it in range(iterations):
+        avail = list(range(n))
+        for j in range(3):
+            r = int(randint(0, len(avail) - 1))
+            out[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return out
+
+
+def sim3_ransac_iterations(prob, min_inliers, max_iterations, n):
+    """mRansacMaxIts of Sim3Solver::SetRansacParameters (:143-196); needs no device"""
+    L = load_library()
+    L.orbx_sim3_ransac_iterations.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    return int(L.orbx_sim3_ransac_iterations(float(prob), int(min_inliers), int(max_iterations), int(n)))
+
+
+class Sim3Candidate:
+    """One solved candidate: the device's per-iteration outputs, and the reference's stateful surface replayed from them on the host.
+    iterate(nIterations) -> (T12 (4,4) float32 or None, bNoMore, vbInliers (mN1) bool, nInliers), call after call, also after a success."""
+
+    def __init__(self, solver, index, out, n, n1, indices1, min_inliers):
+        self._solver, self._index, self.n, self.mN1, self.indices1, self.min_inliers = solver, index, n, n1, indices1, min_inliers
+        self.__dict__.update(out)
+        self.iterations = len(self.count)
+        self.mnIterations = 0
+        self._best, self._best_count = -1, 0
+
+    def inliers(self, iteration):
+        """mvbInliersi (n, compacted) of any iteration: one row of the device's masks"""
+        return self._solver._inliers(self._index, iteration, self.n)
+
+    def T12(self, iteration):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = np.float32(self.s12[iteration]) * self.r12[iteration]
+        T[:3, 3] = self.t12[iteration]
+        return T
+
+    def iterate(self, nIterations):
+        vb = np.zeros(self.mN1, bool)
+        if self.n < self.min_inliers:
+            return None, True, vb, 0
+        cur = 0
+        while self.mnIterations < self.iterations and cur < nIterations:
+            it = self.mnIterations
+            cur += 1
+            self.mnIterations += 1
+            if self.count[it] < self._best_count:
+                continue
+            self._best, self._best_count = it, int(self.count[it])
+            if self.count[it] > self.min_inliers:
+                inl = self.inliers_first if it == self.first_event else self.inliers(it)
+                vb[self.indices1[inl]] = True
+                return self.T12(it), False, vb, int(self.count[it])
+        return None, self.mnIterations >= self.iterations, vb, 0
+
+    def find(self):
+        T, _, vb, k = self.iterate(self.iterations)
+        return T, vb, k
+
+    def GetEstimatedRotation(self):
+        return self.r12[self._best].copy()
+
+    def GetEstimatedTranslation(self):
+        return self.t12[self._best].copy()
+
+    def GetEstimatedScale(self):
+        return np.float32(self.s12[self._best])
+
+
+class Sim3Solver:
+    """Sim3Solver (reference include/Sim3Solver.h, src/Sim3Solver.cc) on the device: every RANSAC iteration of every loop candidate in one launch
+    chain (orbx_sim3_solve), and CheckInliers on explicit transformations (CheckModels)."""
+
+    def __init__(self, max_candidates=8, max_matches=2048, max_iterations=300, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_sim3_solver_create.argtypes = [ci, ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_sim3_solver_destroy.argtypes = [vp]
+        L.orbx_sim3_solver_destroy.restype = None
+        L.orbx_sim3_solve.argtypes = [vp, ctypes.POINTER(Sim3Problem), ci, ctypes.POINTER(Sim3Result)]
+        L.orbx_sim3_inliers.argtypes = [vp, ci, ci, vp]
+        L.orbx_sim3_check_models.argtypes = [vp, ctypes.POINTER(Sim3Problem), vp, vp, ci, vp, vp]
+        L.orbx_sim3_last_timing.argtypes = [vp, vp, vp]
+        self.max_candidates, self.max_matches, self.max_iterations = int(max_candidates), int(max_matches), int(max_iterations)
+        self._h = vp()
+        _check(L.orbx_sim3_solver_create(device, self.max_candidates, self.max_matches, self.max_iterations, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_sim3_solver_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _problem(c, keep):
+        """c: dict(Rcw1 (3,3), tcw1 (3), Rcw2, tcw2, K1 (fx, fy, cx, cy), K2, world1 (n,3), world2 (n,3), sigma2_1 (n), sigma2_2 (n))"""
+        f4 = np.float32
+        w1, w2 = np.ascontiguousarray(c["world1"], f4).reshape(-1, 3), np.ascontiguousarray(c["world2"], f4).reshape(-1, 3)
+        s1, s2 = np.ascontiguousarray(c["sigma2_1"], f4).reshape(-1), np.ascontiguousarray(c["sigma2_2"], f4).reshape(-1)
+        n = len(w1)
+        if not (len(w2) == len(s1) == len(s2) == n):
+            raise ValueError("Sim3Solver: the per-pair arrays of a candidate disagree in length")
+        keep.extend([w1, w2, s1, s2])
+        P = Sim3Problem()
+        for name, key, k in (("rcw1", "Rcw1", 9), ("tcw1", "tcw1", 3), ("rcw2", "Rcw2", 9), ("tcw2", "tcw2", 3)):
+            setattr(P, name, (ctypes.c_float * k)(*np.asarray(c[key], f4).reshape(-1)))
+        P.fx1, P.fy1, P.cx1, P.cy1 = [float(v) for v in c["K1"]]
+        P.fx2, P.fy2, P.cx2, P.cy2 = [float(v) for v in c["K2"]]
+        P.n, P.world1, P.world2, P.sigma2_1, P.sigma2_2 = n, w1.ctypes.data, w2.ctypes.data, s1.ctypes.data, s2.ctypes.data
+        return P, n
+
+    def Solve(self, candidates, sets=None, rng=None, prob=0.99, min_inliers=20, max_iterations=300, fix_scale=False, full=False):
+        """candidates: list of dicts (see _problem; optional "indices1" (n) = mvnIndices1 and "mN1" = len(vpMatched12), default the identity).
+        sets: list of (iterations,3) int32 per candidate or None = mRansacMaxIts sets per candidate drawn by sim3_sets from rng (numpy Generator,
+        default seed 0), candidate after candidate.  -> [Sim3Candidate]; full=True adds every diagnostic of orbx_sim3_result."""
+        C = len(candidates)
+        keep, probs, ns = [], (Sim3Problem * max(C, 1))(), []
+        g = np.random.default_rng(0) if rng is None else rng
+        used = []
+        for c, cd in enumerate(candidates):
+            P, n = self._problem(cd, keep)
+            if sets is None:
+                its = sim3_ransac_iterations(prob, min_inliers, max_iterations, n) if n >= min_inliers else 0
+                s = sim3_sets(n, its, lambda lo, hi: g.integers(lo, hi + 1))
+            else:
+                s = np.ascontiguousarray(sets[c], np.int32).reshape(-1, 3)
+            used.append(s)
+            P.sets, P.iterations, P.min_inliers, P.fix_scale = s.ctypes.data, len(s), int(min_inliers), 1 if fix_scale else 0
+            probs[c] = P
+            ns.append(n)
+        f4, i4, u1 = np.float32, np.int32, np.uint8
+        res, outs = (Sim3Result * max(C, 1))(), []
+        for c in range(C):
+            n, it = ns[c], (len(used[c]) if ns[c] >= min_inliers else 0)
+            o = dict(count=np.zeros(it, i4), r12=np.zeros((it, 3, 3), f4), t12=np.zeros((it, 3), f4), s12=np.zeros(it, f4), is_event=np.zeros(it, u1),
+                     first_event=np.zeros(1, i4), best_iteration=np.zeros(1, i4), no_more=np.zeros(1, i4), inliers_first=np.zeros(n, u1))
+            if full:
+                o.update(x3dc1=np.zeros((n, 3), f4), x3dc2=np.zeros((n, 3), f4), p1im1=np.zeros((n, 2), f4), p2im2=np.zeros((n, 2), f4), max_err1=np.zeros(n, f4),
+                         max_err2=np.zeros(n, f4), nmat=np.zeros((it, 4, 4), f4), quat=np.zeros((it, 4), f4), t12m=np.zeros((it, 4, 4), f4), t21m=np.zeros((it, 4, 4), f4))
+            res[c] = Sim3Result(*[o[k].ctypes.data if k in o and o[k].size else None for k in _SIM3_RESULT_FIELDS])
+            outs.append(o)
+        _check(self._L.orbx_sim3_solve(self._h, probs, C, res))
+        result = []
+        for c, o in enumerate(outs):
+            for k in ("first_event", "best_iteration"):
+                o[k] = int(o[k][0])
+            o["no_more"] = bool(o["no_more"][0])
+            o["is_event"], o["inliers_first"] = o["is_event"].astype(bool), o["inliers_first"].astype(bool)
+            o["sets"] = used[c][:len(o["count"])]
+            cd = candidates[c]
+            idx = np.asarray(cd["indices1"], np.int64) if "indices1" in cd else np.arange(ns[c])
+            result.append(Sim3Candidate(self, c, o, ns[c], int(cd.get("mN1", ns[c])), idx, int(min_inliers)))
+        return result
+
+    def _inliers(self, candidate, iteration, n):
+        out = np.zeros(max(n, 1), np.uint8)
+        _check(self._L.orbx_sim3_inliers(self._h, int(candidate), int(iteration), out.ctypes.data))
+        return out[:n].astype(bool)
+
+    def CheckModels(self, candidate, t12, t21):
+        """CheckInliers of the explicit transformations t12, t21 (M,4,4) over a candidate's pairs -> (count (M) int32, inliers (M,n) bool)"""
+        keep = []
+        P, n = self._problem(candidate, keep)
+        a, b = np.ascontiguousarray(t12, np.float32).reshape(-1, 16), np.ascontiguousarray(t21, np.float32).reshape(-1, 16)
+        M = len(a)
+        if len(b) != M:
+            raise ValueError("Sim3Solver.CheckModels: %d T12 for %d T21" % (M, len(b)))
+        count, inl = np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1) * max(n, 1), np.uint8)
+        _check(self._L.orbx_sim3_check_models(self._h, ctypes.byref(P), a.ctypes.data, b.ctypes.data, M, count.ctypes.data, inl.ctypes.data))
+        return count[:M], inl[:M * n].reshape(M, n).astype(bool)
+
+    def last_timing(self):
+        """(device ms of the last Solve chain, kernel launches)"""
+        ms = ctypes.c_float()
+        n = ctypes.c_int()
+        _check(self._L.orbx_sim3_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
