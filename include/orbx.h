@@ -1180,6 +1180,155 @@ int orbx_sim3_ransac_iterations(double probability, int min_inliers, int max_ite
 /* device time of the last orbx_sim3_solve chain (first to last kernel) and its kernel launches */
 int orbx_sim3_last_timing(orbx_sim3_solver *h, float *device_ms, int *launches);
 
+/* ----------------------------------------------------------------------------------
+ * PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc): EPnP on RANSAC sets of four matches, for ALL relocalisation
+ * candidates of Tracking::Relocalization (src/Tracking.cc) in one launch chain with one wait.
+ *
+ *   The host (the shim) walks the pointers (:120-168): per kept match the undistorted keypoint (mvP2D), mvLevelSigma2[octave]
+ *   and the MapPoint's world position (mvP3Dw).  The device does the rest, every iteration of every candidate.  Iterations are
+ *   independent once the sets are drawn, EXCEPT through Refine (:366-418), whose input is the running-best inlier mask: its
+ *   result depends only on the current RECORD (an iteration at which the running best changes), so it is computed once per
+ *   record, and iterate (:240-363) is a scan over counts, records and refined counts.
+ *     k_pnp_prepare  mvMaxError[i] = sigma2 * th2 as a float product (:227-229); reads the call's inputs in mapped pinned memory
+ *                    once and leaves everything later kernels read many times in device memory.
+ *     k_pnp_models   a team of 16 lanes per (candidate, iteration): compute_pose (:684-759) with everything it calls.
+ *     k_pnp_check    one wave per (candidate, iteration): CheckInliers (:421-458), the ballot of 64 matches is the mask word.
+ *     k_pnp_records  one wave per candidate: the running best changes only on count >= minInliers && count > best (strictly
+ *                    greater, unlike Sim3Solver); record_of[i] = the latest record at or before iteration i.
+ *     k_pnp_refine   one workgroup per (candidate, record): compute_pose on the record's inlier mask (points in index order),
+ *                    then k_pnp_check on the refined models.  Refine succeeds on refined count > minInliers (strict, :404).
+ *     k_pnp_decide   one workgroup per candidate: the RETURN EVENTS (count_i >= minInliers, :301, and record_of[i] refined
+ *                    successfully), the first event and its refined mask, mBestTcw and its mask, the result block.
+ *   All masks, of iterations and of refines, stay on the device; orbx_pnp_inliers copies one row out.
+ *
+ *   SetRansacParameters (:181-223) is evaluated on the HOST with the reference's libm calls (orbx_pnp_ransac_parameters; the
+ *   device library's log and pow are not pinned): int nMinInliers = N * epsilon is a truncated FLOAT product, raised to
+ *   min_inliers and min_set; epsilon is raised to (float)minInliers / N; the iteration count uses pow(epsilon, 3) although a
+ *   set has four points; minInliers == N gives one iteration; the result is clamped to [1, max_iterations].
+ *   N < minInliers (:250-254): no iterations are run whatever `iterations` says, no_more = 1.
+ *
+ *   Arithmetic: FP64 where the reference is double, in its operation order (sums left to right; the library is built with
+ *   -ffp-contract=off), float keypoints and positions widened on use.
+ *     sums over a set's points    centroid, PW0^T PW0, M^T M, the camera-frame centroid, ABt and the reprojection sum are each ONE
+ *                   lane's loop over the points in the set's order (Refine: ascending index); different entries run on
+ *                   different lanes.  No atomics: every sum is bit-reproducible from run to run and from batch to single.
+ *     alphas        a[1..3] = (ci[3j] * d0 + ci[3j+1] * d1) + ci[3j+2] * d2, a[0] = ((1 - a[1]) - a[2]) - a[3] (1.0f is exact)
+ *     cvSVD of PW0^T PW0 and of M^T M: cyclic two-sided Jacobi in FP64 on the symmetric matrix (the rotation of (p, q) applied
+ *                   to the off-diagonal entries of rows / columns p and q and to the columns of V, a_pp -= t a_pq,
+ *                   a_qq += t a_pq, a_pq = 0; an entry <= 2^-60 (|a_pp| + |a_qq|) is set to zero unrotated), at most
+ *                   ORBX_PNP_JACOBI_SWEEPS / ORBX_PNP_SMALL_SWEEPS sweeps, ended by a sweep without a rotation (the
+ *                   later ones would be identities); singular values = |eigenvalues|, descending, the first of equal
+ *                   ones first.
+ *     cvSolve(CV_SVD) of find_betas_approx_1/2/3, cvInvert(CV_SVD) of the control-point matrix, cvSVD of ABt: one-sided
+ *                   (Hestenes) Jacobi on the columns in FP64, ORBX_PNP_SMALL_SWEEPS sweeps, columns with
+ *                   |a_p . a_q| <= 2^-49 |a_p| |a_q| left alone; x = V Sigma^-2 (A V)^T b with squared singular values below
+ *                   2^-104 of the largest dropped; R = U V^T summed in the Jacobi's column order.
+ *     qr_solve      (:1251-1385) restated operation by operation, including the column maximum that looks at rows k .. nr-2;
+ *                   on its "A is singular" return the increment is zero (the reference adds an uninitialised one).
+ *     CheckInliers  Xc, Yc, invZc are double expressions narrowed to float; ue = uc + (fu * Xc) * invZc and ve in double; distX,
+ *                   distY (narrowed differences) and error2 = distX * distX + distY * distY in float; error2 < mvMaxError[i]
+ *                   strictly; no depth test, z <= 0 is not special-cased; a NaN model counts zero inliers.
+ *     Tcw           refined and best poses narrowed from double to float as :310-316 / :407-413.
+ *   PARITY UNPINNED AT THE OPENCV LEVEL: cvSVD, cvSolve(CV_SVD) and cvInvert(CV_SVD) are replaced by the FP64 Jacobi
+ *   routines above and least squares built on them; the signs of eigen- and singular vectors; the basis OpenCV picks inside
+ *   the four-dimensional null space of M^T M for a minimal set (find_betas_approx_2/3 use individual vectors of it, so which
+ *   of the three solutions wins may differ); planar or otherwise rank-deficient control-point sets, where cvInvert takes a
+ *   pseudo-inverse; the accumulation order inside cvMulTransposed.
+ *
+ *   RANSAC sets are the caller's, [iterations][4] indices into the compacted list, distinct inside a set, each drawn by the
+ *   reference's draw, overwrite-with-back, pop scheme (:274-290).  The reference draws lazily, four numbers per iteration,
+ *   interleaved between the candidates of the round-robin loop; a batched call has to draw ahead, so a caller's rand()
+ *   sequence is consumed in ANOTHER ORDER than the reference's.  This is not a parity claim.  `iterations` is the number of
+ *   sets handed over; it may exceed mRansacMaxIts (iterate runs past it, :266).
+ * ---------------------------------------------------------------------------------- */
+/* Sweeps of the 12x12 two-sided Jacobi and of the small ones (3x3 two-sided; one-sided 6x3, 6x4, 6x5, 3x3).  Chosen on the CPU
+ * with the same iterations restated in numpy float64 (tests/pnp_ref.py) over 135 sets of 4 to 130 matches of three scenes: both
+ * iterations set the rotated entry to zero and stop touching entries that are negligible, so they reach a FIXED POINT - no bit of
+ * any output changes after 10 sweeps of the 12x12 (after 9 on all but one set) and after 5 of the small ones; 12 and 8 are run, and
+ * tests/test_pnp_solver.py::test_jacobi_sweeps_settled asserts that k, k + 2 and k + 4 sweeps give the same bits. */
+#define ORBX_PNP_JACOBI_SWEEPS 12
+#define ORBX_PNP_SMALL_SWEEPS 8
+#define ORBX_PNP_MAX_MATCHES 65536
+/* orbx_pnp_epnp(full): doubles per set and the offsets of the stage outputs inside them */
+#define ORBX_PNP_FULL_DOUBLES 472
+#define ORBX_PNP_F_CWS 0      /* [4][3] control points                                            */
+#define ORBX_PNP_F_PCA 12     /* [3][3] PW0^T PW0                                                 */
+#define ORBX_PNP_F_DC 21      /* [3] its singular values, descending                              */
+#define ORBX_PNP_F_UCT 24     /* [3][3] rows = its vectors                                        */
+#define ORBX_PNP_F_CI 33      /* [3][3] cc_inv                                                    */
+#define ORBX_PNP_F_MTM 42     /* [12][12] M^T M                                                   */
+#define ORBX_PNP_F_D 186      /* [12] its singular values, descending                             */
+#define ORBX_PNP_F_UT 198     /* [12][12] rows = its vectors (the last four span the solution)    */
+#define ORBX_PNP_F_L 342      /* [6][10]                                                          */
+#define ORBX_PNP_F_RHO 402    /* [6]                                                              */
+#define ORBX_PNP_F_B0 408     /* [3][4] betas of find_betas_approx_1, _2, _3                      */
+#define ORBX_PNP_F_B1 420     /* [3][4] ... after gauss_newton                                    */
+#define ORBX_PNP_F_RS 432     /* [3][3][3]                                                        */
+#define ORBX_PNP_F_TS 459     /* [3][3]                                                           */
+#define ORBX_PNP_F_ERR 468    /* [3] rep_errors                                                   */
+#define ORBX_PNP_F_CHOICE 471 /* N of :750-752 (1, 2 or 3)                                        */
+
+typedef struct orbx_pnp_solver orbx_pnp_solver;
+/* ORBX_ERR_ARG: max_candidates < 1, max_matches outside 4..ORBX_PNP_MAX_MATCHES, max_iterations < 1 (the last two are PER
+ * CANDIDATE limits); then ORBX_ERR_NODEVICE without a device */
+int orbx_pnp_solver_create(int device, int max_candidates, int max_matches, int max_iterations, orbx_pnp_solver **out);
+void orbx_pnp_solver_destroy(orbx_pnp_solver *h);
+
+typedef struct orbx_pnp_problem {      /* host memory: one candidate */
+    float fx, fy, cx, cy;
+    int n;                             /* kept matches                                                               */
+    const float *p2d;                  /* [n][2] mvP2D                                                               */
+    const float *sigma2;               /* [n] mvLevelSigma2[octave]                                                  */
+    const float *p3dw;                 /* [n][3] mvP3Dw                                                              */
+    double probability;                /* the SetRansacParameters arguments                                          */
+    int min_inliers, max_iterations, min_set;
+    float epsilon, th2;
+    const int32_t *sets;               /* [iterations][4]                                                            */
+    int iterations;                    /* sets handed over (>= mRansacMaxIts for a caller that iterates past it)     */
+} orbx_pnp_problem;
+
+typedef struct orbx_pnp_result {       /* host memory: one candidate; every pointer may be NULL.  it = iterations run */
+    int32_t *count;                    /* [it] mnInliersi                                                            */
+    double *r, *t, *err;               /* [it][9], [it][3], [it]: mRi, mti and compute_pose's return value           */
+    int32_t *record_of;                /* [it] index of the latest record at or before the iteration, -1 = none yet  */
+    uint8_t *is_event;                 /* [it] iterate returns at this iteration                                     */
+    int32_t *nrecords;
+    int32_t *record_iteration;         /* [it], the first nrecords entries: the iteration of each record             */
+    int32_t *refined_count;            /* [it], the first nrecords entries: mnRefinedInliers                         */
+    double *refined_r, *refined_t;     /* [it][9], [it][3], the first nrecords entries                               */
+    float *refined_tcw;                /* [it][12], the first nrecords entries: rows of [R | t] of mRefinedTcw       */
+    float *best_tcw;                   /* [12] mBestTcw after all iterations (zeros without a record)                */
+    int32_t *first_event;              /* the first returning iteration, -1 = none                                   */
+    int32_t *best_iteration;           /* the last record's iteration, -1 = no iteration reached min_inliers         */
+    int32_t *no_more;                  /* n < min_inliers: nothing was run                                           */
+    int32_t *min_inliers;              /* mRansacMinInliers after SetRansacParameters                                */
+    uint8_t *inliers_first;            /* [n] mvbRefinedInliers of the first event, COMPACTED indices; zeros without */
+    uint8_t *inliers_best;             /* [n] mvbBestInliers after all iterations; zeros without a record            */
+    float *max_error;                  /* [n] mvMaxError (diagnostic, a copy of its own behind the call)             */
+} orbx_pnp_result;
+/* ORBX_ERR_ARG: ncandidates < 1, a NULL problem / array, n < 0, iterations < 0, n < 4 with iterations to run, a set index
+ * outside [0, n), a repeated index inside a set; ORBX_ERR_CAPACITY: more candidates, matches or iterations than the handle
+ * was created for.  Nothing is launched on an error and the handle stays usable. */
+int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *problems, int ncandidates, const orbx_pnp_result *results);
+/* One row [n] of the device's masks of the last orbx_pnp_solve: refined = 0, mvbInliersi of iteration `index`; refined = 1,
+ * mvbRefinedInliers of record `index`.  ORBX_ERR_STATE before a solve, ORBX_ERR_ARG outside it. */
+int orbx_pnp_inliers(orbx_pnp_solver *h, int candidate, int index, int refined, uint8_t *inliers);
+/* CheckInliers of m <= max_iterations explicit poses r[m][9], t[m][3] (double) over the problem's matches with the chain's
+ * kernel: count[m], inliers[m][n] (may be NULL).  sets / iterations are not read. */
+int orbx_pnp_check_models(orbx_pnp_solver *h, const orbx_pnp_problem *problem, const double *r, const double *t, int m,
+                          int32_t *count, uint8_t *inliers);
+/* compute_pose of m <= max_iterations explicit index sets sets[m][set_size], 4 <= set_size <= n, distinct inside a set, with
+ * the chain's kernel: r[m][9], t[m][3], err[m]; full[m][ORBX_PNP_FULL_DOUBLES] (the stage outputs, ORBX_PNP_F_*) and
+ * alphas[m][set_size][4] may be NULL.  ORBX_ERR_ARG: set_size < 4 or > n, a bad or repeated index. */
+int orbx_pnp_epnp(orbx_pnp_solver *h, const orbx_pnp_problem *problem, const int32_t *sets, int m, int set_size, double *r,
+                  double *t, double *err, double *full, double *alphas);
+/* SetRansacParameters (:181-223) with the reference's libm calls; n = number of kept matches.  No device.  Outputs may be
+ * NULL: mRansacMinInliers, mRansacMaxIts, mRansacEpsilon. */
+int orbx_pnp_ransac_parameters(double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2,
+                               int n, int *min_inliers_out, int *iterations_out, float *epsilon_out);
+/* device time of the last orbx_pnp_solve chain (first to last kernel) and its kernel launches */
+int orbx_pnp_last_timing(orbx_pnp_solver *h, float *device_ms, int *launches);
+
 
 #ifdef __cplusplus
 }

@@ -1903,3 +1903,279 @@ class Sim3Solver:
         n = ctypes.c_int()
         _check(self._L.orbx_sim3_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+class PnPProblem(ctypes.Structure):
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("n", ctypes.c_int),
+                ("p2d", ctypes.c_void_p), ("sigma2", ctypes.c_void_p), ("p3dw", ctypes.c_void_p), ("probability", ctypes.c_double),
+                ("min_inliers", ctypes.c_int), ("max_iterations", ctypes.c_int), ("min_set", ctypes.c_int), ("epsilon", ctypes.c_float), ("th2", ctypes.c_float),
+                ("sets", ctypes.c_void_p), ("iterations", ctypes.c_int)]
+
+
+_PNP_RESULT_FIELDS = ("count", "r", "t", "err", "record_of", "is_event", "nrecords", "record_iteration", "refined_count", "refined_r", "refined_t", "refined_tcw",
+                      "best_tcw", "first_event", "best_iteration", "no_more", "min_inliers", "inliers_first", "inliers_best", "max_error")
+# orbx_pnp_epnp(full): name -> (offset, shape) inside the ORBX_PNP_FULL_DOUBLES doubles of a set (ORBX_PNP_F_* of include/orbx.h)
+PNP_FULL_DOUBLES = 472
+PNP_FULL_LAYOUT = dict(cws=(0, (4, 3)), pca=(12, (3, 3)), dc=(21, (3,)), uct=(24, (3, 3)), ci=(33, (3, 3)), mtm=(42, (12, 12)), d=(186, (12,)), ut=(198, (12, 12)),
+                       L=(342, (6, 10)), rho=(402, (6,)), b0=(408, (3, 4)), b1=(420, (3, 4)), Rs=(432, (3, 3, 3)), ts=(459, (3, 3)), errs=(468, (3,)), choice=(471, ()))
+
+
+class PnPResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _PNP_RESULT_FIELDS]
+
+
+def pnp_sets(n, iterations, randint):
+    """The minimal sets of PnPsolver::iterate (reference src/PnPsolver.cc:274-290): `iterations` sets of mRansacMinSet = 4 distinct indices into n kept
+    matches, each drawn as randint(0, len(available) - 1) (both bounds inclusive, like DUtils::Random::RandomInt) from the list of indices still
+    available; the drawn slot is overwritten with the list's back and the back is popped.  -> (iterations, 4) int32"""
+    if n < 4 and iterations > 0:
+        raise ValueError("pnp_sets: %d matches, a set needs 4" % n)
+    out = np.zeros((iterations, 4), np.int32)
+    for it in range(iterations):
+        avail = list(range(n))
+        for j in range(4):
+            r = int(randint(0, len(avail) - 1))
+            out[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return out
+
+
+def pnp_ransac_parameters(n, prob=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991):
+    """PnPsolver::SetRansacParameters (:181-223) -> (mRansacMinInliers, mRansacMaxIts, mRansacEpsilon); needs no device"""
+    L = load_library()
+    L.orbx_pnp_ransac_parameters.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    mi, its, eps = ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+    _check(L.orbx_pnp_ransac_parameters(float(prob), int(min_inliers), int(max_iterations), int(min_set), float(epsilon), float(th2), int(n),
+                                        ctypes.byref(mi), ctypes.byref(its), ctypes.byref(eps)))
+    return mi.value, its.value, np.float32(eps.value)
+
+
+class PnPCandidate:
+    """One solved candidate: the device's per-iteration and per-record outputs, and the reference's stateful surface replayed from them on the host.
+    iterate(nIterations) -> (Tcw (4,4) float32 or None, bNoMore, vbInliers (mN) bool, nInliers), call after call, also after a success; the loop
+    condition is the reference's (:266) `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`.  Iterations beyond the sets already solved
+    are solved by a further device call on further sets (drawn from the same generator)."""
+
+    def __init__(self, solver, cand, params, out, rng):
+        self._solver, self._cand, self._params, self._rng = solver, cand, params, rng
+        self.n = len(out["inliers_best"])
+        idx = cand.get("indices")
+        self.indices = np.arange(self.n) if idx is None else np.asarray(idx, np.int64)
+        self.mN = int(cand.get("mN", self.n))
+        self.mnIterations = 0
+        self._take(out)
+        self.mRansacMaxIts = params["max_its"]
+
+    def _take(self, out):
+        self.__dict__.update(out)
+        self.iterations = len(self.count)
+
+    @staticmethod
+    def _tcw(rows):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :] = np.asarray(rows, np.float32).reshape(3, 4)
+        return T
+
+    def Tcw(self, iteration):
+        """mRi, mti of an iteration narrowed to float (:310-316)"""
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = self.r[iteration].astype(np.float32)
+        T[:3, 3] = self.t[iteration].astype(np.float32)
+        return T
+
+    def _extend(self, more):
+        extra = pnp_sets(self.n, int(more), lambda lo, hi: self._rng.integers(lo, hi + 1))
+        sets = np.concatenate([self.sets, extra]).astype(np.int32)
+        self._take(self._solver._solve([self._cand], [sets], self._params, False)[0])
+
+    def iterate(self, nIterations):
+        vb = np.zeros(self.mN, bool)
+        if self.n < self.min_inliers:
+            return None, True, vb, 0
+        cur = 0
+        while self.mnIterations < self.mRansacMaxIts or cur < nIterations:
+            cur += 1
+            it = self.mnIterations
+            self.mnIterations += 1
+            if it >= self.iterations:
+                self._extend(max(1, nIterations - cur + 1, self.mRansacMaxIts - it))
+            if self.count[it] >= self.min_inliers:
+                rec = int(self.record_of[it])
+                if self.refined_count[rec] > self.min_inliers:
+                    vb[self.indices[self.refined_masks[rec]]] = True
+                    return self._tcw(self.refined_tcw[rec]), False, vb, int(self.refined_count[rec])
+        if self.mnIterations >= self.mRansacMaxIts:
+            rec = int(self.record_of[self.mnIterations - 1])
+            if rec >= 0:
+                b = int(self.record_iteration[rec])
+                vb[self.indices[self.record_masks[rec]]] = True
+                return self.Tcw(b), True, vb, int(self.count[b])
+            return None, True, vb, 0
+        return None, False, vb, 0
+
+    def find(self):
+        T, _, vb, k = self.iterate(self.mRansacMaxIts)
+        return T, vb, k
+
+
+class PnPsolver:
+    """PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc) on the device: every RANSAC iteration and every Refine of every relocalisation
+    candidate in one launch chain (orbx_pnp_solve); CheckInliers on explicit poses (CheckModels) and compute_pose on explicit sets (EPnP)."""
+
+    def __init__(self, max_candidates=8, max_matches=2048, max_iterations=300, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_pnp_solver_create.argtypes = [ci, ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_pnp_solver_destroy.argtypes = [vp]
+        L.orbx_pnp_solver_destroy.restype = None
+        L.orbx_pnp_solve.argtypes = [vp, ctypes.POINTER(PnPProblem), ci, ctypes.POINTER(PnPResult)]
+        L.orbx_pnp_inliers.argtypes = [vp, ci, ci, ci, vp]
+        L.orbx_pnp_check_models.argtypes = [vp, ctypes.POINTER(PnPProblem), vp, vp, ci, vp, vp]
+        L.orbx_pnp_epnp.argtypes = [vp, ctypes.POINTER(PnPProblem), vp, ci, ci, vp, vp, vp, vp, vp]
+        L.orbx_pnp_last_timing.argtypes = [vp, vp, vp]
+        self.max_candidates, self.max_matches, self.max_iterations = int(max_candidates), int(max_matches), int(max_iterations)
+        self._h = vp()
+        _check(L.orbx_pnp_solver_create(device, self.max_candidates, self.max_matches, self.max_iterations, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_pnp_solver_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _problem(c, keep, params):
+        """c: dict(K (fx, fy, cx, cy), p2d (n,2) mvP2D, sigma2 (n) mvLevelSigma2[octave], p3d (n,3) mvP3Dw)"""
+        f4 = np.float32
+        p2, p3 = np.ascontiguousarray(c["p2d"], f4).reshape(-1, 2), np.ascontiguousarray(c["p3d"], f4).reshape(-1, 3)
+        s2 = np.ascontiguousarray(c["sigma2"], f4).reshape(-1)
+        n = len(p2)
+        if not (len(p3) == len(s2) == n):
+            raise ValueError("PnPsolver: the per-match arrays of a candidate disagree in length")
+        keep.extend([p2, p3, s2])
+        P = PnPProblem()
+        P.fx, P.fy, P.cx, P.cy = [float(v) for v in c["K"]]
+        P.n, P.p2d, P.sigma2, P.p3dw = n, p2.ctypes.data, s2.ctypes.data, p3.ctypes.data
+        P.probability, P.min_inliers, P.max_iterations, P.min_set = float(params["prob"]), int(params["min_inliers"]), int(params["max_iterations"]), int(params["min_set"])
+        P.epsilon, P.th2 = float(params["epsilon"]), float(params["th2"])
+        return P, n
+
+    def Solve(self, candidates, sets=None, rng=None, prob=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991, full=False):
+        """candidates: list of dicts (see _problem; optional "indices" (n) = mvKeyPointIndices and "mN" = len(vpMapPointMatches), default the identity).
+        sets: list of (iterations,4) int32 per candidate or None = mRansacMaxIts sets per candidate drawn by pnp_sets from rng (numpy Generator,
+        default seed 0), candidate after candidate.  -> [PnPCandidate]; full=True adds the mask of every iteration (masks) and max_error."""
+        params = dict(prob=prob, min_inliers=min_inliers, max_iterations=max_iterations, min_set=min_set, epsilon=epsilon, th2=th2)
+        g = np.random.default_rng(0) if rng is None else rng
+        used = []
+        for c, cd in enumerate(candidates):
+            n = len(np.asarray(cd["p2d"]).reshape(-1, 2))
+            mi, its, _ = pnp_ransac_parameters(n, prob, min_inliers, max_iterations, min_set, epsilon, th2)
+            if sets is None:
+                s = pnp_sets(n, its if n >= mi else 0, lambda lo, hi: g.integers(lo, hi + 1))
+            else:
+                s = np.ascontiguousarray(sets[c], np.int32).reshape(-1, 4)
+            used.append(s)
+        outs = self._solve(candidates, used, params, full)
+        result = []
+        for c, o in enumerate(outs):
+            n = len(o["inliers_best"])
+            _, its, _ = pnp_ransac_parameters(n, prob, min_inliers, max_iterations, min_set, epsilon, th2)
+            result.append(PnPCandidate(self, candidates[c], dict(params, max_its=its), o, g))
+        return result
+
+    def _solve(self, candidates, used, params, full):
+        C = len(candidates)
+        keep, probs, ns = [], (PnPProblem * max(C, 1))(), []
+        for c, cd in enumerate(candidates):
+            P, n = self._problem(cd, keep, params)
+            s = np.ascontiguousarray(used[c], np.int32).reshape(-1, 4)
+            keep.append(s)
+            P.sets, P.iterations = s.ctypes.data, len(s)
+            probs[c] = P
+            ns.append(n)
+        f4, f8, i4, u1 = np.float32, np.float64, np.int32, np.uint8
+        res, outs = (PnPResult * max(C, 1))(), []
+        for c in range(C):
+            n, it = ns[c], len(used[c])
+            o = dict(count=np.zeros(it, i4), r=np.zeros((it, 3, 3), f8), t=np.zeros((it, 3), f8), err=np.zeros(it, f8), record_of=np.full(it, -1, i4), is_event=np.zeros(it, u1),
+                     nrecords=np.zeros(1, i4), record_iteration=np.full(it, -1, i4), refined_count=np.zeros(it, i4), refined_r=np.zeros((it, 3, 3), f8),
+                     refined_t=np.zeros((it, 3), f8), refined_tcw=np.zeros((it, 12), f4), best_tcw=np.zeros(12, f4), first_event=np.full(1, -1, i4),
+                     best_iteration=np.full(1, -1, i4), no_more=np.zeros(1, i4), min_inliers=np.zeros(1, i4), inliers_first=np.zeros(n, u1), inliers_best=np.zeros(n, u1))
+            if full:
+                o["max_error"] = np.zeros(n, f4)
+            res[c] = PnPResult(*[o[k].ctypes.data if k in o and o[k].size else None for k in _PNP_RESULT_FIELDS])
+            outs.append(o)
+        _check(self._L.orbx_pnp_solve(self._h, probs, C, res))
+        for c, o in enumerate(outs):
+            for k in ("first_event", "best_iteration", "nrecords", "min_inliers"):
+                o[k] = int(o[k][0])
+            o["no_more"] = bool(o["no_more"][0])
+            ran = 0 if o["no_more"] else len(used[c])      # n < min_inliers: nothing was run
+            for k in ("count", "r", "t", "err", "record_of", "is_event", "record_iteration", "refined_count", "refined_r", "refined_t", "refined_tcw"):
+                o[k] = o[k][:ran]
+            o["is_event"], o["inliers_first"], o["inliers_best"] = o["is_event"].astype(bool), o["inliers_first"].astype(bool), o["inliers_best"].astype(bool)
+            o["sets"] = np.asarray(used[c], np.int32).reshape(-1, 4)[:ran]
+            # the rows iterate can return: the refined mask of every record and the mask of every record's iteration (host copies, made before
+            # another call overwrites the device's)
+            o["refined_masks"] = [self._inliers(c, r, 1, ns[c]) for r in range(o["nrecords"])]
+            o["record_masks"] = [self._inliers(c, int(o["record_iteration"][r]), 0, ns[c]) for r in range(o["nrecords"])]
+            if full:
+                o["masks"] = np.array([self._inliers(c, i, 0, ns[c]) for i in range(ran)], bool).reshape(ran, ns[c])
+        return outs
+
+    def _inliers(self, candidate, index, refined, n):
+        out = np.zeros(max(n, 1), np.uint8)
+        _check(self._L.orbx_pnp_inliers(self._h, int(candidate), int(index), int(refined), out.ctypes.data))
+        return out[:n].astype(bool)
+
+    _DEFAULTS = dict(prob=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991)
+
+    def CheckModels(self, candidate, R, t, th2=5.991):
+        """CheckInliers of the explicit poses R (M,3,3), t (M,3) (float64) over a candidate's matches -> (count (M) int32, inliers (M,n) bool)"""
+        keep = []
+        P, n = self._problem(candidate, keep, dict(self._DEFAULTS, th2=th2))
+        a, b = np.ascontiguousarray(R, np.float64).reshape(-1, 9), np.ascontiguousarray(t, np.float64).reshape(-1, 3)
+        M = len(a)
+        if len(b) != M:
+            raise ValueError("PnPsolver.CheckModels: %d R for %d t" % (M, len(b)))
+        count, inl = np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1) * max(n, 1), np.uint8)
+        _check(self._L.orbx_pnp_check_models(self._h, ctypes.byref(P), a.ctypes.data, b.ctypes.data, M, count.ctypes.data, inl.ctypes.data))
+        return count[:M], inl[:M * n].reshape(M, n).astype(bool)
+
+    def EPnP(self, candidate, sets, full=False):
+        """compute_pose (:684-759) on explicit index sets (M, set_size >= 4) -> dict(R (M,3,3), t (M,3), err (M)); full=True adds every stage output of
+        PNP_FULL_LAYOUT, each with a leading M, and alphas (M, set_size, 4)"""
+        keep = []
+        P, n = self._problem(candidate, keep, self._DEFAULTS)
+        s = np.ascontiguousarray(sets, np.int32)
+        if s.ndim != 2:
+            raise ValueError("PnPsolver.EPnP: sets must be (M, set_size)")
+        M, k = s.shape
+        R, t, err = np.zeros((max(M, 1), 3, 3)), np.zeros((max(M, 1), 3)), np.zeros(max(M, 1))
+        blk = np.zeros((max(M, 1), PNP_FULL_DOUBLES)) if full else None
+        al = np.zeros((max(M, 1), max(k, 1), 4)) if full else None
+        _check(self._L.orbx_pnp_epnp(self._h, ctypes.byref(P), s.ctypes.data, M, k, R.ctypes.data, t.ctypes.data, err.ctypes.data,
+                                     blk.ctypes.data if full else None, al.ctypes.data if full else None))
+        o = dict(R=R[:M], t=t[:M], err=err[:M])
+        if full:
+            for name, (off, shape) in PNP_FULL_LAYOUT.items():
+                size = int(np.prod(shape)) if shape else 1
+                o[name] = blk[:M, off:off + size].reshape((M,) + shape).copy()
+            o["choice"] = o["choice"].astype(np.int32)
+            o["alphas"] = al[:M]
+        return o
+
+    def last_timing(self):
+        """(device ms of the last Solve chain, kernel launches)"""
+        ms = ctypes.c_float()
+        n = ctypes.c_int()
+        _check(self._L.orbx_pnp_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
