@@ -1181,6 +1181,92 @@ int orbx_sim3_ransac_iterations(double probability, int min_inliers, int max_ite
 int orbx_sim3_last_timing(orbx_sim3_solver *h, float *device_ms, int *launches);
 
 /* ----------------------------------------------------------------------------------
+ * Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1364-1590 with the vendored g2o): the Sim3 refinement of
+ * LoopClosing::ComputeSim3 for ALL of a call's problems (the Sim3Solver events of the loop candidates, each with
+ * SearchBySim3's matches) in ONE launch on the handle's own stream with one wait.  The caller's loop is
+ * orbx_sim3_solve -> SearchBySim3 -> orbx_optimize_sim3.
+ *
+ *   k_optsim3  one workgroup of 256 threads per problem; thread t owns pairs t, t + 256, ... and keeps their two camera
+ *              points, observations, weights and errors in registers for the whole call.  Per linearisation lanes 0-13 of
+ *              wave 0 form the 14 perturbed estimates Sim3(+-1e-9 e_d) * S and their inverses once, in LDS; every thread
+ *              differences its edges through them; the 28 + 7 + 1 sums of H, b and the robust chi2 are block sums in a fixed
+ *              order (no floating-point atomics: repeated calls, and a batch against single calls, give the same bits); one
+ *              thread solves the 7x7 system and takes the Levenberg decision.  Inputs are read from mapped pinned memory,
+ *              the result block is written to mapped pinned memory behind a sequence word, like orbx_sim3_solve's.
+ *
+ *   Arithmetic: FP64, every product / sum / quotient its own IEEE operation (-ffp-contract=off, no fused multiply-add),
+ *   in the order tests/optsim3_ref.py restates:
+ *     camera points  P3D1c = R1w * P3D1w + t1w in FLOAT, (R[0]*x + R[1]*y) + R[2]*z, then + t - k_sim3_prepare's arithmetic,
+ *                    bit for bit - widened to double; observations, 1 / sigma2 and the intrinsics are floats widened;
+ *                    Huber's delta is sqrtf(th2) widened, th2 is compared widened
+ *     estimate       g2o::Sim3(Quaterniond(R), t, s) (Eigen's four branches); oplus = Sim3(update) * estimate with
+ *                    update[6] = 0 under fix_scale; the exponential of sim3.h:70-142 with its four branches
+ *                    (|sigma| < 1e-5, theta < 1e-5); quaternion products are never renormalised; inverse() as sim3.h:233-236
+ *     edges          e12 = obs1 - cam_map1(project(S.map(X2))), e21 = obs2 - cam_map2(project(S.inverse().map(X1))),
+ *                    project = two divisions by z
+ *     Jacobians      g2o's central differences (base_binary_edge.hpp:147-200): delta = 1e-9, column d =
+ *                    (1 / (2 delta)) * (e(+delta) - e(-delta)) through oplus; column 6 is exactly zero under fix_scale
+ *     quadratic form chi2 = invSigma2 * (e0^2 + e1^2), Huber rho as robust_kernel_impl.cpp, H += J^T (rho1 Omega) J,
+ *                    b -= J^T (rho1 Omega e)
+ *     Levenberg      optimization_algorithm_levenberg.cpp:61-164: lambda0 = 1e-5 max|H_jj| at iteration 0 of EACH optimize(),
+ *                    <= 10 trials, rho = (chi - chi_trial) / (x . (lambda x + b) + 1e-3), accepted: lambda *= max(1/3,
+ *                    min(1 - (2 rho - 1)^3, 2/3)), rejected: lambda *= nu, nu *= 2; Terminate on 10 trials or rho == 0;
+ *                    stop after three iterations with (iniChi - chi) * 1e3 < iniChi
+ *     solve          dense 7x7 LDL^T, a non-positive factor makes the trial's chi DBL_MAX
+ *     rounds         optimize(5) over all pairs; a pair is removed when either edge has chi2() > th2; fewer than 10 left:
+ *                    return 0, the estimate stays as passed in; else optimize(nBad > 0 ? 10 : 5) on the kept pairs (the
+ *                    estimate carries over, lambda0 is re-initialised), the same test counts the inliers
+ *     QUIRK, KEPT    chi2() reads _error as the LAST trial left it, accepted or rejected: the reference does not call
+ *                    computeError() before its tests, and neither does the kernel
+ *   PARITY UNPINNED: the device library's sin / cos / exp; Eigen's Quaterniond(R) branch choice beyond rounding; LDL^T
+ *   pivoting (Eigen's LDLT pivots, this factorisation does not); the order in which the edges' contributions are summed.
+ *
+ *   n < 10 is NOT an error: round one still runs (n >= 1), the call returns n_inliers = 0 and the input estimate.
+ * ---------------------------------------------------------------------------------- */
+#define ORBX_SIM3_OPT_MAX_PAIRS 1024
+
+typedef struct orbx_sim3_optimizer orbx_sim3_optimizer;
+/* ORBX_ERR_ARG: max_problems outside 1..4096, max_pairs outside 1..ORBX_SIM3_OPT_MAX_PAIRS (a PER PROBLEM limit); then
+ * ORBX_ERR_NODEVICE without a device */
+int orbx_sim3_optimizer_create(int device, int max_problems, int max_pairs, orbx_sim3_optimizer **out);
+void orbx_sim3_optimizer_destroy(orbx_sim3_optimizer *h);
+
+typedef struct orbx_sim3_opt_problem {  /* host memory: one (candidate, matches, Sim3) triple */
+    float rcw1[9], tcw1[3], rcw2[9], tcw2[3];   /* GetRotation / GetTranslation of pKF1, pKF2                       */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    int n;                                      /* kept pairs (nCorrespondences)                                    */
+    const float *world1, *world2;               /* [n][3] GetWorldPos of pMP1 / pMP2                                */
+    const float *obs1, *obs2;                   /* [n][2] mvKeysUn[i].pt of KF1, mvKeysUn[i2].pt of KF2             */
+    const float *inv_sigma2_1, *inv_sigma2_2;   /* [n] mvInvLevelSigma2[octave]                                     */
+    double r12[9], t12[3], s12;                 /* g2oS12 as passed in: rotation matrix (row-major), t, s           */
+    float th2;
+    int fix_scale;
+} orbx_sim3_opt_problem;
+
+typedef struct orbx_sim3_opt_result {   /* host memory: one problem; every pointer may be NULL */
+    int32_t *n_inliers;                 /* the return value: nIn, 0 when fewer than 10 pairs survive round one        */
+    double *quat, *t, *s;               /* [4] (x, y, z, w), [3], [1]: g2oS12 afterwards (the input on a return 0)     */
+    float *r12;                         /* [9] its rotation().toRotationMatrix(), narrowed                             */
+    uint8_t *removed_first;             /* [n] pairs nulled by the test behind round one                               */
+    uint8_t *removed_final;             /* [n] pairs nulled by the test behind round two (zeros when it did not run)    */
+    int32_t *n_bad;                     /* nBad of round one                                                           */
+    /* diagnostics */
+    double *chi2_round1, *chi2_round2;  /* [2n] chi2() as tested, [2 i] = e12, [2 i + 1] = e21; -1 = not in the graph  */
+    double *stats;                      /* [4] {Levenberg iterations, final robust chi2} of round one, of round two    */
+    float *x3dc1, *x3dc2;               /* [n][3] the camera points                                                    */
+} orbx_sim3_opt_result;
+/* ORBX_ERR_ARG: nproblems < 1, a NULL problem / array, n < 0, non-finite intrinsics or th2; ORBX_ERR_CAPACITY: more
+ * problems or pairs than the handle was created for.  Nothing is launched on an error and the handle stays usable. */
+int orbx_optimize_sim3(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *problems, int nproblems, const orbx_sim3_opt_result *results);
+/* ONE linearisation of the problem's edges at the explicit estimate (quat (x, y, z, w), t, s) with the chain's own device
+ * functions: errors[2n][2], chi2[2n], jac[2n][2][7] (edge 2 i = e12, 2 i + 1 = e21 of pair i; zeros where active[i] == 0),
+ * H[49], b[7].  active [n] may be NULL (= every pair), and so may every output.  r12 / t12 / s12 of the problem are not read. */
+int orbx_optimize_sim3_linearize(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *problem, const double *quat, const double *t, double s,
+                                 const uint8_t *active, double *errors, double *chi2, double *jac, double *H, double *b);
+/* device time of the last orbx_optimize_sim3 launch chain and its kernel launches */
+int orbx_sim3_optimizer_last_timing(orbx_sim3_optimizer *h, float *device_ms, int *launches);
+
+/* ----------------------------------------------------------------------------------
  * PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc): EPnP on RANSAC sets of four matches, for ALL relocalisation
  * candidates of Tracking::Relocalization (src/Tracking.cc) in one launch chain with one wait.
  *

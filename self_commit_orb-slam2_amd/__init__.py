@@ -1905,6 +1905,157 @@ class Sim3Solver:
         return ms.value, n.value
 
 
+class Sim3OptProblem(ctypes.Structure):
+    _fields_ = [("rcw1", ctypes.c_float * 9), ("tcw1", ctypes.c_float * 3), ("rcw2", ctypes.c_float * 9), ("tcw2", ctypes.c_float * 3),
+                ("fx1", ctypes.c_float), ("fy1", ctypes.c_float), ("cx1", ctypes.c_float), ("cy1", ctypes.c_float),
+                ("fx2", ctypes.c_float), ("fy2", ctypes.c_float), ("cx2", ctypes.c_float), ("cy2", ctypes.c_float),
+                ("n", ctypes.c_int), ("world1", ctypes.c_void_p), ("world2", ctypes.c_void_p), ("obs1", ctypes.c_void_p), ("obs2", ctypes.c_void_p),
+                ("inv_sigma2_1", ctypes.c_void_p), ("inv_sigma2_2", ctypes.c_void_p),
+                ("r12", ctypes.c_double * 9), ("t12", ctypes.c_double * 3), ("s12", ctypes.c_double), ("th2", ctypes.c_float), ("fix_scale", ctypes.c_int)]
+
+
+_SIM3_OPT_RESULT_FIELDS = ("n_inliers", "quat", "t", "s", "r12", "removed_first", "removed_final", "n_bad", "chi2_round1", "chi2_round2", "stats", "x3dc1", "x3dc2")
+
+
+class Sim3OptResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _SIM3_OPT_RESULT_FIELDS]
+
+
+class Sim3Refined:
+    """One optimised problem: n_inliers (the reference's return value), quat (x, y, z, w) / t / s (g2oS12 afterwards, float64), r12 (3,3) float32,
+    removed_first / removed_final (n) bool (the pairs the caller nulls in vpMatches1), n_bad; with full=True also chi2_round1 / chi2_round2 (n,2),
+    stats (2,2) = (Levenberg iterations, final robust chi2) per round, x3dc1 / x3dc2 (n,3)."""
+
+    def __init__(self, out):
+        self.__dict__.update(out)
+
+    @property
+    def removed(self):
+        return self.removed_first | self.removed_final
+
+    def T12(self):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = np.float32(self.s) * self.r12
+        T[:3, 3] = self.t.astype(np.float32)
+        return T
+
+
+def sim3_opt_problem(candidate, solved, matches, iteration=None):
+    """A Sim3Optimizer problem from a Sim3Solver event: `candidate` is the dict Sim3Solver.Solve took (poses and intrinsics are read), `solved` the
+    Sim3Candidate it returned, `iteration` the event (default: the first), `matches` SearchBySim3's pairs as a dict(world1 (n,3), world2 (n,3),
+    obs1 (n,2), obs2 (n,2), inv_sigma2_1 (n), inv_sigma2_2 (n)).  The float R, t, s of the event are widened, as LoopClosing::ComputeSim3 builds gScm."""
+    it = solved.first_event if iteration is None else int(iteration)
+    if it < 0:
+        raise ValueError("sim3_opt_problem: the candidate has no event")
+    p = {k: candidate[k] for k in ("Rcw1", "tcw1", "Rcw2", "tcw2", "K1", "K2")}
+    p.update({k: matches[k] for k in ("world1", "world2", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")})
+    p.update(R12=solved.r12[it].astype(np.float64), t12=solved.t12[it].astype(np.float64), s12=float(solved.s12[it]))
+    return p
+
+
+class Sim3Optimizer:
+    """Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1364-1590) on the device: every problem of a call in one launch (orbx_optimize_sim3)."""
+
+    def __init__(self, max_problems=8, max_pairs=1024, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_sim3_optimizer_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_sim3_optimizer_destroy.argtypes = [vp]
+        L.orbx_sim3_optimizer_destroy.restype = None
+        L.orbx_optimize_sim3.argtypes = [vp, ctypes.POINTER(Sim3OptProblem), ci, ctypes.POINTER(Sim3OptResult)]
+        L.orbx_optimize_sim3_linearize.argtypes = [vp, ctypes.POINTER(Sim3OptProblem), vp, vp, ctypes.c_double, vp, vp, vp, vp, vp, vp]
+        L.orbx_sim3_optimizer_last_timing.argtypes = [vp, vp, vp]
+        self.max_problems, self.max_pairs = int(max_problems), int(max_pairs)
+        self._h = vp()
+        _check(L.orbx_sim3_optimizer_create(device, self.max_problems, self.max_pairs, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_sim3_optimizer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _problem(c, keep, th2, fix_scale):
+        """c: dict(Rcw1 (3,3), tcw1 (3), Rcw2, tcw2, K1 (fx, fy, cx, cy), K2, world1 (n,3), world2 (n,3), obs1 (n,2), obs2 (n,2), inv_sigma2_1 (n),
+        inv_sigma2_2 (n), R12 (3,3) float64, t12 (3), s12)"""
+        f4 = np.float32
+        w1, w2 = np.ascontiguousarray(c["world1"], f4).reshape(-1, 3), np.ascontiguousarray(c["world2"], f4).reshape(-1, 3)
+        o1, o2 = np.ascontiguousarray(c["obs1"], f4).reshape(-1, 2), np.ascontiguousarray(c["obs2"], f4).reshape(-1, 2)
+        s1, s2 = np.ascontiguousarray(c["inv_sigma2_1"], f4).reshape(-1), np.ascontiguousarray(c["inv_sigma2_2"], f4).reshape(-1)
+        n = len(w1)
+        if not (len(w2) == len(o1) == len(o2) == len(s1) == len(s2) == n):
+            raise ValueError("Sim3Optimizer: the per-pair arrays of a problem disagree in length")
+        keep.extend([w1, w2, o1, o2, s1, s2])
+        P = Sim3OptProblem()
+        for name, key, k in (("rcw1", "Rcw1", 9), ("tcw1", "tcw1", 3), ("rcw2", "Rcw2", 9), ("tcw2", "tcw2", 3)):
+            setattr(P, name, (ctypes.c_float * k)(*np.asarray(c[key], f4).reshape(-1)))
+        P.fx1, P.fy1, P.cx1, P.cy1 = [float(v) for v in c["K1"]]
+        P.fx2, P.fy2, P.cx2, P.cy2 = [float(v) for v in c["K2"]]
+        P.n = n
+        P.world1, P.world2, P.obs1, P.obs2, P.inv_sigma2_1, P.inv_sigma2_2 = [a.ctypes.data for a in (w1, w2, o1, o2, s1, s2)]
+        P.r12 = (ctypes.c_double * 9)(*np.asarray(c["R12"], np.float64).reshape(-1))
+        P.t12 = (ctypes.c_double * 3)(*np.asarray(c["t12"], np.float64).reshape(-1))
+        P.s12, P.th2, P.fix_scale = float(c["s12"]), float(th2), 1 if fix_scale else 0
+        return P, n
+
+    def OptimizeSim3(self, problems, th2=10, fix_scale=False, full=False):
+        """problems: list of dicts (see _problem, sim3_opt_problem) -> [Sim3Refined]; full=True adds the diagnostics of orbx_sim3_opt_result."""
+        C = len(problems)
+        keep, probs, ns = [], (Sim3OptProblem * max(C, 1))(), []
+        for c, cd in enumerate(problems):
+            probs[c], n = self._problem(cd, keep, th2, fix_scale)
+            ns.append(n)
+        f8, f4, i4, u1 = np.float64, np.float32, np.int32, np.uint8
+        res, outs = (Sim3OptResult * max(C, 1))(), []
+        for c in range(C):
+            n = ns[c]
+            o = dict(n_inliers=np.zeros(1, i4), quat=np.zeros(4, f8), t=np.zeros(3, f8), s=np.zeros(1, f8), r12=np.zeros((3, 3), f4), removed_first=np.zeros(n, u1),
+                     removed_final=np.zeros(n, u1), n_bad=np.zeros(1, i4))
+            if full:
+                o.update(chi2_round1=np.zeros((n, 2), f8), chi2_round2=np.zeros((n, 2), f8), stats=np.zeros((2, 2), f8), x3dc1=np.zeros((n, 3), f4), x3dc2=np.zeros((n, 3), f4))
+            res[c] = Sim3OptResult(*[o[k].ctypes.data if k in o and o[k].size else None for k in _SIM3_OPT_RESULT_FIELDS])
+            outs.append(o)
+        _check(self._L.orbx_optimize_sim3(self._h, probs, C, res))
+        result = []
+        for o in outs:
+            o["n_inliers"], o["n_bad"], o["s"] = int(o["n_inliers"][0]), int(o["n_bad"][0]), float(o["s"][0])
+            o["removed_first"], o["removed_final"] = o["removed_first"].astype(bool), o["removed_final"].astype(bool)
+            result.append(Sim3Refined(o))
+        return result
+
+    def linearize(self, problem, quat, t, s, active=None, th2=10, fix_scale=False):
+        """One linearisation of a problem's edges at the estimate (quat (x, y, z, w), t, s) with the chain's device functions ->
+        dict(errors (2n,2), chi2 (2n), jac (2n,2,7), H (7,7), b (7)); edge 2 i = e12, 2 i + 1 = e21 of pair i; active (n) bool or None = every pair."""
+        keep = []
+        P, n = self._problem(problem, keep, th2, fix_scale)
+        f8 = np.float64
+        q, tt = np.ascontiguousarray(quat, f8).reshape(4), np.ascontiguousarray(t, f8).reshape(3)
+        act = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(-1)
+        if act is not None and len(act) != n:
+            raise ValueError("Sim3Optimizer.linearize: %d active flags for %d pairs" % (len(act), n))
+        m = max(n, 1)
+        o = dict(errors=np.zeros((2 * m, 2), f8), chi2=np.zeros(2 * m, f8), jac=np.zeros((2 * m, 2, 7), f8), H=np.zeros((7, 7), f8), b=np.zeros(7, f8))
+        _check(self._L.orbx_optimize_sim3_linearize(self._h, ctypes.byref(P), q.ctypes.data, tt.ctypes.data, float(s), None if act is None or n == 0 else act.ctypes.data,
+                                                    o["errors"].ctypes.data, o["chi2"].ctypes.data, o["jac"].ctypes.data, o["H"].ctypes.data, o["b"].ctypes.data))
+        for k in ("errors", "chi2", "jac"):
+            o[k] = o[k][:2 * n]
+        return o
+
+    def last_timing(self):
+        """(device ms of the last OptimizeSim3 launch chain, kernel launches)"""
+        ms = ctypes.c_float()
+        n = ctypes.c_int()
+        _check(self._L.orbx_sim3_optimizer_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
+
+
 class PnPProblem(ctypes.Structure):
     _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("n", ctypes.c_int),
                 ("p2d", ctypes.c_void_p), ("sigma2", ctypes.c_void_p), ("p3dw", ctypes.c_void_p), ("probability", ctypes.c_double),
