@@ -1415,6 +1415,98 @@ int orbx_pnp_ransac_parameters(double probability, int min_inliers, int max_iter
 /* device time of the last orbx_pnp_solve chain (first to last kernel) and its kernel launches */
 int orbx_pnp_last_timing(orbx_pnp_solver *h, float *device_ms, int *launches);
 
+/* ----------------------------------------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1017-1339 with the vendored g2o): the pose graph of
+ * LoopClosing::CorrectLoop - every keyframe a 7-dof VertexSim3Expmap, every LoopConnections / spanning-tree / loop /
+ * covisibility pair an EdgeSim3 with identity information and no robust kernel - under g2o's Levenberg driver with
+ * setUserLambdaInit(1e-16), then the pose and map-point write-back.  The host (the shim) walks the pointers and selects the
+ * edges; the device does the arithmetic.
+ *
+ *   k_eg_init       measurements Sji = Sjw * Swi (Sim3::inverse, operator*; kind 0 from `est`, kind 1 from `meas`)
+ *   k_eg_linearize  16 threads per edge: 14 take one column each of g2o's central differences (delta = 1e-9, through oplus =
+ *                   Sim3(update) * estimate, update[6] = 0 under fix_scale; a fixed vertex has no block), one the error
+ *                   log(C * v1 * v2^-1) at the estimate (Sim3::log's four branches; W u = t by the adjugate)
+ *   k_eg_assemble   one wave per block of H on the pattern of L: the edges' J^T J in edge order, each entry a sum over the
+ *                   seven rows in row order; b += J^T (-e) likewise.  Every copy of a duplicated edge is added.  No atomics.
+ *   k_eg_solve      (H + lambda I) x = b: block-sparse FP64 LDL^T on 7x7 blocks, right-looking, no pivoting, in ONE
+ *                   workgroup (column steps are dependent; nothing waits across workgroups), then both substitutions,
+ *                   x . (lambda x + b), and the trial estimates Sim3(x) * estimate.  A non-positive or non-finite pivot
+ *                   makes the trial's chi2 DBL_MAX.  Under fix_scale the seventh pivot of every block is lambda itself and
+ *                   the seventh component of x exactly 0.
+ *   k_eg_error / k_eg_reduce   the trial's errors, chi2 = e^T e per edge, and their sum in a fixed order; one 32-byte record
+ *                   per trial in mapped pinned memory behind a sequence word, from which the host takes the Levenberg
+ *                   decision (optimization_algorithm_levenberg.cpp:61-164, as orbx_optimize_sim3's list above says, with
+ *                   lambda0 = lambda_init).  No copy engine and no stream synchronisation inside the loop.
+ *   k_eg_writeback  the estimates, their inverses (vCorrectedSwc), Tiw = [R | t / s] narrowed to float, and the map points
+ *                   float(correctedSwr.map(Srw.map(double(p)))).
+ *
+ *   The symbolic phase runs on the host once per call: the elimination order (the free keyframes in the caller's order) and
+ *   the exact block pattern of L.  Device memory is proportional to that pattern, never to n^2.  fill_blocks counts the blocks
+ *   of L's lower triangle, diagonal blocks included.
+ *   Arithmetic: FP64, every product / sum / quotient its own IEEE operation, in the order tests/essential_graph_ref.py
+ *   restates; exp, sin, cos, log and acos are the kernels' own series of IEEE operations (a few ulps from libm's), restated too.
+ *   PARITY UNPINNED against the reference: libm's last bits of those five; W.lu().solve (the adjugate here); the order of
+ *   the block sums and Eigen's sparse LDL^T with its AMD ordering (natural order, no pivoting here).
+ * ---------------------------------------------------------------------------------- */
+typedef struct orbx_essential_graph orbx_essential_graph;
+/* ORBX_ERR_ARG: max_keyframes < 1, max_edges outside 0..2^26, max_points < 0, max_fill_blocks < 1; then ORBX_ERR_NODEVICE without a device */
+int orbx_essential_graph_create(int device, int max_keyframes, int max_edges, int max_points, int max_fill_blocks,
+                                orbx_essential_graph **out);
+void orbx_essential_graph_destroy(orbx_essential_graph *h);
+
+#define ORBX_EG_MAX_TRIALS 10      /* _maxTrialsAfterFailure */
+#define ORBX_EG_END_ITERATIONS 0   /* why a run ended: every iteration ran, */
+#define ORBX_EG_END_TRIALS 1       /* ten trials in one iteration,          */
+#define ORBX_EG_END_RHO0 2         /* rho == 0,                             */
+#define ORBX_EG_END_THREE 3        /* three iterations without progress     */
+
+typedef struct orbx_essential_graph_problem {   /* host memory */
+    int n;                          /* keyframes, in the caller's order (the shim: ascending mnId)                     */
+    const double *est;              /* [n][8] q (x, y, z, w), t, s: vScw                                                */
+    const double *meas;             /* [n][8] NonCorrectedSim3 where present, else est; NULL = est                      */
+    int fixed;                      /* index of the loop keyframe                                                       */
+    int fix_scale;
+    int n_edges;
+    const int32_t *edges;           /* [n_edges][3] i (vertex 0), j (vertex 1), kind (0: from est, 1: from meas)        */
+    int n_points;
+    const float *points;            /* [n_points][3]                                                                    */
+    const int32_t *point_ref;       /* [n_points] vertex index of the reference keyframe, -1 = no vertex                */
+    int iterations;                 /* <= 0: 20                                                                         */
+    double lambda_init;             /* <= 0: 1e-16                                                                      */
+} orbx_essential_graph_problem;
+
+typedef struct orbx_essential_graph_result {    /* host memory; every pointer may be NULL */
+    double *est;                    /* [n][8] the final estimates                                                       */
+    float *tiw;                     /* [n][12] rows of [R | t / s]                                                      */
+    double *inv;                    /* [n][8] their inverses (vCorrectedSwc)                                            */
+    float *points;                  /* [n_points][3]                                                                    */
+    double *chi2;                   /* [2] initial, final                                                               */
+    int32_t *iterations;            /* [1] iterations run                                                               */
+    int32_t *ended;                 /* [1] ORBX_EG_END_*                                                                */
+    int32_t *iter_trials;           /* [iterations] trials of each iteration                                            */
+    double *iter_chi2, *iter_lambda, *iter_rho;   /* [iterations] chi2 and lambda after it, rho of its last trial       */
+    int32_t *order;                 /* [n - 1] the elimination order: vertex indices of the free keyframes              */
+    int32_t *fill_blocks;           /* [1]                                                                              */
+} orbx_essential_graph_result;
+/* ORBX_ERR_ARG, before any launch: n < 1, fixed or an edge index or a point_ref outside its range, i == j, kind not 0 / 1,
+ * s <= 0, a non-finite input; ORBX_ERR_CAPACITY: more keyframes, edges, points or fill blocks than the handle was created
+ * for.  The handle stays usable.  n_edges == 0 is not an error: the estimates come back as passed in. */
+int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx_essential_graph_problem *problem,
+                                  const orbx_essential_graph_result *result);
+/* ONE linearisation at the explicit estimates at[n][8] (NULL = problem->est) with the chain's kernels: meas[E][8] the edges'
+ * measurements, errors[E][7], chi2[1], jac[E][2][7][7] (vertex 0 / 1, row, column; zeros for the fixed vertex), h_diag[n][49]
+ * and b[n][7] by vertex (zeros for the fixed one), h_off[E][49] the assembled block H(i, j) of each edge's pair (zeros when
+ * either end is fixed).  Every output may be NULL. */
+int orbx_essential_graph_linearize(orbx_essential_graph *h, const orbx_essential_graph_problem *problem, const double *at,
+                                   double *meas, double *errors, double *chi2, double *jac, double *h_diag, double *h_off, double *b);
+/* (H + lambda I) x = b on the last orbx_essential_graph_linearize: x[n][7] by vertex (zeros for the fixed one), ok[1] = 0 on
+ * a non-positive or non-finite pivot, and x is then all zeros.  ORBX_ERR_STATE without a linearisation. */
+int orbx_essential_graph_solve(orbx_essential_graph *h, double lambda, double *x, int32_t *ok);
+/* device time of the last orbx_optimize_essential_graph chain, its kernel launches, and the part of that time inside
+ * k_eg_solve (factorisation and substitutions; the kernel's own clock: what tools/latency_essential_graph.py reports as the
+ * factorisation's share).  Every output may be NULL. */
+int orbx_essential_graph_last_timing(orbx_essential_graph *h, float *device_ms, int *launches, float *solve_ms);
+
 
 #ifdef __cplusplus
 }

@@ -2330,3 +2330,215 @@ class PnPsolver:
         n = ctypes.c_int()
         _check(self._L.orbx_pnp_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+class EssentialGraphProblem(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("est", ctypes.c_void_p), ("meas", ctypes.c_void_p), ("fixed", ctypes.c_int), ("fix_scale", ctypes.c_int),
+                ("n_edges", ctypes.c_int), ("edges", ctypes.c_void_p), ("n_points", ctypes.c_int), ("points", ctypes.c_void_p), ("point_ref", ctypes.c_void_p),
+                ("iterations", ctypes.c_int), ("lambda_init", ctypes.c_double)]
+
+
+_EG_RESULT_FIELDS = ("est", "tiw", "inv", "points", "chi2", "iterations", "ended", "iter_trials", "iter_chi2", "iter_lambda", "iter_rho", "order", "fill_blocks")
+EG_ENDED = ("iterations", "trials", "rho0", "three")
+
+
+class EssentialGraphCResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _EG_RESULT_FIELDS]
+
+
+class EssentialGraphResult:
+    """One optimised essential graph: est (N,8) float64 rows [qx, qy, qz, qw, tx, ty, tz, s] (the final estimates), Tiw (N,3,4) float32 = [R | t / s] (what
+    SetPose takes), inv (N,8) (vCorrectedSwc), points (M,3) float32, chi2 (initial, final), iterations, ended ("iterations", "trials", "rho0", "three"),
+    order (N - 1) the elimination order as vertex indices, fill_blocks; with full=True also trials / iter_chi2 / iter_lambda / iter_rho per iteration."""
+
+    def __init__(self, out):
+        self.__dict__.update(out)
+
+
+def _quat_from_R(R):
+    """Eigen::Quaterniond(Matrix3d) -> [x, y, z, w]"""
+    import math
+    R = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+    q = [0.0] * 4
+    t = (R[0] + R[4]) + R[8]
+    if t > 0.0:
+        t = math.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[0], q[1], q[2] = (R[7] - R[5]) * t, (R[2] - R[6]) * t, (R[3] - R[1]) * t
+        return q
+    i = 0
+    if R[4] > R[0]:
+        i = 1
+    if R[8] > R[4 * i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = math.sqrt(((R[4 * i] - R[4 * j]) - R[4 * k]) + 1.0)
+    q[i] = 0.5 * t
+    t = 0.5 / t
+    q[3] = (R[3 * k + j] - R[3 * j + k]) * t
+    q[j] = (R[3 * j + i] + R[3 * i + j]) * t
+    q[k] = (R[3 * k + i] + R[3 * i + k]) * t
+    return q
+
+
+def essential_graph_edges(keyframes, loop_kf, cur_kf, corrected, non_corrected, loop_connections, min_feat=100):
+    """The vertex and edge selection of Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1059-1262) on plain data.
+    keyframes: the map's keyframes in any order (they are walked in ascending id, as shim/EssentialGraph_hip.cc does), each a dict(id, parent (id or None), children (ids), loop_edges (ids), covisibles (ids by
+    descending weight: GetCovisiblesByWeight keeps those with weight >= min_feat, in this order), weights (id -> weight), bad, Rcw (3,3), tcw (3));
+    loop_kf / cur_kf: ids; corrected / non_corrected: id -> Sim3 [qx, qy, qz, qw, tx, ty, tz, s]; loop_connections: id -> ids.
+    -> dict(ids (ascending, the bad keyframes left out), est (N,8) = vScw, meas (N,8), fixed, edges (E,3) int32 = (i, j, kind)): vertex 0 of an edge is i;
+    kind 0 = a LoopConnections edge (measured from est), kind 1 = spanning tree, loop or covisibility (measured from meas).  The rules: a
+    LoopConnections edge below min_feat is skipped unless it is the (current, loop) pair; sInsertedEdges holds the LoopConnections pairs and
+    dedupes covisibility edges only; loop and covisibility edges go towards the smaller id; covisibility edges skip the parent, the children,
+    the loop edges and bad keyframes."""
+    good = [kf for kf in keyframes if not kf.get("bad", False)]
+    ids = sorted(kf["id"] for kf in good)
+    index = {k: n for n, k in enumerate(ids)}
+    by_id = {kf["id"]: kf for kf in keyframes}
+    est, meas = np.zeros((len(ids), 8)), np.zeros((len(ids), 8))
+    for kf in good:
+        k = kf["id"]
+        if k in corrected:
+            est[index[k]] = np.asarray(corrected[k], np.float64).reshape(8)
+        else:
+            est[index[k]] = _quat_from_R(kf["Rcw"]) + [float(v) for v in np.asarray(kf["tcw"], np.float64).reshape(3)] + [1.0]
+        meas[index[k]] = np.asarray(non_corrected[k], np.float64).reshape(8) if k in non_corrected else est[index[k]]
+    edges, inserted = [], set()
+    for ki, conns in loop_connections.items():
+        for kj in (sorted(conns) if isinstance(conns, (set, frozenset)) else conns):
+            if (ki != cur_kf or kj != loop_kf) and by_id[ki]["weights"].get(kj, 0) < min_feat:
+                continue
+            if ki in index and kj in index:
+                edges.append((index[ki], index[kj], 0))
+            inserted.add((min(ki, kj), max(ki, kj)))
+    for kf in sorted(good, key=lambda k: k["id"]):      # ascending id, as the shim walks them: the edge order is the summation order
+        ki = kf["id"]
+        par = kf.get("parent")
+        if par is not None and par in index:
+            edges.append((index[ki], index[par], 1))
+        loops = set(kf.get("loop_edges", ()))
+        for kl in sorted(loops):
+            if kl < ki and kl in index:
+                edges.append((index[ki], index[kl], 1))
+        children = set(kf.get("children", ()))
+        for kn in kf.get("covisibles", ()):
+            if kf["weights"].get(kn, 0) < min_feat:
+                continue
+            if kn == par or kn in children or kn in loops:
+                continue
+            if by_id[kn].get("bad", False) or not kn < ki:
+                continue
+            if (min(ki, kn), max(ki, kn)) in inserted:
+                continue
+            edges.append((index[ki], index[kn], 1))
+    return dict(ids=np.array(ids, np.int64), est=est, meas=meas, fixed=index[loop_kf], edges=np.array(edges, np.int32).reshape(-1, 3))
+
+
+class EssentialGraphOptimizer:
+    """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1017-1339) on the device (orbx_optimize_essential_graph)."""
+
+    def __init__(self, max_keyframes, max_edges, max_points=0, max_fill_blocks=None, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_essential_graph_create.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_essential_graph_destroy.argtypes = [vp]
+        L.orbx_essential_graph_destroy.restype = None
+        L.orbx_optimize_essential_graph.argtypes = [vp, ctypes.POINTER(EssentialGraphProblem), ctypes.POINTER(EssentialGraphCResult)]
+        L.orbx_essential_graph_linearize.argtypes = [vp, ctypes.POINTER(EssentialGraphProblem)] + [vp] * 8
+        L.orbx_essential_graph_solve.argtypes = [vp, ctypes.c_double, vp, vp]
+        L.orbx_essential_graph_last_timing.argtypes = [vp, vp, vp, vp]
+        self.max_keyframes, self.max_edges, self.max_points = int(max_keyframes), int(max_edges), int(max_points)
+        nk = self.max_keyframes
+        self.max_fill_blocks = int(max_fill_blocks) if max_fill_blocks is not None else max(1, min(nk * (nk + 1) // 2, 64 * nk))
+        self._n = 0
+        self._h = vp()
+        _check(L.orbx_essential_graph_create(device, self.max_keyframes, self.max_edges, self.max_points, self.max_fill_blocks, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_essential_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _problem(g, keep, fix_scale, iterations, lambda_init):
+        """g: dict(est (N,8), meas (N,8) or None, fixed, edges (E,3), points (M,3) and ref (M), both optional), or an object with these attributes"""
+        get = (lambda k: g.get(k)) if isinstance(g, dict) else (lambda k: getattr(g, k, None))
+        est = np.ascontiguousarray(get("est"), np.float64).reshape(-1, 8)
+        meas = None if get("meas") is None else np.ascontiguousarray(get("meas"), np.float64).reshape(-1, 8)
+        edges = np.ascontiguousarray(get("edges") if get("edges") is not None else np.zeros((0, 3)), np.int32).reshape(-1, 3)
+        pts = np.ascontiguousarray(get("points") if get("points") is not None else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+        ref = np.ascontiguousarray(get("ref") if get("ref") is not None else np.zeros(0), np.int32).reshape(-1)
+        if meas is not None and len(meas) != len(est):
+            raise ValueError("EssentialGraphOptimizer: %d measured poses for %d keyframes" % (len(meas), len(est)))
+        if len(ref) != len(pts):
+            raise ValueError("EssentialGraphOptimizer: %d references for %d points" % (len(ref), len(pts)))
+        keep.extend([est, meas, edges, pts, ref])
+        P = EssentialGraphProblem()
+        P.n, P.est, P.meas = len(est), est.ctypes.data, None if meas is None else meas.ctypes.data
+        P.fixed, P.fix_scale = int(get("fixed")), 1 if fix_scale else 0
+        P.n_edges, P.edges = len(edges), edges.ctypes.data if len(edges) else None
+        P.n_points, P.points, P.point_ref = len(pts), pts.ctypes.data if len(pts) else None, ref.ctypes.data if len(pts) else None
+        P.iterations, P.lambda_init = int(iterations), float(lambda_init)
+        return P
+
+    def OptimizeEssentialGraph(self, graph, fix_scale=False, full=False, iterations=20, lambda_init=1e-16):
+        """graph: see _problem (essential_graph_edges returns one) -> EssentialGraphResult"""
+        keep = []
+        P = self._problem(graph, keep, fix_scale, iterations, lambda_init)
+        n, m, it = max(P.n, 1), max(P.n_points, 1), max(int(iterations) if iterations > 0 else 20, 1)
+        f8, f4, i4 = np.float64, np.float32, np.int32
+        o = dict(est=np.zeros((n, 8), f8), tiw=np.zeros((n, 3, 4), f4), inv=np.zeros((n, 8), f8), points=np.zeros((m, 3), f4), chi2=np.zeros(2, f8),
+                 iterations=np.zeros(1, i4), ended=np.zeros(1, i4), order=np.zeros(n, i4), fill_blocks=np.zeros(1, i4))
+        if full:
+            o.update(iter_trials=np.zeros(it, i4), iter_chi2=np.zeros(it, f8), iter_lambda=np.zeros(it, f8), iter_rho=np.zeros(it, f8))
+        R = EssentialGraphCResult(*[o[k].ctypes.data if k in o else None for k in _EG_RESULT_FIELDS])
+        _check(self._L.orbx_optimize_essential_graph(self._h, ctypes.byref(P), ctypes.byref(R)))
+        done = int(o["iterations"][0])
+        out = dict(est=o["est"][:P.n], Tiw=o["tiw"][:P.n], inv=o["inv"][:P.n], points=o["points"][:P.n_points], chi2=(float(o["chi2"][0]), float(o["chi2"][1])),
+                   iterations=done, ended=EG_ENDED[int(o["ended"][0])], order=o["order"][:max(P.n - 1, 0)].copy(), fill_blocks=int(o["fill_blocks"][0]))
+        if full:
+            out.update(trials=o["iter_trials"][:done], iter_chi2=o["iter_chi2"][:done], iter_lambda=o["iter_lambda"][:done], iter_rho=o["iter_rho"][:done])
+        return EssentialGraphResult(out)
+
+    def linearize(self, graph, at=None, fix_scale=False):
+        """One linearisation at the estimates `at` (N,8; default: the graph's est) with the chain's kernels -> dict(meas (E,8), errors (E,7), chi2,
+        jac (E,2,7,7), h_diag (N,7,7), h_off (E,7,7), b (N,7)); solve() then runs on it."""
+        keep = []
+        P = self._problem(graph, keep, fix_scale, 20, 1e-16)
+        a = None if at is None else np.ascontiguousarray(at, np.float64).reshape(-1, 8)
+        if a is not None and len(a) != P.n:
+            raise ValueError("EssentialGraphOptimizer.linearize: %d estimates for %d keyframes" % (len(a), P.n))
+        n, e = max(P.n, 1), max(P.n_edges, 1)
+        f8 = np.float64
+        o = dict(meas=np.zeros((e, 8), f8), errors=np.zeros((e, 7), f8), chi2=np.zeros(1, f8), jac=np.zeros((e, 2, 7, 7), f8), h_diag=np.zeros((n, 7, 7), f8),
+                 h_off=np.zeros((e, 7, 7), f8), b=np.zeros((n, 7), f8))
+        _check(self._L.orbx_essential_graph_linearize(self._h, ctypes.byref(P), None if a is None else a.ctypes.data,
+                                                      *[o[k].ctypes.data for k in ("meas", "errors", "chi2", "jac", "h_diag", "h_off", "b")]))
+        self._n = P.n
+        for k in ("meas", "errors", "jac", "h_off"):
+            o[k] = o[k][:P.n_edges]
+        for k in ("h_diag", "b"):
+            o[k] = o[k][:P.n]
+        o["chi2"] = float(o["chi2"][0])
+        return o
+
+    def solve(self, lam):
+        """(H + lam I) x = b on the last linearize() -> (ok, x (N,7) by vertex, zeros for the fixed one)"""
+        x, ok = np.zeros((max(self._n, 1), 7), np.float64), np.zeros(1, np.int32)
+        _check(self._L.orbx_essential_graph_solve(self._h, float(lam), x.ctypes.data, ok.ctypes.data))
+        return bool(ok[0]), x[:self._n]
+
+    def last_timing(self):
+        """(device ms of the last OptimizeEssentialGraph chain, kernel launches, ms inside the solve kernel)"""
+        ms, sv = ctypes.c_float(), ctypes.c_float()
+        n = ctypes.c_int()
+        _check(self._L.orbx_essential_graph_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(sv)))
+        return ms.value, n.value, sv.value
