@@ -1507,6 +1507,101 @@ int orbx_essential_graph_solve(orbx_essential_graph *h, double lambda, double *x
  * factorisation's share).  Every output may be NULL. */
 int orbx_essential_graph_last_timing(orbx_essential_graph *h, float *device_ms, int *launches, float *solve_ms);
 
+/* ----------------------------------------------------------------------------------
+ * KeyFrameDatabase::DetectLoopCandidates / DetectRelocalizationCandidates (reference src/KeyFrameDatabase.cc:104-374) with
+ * L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) and the minimum-score loop of LoopClosing::DetectLoop
+ * (src/LoopClosing.cc:160-176): place recognition for all queries of a call in one chain.  The database lives on the device:
+ * an append-only pool of (word, value) entries and per keyframe id, `add` sequence number, offset, length, alive, the
+ * up-to-ten best covisible ids and the persistent reloc_score.  There is no inverted file: the order of the reference's
+ * lKFsSharingWords is the order by (smallest word shared with the query, `add` sequence number), which every keyframe finds
+ * by intersecting its own sorted BowVector with the query (tests/test_kfdb.py proves the equivalence on a literal restatement
+ * of the inverted-file walk).
+ *
+ *   k_kfdb_intersect  per (query, alive keyframe): shared words, first shared word; per query n_sharing and maxCommonWords
+ *                     over the keyframes outside the connected set; minCommonWords = (int)((float)maxCommonWords * 0.8f)
+ *   k_kfdb_score      the keyframes with words > minCommonWords and, loop mode, the connected ones: sum += fabs(v - w) -
+ *                     fabs(v) - fabs(w) over the shared words in ascending order by one running double sum (no tree),
+ *                     score = (float)(-sum / 2.0)
+ *   k_kfdb_commit     the reloc_score state behind this call
+ *   k_kfdb_select     the scored keyframes ranked by (first word, seq); minScore; lScoreAndMatch; the covisibility groups in
+ *                     float with the strictly-greater best; bestAccScore; 0.75f; each group's best keyframe once, at its
+ *                     first occurrence; results into mapped pinned memory
+ *
+ *   erase clears `alive`; an `add` that finds more dead entries than half of the entries in use (or that needs the room)
+ *   compacts pool and slots first, keeping the sequence numbers.
+ *   Loop mode: a covisible contributes only if THIS query scored it (:201).  minScore = min(min_score_in, the float scores of
+ *   the listed connected keyframes that are in the database and have a count != 0).
+ *   Relocalisation mode keeps the reference's quirk (:336-339): a covisible that shares at least one word with the query
+ *   contributes its reloc_score even when this query did not score it.  Within one call a query reads its own score where it
+ *   scored a keyframe and otherwise the value from before the call; after the call every keyframe holds the score of the
+ *   highest-numbered relocalisation query that scored it (nq = 1: the reference exactly).
+ *   PARITY UNPINNED against the reference: reloc_score is 0 from `add` until a query scores the keyframe (mRelocScore is
+ *   uninitialised there); a query reads the covisibles as last pushed by orbx_kfdb_set_covisibles, not as of the query.
+ * ---------------------------------------------------------------------------------- */
+typedef struct orbx_kf_database orbx_kf_database;
+#define ORBX_KFDB_LOOP 0
+#define ORBX_KFDB_RELOC 1
+#define ORBX_KFDB_MAX_QUERY_WORDS 8192
+
+typedef struct orbx_kfdb_query_t {      /* host memory */
+    int mode;                        /* ORBX_KFDB_LOOP / ORBX_KFDB_RELOC                                                 */
+    const int32_t *words;            /* [n] ascending, distinct, 0..n_words-1: the BowVector in map order                */
+    const double *values;            /* [n]                                                                              */
+    int n;
+    const int64_t *connected;        /* [n_connected] loop mode: GetConnectedKeyFrames (ids need not be present)         */
+    const int32_t *connected_counts; /* [n_connected] 0 = isBad(): excluded from the sharers, not part of minScore       */
+    int n_connected;
+    float min_score_in;              /* loop mode: what the caller scored itself (1.0f = nothing)                        */
+    int capacity;                    /* entries of each list output of this query's result                               */
+} orbx_kfdb_query_t;
+
+typedef struct orbx_kfdb_result {       /* host memory; every pointer may be NULL */
+    int32_t *n_sharing;              /* lKFsSharingWords.size()                                                          */
+    int32_t *max_common_words, *min_common_words;
+    float *min_score;                /* loop mode; 0 in relocalisation mode                                              */
+    float *connected_score;          /* [n_connected] loop mode; -1 where the id is not in the database                  */
+    int64_t *scored_id;              /* [n_scored] the keyframes with words > minCommonWords in the reference's order    */
+    int32_t *scored_words;           /* ... mnLoopWords / mnRelocWords                                                   */
+    float *scored_score;             /* ... mLoopScore / mRelocScore                                                     */
+    int32_t *n_scored;
+    int32_t *kept;                   /* [n_kept] lScoreAndMatch: index into the scored list                              */
+    float *acc_score;                /* [n_kept] lAccScoreAndMatch: accScore                                             */
+    int64_t *best_id;                /* [n_kept] ... pBestKF                                                             */
+    int32_t *n_kept;
+    float *best_acc_score;           /* bestAccScore (its start value, minScore or 0, where lScoreAndMatch is empty)     */
+    int64_t *candidates;             /* [n_candidates]                                                                   */
+    int32_t *n_candidates;
+} orbx_kfdb_result;
+
+/* ORBX_ERR_ARG: n_words, max_keyframes, max_entries, max_queries < 1, max_query_words outside 1..ORBX_KFDB_MAX_QUERY_WORDS,
+ * max_queries * max_keyframes > 2^28; then ORBX_ERR_NODEVICE without a device */
+int orbx_kfdb_create(int device, int n_words, int max_keyframes, int max_entries, int max_queries, int max_query_words,
+                     orbx_kf_database **out);
+void orbx_kfdb_destroy(orbx_kf_database *h);
+/* ORBX_ERR_ARG: NULL handle, n < 0, a word outside 0..n_words-1, unsorted or repeated words; ORBX_ERR_STATE: the id is
+ * present; ORBX_ERR_CAPACITY: no slot or no room in the pool even after compaction (the database is unchanged). */
+int orbx_kfdb_add(orbx_kf_database *h, int64_t id, const int32_t *words, const double *values, int n);
+int orbx_kfdb_erase(orbx_kf_database *h, int64_t id);          /* absent id: ORBX_OK, as the reference */
+int orbx_kfdb_clear(orbx_kf_database *h);
+/* n <= 10 ids in GetBestCovisibilityKeyFrames(10) order; they need not be present (an id added later counts from then on).
+ * ORBX_ERR_ARG: n outside 0..10; ORBX_ERR_STATE: `id` is not in the database. */
+int orbx_kfdb_set_covisibles(orbx_kf_database *h, int64_t id, const int64_t *ids, int n);
+/* alive keyframes, pool entries in use (dead ones included), dead entries; every output may be NULL */
+int orbx_kfdb_size(orbx_kf_database *h, int *keyframes, int *entries, int *dead_entries);
+/* the persistent reloc_score of a keyframe; ORBX_ERR_STATE: not in the database */
+int orbx_kfdb_reloc_score(orbx_kf_database *h, int64_t id, float *score);
+/* ORBX_ERR_ARG: nq < 1, an unknown mode, bad words (as orbx_kfdb_add), n_connected < 0, capacity < 0; ORBX_ERR_CAPACITY: more
+ * queries or query words than the handle was created for (nothing runs), or a list longer than its query's capacity (nothing
+ * is written to any result; the queries HAVE run, so the reloc scores are those after the call).  An empty database, n = 0 and
+ * a query that shares no word give empty lists and ORBX_OK. */
+int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *queries, int nq, const orbx_kfdb_result *results);
+/* device time of the last orbx_kfdb_query chain and its kernel launches (0, 0 when nothing was launched) */
+int orbx_kfdb_last_timing(orbx_kf_database *h, float *device_ms, int *launches);
+/* Measurement only: stage_ms[5] (may be NULL) = device time of the last query's staging, k_kfdb_intersect, k_kfdb_score,
+ * k_kfdb_commit and k_kfdb_select, when that query ran with the events enabled (ORBX_ERR_STATE otherwise); then `enable`
+ * switches the four extra event records per query on or off (off in a new handle). */
+int orbx_kfdb_stage_timing(orbx_kf_database *h, int enable, float *stage_ms);
+
 
 #ifdef __cplusplus
 }

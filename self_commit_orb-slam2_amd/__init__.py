@@ -2542,3 +2542,165 @@ class EssentialGraphOptimizer:
         n = ctypes.c_int()
         _check(self._L.orbx_essential_graph_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(sv)))
         return ms.value, n.value, sv.value
+
+
+KFDB_LOOP, KFDB_RELOC = 0, 1
+
+
+class KfdbQuery(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("words", ctypes.c_void_p), ("values", ctypes.c_void_p), ("n", ctypes.c_int), ("connected", ctypes.c_void_p),
+                ("connected_counts", ctypes.c_void_p), ("n_connected", ctypes.c_int), ("min_score_in", ctypes.c_float), ("capacity", ctypes.c_int)]
+
+
+_KFDB_RESULT_FIELDS = ("n_sharing", "max_common_words", "min_common_words", "min_score", "connected_score", "scored_id", "scored_words", "scored_score", "n_scored",
+                       "kept", "acc_score", "best_id", "n_kept", "best_acc_score", "candidates", "n_candidates")
+
+
+class KfdbCResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _KFDB_RESULT_FIELDS]
+
+
+def _kfdb_bow(bow):
+    """(words, values) or {word: value} -> (int32 words ascending as given, float64 values)"""
+    if isinstance(bow, dict):
+        if "words" in bow and "values" in bow:
+            bow = (bow["words"], bow["values"])
+        else:
+            ks = sorted(bow)
+            bow = (ks, [bow[k] for k in ks])
+    w = np.ascontiguousarray(bow[0], np.int32).reshape(-1)
+    v = np.ascontiguousarray(bow[1], np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("KeyFrameDatabase: %d words for %d values" % (len(w), len(v)))
+    return w, v
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (reference src/KeyFrameDatabase.cc) on the device: add / erase / clear as there, set_covisibles pushes GetBestCovisibilityKeyFrames(10)
+    of a keyframe (a query reads the covisibles as last pushed), DetectLoopCandidates / DetectRelocalizationCandidates return the candidate ids in the
+    reference's order (full=True: every field of orbx_kfdb_result as a dict), query() runs several queries in one call.  A bow is (words, values) with ascending
+    words, or a dict word -> value."""
+
+    def __init__(self, n_words, max_keyframes, max_entries, max_queries=8, max_query_words=4096, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+        L.orbx_kfdb_create.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
+        L.orbx_kfdb_destroy.argtypes = [vp]
+        L.orbx_kfdb_destroy.restype = None
+        L.orbx_kfdb_add.argtypes = [vp, i64, vp, vp, ci]
+        L.orbx_kfdb_erase.argtypes = [vp, i64]
+        L.orbx_kfdb_clear.argtypes = [vp]
+        L.orbx_kfdb_set_covisibles.argtypes = [vp, i64, vp, ci]
+        L.orbx_kfdb_size.argtypes = [vp, vp, vp, vp]
+        L.orbx_kfdb_reloc_score.argtypes = [vp, i64, vp]
+        L.orbx_kfdb_query.argtypes = [vp, ctypes.POINTER(KfdbQuery), ci, ctypes.POINTER(KfdbCResult)]
+        L.orbx_kfdb_last_timing.argtypes = [vp, vp, vp]
+        self.n_words, self.max_keyframes, self.max_entries = int(n_words), int(max_keyframes), int(max_entries)
+        self._h = vp()
+        _check(L.orbx_kfdb_create(device, self.n_words, self.max_keyframes, self.max_entries, int(max_queries), int(max_query_words), ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, kf_id, bow):
+        w, v = _kfdb_bow(bow)
+        _check(self._L.orbx_kfdb_add(self._h, int(kf_id), w.ctypes.data, v.ctypes.data, len(w)))
+
+    def erase(self, kf_id):
+        _check(self._L.orbx_kfdb_erase(self._h, int(kf_id)))
+
+    def clear(self):
+        _check(self._L.orbx_kfdb_clear(self._h))
+
+    def set_covisibles(self, kf_id, ids):
+        a = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        _check(self._L.orbx_kfdb_set_covisibles(self._h, int(kf_id), a.ctypes.data, len(a)))
+
+    def size(self):
+        """(alive keyframes, pool entries in use, dead entries)"""
+        k, e, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _check(self._L.orbx_kfdb_size(self._h, ctypes.byref(k), ctypes.byref(e), ctypes.byref(d)))
+        return k.value, e.value, d.value
+
+    def __len__(self):
+        return self.size()[0]
+
+    def reloc_score(self, kf_id):
+        s = ctypes.c_float()
+        _check(self._L.orbx_kfdb_reloc_score(self._h, int(kf_id), ctypes.byref(s)))
+        return np.float32(s.value)
+
+    def stage_timing(self, enable=True, read=False):
+        """read=True: device ms of the last query's (staging, intersect, score, commit, select), which must have run with the events enabled; then switch them"""
+        ms = (ctypes.c_float * 5)()
+        self._L.orbx_kfdb_stage_timing.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        _check(self._L.orbx_kfdb_stage_timing(self._h, 1 if enable else 0, ms if read else None))
+        return tuple(ms) if read else None
+
+    def query(self, queries, marshal_only=False):
+        """queries: dicts with mode (KFDB_LOOP / KFDB_RELOC), bow (or words and values), and for loop mode connected (ids), counts (default: all 1),
+        min_score_in (default 1.0); capacity (default: the keyframes in the database) -> one dict per query with every field of orbx_kfdb_result"""
+        nq = len(queries)
+        keep, outs = [], []
+        Q, R = (KfdbQuery * max(nq, 1))(), (KfdbCResult * max(nq, 1))()
+        alive = len(self)
+        for i, q in enumerate(queries):
+            w, v = _kfdb_bow(q["bow"] if "bow" in q else (q["words"], q["values"]))
+            con = np.ascontiguousarray(q.get("connected", ()), np.int64).reshape(-1)
+            cnt = np.ascontiguousarray(q["counts"] if q.get("counts") is not None else np.ones(len(con)), np.int32).reshape(-1)
+            if len(cnt) != len(con):
+                raise ValueError("KeyFrameDatabase.query: %d counts for %d connected keyframes" % (len(cnt), len(con)))
+            cap = int(q.get("capacity", alive))
+            keep.extend([w, v, con, cnt])
+            Q[i].mode, Q[i].words, Q[i].values, Q[i].n = int(q["mode"]), w.ctypes.data, v.ctypes.data, len(w)
+            Q[i].connected, Q[i].connected_counts, Q[i].n_connected = con.ctypes.data, cnt.ctypes.data, len(con)
+            Q[i].min_score_in, Q[i].capacity = float(q.get("min_score_in", 1.0)), cap
+            c, i4, i8, f4 = max(cap, 1), np.int32, np.int64, np.float32
+            o = dict(n_sharing=np.zeros(1, i4), max_common_words=np.zeros(1, i4), min_common_words=np.zeros(1, i4), min_score=np.zeros(1, f4),
+                     connected_score=np.zeros(max(len(con), 1), f4), scored_id=np.zeros(c, i8), scored_words=np.zeros(c, i4), scored_score=np.zeros(c, f4),
+                     n_scored=np.zeros(1, i4), kept=np.zeros(c, i4), acc_score=np.zeros(c, f4), best_id=np.zeros(c, i8), n_kept=np.zeros(1, i4),
+                     best_acc_score=np.zeros(1, f4), candidates=np.zeros(c, i8), n_candidates=np.zeros(1, i4))
+            outs.append((o, len(con) if int(q["mode"]) == KFDB_LOOP else 0))
+            R[i] = KfdbCResult(*[o[k].ctypes.data for k in _KFDB_RESULT_FIELDS])
+        if marshal_only:
+            return Q, R, nq, keep, outs
+        _check(self._L.orbx_kfdb_query(self._h, Q, nq, R))
+        res = []
+        for o, ncon in outs:
+            ns, nk, ncand = int(o["n_scored"][0]), int(o["n_kept"][0]), int(o["n_candidates"][0])
+            res.append(dict(n_sharing=int(o["n_sharing"][0]), max_common_words=int(o["max_common_words"][0]), min_common_words=int(o["min_common_words"][0]),
+                            min_score=o["min_score"][0], connected_score=o["connected_score"][:ncon], scored_id=o["scored_id"][:ns], scored_words=o["scored_words"][:ns],
+                            scored_score=o["scored_score"][:ns], kept=o["kept"][:nk], acc_score=o["acc_score"][:nk], best_id=o["best_id"][:nk],
+                            best_acc_score=o["best_acc_score"][0], candidates=o["candidates"][:ncand]))
+        return res
+
+    def DetectLoopCandidates(self, bow, connected, min_score_in=1.0, full=False):
+        """connected: GetConnectedKeyFrames as ids, (id, count) pairs or a dict id -> count (count 0 = isBad())"""
+        if isinstance(connected, dict):
+            connected = list(connected.items())
+        connected = list(connected)
+        if connected and np.ndim(connected[0]) == 1:
+            ids, counts = [c[0] for c in connected], [c[1] for c in connected]
+        else:
+            ids, counts = connected, None
+        r = self.query([dict(mode=KFDB_LOOP, bow=bow, connected=ids, counts=counts, min_score_in=min_score_in)])[0]
+        return r if full else [int(i) for i in r["candidates"]]
+
+    def DetectRelocalizationCandidates(self, bow, full=False):
+        r = self.query([dict(mode=KFDB_RELOC, bow=bow)])[0]
+        return r if full else [int(i) for i in r["candidates"]]
+
+    def last_timing(self):
+        """(device ms of the last query chain, kernel launches)"""
+        ms, n = ctypes.c_float(), ctypes.c_int()
+        _check(self._L.orbx_kfdb_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
