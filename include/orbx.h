@@ -1602,6 +1602,90 @@ int orbx_kfdb_last_timing(orbx_kf_database *h, float *device_ms, int *launches);
  * switches the four extra event records per query on or off (off in a new handle). */
 int orbx_kfdb_stage_timing(orbx_kf_database *h, int enable, float *stage_ms);
 
+/* ----------------------------------------------------------------------------------
+ * Covisibility: the counting inside KeyFrame::UpdateConnections (reference src/KeyFrame.cc:386-507), the vote that opens
+ * Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1895-1955) and LocalMapping::KeyFrameCulling (src/LocalMapping.cc:873-956).
+ * Integer counting over ragged observation lists: every result is exact.  Stateless and synchronous: a slice of the map in
+ * host arrays goes in, host arrays come out, one wait per call (per culling round, see below).  AddConnection, the spanning
+ * tree and the rest of SetBadFlag stay with the caller (shim/Covisibility_hip.cc).
+ *
+ * The slice.  num_keyframes slots: every keyframe the call names as a list owner or an observer.  kf_rank are distinct values
+ * that give the iteration order of std::map<KeyFrame*, ...> (the rank of the pointer value); kf_flags bit 0: mnId == 0, bit 1:
+ * mbNotErase, bit 2: isBad().  Points: CSR observation lists (obs_offset, obs_kf = the observer's slot, obs_octave =
+ * mvKeysUn[idx].octave there, obs_stereo = mvuRight[idx] >= 0), a keyframe at most once per point; point_bad.  A point's
+ * Observations() is the sum of 1 (2 where obs_stereo) over its observations: derived, not passed.  Lists: CSR (list_offset),
+ * list_kf = the owner's slot or -1 for a Frame, list_point = the non-NULL mvpMapPoints in feature order (a point may repeat:
+ * both entries count), list_octave = mvKeysUn[i].octave, list_close = 0 where the sensor is not monocular and mvDepth[i] is
+ * beyond mThDepth or negative, else 1.  The octave, stereo and close arrays are read by the culling only and may be NULL for
+ * orbx_covis_update_connections.
+ *
+ * orbx_covis_update_connections, all lists of the call in one launch.  Per list: KFcounter over the points that are not bad,
+ * without the owner, as (slot, weight) in ascending rank; n_max / kf_max = the first slot in ascending rank with the strictly
+ * greatest weight (a Frame's list, list_kf = -1: slots flagged bad are no candidates but stay in the counter; kf_max = -1
+ * and n_max = 0 when no candidate is left); the connections = the slots with weight >= th by descending weight and, within a
+ * weight, descending rank (sort + push_front of pair<int, KeyFrame*>), or the single (kf_max, n_max) when none reaches th.
+ * An empty counter: n_counter = 0, kf_max = -1, no connection.  The histogram of a list lives in LDS up to
+ * ORBX_COVIS_LDS_KEYFRAMES slots and in device memory beyond: the results are the same.
+ *
+ * orbx_covis_keyframe_culling: the lists are vpLocalKeyFrames in the caller's order, each owned by a different keyframe.
+ * Equal to the sequential loop with its side effects: a keyframe with bit 0 is skipped; n_mps counts the entries that are not
+ * bad and are close; n_redundant those of them with Observations() > 3 and at least 3 live observers other than the owner
+ * with obs_octave <= list_octave + 1; culled = n_redundant > 0.9 * n_mps as the double product.  A culled keyframe without
+ * bit 1 has its observations erased before the next list is looked at: each of its points loses 1 or 2 from Observations()
+ * and goes bad (for good, with all its observations) when that leaves <= 2; only an erase makes a point bad.  A culled
+ * keyframe with bit 1 is reported and changes nothing.  c erasing culls take c + 1 rounds: 2 c + 3 launches, c + 1 waits.
+ * ---------------------------------------------------------------------------------- */
+typedef struct orbx_covis orbx_covis;
+#define ORBX_COVIS_LDS_KEYFRAMES 4096
+
+typedef struct orbx_covis_slice {       /* host memory */
+    int num_keyframes;
+    const int32_t *kf_rank;          /* [num_keyframes] distinct                                                         */
+    const uint8_t *kf_flags;         /* [num_keyframes]                                                                  */
+    int num_points, num_obs;
+    const int32_t *obs_offset;       /* [num_points + 1]                                                                 */
+    const int32_t *obs_kf;           /* [num_obs] 0..num_keyframes-1                                                     */
+    const uint8_t *obs_octave;       /* [num_obs]                                                                        */
+    const uint8_t *obs_stereo;       /* [num_obs]                                                                        */
+    const uint8_t *point_bad;        /* [num_points]                                                                     */
+    int num_lists, num_entries;
+    const int32_t *list_offset;      /* [num_lists + 1]                                                                  */
+    const int32_t *list_kf;          /* [num_lists] owner slot, -1 = a Frame (update_connections only)                   */
+    const int32_t *list_point;       /* [num_entries] 0..num_points-1                                                    */
+    const uint8_t *list_octave;      /* [num_entries]                                                                    */
+    const uint8_t *list_close;       /* [num_entries]                                                                    */
+} orbx_covis_slice;
+
+typedef struct orbx_covis_connections {  /* host memory; every pointer may be NULL */
+    int32_t *counter_offset;         /* [num_lists + 1] CSR of the counters: n_counter of list q = the difference        */
+    int32_t *counter_kf, *counter_weight;   /* [counter_capacity]                                                        */
+    int counter_capacity;
+    int32_t *n_max, *kf_max;         /* [num_lists]                                                                      */
+    int32_t *conn_offset;            /* [num_lists + 1] CSR of the ordered connections                                   */
+    int32_t *conn_kf, *conn_weight;  /* [conn_capacity]                                                                  */
+    int conn_capacity;
+} orbx_covis_connections;
+
+typedef struct orbx_covis_culling {      /* host memory; every pointer may be NULL */
+    int32_t *n_mps, *n_redundant;    /* [num_lists]                                                                      */
+    uint8_t *culled;                 /* [num_lists]                                                                      */
+    uint8_t *point_bad;              /* [num_points] after the loop                                                      */
+    int32_t *point_obs;              /* [num_points] Observations() after the loop                                       */
+} orbx_covis_culling;
+
+/* ORBX_ERR_ARG: NULL out, device out of range; ORBX_ERR_NODEVICE without a device */
+int orbx_covis_create(int device, orbx_covis **out);
+void orbx_covis_destroy(orbx_covis *h);
+/* ORBX_ERR_ARG, before anything is launched: a NULL array, num_keyframes or num_lists < 1, an offset array that does not
+ * start at 0, decreases or does not end at its total, a slot or point index out of range, two slots with one rank, a negative
+ * capacity.  ORBX_ERR_CAPACITY: the counters (the connections) of all lists together exceed counter_capacity
+ * (conn_capacity): nothing is written to any output; the handle stays usable. */
+int orbx_covis_update_connections(orbx_covis *h, const orbx_covis_slice *slice, int th, const orbx_covis_connections *out);
+/* ORBX_ERR_ARG as above, and: a list without an owner, two lists of one keyframe */
+int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice *slice, const orbx_covis_culling *out);
+/* device time of the last call's chain (the host's decisions between culling rounds included) and its kernel launches */
+int orbx_covis_last_timing(orbx_covis *h, float *kernel_ms, int *launches);
+
 
 #ifdef __cplusplus
 }

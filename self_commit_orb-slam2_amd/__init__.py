@@ -2704,3 +2704,151 @@ class KeyFrameDatabase:
         ms, n = ctypes.c_float(), ctypes.c_int()
         _check(self._L.orbx_kfdb_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+class CovisSlice(ctypes.Structure):
+    _fields_ = [("num_keyframes", ctypes.c_int), ("kf_rank", ctypes.c_void_p), ("kf_flags", ctypes.c_void_p), ("num_points", ctypes.c_int), ("num_obs", ctypes.c_int),
+                ("obs_offset", ctypes.c_void_p), ("obs_kf", ctypes.c_void_p), ("obs_octave", ctypes.c_void_p), ("obs_stereo", ctypes.c_void_p), ("point_bad", ctypes.c_void_p),
+                ("num_lists", ctypes.c_int), ("num_entries", ctypes.c_int), ("list_offset", ctypes.c_void_p), ("list_kf", ctypes.c_void_p), ("list_point", ctypes.c_void_p),
+                ("list_octave", ctypes.c_void_p), ("list_close", ctypes.c_void_p)]
+
+
+class CovisConnections(ctypes.Structure):
+    _fields_ = [("counter_offset", ctypes.c_void_p), ("counter_kf", ctypes.c_void_p), ("counter_weight", ctypes.c_void_p), ("counter_capacity", ctypes.c_int),
+                ("n_max", ctypes.c_void_p), ("kf_max", ctypes.c_void_p), ("conn_offset", ctypes.c_void_p), ("conn_kf", ctypes.c_void_p), ("conn_weight", ctypes.c_void_p),
+                ("conn_capacity", ctypes.c_int)]
+
+
+class CovisCulling(ctypes.Structure):
+    _fields_ = [("n_mps", ctypes.c_void_p), ("n_redundant", ctypes.c_void_p), ("culled", ctypes.c_void_p), ("point_bad", ctypes.c_void_p), ("point_obs", ctypes.c_void_p)]
+
+
+COVIS_MNID0, COVIS_NOT_ERASE, COVIS_BAD = 1, 2, 4      # kf_flags
+COVIS_LDS_KEYFRAMES = 4096      # ORBX_COVIS_LDS_KEYFRAMES
+
+_COVIS_ARRAYS = (("kf_rank", np.int32), ("kf_flags", np.uint8), ("obs_offset", np.int32), ("obs_kf", np.int32), ("obs_octave", np.uint8), ("obs_stereo", np.uint8),
+                 ("point_bad", np.uint8), ("list_offset", np.int32), ("list_kf", np.int32), ("list_point", np.int32), ("list_octave", np.uint8), ("list_close", np.uint8))
+
+
+def covis_slice(keyframes, lists=None, n_points=None, point_bad=None, ranks=None, flags=None):
+    """The arrays of orbx_covis_slice from per-keyframe observation tuples.  keyframes[slot] = the keyframe's non-NULL mvpMapPoints in feature order as
+    (point, octave, stereo) or (point, octave, stereo, close) tuples (close defaults to 1); a point that a keyframe lists twice is observed by it once (the
+    first tuple: mObservations is a map) and stays twice in its list.  lists = the lists of the call: a slot (that keyframe's list) or (-1, tuples) for a
+    Frame; default: every keyframe in slot order.  ranks default to the slot numbers, flags and point_bad to 0."""
+    NK = len(keyframes)
+    M = int(n_points) if n_points is not None else 1 + max([int(t[0]) for kf in keyframes for t in kf] + [int(t[0]) for l in (lists or ()) if not np.isscalar(l) for t in l[1]] + [-1])
+    per_point = [[] for _ in range(M)]
+    for k, kf in enumerate(keyframes):
+        seen = set()
+        for t in kf:
+            if int(t[0]) not in seen:
+                seen.add(int(t[0]))
+                per_point[int(t[0])].append((k, int(t[1]), 1 if t[2] else 0))
+    off = np.zeros(M + 1, np.int32)
+    off[1:] = np.cumsum([len(o) for o in per_point])
+    flat = [o for p in per_point for o in p]
+    ent, loff, lkf = [], [0], []
+    for l in (range(NK) if lists is None else lists):
+        owner, tuples = (int(l), keyframes[int(l)]) if np.isscalar(l) else (int(l[0]), l[1])
+        ent.extend((int(t[0]), int(t[1]), int(t[3]) if len(t) > 3 else 1) for t in tuples)
+        loff.append(len(ent))
+        lkf.append(owner)
+    col = lambda rows, i, dt: np.array([r[i] for r in rows], dt).reshape(-1)      # noqa: E731
+    return dict(kf_rank=np.arange(NK, dtype=np.int32) if ranks is None else np.ascontiguousarray(ranks, np.int32),
+                kf_flags=np.zeros(NK, np.uint8) if flags is None else np.ascontiguousarray(flags, np.uint8),
+                obs_offset=off, obs_kf=col(flat, 0, np.int32), obs_octave=col(flat, 1, np.uint8), obs_stereo=col(flat, 2, np.uint8),
+                point_bad=np.zeros(M, np.uint8) if point_bad is None else np.ascontiguousarray(point_bad, np.uint8),
+                list_offset=np.array(loff, np.int32), list_kf=np.array(lkf, np.int32).reshape(-1), list_point=col(ent, 0, np.int32), list_octave=col(ent, 1, np.uint8),
+                list_close=col(ent, 2, np.uint8))
+
+
+def covis_marshal(map_slice, keep):
+    """orbx_covis_slice of a dict of arrays (covis_slice's keys); the converted arrays are appended to `keep`, which must outlive the call"""
+    a = {k: np.ascontiguousarray(map_slice[k], dt).reshape(-1) for k, dt in _COVIS_ARRAYS}
+    keep.append(a)
+    NK, M, T, Q, S = len(a["kf_rank"]), len(a["point_bad"]), len(a["obs_kf"]), len(a["list_kf"]), len(a["list_point"])
+    if len(a["kf_flags"]) != NK or len(a["obs_offset"]) != M + 1 or len(a["obs_octave"]) != T or len(a["obs_stereo"]) != T or len(a["list_offset"]) != Q + 1 or \
+            len(a["list_octave"]) != S or len(a["list_close"]) != S:
+        raise ValueError("covisibility slice: array sizes do not agree")
+    p = {k: v.ctypes.data for k, v in a.items()}
+    return CovisSlice(NK, p["kf_rank"], p["kf_flags"], M, T, p["obs_offset"], p["obs_kf"], p["obs_octave"], p["obs_stereo"], p["point_bad"], Q, S, p["list_offset"], p["list_kf"],
+                      p["list_point"], p["list_octave"], p["list_close"]), a
+
+
+class Covisibility:
+    """The counting of KeyFrame::UpdateConnections (reference src/KeyFrame.cc:386-507), Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1895-1955) and
+    LocalMapping::KeyFrameCulling (src/LocalMapping.cc:873-956) on the device, over a slice of the map (covis_slice); keyframes are slot numbers, their
+    std::map order is the slice's kf_rank.  Exact integers; AddConnection, the spanning tree and SetBadFlag stay with the caller."""
+
+    def __init__(self, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_covis_create.argtypes = [ci, ctypes.POINTER(vp)]
+        L.orbx_covis_destroy.argtypes = [vp]
+        L.orbx_covis_destroy.restype = None
+        L.orbx_covis_update_connections.argtypes = [vp, ctypes.POINTER(CovisSlice), ci, ctypes.POINTER(CovisConnections)]
+        L.orbx_covis_keyframe_culling.argtypes = [vp, ctypes.POINTER(CovisSlice), ctypes.POINTER(CovisCulling)]
+        L.orbx_covis_last_timing.argtypes = [vp, vp, vp]
+        self._h = vp()
+        _check(L.orbx_covis_create(device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_covis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def UpdateConnections(self, map_slice, th=15, counter_capacity=None, conn_capacity=None):
+        """All lists of the slice in one call -> dict(counter_offset, conn_offset (Q+1); counter_kf, counter_weight: KFcounter in ascending rank;
+        n_max, kf_max (Q); conn_kf, conn_weight: mvpOrderedConnectedKeyFrames / mvOrderedWeights).  The capacities default to the worst case."""
+        keep = []
+        S, a = covis_marshal(map_slice, keep)
+        Q = S.num_lists
+        worst = Q + min(Q * S.num_keyframes, int(np.diff(a["obs_offset"])[a["list_point"]].sum()) if S.num_entries and (a["list_point"] < S.num_points).all() and
+                        (a["list_point"] >= 0).all() else 0)
+        cc, nc = int(worst if counter_capacity is None else counter_capacity), int(worst if conn_capacity is None else conn_capacity)
+        i4 = np.int32
+        o = dict(counter_offset=np.zeros(Q + 1, i4), counter_kf=np.zeros(max(cc, 1), i4), counter_weight=np.zeros(max(cc, 1), i4), n_max=np.zeros(max(Q, 1), i4),
+                 kf_max=np.zeros(max(Q, 1), i4), conn_offset=np.zeros(Q + 1, i4), conn_kf=np.zeros(max(nc, 1), i4), conn_weight=np.zeros(max(nc, 1), i4))
+        R = CovisConnections(o["counter_offset"].ctypes.data, o["counter_kf"].ctypes.data, o["counter_weight"].ctypes.data, cc, o["n_max"].ctypes.data, o["kf_max"].ctypes.data,
+                             o["conn_offset"].ctypes.data, o["conn_kf"].ctypes.data, o["conn_weight"].ctypes.data, nc)
+        _check(self._L.orbx_covis_update_connections(self._h, ctypes.byref(S), int(th), ctypes.byref(R)))
+        n, m = int(o["counter_offset"][Q]), int(o["conn_offset"][Q])
+        for k in ("counter_kf", "counter_weight"):
+            o[k] = o[k][:n]
+        for k in ("conn_kf", "conn_weight"):
+            o[k] = o[k][:m]
+        o["n_max"], o["kf_max"] = o["n_max"][:Q], o["kf_max"][:Q]
+        return o
+
+    def UpdateLocalKeyFrames(self, map_slice):
+        """The vote of Tracking::UpdateLocalKeyFrames: every list taken as a Frame's (list_kf = -1: no self-exclusion, bad keyframes are no candidates
+        for kf_max) -> dict(counter_offset, counter_kf, counter_weight, n_max, kf_max)"""
+        s = dict(map_slice)
+        s["list_kf"] = np.full(len(np.ascontiguousarray(map_slice["list_kf"]).reshape(-1)), -1, np.int32)
+        o = self.UpdateConnections(s)
+        return {k: o[k] for k in ("counter_offset", "counter_kf", "counter_weight", "n_max", "kf_max")}
+
+    def KeyFrameCulling(self, map_slice):
+        """The lists are vpLocalKeyFrames in order -> dict(n_mps, n_redundant (Q) int32, culled (Q) uint8; point_bad (M) uint8 and point_obs (M) int32
+        after the loop's erases)"""
+        keep = []
+        S, _ = covis_marshal(map_slice, keep)
+        Q, M = S.num_lists, S.num_points
+        o = dict(n_mps=np.zeros(max(Q, 1), np.int32), n_redundant=np.zeros(max(Q, 1), np.int32), culled=np.zeros(max(Q, 1), np.uint8), point_bad=np.zeros(max(M, 1), np.uint8),
+                 point_obs=np.zeros(max(M, 1), np.int32))
+        R = CovisCulling(*[o[k].ctypes.data for k in ("n_mps", "n_redundant", "culled", "point_bad", "point_obs")])
+        _check(self._L.orbx_covis_keyframe_culling(self._h, ctypes.byref(S), ctypes.byref(R)))
+        return dict(n_mps=o["n_mps"][:Q], n_redundant=o["n_redundant"][:Q], culled=o["culled"][:Q], point_bad=o["point_bad"][:M], point_obs=o["point_obs"][:M])
+
+    def last_timing(self):
+        """(device ms of the last call's chain, kernel launches)"""
+        ms, n = ctypes.c_float(), ctypes.c_int()
+        _check(self._L.orbx_covis_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value

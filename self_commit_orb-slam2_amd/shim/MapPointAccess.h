@@ -59,6 +59,16 @@ struct MapPointAccess : public MapPoint {
         std::unique_lock<std::mutex> lock(q->mMutexFeatures);
         for (std::map<KeyFrame *, size_t>::const_iterator it = q->mObservations.begin(); it != q->mObservations.end(); ++it) out.push_back(*it);
     }
+    // isBad() and GetObservations() in one visit (the covisibility gather, shim/Covisibility_hip.cc): the observers in the map's order; -> isBad
+    static bool BadAndObservations(MapPoint *p, std::vector<std::pair<KeyFrame *, size_t> > &out)
+    {
+        MapPointAccess *q = static_cast<MapPointAccess *>(p);
+        out.clear();
+        std::unique_lock<std::mutex> lock(q->mMutexFeatures);
+        std::unique_lock<std::mutex> lock2(q->mMutexPos);
+        for (std::map<KeyFrame *, size_t>::const_iterator it = q->mObservations.begin(); it != q->mObservations.end(); ++it) out.push_back(*it);
+        return q->mbBad;
+    }
     // isBad() and Observations() > 0 in one visit: 0 = bad, 1 = good without observations, 2 = good with
     static int GoodAndObserved(MapPoint *p)
     {
