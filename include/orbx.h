@@ -1686,6 +1686,105 @@ int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice *slice, co
 /* device time of the last call's chain (the host's decisions between culling rounds included) and its kernel launches */
 int orbx_covis_last_timing(orbx_covis *h, float *kernel_ms, int *launches);
 
+/* ----------------------------------------------------------------------------------
+ * Loop correction: the two passes of the loop closer that move the map.  orbx_loop_correct_sim3 is the Sim3 propagation of
+ * LoopClosing::CorrectLoop (reference src/LoopClosing.cc:617-716), orbx_loop_propagate_gba the map update after global bundle
+ * adjustment (:930-1003).  Stateless and synchronous: host arrays in, host arrays out, one launch chain and one wait per call;
+ * the handle has no capacities, its buffers grow.  Keyframes are slot numbers 0..num_keyframes-1; a pose is the 12 floats of the
+ * first three rows of the 4x4 Tcw, a Sim3 is 8 doubles q(x, y, z, w), t, s (the layout of orbx_essential_graph_problem.est).
+ * Float results are bit for bit those of the reference on the project's OpenCV stand-in: every 4x4 and 3x3 product is a float
+ * sum accumulated left to right over all its terms, the Sim3 arithmetic is g2o's in double, operation by operation.
+ *
+ * orbx_loop_correct_sim3.  The group = mvpCurrentConnectedKFs in the order in which the reference iterates CorrectedSim3 (a
+ * std::map<KeyFrame*, ...>: ascending pointer; the caller's order here), `current` = the position of mpCurrentKF in it, scw =
+ * mg2oScw.  Twc of the current keyframe is DERIVED on the device from its tcw by KeyFrame::SetPose's own steps (Rwc = Rcw^T,
+ * Ow = (-Rwc) * tcw), so tcw must be what the keyframe's last SetPose was given; ow is GetCameraCenter() as stored.  Lists:
+ * CSR over the group, list_point = GetMapPointMatches() with -1 for a NULL entry.  Points: point_done = mnCorrectedByKF ==
+ * mpCurrentKF->mnId already, point_ref = the slot of mpRefKF, ref_scale / top_scale as in orbx_mappoint_batch; CSR observation
+ * lists in the order of the observation map, never reordered.
+ *   noncorrected[g] = Sim3(Riw, tiw, 1); corrected[g] = Sim3(Ric, tic, 1) * scw with Tic = Tiw * Twc, or scw itself at `current`;
+ *   tiw[g] = [R | t / s] of corrected[g] (toRotationMatrix, t *= 1. / s, toCvSE3), ow_new[g] the centre SetPose derives from it;
+ *   scw_mat[g] = Converter::toCvMat(corrected[g]) = [sR | t], what orbx_fuse_search takes for SearchAndFuse.
+ *   A point is moved ONCE, by the first group position whose list holds it while it is neither bad nor done: pos =
+ *   corrected.inverse().map(noncorrected.map(double(P))) narrowed to float, corrected_by = that position (mnCorrectedReference
+ *   is that keyframe's id), -1 and the old position for an untouched point.  UpdateNormalAndDepth runs at that moment: group
+ *   keyframes at EARLIER positions have had their SetPose, so their centre (as an observer and as the reference keyframe) is
+ *   ow_new, every other centre is ow.  normal / max_dist / min_dist / updated as in orbx_mappoint_result (updated = moved and
+ *   observed; the rest 0 otherwise).
+ *
+ * orbx_loop_propagate_gba.  parent[i] = the slot of the spanning-tree parent, -1 for a member of mvpKeyFrameOrigins, -2 for a
+ * keyframe outside the tree (the walk never reaches it, nor its descendants).  in_gba = mnBAGlobalForKF == nLoopKF before the
+ * walk; tcw_gba = mTcwGBA where in_gba (and of the origins), ignored elsewhere.
+ *   tcw_gba, completed: a reached keyframe with in_gba == 0 and a parent gets (Tchild * Twc_parent) * TcwGBA_parent, both factors
+ *   of the first product from the poses before the update; everything else is returned as it came.  reached[i] = the walk
+ *   visits i (then mnBAGlobalForKF == nLoopKF, mTcwBefGBA = tcw and SetPose(tcw_gba) hold after it).
+ *   moved[p]: 0 untouched (bad, point_ref -1, or the reference keyframe not reached), 1 copied from pos_gba (point_in_gba),
+ *   2 re-projected: Rwc * (Rcw_bef * X + tcw_bef) + twc with Rwc, twc as SetPose(tcw_gba) stores them.
+ * ---------------------------------------------------------------------------------- */
+typedef struct orbx_loop orbx_loop;
+
+typedef struct orbx_loop_sim3_problem {  /* host memory */
+    int num_keyframes;
+    const float *tcw;                /* [num_keyframes][12]                                                              */
+    const float *ow;                 /* [num_keyframes][3]                                                               */
+    int num_group, current;
+    const int32_t *group_kf;         /* [num_group] distinct slots                                                       */
+    const double *scw;               /* [8]                                                                              */
+    int num_entries;
+    const int32_t *list_offset;      /* [num_group + 1]                                                                  */
+    const int32_t *list_point;       /* [num_entries] 0..num_points-1, or -1                                             */
+    int num_points, num_obs;
+    const float *pos;                /* [num_points][3]                                                                  */
+    const uint8_t *point_bad, *point_done;   /* [num_points]                                                             */
+    const int32_t *point_ref;        /* [num_points] 0..num_keyframes-1                                                  */
+    const float *ref_scale, *top_scale;      /* [num_points]                                                             */
+    const int32_t *obs_offset;       /* [num_points + 1]                                                                 */
+    const int32_t *obs_kf;           /* [num_obs] 0..num_keyframes-1                                                     */
+} orbx_loop_sim3_problem;
+
+typedef struct orbx_loop_sim3_result {   /* host memory; every pointer may be NULL */
+    double *noncorrected, *corrected;        /* [num_group][8]                                                           */
+    float *tiw;                      /* [num_group][12]                                                                  */
+    float *ow_new;                   /* [num_group][3]                                                                   */
+    float *scw_mat;                  /* [num_group][12]                                                                  */
+    float *pos;                      /* [num_points][3]                                                                  */
+    int32_t *corrected_by;           /* [num_points]                                                                     */
+    float *normal;                   /* [num_points][3]                                                                  */
+    float *max_dist, *min_dist;      /* [num_points]                                                                     */
+    uint8_t *updated;                /* [num_points]                                                                     */
+} orbx_loop_sim3_result;
+
+typedef struct orbx_loop_gba_problem {   /* host memory */
+    int num_keyframes;
+    const int32_t *parent;           /* [num_keyframes] slot, -1 origin, -2 not in the tree                              */
+    const float *tcw, *tcw_gba;      /* [num_keyframes][12]                                                              */
+    const uint8_t *in_gba;           /* [num_keyframes]                                                                  */
+    int num_points;
+    const float *pos, *pos_gba;      /* [num_points][3]                                                                  */
+    const uint8_t *point_in_gba, *point_bad; /* [num_points]                                                             */
+    const int32_t *point_ref;        /* [num_points] slot, or -1                                                         */
+} orbx_loop_gba_problem;
+
+typedef struct orbx_loop_gba_result {    /* host memory; every pointer may be NULL */
+    float *tcw_gba;                  /* [num_keyframes][12]                                                              */
+    uint8_t *reached;                /* [num_keyframes]                                                                  */
+    float *pos;                      /* [num_points][3]                                                                  */
+    uint8_t *moved;                  /* [num_points]                                                                     */
+} orbx_loop_gba_result;
+
+/* ORBX_ERR_ARG: NULL out, device out of range; ORBX_ERR_NODEVICE without a device */
+int orbx_loop_create(int device, orbx_loop **out);
+void orbx_loop_destroy(orbx_loop *h);
+/* ORBX_ERR_ARG, before the handle is looked at and before anything is launched: a NULL required array, an offset array that does
+ * not start at 0, decreases or does not end at its total, a slot or point index out of range, two group entries with one slot,
+ * `current` out of range, a scale of scw that is not positive, a pose, centre or point that is not finite.  `result` may be NULL. */
+int orbx_loop_correct_sim3(orbx_loop *h, const orbx_loop_sim3_problem *problem, const orbx_loop_sim3_result *result);
+/* ORBX_ERR_ARG likewise: a NULL required array, a parent or point_ref out of range, a keyframe that is its own ancestor, no
+ * origin, a pose or point that is not finite */
+int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem *problem, const orbx_loop_gba_result *result);
+/* device time of the last call's launch chain and its kernel launches */
+int orbx_loop_last_timing(orbx_loop *h, float *device_ms, int *launches);
+
 
 #ifdef __cplusplus
 }

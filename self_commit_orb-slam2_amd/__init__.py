@@ -2852,3 +2852,124 @@ class Covisibility:
         ms, n = ctypes.c_float(), ctypes.c_int()
         _check(self._L.orbx_covis_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+class LoopSim3Problem(ctypes.Structure):
+    _fields_ = [("num_keyframes", ctypes.c_int), ("tcw", ctypes.c_void_p), ("ow", ctypes.c_void_p), ("num_group", ctypes.c_int), ("current", ctypes.c_int),
+                ("group_kf", ctypes.c_void_p), ("scw", ctypes.c_void_p), ("num_entries", ctypes.c_int), ("list_offset", ctypes.c_void_p), ("list_point", ctypes.c_void_p),
+                ("num_points", ctypes.c_int), ("num_obs", ctypes.c_int), ("pos", ctypes.c_void_p), ("point_bad", ctypes.c_void_p), ("point_done", ctypes.c_void_p),
+                ("point_ref", ctypes.c_void_p), ("ref_scale", ctypes.c_void_p), ("top_scale", ctypes.c_void_p), ("obs_offset", ctypes.c_void_p), ("obs_kf", ctypes.c_void_p)]
+
+
+class LoopSim3Result(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("noncorrected", "corrected", "tiw", "ow_new", "scw_mat", "pos", "corrected_by", "normal", "max_dist", "min_dist", "updated")]
+
+
+class LoopGbaProblem(ctypes.Structure):
+    _fields_ = [("num_keyframes", ctypes.c_int), ("parent", ctypes.c_void_p), ("tcw", ctypes.c_void_p), ("tcw_gba", ctypes.c_void_p), ("in_gba", ctypes.c_void_p),
+                ("num_points", ctypes.c_int), ("pos", ctypes.c_void_p), ("pos_gba", ctypes.c_void_p), ("point_in_gba", ctypes.c_void_p), ("point_bad", ctypes.c_void_p),
+                ("point_ref", ctypes.c_void_p)]
+
+
+class LoopGbaResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("tcw_gba", "reached", "pos", "moved")]
+
+
+_LOOP_SIM3_ARRAYS = (("tcw", np.float32), ("ow", np.float32), ("group_kf", np.int32), ("scw", np.float64), ("list_offset", np.int32), ("list_point", np.int32),
+                     ("pos", np.float32), ("point_bad", np.uint8), ("point_done", np.uint8), ("point_ref", np.int32), ("ref_scale", np.float32), ("top_scale", np.float32),
+                     ("obs_offset", np.int32), ("obs_kf", np.int32))
+_LOOP_GBA_ARRAYS = (("parent", np.int32), ("tcw", np.float32), ("tcw_gba", np.float32), ("in_gba", np.uint8), ("pos", np.float32), ("pos_gba", np.float32),
+                    ("point_in_gba", np.uint8), ("point_bad", np.uint8), ("point_ref", np.int32))
+LOOP_SIM3_FIELDS = (("noncorrected", np.float64, "G", 8), ("corrected", np.float64, "G", 8), ("tiw", np.float32, "G", 12), ("ow_new", np.float32, "G", 3),
+                    ("scw_mat", np.float32, "G", 12), ("pos", np.float32, "M", 3), ("corrected_by", np.int32, "M", 1), ("normal", np.float32, "M", 3),
+                    ("max_dist", np.float32, "M", 1), ("min_dist", np.float32, "M", 1), ("updated", np.uint8, "M", 1))
+LOOP_GBA_FIELDS = (("tcw_gba", np.float32, "n", 12), ("reached", np.uint8, "n", 1), ("pos", np.float32, "M", 3), ("moved", np.uint8, "M", 1))
+
+
+def loop_marshal(problem, keep):
+    """orbx_loop_sim3_problem (a dict with "scw": the keys of _LOOP_SIM3_ARRAYS and "current") or orbx_loop_gba_problem (the keys of _LOOP_GBA_ARRAYS) of a
+    dict of arrays -> (struct, arrays); the converted arrays are appended to `keep`, which must outlive the call"""
+    sim3 = "scw" in problem
+    a = {k: np.ascontiguousarray(problem[k], dt).reshape(-1) for k, dt in (_LOOP_SIM3_ARRAYS if sim3 else _LOOP_GBA_ARRAYS)}
+    keep.append(a)
+    p = {k: v.ctypes.data for k, v in a.items()}
+    if sim3:
+        NK, G, S, M, T = len(a["tcw"]) // 12, len(a["group_kf"]), len(a["list_point"]), len(a["point_bad"]), len(a["obs_kf"])
+        if len(a["tcw"]) != 12 * NK or len(a["ow"]) != 3 * NK or len(a["scw"]) != 8 or len(a["list_offset"]) != G + 1 or len(a["pos"]) != 3 * M or len(a["obs_offset"]) != M + 1 or \
+                any(len(a[k]) != M for k in ("point_done", "point_ref", "ref_scale", "top_scale")):
+            raise ValueError("loop correction problem: array sizes do not agree")
+        return LoopSim3Problem(NK, p["tcw"], p["ow"], G, int(problem["current"]), p["group_kf"], p["scw"], S, p["list_offset"], p["list_point"], M, T, p["pos"], p["point_bad"],
+                               p["point_done"], p["point_ref"], p["ref_scale"], p["top_scale"], p["obs_offset"], p["obs_kf"]), a
+    n, M = len(a["parent"]), len(a["point_bad"])
+    if len(a["tcw"]) != 12 * n or len(a["tcw_gba"]) != 12 * n or len(a["in_gba"]) != n or len(a["pos"]) != 3 * M or len(a["pos_gba"]) != 3 * M or \
+            len(a["point_in_gba"]) != M or len(a["point_ref"]) != M:
+        raise ValueError("loop correction problem: array sizes do not agree")
+    return LoopGbaProblem(n, p["parent"], p["tcw"], p["tcw_gba"], p["in_gba"], M, p["pos"], p["pos_gba"], p["point_in_gba"], p["point_bad"], p["point_ref"]), a
+
+
+def _loop_outputs(fields, sizes):
+    o = {k: np.zeros((max(sizes[s], 1), w) if w > 1 else max(sizes[s], 1), dt) for k, dt, s, w in fields}
+    return o, (lambda: {k: o[k][:sizes[s]] for k, dt, s, w in fields})
+
+
+class LoopCorrection:
+    """The two passes of the loop closer that move the map, on the device: CorrectLoop = the Sim3 propagation of LoopClosing::CorrectLoop (reference
+    src/LoopClosing.cc:617-716: CorrectedSim3 / NonCorrectedSim3, every point of the group moved once by the first keyframe that reaches it, its
+    UpdateNormalAndDepth, the SE3 poses), PropagateGBA = the map update after global BA (:930-1003: poses through the spanning tree, then every point).
+    Keyframes are slot numbers; floats are bit for bit the reference's on the project's OpenCV stand-in.  Replace, AddObservation, UpdateConnections
+    and the mutexes stay with the caller."""
+
+    def __init__(self, device=0):
+        self._L = load_library()
+        L = self._L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.orbx_loop_create.argtypes = [ci, ctypes.POINTER(vp)]
+        L.orbx_loop_destroy.argtypes = [vp]
+        L.orbx_loop_destroy.restype = None
+        L.orbx_loop_correct_sim3.argtypes = [vp, ctypes.POINTER(LoopSim3Problem), ctypes.POINTER(LoopSim3Result)]
+        L.orbx_loop_propagate_gba.argtypes = [vp, ctypes.POINTER(LoopGbaProblem), ctypes.POINTER(LoopGbaResult)]
+        L.orbx_loop_last_timing.argtypes = [vp, vp, vp]
+        self._h = vp()
+        _check(L.orbx_loop_create(device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_loop_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def CorrectLoop(self, problem):
+        """problem: dict(tcw (NK,12), ow (NK,3), group_kf (G), current, scw (8), list_offset (G+1), list_point, pos (M,3), point_bad, point_done, point_ref,
+        ref_scale, top_scale (M), obs_offset (M+1), obs_kf) -> dict(noncorrected, corrected (G,8) float64; tiw (G,12), ow_new (G,3), scw_mat (G,12); pos
+        (M,3), corrected_by (M) int32 = the group position that moved the point or -1, normal (M,3), max_dist, min_dist, updated (M))"""
+        keep = []
+        P, _ = loop_marshal(problem, keep)
+        if not isinstance(P, LoopSim3Problem):
+            raise ValueError("CorrectLoop takes a Sim3 problem (with scw)")
+        o, cut = _loop_outputs(LOOP_SIM3_FIELDS, dict(G=P.num_group, M=P.num_points))
+        R = LoopSim3Result(*[o[k].ctypes.data for k, _, _, _ in LOOP_SIM3_FIELDS])
+        _check(self._L.orbx_loop_correct_sim3(self._h, ctypes.byref(P), ctypes.byref(R)))
+        return cut()
+
+    def PropagateGBA(self, problem):
+        """problem: dict(parent (n) slot / -1 origin / -2 outside the tree, tcw, tcw_gba (n,12), in_gba (n), pos, pos_gba (M,3), point_in_gba, point_bad (M),
+        point_ref (M) slot or -1) -> dict(tcw_gba (n,12) completed, reached (n), pos (M,3), moved (M): 0 untouched, 1 mPosGBA, 2 re-projected)"""
+        keep = []
+        P, _ = loop_marshal(problem, keep)
+        if not isinstance(P, LoopGbaProblem):
+            raise ValueError("PropagateGBA takes a global BA problem (without scw)")
+        o, cut = _loop_outputs(LOOP_GBA_FIELDS, dict(n=P.num_keyframes, M=P.num_points))
+        R = LoopGbaResult(*[o[k].ctypes.data for k, _, _, _ in LOOP_GBA_FIELDS])
+        _check(self._L.orbx_loop_propagate_gba(self._h, ctypes.byref(P), ctypes.byref(R)))
+        return cut()
+
+    def last_timing(self):
+        """(device ms of the last call's launch chain, kernel launches)"""
+        ms, n = ctypes.c_float(), ctypes.c_int()
+        _check(self._L.orbx_loop_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "orbx_internal.h"
+#include "orbx_normal_depth.h"
 
 namespace {
 
@@ -54,36 +55,13 @@ __device__ __forceinline__ int mp_dist(const uint4 &a0, const uint4 &a1, const u
     return d;
 }
 
-// u = (pos - Ow) / |pos - Ow| as the header spells it (no contraction: the file is compiled with -ffp-contract=off; f64 sqrt and division are IEEE)
-__device__ __forceinline__ void mp_unit(const float *__restrict__ pos, const float *__restrict__ ow, float *u)
-{
-    const float v0 = pos[0] - ow[0], v1 = pos[1] - ow[1], v2 = pos[2] - ow[2];
-    double s = 0.0;
-    s = s + (double)v0 * (double)v0;
-    s = s + (double)v1 * (double)v1;
-    s = s + (double)v2 * (double)v2;
-    s = sqrt(s);
-    u[0] = (float)((double)v0 / s); u[1] = (float)((double)v1 / s); u[2] = (float)((double)v2 / s);
-}
+// (mp_unit, mp_normal_component and mp_depth, the arithmetic the header spells, live in orbx_normal_depth.h: the loop corrector shares them)
 
 // the ordered part, after the unit vectors are visible to the workgroup: threads 0..2 sum one component each over the list, thread 3 the distances
 __device__ __forceinline__ void mp_normal_depth(const MpDev &D, int p, int n, const float *unit, int t)
 {
-    if (t < 3) {
-        float acc = 0.0f;
-        for (int o = 0; o < n; o++) acc = acc + unit[o * 3 + t];
-        D.normal[(size_t)p * 3 + t] = (float)((double)acc / (double)n);
-    } else if (t == 3) {
-        const float v0 = D.pos[(size_t)p * 3] - D.refc[(size_t)p * 3], v1 = D.pos[(size_t)p * 3 + 1] - D.refc[(size_t)p * 3 + 1], v2 = D.pos[(size_t)p * 3 + 2] - D.refc[(size_t)p * 3 + 2];
-        double s = 0.0;
-        s = s + (double)v0 * (double)v0;
-        s = s + (double)v1 * (double)v1;
-        s = s + (double)v2 * (double)v2;
-        const float dist = (float)sqrt(s);
-        const float mx = dist * D.rsc[p];
-        D.maxD[p] = mx;
-        D.minD[p] = mx / D.tsc[p];
-    }
+    if (t < 3) D.normal[(size_t)p * 3 + t] = mp_normal_component(unit, n, t);
+    else if (t == 3) mp_depth(D.pos + (size_t)p * 3, D.refc + (size_t)p * 3, D.rsc[p], D.tsc[p], &D.maxD[p], &D.minD[p]);
 }
 
 __device__ __forceinline__ unsigned mp_wave_min(unsigned key)

@@ -69,6 +69,31 @@ struct MapPointAccess : public MapPoint {
         for (std::map<KeyFrame *, size_t>::const_iterator it = q->mObservations.begin(); it != q->mObservations.end(); ++it) out.push_back(*it);
         return q->mbBad;
     }
+    // what LoopClosing::CorrectLoop and MapPoint::UpdateNormalAndDepth read of a point, in one visit (the loop correction gather,
+    // shim/LoopClosing_hip.cc): the observers in the map's order, mpRefKF and the position; -> isBad
+    static bool BadObservationsRefAndPos(MapPoint *p, std::vector<std::pair<KeyFrame *, size_t> > &out, KeyFrame *&ref, float pos[3])
+    {
+        MapPointAccess *q = static_cast<MapPointAccess *>(p);
+        out.clear();
+        std::unique_lock<std::mutex> lock(q->mMutexFeatures);
+        std::unique_lock<std::mutex> lock2(q->mMutexPos);
+        for (std::map<KeyFrame *, size_t>::const_iterator it = q->mObservations.begin(); it != q->mObservations.end(); ++it) out.push_back(*it);
+        ref = q->mpRefKF;
+        for (int c = 0; c < 3; c++) pos[c] = q->mWorldPos.at<float>(c);
+        return q->mbBad;
+    }
+    // the three stores that end MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:514-520); a point that went bad meanwhile is left alone
+    static void StoreNormalAndDepth(MapPoint *p, const float nrm[3], float maxD, float minD)
+    {
+        MapPointAccess *q = static_cast<MapPointAccess *>(p);
+        cv::Mat n(3, 1, CV_32F);
+        for (int c = 0; c < 3; c++) n.at<float>(c) = nrm[c];
+        std::unique_lock<std::mutex> lock(q->mMutexPos);
+        if (q->mbBad) return;
+        q->mfMaxDistance = maxD;
+        q->mfMinDistance = minD;
+        q->mNormalVector = n;
+    }
     // isBad() and Observations() > 0 in one visit: 0 = bad, 1 = good without observations, 2 = good with
     static int GoodAndObserved(MapPoint *p)
     {
