@@ -1786,6 +1786,85 @@ int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem *problem, 
 int orbx_loop_last_timing(orbx_loop *h, float *device_ms, int *launches);
 
 
+/* ------------------------------------------------------------------------------------
+ * Image front end  ==  what the reference does to a camera image BEFORE ORBextractor::operator():
+ *   colour to grey     Tracking::GrabImageMonocular / GrabImageStereo / GrabImageRGBD (src/Tracking.cc:250-278, 311-326, 369-384):
+ *                      cvtColor(RGB2GRAY / BGR2GRAY / RGBA2GRAY / BGRA2GRAY) by mbRGB
+ *   rectification      Examples/Stereo/stereo_euroc.cc:124-134, 181-188: cv::initUndistortRectifyMap once, cv::remap(INTER_LINEAR) per image
+ * A batch of frames in device memory goes in; grey, rectified frames come out in a handle-owned device buffer in the padded layout
+ * orbx_extract_batch_device prefers (stride >= round_up(width, 4) + 12, frame_pitch = stride * height, every pad byte 0).
+ *
+ * Arithmetic (the project's pinned choice; PARITY WITH OpenCV IS UNPINNED - the OpenCV version and its SIMD path, the LU inverse of
+ * initUndistortRectifyMap and remap's weight fix-up are not reproduced bit for bit; tests/imgprep_ref.py is the
+ * restatement the device is held to, byte for byte):
+ *   grey    (c[R] r + c[G] g + c[B] b + (1 << (shift - 1))) >> shift in 32-bit unsigned; the alpha byte of 4-channel input is ignored.
+ *   maps    once per map: sx = rint(map_x * 32), sy = rint(map_y * 32) (half to even; |s| clamped to 2^30, which changes no result);
+ *           ix = saturate_int16(sx >> 5) (arithmetic shift), fx = sx & 31; iy, fy likewise.
+ *   remap   taps p00 = src(iy, ix), p01 = src(iy, ix + 1), p10 = src(iy + 1, ix), p11 = src(iy + 1, ix + 1), a tap outside the image
+ *           reads 0 (BORDER_CONSTANT, value 0: cv::remap's default);
+ *           out = ((32 - fx)(32 - fy) p00 + fx (32 - fy) p01 + (32 - fx) fy p10 + fx fy p11 + 512) >> 10.
+ *   ORDER   colour input that is also rectified is converted to grey FIRST (per tap) and the grey image is remapped, in one launch:
+ *           the reference's examples rectify grey images.  Remapping the colour planes and converting afterwards rounds differently
+ *           and is not offered.
+ * ---------------------------------------------------------------------------------- */
+typedef struct orbx_image_prep orbx_image_prep;
+
+typedef struct orbx_image_prep_config {
+    int device;                 /* HIP device ordinal                                                             */
+    int max_width, max_height;  /* largest image accepted (each 1..16384)                                         */
+    int max_batch;              /* most frames per call (>= 1)                                                    */
+    /* 8-bit fixed-point grey weights of R, G, B.  All zero selects OpenCV 4.x's 9798, 19235, 3735 with shift 15; OpenCV 3.x used
+     * 4899, 9617, 1868 with shift 14.  The sum must be 1 << gray_shift and gray_shift must lie in 8..16 (ORBX_ERR_ARG otherwise). */
+    uint16_t gray_coef[3];
+    uint16_t gray_shift;
+} orbx_image_prep_config;
+
+/* ORBX_ERR_ARG: NULL argument, a size out of range, bad grey weights, device out of range; ORBX_ERR_NODEVICE without a device */
+int orbx_image_prep_create(const orbx_image_prep_config *cfg, orbx_image_prep **out);
+void orbx_image_prep_destroy(orbx_image_prep *h);
+
+/* cv::initUndistortRectifyMap(K, D, R, Pnew(0:3, 0:3), (width, height), CV_32FC1): HOST code in double, no handle and no device.
+ * K, R, Pnew row major; D = k1 k2 p1 p2 [k3] (num_d = 4 or 5); map_x / map_y hold width * height floats, rows `width` apart.
+ *   iR = inverse(Pnew * R) by the cofactor formula (OpenCV: LU - the last bits are unpinned);
+ *   row i: _x = i iR[1] + iR[2], _y = i iR[4] + iR[5], _w = i iR[7] + iR[8]; column j: w = 1 / _w, x = _x w, y = _y w, x2 = x x, y2 = y y,
+ *   r2 = x2 + y2, _2xy = 2 x y, kr = 1 + ((k3 r2 + k2) r2 + k1) r2, u = fx (x kr + p1 _2xy + p2 (r2 + 2 x2)) + u0,
+ *   v = fy (y kr + p1 (r2 + 2 y2) + p2 _2xy) + v0, stored as float; then _x += iR[0], _y += iR[3], _w += iR[6] (incremental, as OpenCV's loop).
+ * ORBX_ERR_ARG: a NULL pointer, num_d not 4 or 5, an empty size, Pnew * R singular or not finite. */
+int orbx_rectify_maps(const double K[9], const double *D, int num_d, const double R[9], const double Pnew[9], int width, int height,
+                      float *map_x, float *map_y);
+
+/* The two CV_32FC1 maps the reference hands to cv::remap, for `side` 0 (left) or 1 (right): uploaded and converted ONCE (k_maps_fixed) to
+ * 6 bytes per pixel, ix | iy << 16 and fx | fy << 5.  Rows are map_stride_floats apart.  A value that is not finite is the caller's error:
+ * ORBX_ERR_ARG, found in a host pass before anything is uploaded.  Returns when the maps are in place. */
+int orbx_image_prep_set_maps(orbx_image_prep *h, int side, const float *map_x, const float *map_y, int map_stride_floats, int width, int height);
+
+/* `batch` frames in DEVICE memory, frame f at src_dev + f * src_pitch, rows src_stride bytes apart, `channels` (1, 3 or 4) interleaved
+ * bytes per pixel; rgb_order 1: the first byte is R, 0: B (ignored for one channel).  rectify_side -1: no rectification, 0 / 1: remap
+ * through that side's maps, whose size must be width x height.  One channel without rectification is a plain copy into the padded
+ * layout.  The work is enqueued on the stream of `consumer` (orbx_extractor_stream_internal, as orbx_frame_finish_device does), so an
+ * orbx_extract_batch_device(consumer, <the results below>, ...) that follows is ordered behind it with no wait in between; consumer ==
+ * NULL: the handle's own stream.  Nothing is waited for.  Sources whose pointer, stride and pitch are multiples of 4 take the dword
+ * path, every other source the byte path - same results. */
+int orbx_image_prep_batch_device(orbx_image_prep *h, orbx_extractor *consumer, const void *src_dev, int batch, int width, int height,
+                                 int channels, int rgb_order, int src_stride, size_t src_pitch, int rectify_side);
+/* The last call's output: frame f at *images_dev + f * *frame_pitch (ORBX_ERR_STATE before the first call). */
+int orbx_image_prep_results_device(orbx_image_prep *h, const void **images_dev, int *stride, size_t *frame_pitch);
+int orbx_image_prep_sync(orbx_image_prep *h);
+/* Host frames (rows `stride` bytes apart) into a handle-owned device source buffer, for callers without a device allocator (tests, the
+ * shim), like orbx_upload_frames.  dev_stride 0: rows padded to a multiple of 16 bytes; otherwise the row pitch to use (>= width *
+ * channels).  dev_offset (0..15) shifts the whole buffer by that many bytes - a caller's own sources are not always aligned, and this
+ * is how the byte path is reached through this entry point.  *src_pitch = *src_stride * height.  Returns when the copy is complete. */
+int orbx_image_prep_upload(orbx_image_prep *h, const uint8_t *const *images, int batch, int width, int height, int channels, int stride,
+                           int dev_stride, int dev_offset, const void **src_dev, int *src_stride, size_t *src_pitch);
+/* Wait for the last batch and copy its first `batch` frames to the host: frame f at out + f * out_stride * height, width bytes per row. */
+int orbx_image_prep_download(orbx_image_prep *h, int batch, int width, int height, uint8_t *out, int out_stride);
+/* The synchronous form (upload + batch + download): host frames in, host frames out (frame f at out + f * out_stride * height, width bytes per row written). */
+int orbx_image_prep_run(orbx_image_prep *h, const uint8_t *const *images, int batch, int width, int height, int channels, int rgb_order,
+                        int stride, int rectify_side, uint8_t *out, int out_stride);
+/* device time of the last call's kernel (HIP events on the stream it ran on) and its kernel launches */
+int orbx_image_prep_last_timing(orbx_image_prep *h, float *device_ms, int *launches);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -2973,3 +2973,134 @@ class LoopCorrection:
         ms, n = ctypes.c_float(), ctypes.c_int()
         _check(self._L.orbx_loop_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+# ------------------------------------------------------------------------------------------------
+# Image front end: colour to grey and stereo rectification (csrc/orbx_image.hip)
+# ------------------------------------------------------------------------------------------------
+class ImagePrepConfig(ctypes.Structure):
+    """orbx_image_prep_config (include/orbx.h)."""
+    _fields_ = [("device", ctypes.c_int), ("max_width", ctypes.c_int), ("max_height", ctypes.c_int), ("max_batch", ctypes.c_int),
+                ("gray_coef", ctypes.c_uint16 * 3), ("gray_shift", ctypes.c_uint16)]
+
+
+GRAY_COEF_CV4 = ((9798, 19235, 3735), 15)      # R, G, B and the shift of OpenCV 4.x's 8-bit cvtColor (the default)
+GRAY_COEF_CV3 = ((4899, 9617, 1868), 14)       # ... of OpenCV 3.x
+
+
+def _bind_image_prep(L):
+    vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    L.orbx_image_prep_create.argtypes = [ctypes.POINTER(ImagePrepConfig), ctypes.POINTER(vp)]
+    L.orbx_image_prep_destroy.argtypes = [vp]
+    L.orbx_image_prep_destroy.restype = None
+    L.orbx_rectify_maps.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp]
+    L.orbx_image_prep_set_maps.argtypes = [vp, ci, vp, vp, ci, ci, ci]
+    L.orbx_image_prep_batch_device.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, sz, ci]
+    L.orbx_image_prep_results_device.argtypes = [vp, vp, vp, vp]
+    L.orbx_image_prep_sync.argtypes = [vp]
+    L.orbx_image_prep_upload.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
+    L.orbx_image_prep_download.argtypes = [vp, ci, ci, ci, vp, ci]
+    L.orbx_image_prep_run.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci]
+    L.orbx_image_prep_last_timing.argtypes = [vp, vp, vp]
+    return L
+
+
+def rectify_maps(K, D, R, P, w, h):
+    """cv::initUndistortRectifyMap(K, D, R, P[:3, :3], (w, h), CV_32FC1) -> (map_x, map_y), float32 (h, w): host code in double, no device
+    (orbx_rectify_maps).  D = k1 k2 p1 p2 [k3]; P may be the 3 x 4 projection matrix of the calibration file."""
+    L = _bind_image_prep(load_library())
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(3, 3))
+    P = np.ascontiguousarray(np.asarray(P, np.float64).reshape(3, -1)[:, :3])
+    D = np.ascontiguousarray(np.asarray(D, np.float64).reshape(-1))
+    mx, my = np.empty((max(h, 0), max(w, 0)), np.float32), np.empty((max(h, 0), max(w, 0)), np.float32)
+    _check(L.orbx_rectify_maps(_ptr(K), _ptr(D), len(D), _ptr(R), _ptr(P), w, h, _ptr(mx), _ptr(my)))
+    return mx, my
+
+
+class ImagePrep:
+    """What the reference does to a camera image in front of ORBextractor::operator(), on the device: cvtColor to grey (Tracking::GrabImage*,
+    src/Tracking.cc:250-278, 311-326, 369-384) and cv::remap through the maps of cv::initUndistortRectifyMap (Examples/Stereo/stereo_euroc.cc:124-134,
+    181-188).  The grey, rectified frames land in a device buffer in the padded layout ORBextractor.run_device prefers.  Colour frames that are also
+    rectified are converted to grey first, then remapped (one launch).  Parity with OpenCV is unpinned; tests/imgprep_ref.py restates the arithmetic."""
+
+    def __init__(self, max_width, max_height, max_batch, gray_coef=None, gray_shift=0, device=0):
+        self._L = _bind_image_prep(load_library())
+        cfg = ImagePrepConfig(device, max_width, max_height, max_batch)
+        if gray_coef is not None:
+            for i in range(3):
+                cfg.gray_coef[i] = int(gray_coef[i])
+        cfg.gray_shift = int(gray_shift)
+        self._h = ctypes.c_void_p()
+        _check(self._L.orbx_image_prep_create(ctypes.byref(cfg), ctypes.byref(self._h)))
+        self.max_batch = max_batch
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.orbx_image_prep_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_maps(self, side, mx, my):
+        """The two CV_32FC1 maps of `side` (0 left, 1 right), converted once to fixed point on the device."""
+        mx, my = np.ascontiguousarray(mx, np.float32), np.ascontiguousarray(my, np.float32)
+        if mx.ndim != 2 or mx.shape != my.shape:
+            raise ValueError("set_maps: two float maps of one 2-d shape")
+        _check(self._L.orbx_image_prep_set_maps(self._h, side, _ptr(mx), _ptr(my), mx.shape[1], mx.shape[1], mx.shape[0]))
+
+    @staticmethod
+    def _frames(images):
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+        shp = imgs[0].shape
+        if len(shp) not in (2, 3) or any(im.shape != shp for im in imgs):
+            raise ValueError("frames of one shape (H, W) or (H, W, C)")
+        return imgs, shp[1], shp[0], (1 if len(shp) == 2 else shp[2])
+
+    def upload(self, images, dev_stride=0, dev_offset=0):
+        """Host frames (H, W) or (H, W, C) into the handle's device source buffer -> (pointer, stride, pitch, (B, W, H, C))"""
+        imgs, W, H, C = self._frames(images)
+        arr = (ctypes.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        dev, st, fp = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_size_t()
+        _check(self._L.orbx_image_prep_upload(self._h, arr, len(imgs), W, H, C, W * C, dev_stride, dev_offset, ctypes.byref(dev), ctypes.byref(st), ctypes.byref(fp)))
+        return dev, st.value, fp.value, (len(imgs), W, H, C)
+
+    def run_device(self, ext, src, stride, pitch, shape, rgb=True, rectify=None):
+        """Enqueue one batch on `ext`'s stream (None: the handle's own); nothing is waited for.  Follow it with
+        ext.run_device(*prep.results_device(), (B, W, H)): the extraction is ordered behind it."""
+        B, W, H, C = shape
+        _check(self._L.orbx_image_prep_batch_device(self._h, ext._h if ext is not None else None, src, B, W, H, C, 1 if rgb else 0, stride, pitch,
+                                                    -1 if rectify is None else int(rectify)))
+
+    def results_device(self):
+        """(device pointer, stride, frame pitch) of the last batch's grey frames"""
+        dev, st, fp = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_size_t()
+        _check(self._L.orbx_image_prep_results_device(self._h, ctypes.byref(dev), ctypes.byref(st), ctypes.byref(fp)))
+        return dev, st.value, fp.value
+
+    def sync(self):
+        _check(self._L.orbx_image_prep_sync(self._h))
+
+    def download(self, batch, width, height):
+        """Wait for the last batch and return its grey frames (batch, height, width) without their padding"""
+        out = np.empty((batch, height, width), np.uint8)
+        _check(self._L.orbx_image_prep_download(self._h, batch, width, height, _ptr(out), width))
+        return out
+
+    def run(self, images, rgb=True, rectify=None):
+        """The synchronous form: frames (H, W) or (H, W, 3 / 4) uint8 -> grey (B, H, W) uint8"""
+        imgs, W, H, C = self._frames(images)
+        arr = (ctypes.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        out = np.empty((len(imgs), H, W), np.uint8)
+        _check(self._L.orbx_image_prep_run(self._h, arr, len(imgs), W, H, C, 1 if rgb else 0, W * C, -1 if rectify is None else int(rectify), _ptr(out), W))
+        return out
+
+    def last_timing(self):
+        """(device ms of the last call's kernel, kernel launches)"""
+        ms, n = ctypes.c_float(), ctypes.c_int()
+        _check(self._L.orbx_image_prep_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
