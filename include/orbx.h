@@ -1865,6 +1865,75 @@ int orbx_image_prep_run(orbx_image_prep *h, const uint8_t *const *images, int ba
 int orbx_image_prep_last_timing(orbx_image_prep *h, float *device_ms, int *launches);
 
 
+/* ------------------------------------------------------------------------------------
+ * Vocabulary training  ==  DBoW2::TemplatedVocabulary<FORB::TDescriptor,FORB>::create(training_features, k, L, weighting, scoring)
+ * (reference Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:557-587): HKmeansStep (:641-819), initiateClustersKMpp (:832-913),
+ * FORB::meanValue / FORB::distance (FORB.cpp:28-101), createWords (:917-938) and setNodeWeights (:942-996) for 256-bit descriptors, one
+ * level of the tree at a time for all its nodes.  Three stated differences:
+ *   1. random draws: the reference consumes rand() lazily in depth-first order; here draw(seed, slot, j) is the top 53 bits r of
+ *      splitmix64's output function chained over the caller's seed, the heap index of the node being split in the complete k-ary tree
+ *      (root 0, child c of slot s is s * k + c + 1) and the draw number j inside the node.  The first centre of a node with n features is
+ *      min(n - 1, floor((r * 2^-53) * n)); centre j >= 1 uses cut_d = ((r + 1) * 2^-53) * dist_sum;
+ *   2. a cluster that receives no feature in an assignment pass keeps its previous centre (the reference reads a released cv::Mat there);
+ *      its child node is still created, a word with Ni = 0 and weight 0;
+ *   3. max_iterations (>= 2) caps the assignment passes per node (the reference has none); the summary counts the nodes that hit it.
+ * Everything else is literal: stable feature order inside a node, min_dists against the last centre only, the first feature whose
+ * running sum reaches cut_d, D(x) not D(x)^2, dist_sum == 0 ends the seeding early, one cluster per feature where n <= k, strict '<' in
+ * the assignment, the mean's tie sets the bit, recursion only below level L into children with more than one feature, node ids in the
+ * reference's depth-first order, word ids by node id, Ni from the real descent, log() from the host's libm on device-counted Ni.
+ * ---------------------------------------------------------------------------------- */
+#define ORBX_VOC_MAX_K 32
+#define ORBX_VOC_MAX_L 10
+typedef struct orbx_voc_trainer orbx_voc_trainer;
+typedef struct orbx_voc_train_params {
+    uint64_t seed;
+    int weighting;        /* DBoW2::WeightingType: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY */
+    int max_iterations;   /* >= 2 */
+} orbx_voc_train_params;
+typedef struct orbx_voc_train_summary {
+    int num_nodes, num_words;
+    int unconverged_nodes;                       /* nodes whose association still changed in pass max_iterations */
+    int passes_per_level[ORBX_VOC_MAX_L];        /* assignment passes run for level l + 1 (the most any of its nodes needed; 0: no node with n > k) */
+} orbx_voc_train_summary;
+/* ORBX_ERR_ARG, before a device is looked for: k outside 2..ORBX_VOC_MAX_K, L outside 1..ORBX_VOC_MAX_L, a complete tree of 2^31 nodes
+ * or more, max_descriptors outside 1..2^26, max_images < 1; then ORBX_ERR_NODEVICE without a device. */
+int orbx_voc_trainer_create(int device, int k, int L, int max_descriptors, int max_images, orbx_voc_trainer **out);
+void orbx_voc_trainer_destroy(orbx_voc_trainer *h);
+/* Appends num_images images from host arrays: counts[i] descriptors of 32 bytes each, image after image.  ORBX_ERR_CAPACITY (nothing
+ * appended) beyond max_descriptors / max_images. */
+int orbx_voc_trainer_add(orbx_voc_trainer *h, const uint8_t *descriptors, const int32_t *counts, int num_images);
+/* Appends every frame of the extractor's last batch as one image each: the descriptors are read where the extractor left them on the
+ * device, on its stream; nothing is downloaded and nothing is waited for.  ORBX_ERR_STATE where the extractor's "last batch" views are
+ * (e.g. after a chunked host batch).  A batch that does not fit is dropped whole; the next call that reads the trainer's size
+ * (_add, _size, orbx_voc_train) reports it once as ORBX_ERR_CAPACITY. */
+int orbx_voc_trainer_add_extracted(orbx_voc_trainer *h, orbx_extractor *ext);
+int orbx_voc_trainer_clear(orbx_voc_trainer *h);
+int orbx_voc_trainer_size(orbx_voc_trainer *h, int *descriptors, int *images);
+/* Trains on everything added.  ORBX_ERR_ARG: weighting outside 0..3, max_iterations < 2; ORBX_ERR_STATE: no descriptors.  Synchronous. */
+int orbx_voc_train(orbx_voc_trainer *h, const orbx_voc_train_params *params, orbx_voc_train_summary *summary);
+/* The trained tree as flat arrays in the layout of orbx_vocabulary_create (any pointer may be NULL), plus ni per node: the number of
+ * training images with a feature on that word, 0 on inner nodes.  ORBX_ERR_STATE before a training, ORBX_ERR_CAPACITY when
+ * capacity_nodes < summary.num_nodes. */
+int orbx_voc_trainer_result(orbx_voc_trainer *h, int32_t *parent, uint8_t *is_leaf, uint8_t *descriptors, double *weights, int32_t *ni, int capacity_nodes);
+/* The device vocabulary of the last training (the caller destroys it). */
+int orbx_voc_trainer_vocabulary(orbx_voc_trainer *h, orbx_vocabulary **voc);
+/* Host time of the last training and of each level (level_ms[ORBX_VOC_MAX_L]), its kernel launches, and - when the training ran with
+ * profiling enabled - the device time of its stages from HIP events: stage_ms[5] = seeding, assignment, mean, partition, everything else. */
+int orbx_voc_trainer_set_profiling(orbx_voc_trainer *h, int enable);
+int orbx_voc_trainer_last_timing(orbx_voc_trainer *h, float *total_ms, float *level_ms, float *stage_ms, int *launches);
+/* The two stages on explicit inputs (n <= max_descriptors descriptors in host memory; segment s = features seg_offsets[s] ..
+ * seg_offsets[s + 1] - 1, offsets from 0 to n, no empty segment).
+ * Seeding: slots[s] keys the draws of segment s.  chosen[s * k + j] = index inside the segment of the j-th centre, -1 where the seeding
+ * ended early; a segment with n <= k features reports 0 .. n - 1. */
+int orbx_voc_seed_segments(orbx_voc_trainer *h, const uint8_t *descriptors, int n, const int32_t *seg_offsets, const uint64_t *slots, int num_segments,
+                           uint64_t seed, int32_t *chosen);
+/* One Lloyd pass: centres[(s * k + c) * 32] for c < num_centres[s] (1..k).  With prev_assoc (cluster per feature, inside its segment's
+ * centres) the centres are first replaced by the means of its groups (an empty group keeps its centre); then every feature is assigned.
+ * changed_out[s] = 1 when an association of segment s differs from prev_assoc (0 without one).  Outputs may be NULL. */
+int orbx_voc_lloyd_pass(orbx_voc_trainer *h, const uint8_t *descriptors, int n, const int32_t *seg_offsets, int num_segments, const uint8_t *centres,
+                        const int32_t *num_centres, const int32_t *prev_assoc, uint8_t *centres_out, int32_t *assoc_out, uint8_t *changed_out);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -986,9 +986,8 @@ class Vocabulary:
     """DBoW2 vocabulary tree on the device: transform() == TemplatedVocabulary::transform
     (reference Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1262), i.e. Frame::ComputeBoW."""
 
-    def __init__(self, voc, device=0):
-        self._L = load_library()
-        L = self._L
+    @staticmethod
+    def _bind(L):
         vp, ci = ctypes.c_void_p, ctypes.c_int
         L.orbx_vocabulary_create.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, ctypes.POINTER(vp)]
         L.orbx_vocabulary_destroy.argtypes = [vp]
@@ -998,6 +997,12 @@ class Vocabulary:
         L.orbx_bow_results_device.argtypes = [vp, vp, vp, vp, vp]
         L.orbx_bow_download.argtypes = [vp, vp, ci, vp, vp, vp]
         L.orbx_bow_transform.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+
+    def __init__(self, voc, device=0):
+        self._L = load_library()
+        L = self._L
+        vp = ctypes.c_void_p
+        self._bind(L)
         self._h = vp()
         par = np.ascontiguousarray(voc["parent"], np.int32)
         leaf = np.ascontiguousarray(voc["is_leaf"], np.uint8)
@@ -1078,6 +1083,126 @@ class Vocabulary:
         w, nd, wt = np.zeros((batch, cap), np.int32), np.zeros((batch, cap), np.int32), np.zeros((batch, cap), np.float64)
         _check(self._L.orbx_bow_download(self._h, extractor._h, batch, _ptr(w), _ptr(nd), _ptr(wt)))
         return w, nd, wt
+
+
+VOC_MAX_K, VOC_MAX_L = 32, 10      # ORBX_VOC_MAX_K, ORBX_VOC_MAX_L
+VOC_TF_IDF, VOC_TF, VOC_IDF, VOC_BINARY = 0, 1, 2, 3      # DBoW2::WeightingType
+
+
+class VocTrainParams(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_uint64), ("weighting", ctypes.c_int), ("max_iterations", ctypes.c_int)]
+
+
+class VocTrainSummary(ctypes.Structure):
+    _fields_ = [("num_nodes", ctypes.c_int), ("num_words", ctypes.c_int), ("unconverged_nodes", ctypes.c_int), ("passes_per_level", ctypes.c_int * VOC_MAX_L)]
+
+
+class VocabularyTrainer:
+    """TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the device (reference
+    Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:557-996): hierarchical k-means++ over 256-bit descriptors and the IDF weights, with the three
+    stated differences of include/orbx.h (counter-hash draws, an empty cluster keeps its centre, a cap on the assignment passes)."""
+
+    def __init__(self, k, L, max_descriptors, max_images, device=0):
+        self._L = load_library()
+        L_ = self._L
+        vp, ci, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
+        L_.orbx_voc_trainer_create.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
+        L_.orbx_voc_trainer_destroy.argtypes = [vp]
+        L_.orbx_voc_trainer_destroy.restype = None
+        L_.orbx_voc_trainer_add.argtypes = [vp, vp, vp, ci]
+        L_.orbx_voc_trainer_add_extracted.argtypes = [vp, vp]
+        L_.orbx_voc_trainer_clear.argtypes = [vp]
+        L_.orbx_voc_trainer_size.argtypes = [vp, vp, vp]
+        L_.orbx_voc_train.argtypes = [vp, ctypes.POINTER(VocTrainParams), ctypes.POINTER(VocTrainSummary)]
+        L_.orbx_voc_trainer_result.argtypes = [vp, vp, vp, vp, vp, vp, ci]
+        L_.orbx_voc_trainer_vocabulary.argtypes = [vp, ctypes.POINTER(vp)]
+        L_.orbx_voc_trainer_set_profiling.argtypes = [vp, ci]
+        L_.orbx_voc_trainer_last_timing.argtypes = [vp, vp, vp, vp, vp]
+        L_.orbx_voc_seed_segments.argtypes = [vp, vp, ci, vp, vp, ci, u64, vp]
+        L_.orbx_voc_lloyd_pass.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+        self.k, self.L = int(k), int(L)
+        self._h = vp()
+        _check(L_.orbx_voc_trainer_create(device, int(k), int(L), int(max_descriptors), int(max_images), ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_voc_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, images):
+        """one uint8 array (n_i, 32) per image; an image may be empty"""
+        arrs = [np.ascontiguousarray(a, np.uint8).reshape(-1, 32) for a in images]
+        counts = np.array([len(a) for a in arrs], np.int32)
+        d = np.concatenate(arrs) if arrs else np.zeros((0, 32), np.uint8)
+        _check(self._L.orbx_voc_trainer_add(self._h, _ptr(d) if len(d) else None, _ptr(counts), len(counts)))
+
+    def add_extracted(self, extractor):
+        """every frame of `extractor`'s last batch as one image, read where the extractor left it on the device"""
+        _check(self._L.orbx_voc_trainer_add_extracted(self._h, extractor._h))
+
+    def clear(self):
+        _check(self._L.orbx_voc_trainer_clear(self._h))
+
+    def size(self):
+        """(descriptors, images)"""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        _check(self._L.orbx_voc_trainer_size(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def train(self, seed=0, weighting=VOC_TF_IDF, max_iterations=100):
+        """-> dict in voc_synth's format (usable as Vocabulary(voc) and by voc_synth.write_text) plus ni per node and the summary
+        (num_words, unconverged_nodes, passes_per_level)."""
+        p, s = VocTrainParams(int(seed) & (2 ** 64 - 1), int(weighting), int(max_iterations)), VocTrainSummary()
+        _check(self._L.orbx_voc_train(self._h, ctypes.byref(p), ctypes.byref(s)))
+        n = s.num_nodes
+        par, leaf, desc = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+        wt, ni = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        _check(self._L.orbx_voc_trainer_result(self._h, _ptr(par), _ptr(leaf), _ptr(desc), _ptr(wt), _ptr(ni), n))
+        return dict(k=self.k, L=self.L, parent=par, is_leaf=leaf, desc=desc, weight=wt, num_nodes=n, ni=ni, num_words=s.num_words,
+                    unconverged_nodes=s.unconverged_nodes, passes_per_level=list(s.passes_per_level)[:self.L])
+
+    def vocabulary(self):
+        """the device Vocabulary of the last training"""
+        v = Vocabulary.__new__(Vocabulary)
+        v._L = self._L
+        Vocabulary._bind(v._L)
+        v._h = ctypes.c_void_p()
+        _check(self._L.orbx_voc_trainer_vocabulary(self._h, ctypes.byref(v._h)))
+        return v
+
+    def set_profiling(self, enable=True):
+        _check(self._L.orbx_voc_trainer_set_profiling(self._h, int(bool(enable))))
+
+    def last_timing(self):
+        """dict(total_ms, level_ms (L), stage_ms: seeding / assignment / mean / partition / other (device time, profiling only), launches)"""
+        t, n = ctypes.c_float(), ctypes.c_int()
+        lv, st = (ctypes.c_float * VOC_MAX_L)(), (ctypes.c_float * 5)()
+        _check(self._L.orbx_voc_trainer_last_timing(self._h, ctypes.byref(t), lv, st, ctypes.byref(n)))
+        return dict(total_ms=t.value, level_ms=list(lv)[:self.L], stage_ms=dict(zip(("seeding", "assignment", "mean", "partition", "other"), list(st))), launches=n.value)
+
+    def seed_segments(self, descriptors, offsets, slots, seed=0):
+        """orbx_voc_seed_segments -> chosen (S, k): index inside segment s of its j-th centre, -1 where the seeding ended early"""
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        off, sl = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(slots, np.uint64)
+        out = np.zeros((len(sl), self.k), np.int32)
+        _check(self._L.orbx_voc_seed_segments(self._h, _ptr(d), len(d), _ptr(off), _ptr(sl), len(sl), int(seed) & (2 ** 64 - 1), _ptr(out)))
+        return out
+
+    def lloyd_pass(self, descriptors, offsets, centres, num_centres, prev=None):
+        """orbx_voc_lloyd_pass -> (centres (S, k, 32), association (n), changed (S))"""
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        off, nc = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(num_centres, np.int32)
+        c = np.ascontiguousarray(centres, np.uint8).reshape(len(nc), self.k, 32)
+        pv = None if prev is None else np.ascontiguousarray(prev, np.int32)
+        co, ao, ch = np.zeros_like(c), np.zeros(len(d), np.int32), np.zeros(len(nc), np.uint8)
+        _check(self._L.orbx_voc_lloyd_pass(self._h, _ptr(d), len(d), _ptr(off), len(nc), _ptr(c), _ptr(nc), None if pv is None else _ptr(pv), _ptr(co), _ptr(ao), _ptr(ch)))
+        return co, ao, ch
 
 
 class Camera(ctypes.Structure):
