@@ -97,6 +97,7 @@ __global__ __launch_bounds__(256) void k_bow_ranks(const int32_t *__restrict__ w
             rn += (n4.x < ni || (n4.x == ni && kk < i)) + (n4.y < ni || (n4.y == ni && kk + 1 < i)) + (n4.z < ni || (n4.z == ni && kk + 2 < i)) + (n4.w < ni || (n4.w == ni && kk + 3 < i));
         }
     }
+    // (not wave_sum_xor<8>: its steps run 4, 2, 1, and the other order costs this kernel three registers and nine instructions)
     rw += __shfl_xor(rw, 1); rw += __shfl_xor(rw, 2); rw += __shfl_xor(rw, 4);
     rn += __shfl_xor(rn, 1); rn += __shfl_xor(rn, 2); rn += __shfl_xor(rn, 4);
     filed += __shfl_xor(filed, 1); filed += __shfl_xor(filed, 2); filed += __shfl_xor(filed, 4);
@@ -148,10 +149,7 @@ extern "C" int orbx_vocabulary_create(int device, int k, int L, int num_nodes, c
     }
     std::vector<uint8_t> cdesc(childList.size() * 32);
     for (size_t c = 0; c < childList.size(); c++) memcpy(&cdesc[32 * c], descriptors + 32 * (size_t)childList[c], 32);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_vocabulary *v = new orbx_vocabulary();
     v->device = device; v->k = k; v->L = L; v->numNodes = num_nodes; v->numWords = words;
     int rc;

@@ -61,15 +61,6 @@ struct CvDev {
     uint8_t *outBad;                  // mapped [M]
 };
 
-__device__ __forceinline__ unsigned long long cv_wave_max(unsigned long long k)
-{
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long o = __shfl_xor(k, s);
-        k = o > k ? o : k;
-    }
-    return k;
-}
-
 template <bool LDS> __global__ __launch_bounds__(COVIS_THREADS) void k_covis_connect(CvDev D, unsigned *counter, unsigned long long *flag, unsigned long long seq)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t cvLds[];
@@ -123,7 +114,7 @@ template <bool LDS> __global__ __launch_bounds__(COVIS_THREADS) void k_covis_con
             n += tot;
             __syncthreads();
         }
-        best = cv_wave_max(best);
+        best = wave_max(best);
         if (lane == 0) sBest[w] = best;
         int sel = 0;
         for (int i = t; i < n; i += COVIS_THREADS) sel += (int)(keys[i] >> 32) >= D.th ? 1 : 0;      // (own workgroup's stores, behind a barrier)
@@ -254,10 +245,7 @@ extern "C" int orbx_covis_create(int device, orbx_covis **out)
 {
     if (!out) { orbx_set_error("orbx_covis_create: NULL argument"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_covis *h = new orbx_covis();
     h->device = device;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {

@@ -189,6 +189,7 @@ __device__ __forceinline__ void eg_oplus(const OsSim3 &S, const double (&x)[7], 
 }
 
 // thread t adds v[t], v[t + 256], ...; then a binary tree over the 256 partial sums.  Every thread returns the sum.
+// (an FP64 LDS tree: a third order of additions, neither of orbx_wave.h's two, with a barrier pattern of its own - it stays here)
 __device__ __forceinline__ double eg_block_sum(double part, double *red)
 {
     const int tid = threadIdx.x;
@@ -739,10 +740,7 @@ extern "C" int orbx_essential_graph_create(int device, int max_keyframes, int ma
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_essential_graph *h = new orbx_essential_graph();
     h->device = device; h->maxKf = max_keyframes; h->maxEdges = max_edges; h->maxPoints = max_points; h->maxFill = max_fill_blocks;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

@@ -242,9 +242,7 @@ __global__ __launch_bounds__(FT) void k_frame_finish(CamDev c, orbx_frame_grid g
     const int PER = NCELL / FT;
     int local = 0;
     for (int t = 0; t < PER; t++) local += cnt[tid * PER + t];
-    int incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+    const int incl = wave_incl_scan_shfl(local, lane);
     if (lane == 63) sWave[wv] = incl;
     __syncthreads();
     int base = incl - local;
@@ -372,10 +370,7 @@ extern "C" int orbx_frame_ops_create(int device, const orbx_camera *cam, orbx_fr
     *out = nullptr;
     if (cam->ndist != 4 && cam->ndist != 5) { orbx_set_error("ndist must be 4 or 5 (k1 k2 p1 p2 [k3]), got %d", cam->ndist); return ORBX_ERR_ARG; }
     if (!(cam->fx != 0.0f) || !(cam->fy != 0.0f)) { orbx_set_error("focal length must be non-zero"); return ORBX_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_frame_ops *h = new orbx_frame_ops();
     h->device = device;
     // (a plain stream: on a high-priority one - tried for the latency forms - the kernel shared a hardware queue with the combiner's second engines,

@@ -247,6 +247,7 @@ __global__ __launch_bounds__(64) void k_init_models(InitModelArgs P)
                 double x1 = 0.0, y1 = 0.0;
                 if (l < 9) { x1 = col[p][16 + l]; y1 = col[q][16 + l]; }
                 double alpha = x0 * x0, beta = y0 * y0, gamma = x0 * y0;
+                // (not wave_sum_xor<16>: the three chains interleaved, shuffled at full width, are the instruction order the FP64 results were pinned with)
 #pragma unroll
                 for (int o = 8; o > 0; o >>= 1) {
                     alpha = alpha + __shfl_xor(alpha, o);
@@ -829,10 +830,7 @@ extern "C" int orbx_initializer_create(int device, int max_matches, int max_iter
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_initializer *h = new orbx_initializer();
     h->device = device; h->maxMatches = max_matches; h->maxIters = max_iterations;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "orbx_wave.h"
 
 #define ORBX_MAX_LEVELS 12
 #define ORBX_EDGE 19          /* EDGE_THRESHOLD, reference src/ORBextractor.cc:93 */
@@ -125,6 +126,8 @@ struct OrbxCombMember {
 struct OrbxLevelKp { uint16_t x, y; uint8_t score, pad[3]; float angle, ca, sb; };
 
 void orbx_set_error(const char *fmt, ...);
+/* head of a *_create: ORBX_ERR_NODEVICE without a HIP device, ORBX_ERR_ARG for a device out of range, else hipSetDevice (orbx_extractor.hip) */
+int orbx_select_device(int device);
 #define ORBX_HIP_CHECK(expr)                                                                           \
     do {                                                                                               \
         hipError_t e_ = (expr);                                                                        \
@@ -202,6 +205,12 @@ void orbx_extractor_set_consumer_event_internal(orbx_extractor *h, hipEvent_t ev
 /* device word holding the OR of the capacity bits of the producer's last batch (nullptr before the first batch) */
 const int *orbx_extractor_status_word_internal(orbx_extractor *h);
 
+
+/* bit i of the inlier rows that the RANSAC kernels write with __ballot -> out[i] (Sim3Solver, PnPsolver) */
+static inline void expand_mask(const unsigned long long *row, int n, uint8_t *out)
+{
+    for (int i = 0; i < n; i++) out[i] = (uint8_t)((row[i >> 6] >> (i & 63)) & 1ull);
+}
 
 /* Grow-only device array owned by a handle (hipMalloc on demand, never shrinks, released by the handle's destroy). */
 template <typename T> struct OrbxDevBuf {

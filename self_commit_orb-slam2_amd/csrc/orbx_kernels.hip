@@ -70,16 +70,6 @@ __device__ __forceinline__ int find_level(const int *base, int nlevels, int idx)
     return l;
 }
 
-__device__ __forceinline__ int wave_incl_scan_i(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 // ------------------------------------------------------------------------------------
 // Pyramid: level L = cv::resize(level L-1, INTER_LINEAR) (src/ORBextractor.cc:1696-1701),
 // 11-bit fixed point; the column/row tables are built on the host with the exact
@@ -396,19 +386,6 @@ __device__ __forceinline__ uint4 load16u(const uint8_t *p)      // unaligned 16-
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// inclusive prefix sum over the 64 lanes with data-parallel-primitive adds: four shifts inside the rows of 16, then the two row broadcasts of gfx9
-// (six VALU instructions; __shfl_up is six dependent LDS-crossbar round trips)
-__device__ __forceinline__ int wave_incl_scan_dpp(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);     // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);     // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);     // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);     // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
 // P = LDS row pitch of both tiles, an ODD multiple of 16 bytes (48 for cells up to 32 px wide, 80 up to 64): the rows of a window land on all 32 banks.
 // NS = 16-byte units of a cell's window per lane (window rows x units per row <= 64 NS), K (an argument) = cells per wave.
 // A wave takes K consecutive cells of a frame through the phases one after the other; everything it needs to know about a cell is ONE 32-byte table
@@ -697,60 +674,6 @@ __global__ __launch_bounds__(64) void k_fast_cells(const OrbxFcCell *__restrict_
 // worst case, every second pixel in both directions a maximum).
 // ------------------------------------------------------------------------------------
 struct OtBox { short x0, y0, x1, y1; };
-
-template <typename T> __device__ __forceinline__ T wave_incl_scan(T v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// exclusive scan of arr[0..n) in place (LDS); returns the total.  All BT threads of the workgroup call.
-template <int BT = 256, typename T> __device__ T block_exscan(T *arr, int n, T *wsum /* >= BT / 64 entries */)
-{
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int per = (n + BT - 1) / BT;
-    const int b = tid * per;
-    T s = 0;
-    for (int k = 0; k < per; k++) if (b + k < n) s += arr[b + k];
-    T inc = wave_incl_scan(s, lane);
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    T off = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < BT / 64; i++) { const T v = wsum[i]; off += i < w ? v : (T)0; total += v; }
-    T run = off + inc - s;
-    for (int k = 0; k < per; k++)
-        if (b + k < n) { T v = arr[b + k]; arr[b + k] = run; run += v; }
-    __syncthreads();
-    return total;
-}
-
-// Two exclusive scans at once over entries that the calling thread FILLS itself: thread t owns the contiguous entries
-// [t*per, (t+1)*per), fill(i, a, b) produces entry i of both arrays, so no barrier is needed between filling and scanning.
-template <int BT = 256, typename F> __device__ __forceinline__ void block_fill_exscan2(int *A, int *B, int n, int *wsA, int *wsB, int &totA, int &totB, F fill)
-{
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int per = (n + BT - 1) / BT;
-    const int b = tid * per;
-    int sa = 0, sb = 0;
-    for (int k = 0; k < per; k++)
-        if (b + k < n) { int a, c; fill(b + k, a, c); A[b + k] = a; B[b + k] = c; sa += a; sb += c; }
-    const int incA = wave_incl_scan(sa, lane), incB = wave_incl_scan(sb, lane);
-    if (lane == 63) { wsA[w] = incA; wsB[w] = incB; }
-    __syncthreads();
-    int offA = 0, offB = 0;
-    totA = 0; totB = 0;
-#pragma unroll
-    for (int i = 0; i < BT / 64; i++) { const int va = wsA[i], vb = wsB[i]; offA += i < w ? va : 0; offB += i < w ? vb : 0; totA += va; totB += vb; }
-    int runA = offA + incA - sa, runB = offB + incB - sb;
-    for (int k = 0; k < per; k++)
-        if (b + k < n) { const int a = A[b + k], c = B[b + k]; A[b + k] = runA; B[b + k] = runB; runA += a; runB += c; }
-    __syncthreads();
-}
 
 __device__ __forceinline__ int ot_quadrant(uint32_t p, const OtBox b)
 {
@@ -1542,19 +1465,6 @@ __global__ __launch_bounds__(OB_THREADS) void k_octree_blur(const OrbxGeom *__re
 // round trip covers both stages and a load instruction touches ~7 lines.  fastAtan2 and the libm-exact sin / cos run
 // once per workgroup on four lanes (one per keypoint) between two barriers instead of on all 64 lanes of every wave.
 // ------------------------------------------------------------------------------------
-// sum over the 64 lanes with data-parallel-primitive adds (one VALU instruction per step, no LDS crossbar): quad, half row, row, then the
-// two row broadcasts of gfx9; the total lands in lane 63 and is returned as a scalar
-__device__ __forceinline__ int wave_sum_dpp(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4e, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);     // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);     // row_mirror: every lane holds its row's sum
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);     // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);     // row_bcast:31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // per-level constants of the geometry as a kernel ARGUMENT: the level lookup and the addresses come from a few wide scalar loads of the
 // kernarg segment instead of a chain of dependent loads through OrbxGeom (the prologue is most of a wave's latency here)
 struct OdLevels {

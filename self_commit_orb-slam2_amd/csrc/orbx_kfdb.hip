@@ -220,26 +220,6 @@ static __global__ __launch_bounds__(KF_THREADS) void k_kfdb_commit(KfDev D)
     D.relocNew[s] = v;
 }
 
-// position of a thread with `pred` among the workgroup's, behind *base; *base advances by the workgroup's count (uniform)
-static __device__ __forceinline__ int kf_scan(bool pred, int *base, int *sh)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long mask = __ballot(pred);
-    const int pre = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) sh[wave] = __popcll(mask);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int w = 0; w < KF_SEL_THREADS / 64; w++) {
-        const int c = sh[w];
-        if (w < wave) off += c;
-        tot += c;
-    }
-    __syncthreads();
-    const int r = *base + off + pre;
-    *base += tot;
-    return r;
-}
-
 static __global__ __launch_bounds__(KF_SEL_THREADS) void k_kfdb_select(KfDev D, unsigned *counter, unsigned long long *flagWord, unsigned long long seq)
 {
     __shared__ int sh[KF_SEL_THREADS / 64];
@@ -266,7 +246,7 @@ static __global__ __launch_bounds__(KF_SEL_THREADS) void k_kfdb_select(KfDev D, 
     for (int s0 = 0; s0 < Ns; s0 += KF_SEL_THREADS) {
         const int s = s0 + tid;
         const bool pred = s < Ns && flg[s] == KF_FLAG_SCORED;
-        const int k = kf_scan(pred, &M, sh);
+        const int k = block_ballot_rank<KF_SEL_THREADS>(pred, &M, sh);
         if (pred) { list[k] = s; key[k] = ((unsigned long long)(uint32_t)first[s] << 32) | (uint32_t)D.slots[s].seq; }
     }
     __syncthreads();
@@ -301,7 +281,7 @@ static __global__ __launch_bounds__(KF_SEL_THREADS) void k_kfdb_select(KfDev D, 
     for (int r0 = 0; r0 < M; r0 += KF_SEL_THREADS) {
         const int r = r0 + tid;
         const bool pred = r < M && (!loop || score[order[r]] >= minScore);
-        const int e = kf_scan(pred, &E, sh);
+        const int e = block_ballot_rank<KF_SEL_THREADS>(pred, &E, sh);
         if (pred) lsm[e] = r;
     }
     __syncthreads();
@@ -362,7 +342,7 @@ static __global__ __launch_bounds__(KF_SEL_THREADS) void k_kfdb_select(KfDev D, 
     for (int e0 = 0; e0 < E; e0 += KF_SEL_THREADS) {
         const int e = e0 + tid;
         const bool pred = e < E && acc[e] > minRetain && focc[best[e]] == e;
-        const int c = kf_scan(pred, &C, sh);
+        const int c = block_ballot_rank<KF_SEL_THREADS>(pred, &C, sh);
         if (pred) oCand[c] = D.slots[best[e]].id;
     }
     if (tid == 0) {
@@ -530,10 +510,7 @@ extern "C" int orbx_kfdb_create(int device, int n_words, int max_keyframes, int 
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_kf_database *h = new orbx_kf_database();
     h->device = device; h->nWords = n_words; h->maxKf = max_keyframes; h->maxEntries = max_entries; h->maxQueries = max_queries; h->maxQueryWords = max_query_words;
     h->slots.resize((size_t)max_keyframes);

@@ -304,11 +304,11 @@ __device__ inline void huber_rho(const Huber &h, bool stereo, double chi, double
     else { const double s = sqrt(chi); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
 }
 
-// sum over the workgroup in a fixed order (lanes by butterfly, the four waves in order); the result is valid in thread 0
+// sum over the workgroup in a fixed order (lanes by xor butterfly, the four waves in order); the result is valid in thread 0
 __device__ __forceinline__ double block_sum256(double v, double *sw /* 4 */)
 {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);      // (wave_sum_xor's order, written out: as a call an address shift moves across the last add in k_errors / k_backsub_update)
     if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
     __syncthreads();
     return sw[0] + sw[1] + sw[2] + sw[3];
@@ -468,14 +468,6 @@ __global__ __launch_bounds__(256) void k_linearize(LbaDev d, Huber h, int robust
 }
 
 // Hll (9, full symmetric) and b_l (3) of every active landmark: its edges in insertion order
-__device__ __forceinline__ double sum16(double x)
-{
-    // sum over the 16 lanes of a landmark's group (xor butterfly inside the group)
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) x += __shfl_xor(x, o, 16);
-    return x;
-}
-
 // 16 lanes per landmark (a landmark has ~12 observations: one thread walking them serially leaves the launch at 20 waves and a
 // dozen dependent loads deep), partial sums combined by a butterfly inside the group
 __global__ __launch_bounds__(256) void k_sum_points(LbaDev d, const int *ptStart, const int *ptEdges, double *Hll, double *bl, const int *gate, int want)
@@ -496,7 +488,7 @@ __global__ __launch_bounds__(256) void k_sum_points(LbaDev d, const int *ptStart
         for (int i = 0; i < 3; i++) v[6 + i] += blk[EB_BL + i];
     }
 #pragma unroll
-    for (int i = 0; i < 9; i++) v[i] = sum16(v[i]);
+    for (int i = 0; i < 9; i++) v[i] = wave_sum_xor<16>(v[i]);
     if (a == 0) {
         double *o = Hll + (size_t)li * 9;
         o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[1]; o[4] = v[3]; o[5] = v[4]; o[6] = v[2]; o[7] = v[4]; o[8] = v[5];
@@ -592,7 +584,7 @@ __global__ __launch_bounds__(256) void k_lin_sums(LbaDev d, Huber h, int robust,
             for (int i = 0; i < 3; i++) v[6 + i] += LIN_DOT(A[i] * omr[0], A[3 + i] * omr[1], A[6 + i] * omr[2]);
         }
 #pragma unroll
-        for (int i = 0; i < 9; i++) v[i] = sum16(v[i]);
+        for (int i = 0; i < 9; i++) v[i] = wave_sum_xor<16>(v[i]);
         if (a == 0) {
             double *o = Hll + (size_t)li * 9;
             o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[1]; o[4] = v[3]; o[5] = v[4]; o[6] = v[2]; o[7] = v[4]; o[8] = v[5];
@@ -686,13 +678,6 @@ __global__ __launch_bounds__(256) void k_sum_poses_fin(LbaDev d, const double *_
 // ---------------------------------------------------------------------------------------------
 // (LmState: before the batch descriptor, see the Levenberg-Marquardt section below)
 
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
 __device__ __forceinline__ void lm_mirror(const LmState *st, double *host, double seq, double o1, double o2, double okf)
 {
     host[0] = st->tempChi; host[1] = st->currentChi; host[2] = st->lambda; host[3] = st->rho; host[4] = o1; host[5] = o2; host[6] = st->chi0;
@@ -718,7 +703,7 @@ __global__ __launch_bounds__(256) void k_lm_begin(LmState *st, const double *par
     if (tid < 6) scaleBits[tid] = 0ull;      // (the maxima of the Schur scale: raised by the next k_schur_setup)
     double v0 = 0;
     for (int i = tid; i < nChi; i += 256) v0 += partChi[i];
-    v0 = wave_sum(v0);
+    v0 = wave_sum_xor(v0);
     if (lane == 0) sw[wave] = v0;
     __syncthreads();
     if (tid == 0) {
@@ -793,7 +778,7 @@ __device__ __forceinline__ void lm_decide_block(LmState *st, const double *partC
     for (int i = tid; i < nChi; i += 256) v0 += partChi[i];
     for (int i = tid; i < nP6; i += 256) v1 += xp[i] * (lambda * xp[i] + bp[i]);
     for (int i = tid; i < nL; i += 256) v2 += partL[i];
-    v0 = wave_sum(v0); v1 = wave_sum(v1); v2 = wave_sum(v2);
+    v0 = wave_sum_xor(v0); v1 = wave_sum_xor(v1); v2 = wave_sum_xor(v2);
     if (lane == 0) { sw[0][wave] = v0; sw[1][wave] = v1; sw[2][wave] = v2; }
     __syncthreads();
     if (tid == 0) {
@@ -911,7 +896,7 @@ __global__ __launch_bounds__(256) void k_csr_kf_scan(const int *__restrict__ kfS
     for (int c0 = 0; c0 < nChunk; c0 += 256) {
         const int c = c0 + tid;
         const int v = c < nChunk ? chunkCnt[(size_t)c * K + k] : 0;
-        int x = v;
+        int x = v;      // (wave_incl_scan_shfl written out: as a call the compiler allocates this kernel's compare masks differently)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(x, o); if (lane >= o) x += u; }
         __syncthreads();
@@ -1012,7 +997,7 @@ __global__ __launch_bounds__(256) void k_stage_pairs(int E, const int *__restric
 __device__ __forceinline__ int block_incl_scan1024(int v, int *wsum /* 17 */, int *total)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
+    int x = v;      // (wave_incl_scan_shfl written out: as a call two instructions of k_stage_index change places)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(x, o); if (lane >= o) x += u; }
     __syncthreads();                       // wsum may still be read from the previous call
@@ -1586,14 +1571,6 @@ __global__ __launch_bounds__(1024) void k_chol_solve(double *S, const double *bs
 #define CNB 32
 #define CHOL_RPW 63          /* panel rows per workgroup of k_chol_step: one wave, lane 63 carries the right-hand side */
 
-// value of lane `src` (compile-time constant after unrolling) as a scalar broadcast: two v_readlane_b32 instead of two ds_bpermute_b32
-__device__ __forceinline__ double readlane_f64(double v, int src)
-{
-    const unsigned long long u = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(u & 0xffffffffu), src), hi = (unsigned)__builtin_amdgcn_readlane((int)(u >> 32), src);
-    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-
 // The panel step: nothing goes through synchronised column steps (a version with the 32x32 block in LDS and two workgroup barriers
 // per column took 31 us per panel; a wave factoring the block in registers with one v_readlane pair per multiply-add and a second wave
 // eliminating the rows afterwards 17; the blocked one-wave elimination with the panel rows inside it 7.9, with the rows on a wave of their own 5).
@@ -2081,7 +2058,7 @@ __global__ __launch_bounds__(256) void k_backsub_update(LbaDev d, const int *ptS
                 for (int q = 0; q < 3; q++) { double acc = 0; for (int r = 0; r < 6; r++) acc += B1[3 * r + q] * xp[6 * pi + r]; c[q] += acc; }
             }
 #pragma unroll
-        for (int q = 0; q < 3; q++) c[q] = sum16(c[q]);
+        for (int q = 0; q < 3; q++) c[q] = wave_sum_xor<16>(c[q]);
         if (a == 0) {
             double X[3] = {d.pt[3 * (size_t)t], d.pt[3 * (size_t)t + 1], d.pt[3 * (size_t)t + 2]};
             for (int i = 0; i < 3; i++) ptBak[3 * (size_t)t + i] = X[i];
@@ -2186,41 +2163,6 @@ __device__ __forceinline__ void huber_rho_nb(const Huber &h, bool stereo, double
     const bool in = chi <= dsqr;
     rho0 = in ? chi : __builtin_fma(2 * s, delta, -dsqr);
     rho1 = in ? 1. : delta * rs;
-}
-
-// a lane's value moved by a DPP control (two full-rate v_mov_b32_dpp, ~8 cycles of latency; __shfl_xor of a double is two ds_bpermute_b32 through the LDS
-// crossbar, ~130 cycles per step of a dependent chain)
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u & 0xffffffffu), CTRL, 0xf, 0xf, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// the wave's sum in every lane, in a fixed order: pairs, quads, half rows, rows (DPP butterflies), then the four rows' sums as scalar broadcasts
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    v += dpp_f64<0xb1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4e>(v);      // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);     // row_half_mirror
-    v += dpp_f64<0x140>(v);     // row_mirror: every lane holds its row's sum
-    const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
-    return (r0 + r1) + (r2 + r3);
-}
-
-template <int N> __device__ inline void po_block_reduce(double (&v)[N], double (*red)[PO_NRED], int tid)
-{
-    // v[0..N) per thread -> v[0..N) of EVERY thread = the sums over the workgroup (N is a template argument: v stays in registers).  One barrier: the four
-    // waves' sums meet in red[wave][k] and every thread adds them itself, in the same order.  The caller keeps a barrier between two calls (red is reused).
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        const double x = wave_sum_f64(v[k]);
-        if (lane == 0) red[wave][k] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
 }
 
 // The 28 sums of an iteration (21 entries of H, 6 of b, chi2) through a transposed LDS tile instead of 28 x 6 double shuffles per thread
@@ -2513,7 +2455,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(PoseOptDev P, Huber hub)
                     cacc[0] += on ? r0 : 0.0;
                 }
                 PO_STAMP(8);      // error pass at the trial pose
-                po_block_reduce(cacc, red, tid);
+                block_sum_f64(cacc, red, tid);
                 PO_STAMP(9);      // reduce (chi2)
                 if (tid == 0) {
                     double tempChi = cacc[0];
@@ -2574,7 +2516,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(PoseOptDev P, Huber hub)
         }
         {
             double v[1] = {(double)nb};
-            po_block_reduce(v, red, tid);
+            block_sum_f64(v, red, tid);
             nAct = n - (int)v[0];      // the next round's active edges (every thread holds the sum)
             if (tid == 0) P.ret[f] = nAct;
             __syncthreads();
@@ -2690,10 +2632,7 @@ struct LbaCore : LbaBuffers {
 // device check, stream, events, CU count, the mapped words; lba_close() undoes whatever part of it was reached
 int lba_open(LbaCore *h, int device, int maxW, int maxK, int maxP, int maxE)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     h->device = device; h->maxW = maxW; h->maxK = maxK; h->maxP = maxP; h->maxE = maxE;
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
@@ -3301,10 +3240,7 @@ extern "C" int orbx_pose_optimizer_create(int device, int max_frames, int max_fe
 {
     if (!out || max_frames < 1 || max_features < 1) { orbx_set_error("bad pose optimizer arguments"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_pose_optimizer *h = new orbx_pose_optimizer();
     h->device = device; h->maxFrames = max_frames; h->maxFeatures = max_features;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

@@ -305,10 +305,7 @@ extern "C" int orbx_loop_create(int device, orbx_loop **out)
 {
     if (!out) { orbx_set_error("orbx_loop_create: NULL argument"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_loop *h = new orbx_loop();
     h->device = device;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {

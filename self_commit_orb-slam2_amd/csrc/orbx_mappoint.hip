@@ -64,12 +64,6 @@ __device__ __forceinline__ void mp_normal_depth(const MpDev &D, int p, int n, co
     else if (t == 3) mp_depth(D.pos + (size_t)p * 3, D.refc + (size_t)p * 3, D.rsc[p], D.tsc[p], &D.maxD[p], &D.minD[p]);
 }
 
-__device__ __forceinline__ unsigned mp_wave_min(unsigned key)
-{
-    for (int s = 32; s >= 1; s >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, s));
-    return key;
-}
-
 constexpr size_t mp_block_lds(int tpp) { return (size_t)tpp * 32 + (size_t)tpp * tpp * 2 + (size_t)tpp * 12 + (size_t)tpp * 2 + 64; }
 
 // One workgroup of TPP threads per point with n <= TPP observations.
@@ -128,7 +122,7 @@ template <int TPP> __global__ __launch_bounds__(TPP) void k_mp_block(MpDev D)
         }
         key = (unsigned)lo << 16 | (unsigned)t;
     }
-    key = mp_wave_min(key);
+    key = wave_min(key);
     if (NW > 1) {
         if (lane == 0) sW[4 + w] = (int)key;
         __syncthreads();
@@ -215,7 +209,7 @@ __global__ __launch_bounds__(256) void k_mp_strided(MpDev D)
             key = min(key, (unsigned)med << 16 | (unsigned)i);
         }
     }
-    key = mp_wave_min(key);
+    key = wave_min(key);
     if (lane == 0) sW[4 + w] = (int)key;
     __syncthreads();
     for (int i = 0; i < 4; i++) key = min(key, (unsigned)sW[4 + i]);
@@ -249,10 +243,7 @@ extern "C" int orbx_mappoint_ops_create(int device, int max_points, int max_obs_
 {
     if (!out || max_points < 1 || max_obs_total < 1) { orbx_set_error("bad map point ops arguments"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_mappoint_ops *h = new orbx_mappoint_ops();
     h->device = device; h->maxPoints = max_points; h->maxObs = max_obs_total;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||

@@ -442,7 +442,7 @@ __global__ __launch_bounds__(256) void k_bow_topk_pair(FeatDev A, FeatDev B, int
                 rank += (g4.w < gi) || (g4.w == gi && kk + 3 < i);
             }
         }
-        rank += __shfl_xor(rank, 1); rank += __shfl_xor(rank, 2); rank += __shfl_xor(rank, 4);
+        rank += __shfl_xor(rank, 1); rank += __shfl_xor(rank, 2); rank += __shfl_xor(rank, 4);      // (not wave_sum_xor<8>: steps 4, 2, 1 put k_bow_topk_pair into scratch)
         if (seg == 0 && i < nA) order[rank] = i;
         return;
     }
@@ -691,9 +691,9 @@ __global__ __launch_bounds__(GREEDY_THREADS) void k_bow_greedy(FeatDev A, FeatDe
                 }
                 if (kk < k0) { k1 = k0; k0 = kk; } else if (kk < k1) k1 = kk;
             }
-            uint32_t bestKey = wave_min_u32(k0);
+            uint32_t bestKey = wave_min(k0);
             if (k0 == bestKey) k0 = k1;
-            const uint32_t second = wave_min_u32(k0);
+            const uint32_t second = wave_min(k0);
             uint32_t nd = KEY_EMPTY;
             if (bestKey != KEY_EMPTY) {
                 const int best1 = (int)(bestKey >> 16), best2 = second != KEY_EMPTY ? (int)(second >> 16) : 256;
@@ -730,8 +730,7 @@ __global__ __launch_bounds__(GREEDY_THREADS) void k_bow_greedy(FeatDev A, FeatDe
             atomicAdd(&hist[bin], 1);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+    total = wave_sum_xor(total);
     if (lane == 0 && total) atomicAdd(&sTotal, total);
     __syncthreads();
     if (checkOri) {
@@ -749,8 +748,7 @@ __global__ __launch_bounds__(GREEDY_THREADS) void k_bow_greedy(FeatDev A, FeatDe
                 if (sRes) sRes[slot] = -1;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+        removed = wave_sum_xor(removed);
         if (lane == 0 && removed) atomicAdd(&sRemoved, removed);
     }
     __syncthreads();
@@ -796,7 +794,7 @@ __global__ __launch_bounds__(256) void k_stereo(FeatDev Lf, FeatDev Rf, const in
             if (d < TH_HIGH && key < best) best = key;
         }
     }
-    best = wave_min_u32(best);
+    best = wave_min(best);
     if (lane == 0) {
         const int d = (int)(best >> 16);
         bestDist[(size_t)p * stride + iL] = d;
@@ -861,9 +859,7 @@ __global__ __launch_bounds__(256) void k_stereo_rows(FeatDev Rf, const int32_t *
         const int per = (H + 1 + 255) / 256, b = tid * per;
         int ssum = 0;
         for (int k = 0; k < per; k++) if (b + k <= H) ssum += cnt[b + k];
-        int inc = ssum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+        const int inc = wave_incl_scan_shfl(ssum, lane);
         if (lane == 63) wsum[wv] = inc;
         __syncthreads();
         int off = 0;
@@ -947,7 +943,7 @@ __device__ __forceinline__ void stereo_full_body(const int iL, const int p, cons
             if (d < TH_HIGH && key < best) best = key;
         }
     }
-    best = wave_min_u32(best);
+    best = wave_min(best);
     const int bd = (int)(best >> 16);
     const size_t o = (size_t)p * stride + iL;
     float outU = -1.0f, outZ = -1.0f;
@@ -1075,8 +1071,7 @@ __global__ __launch_bounds__(256) void k_stereo_cut(FeatDev Lf, const int32_t *_
         if ((float)v < thDist) kept++;
         else { uRight[(size_t)p * stride + i] = -1.0f; depth[(size_t)p * stride + i] = -1.0f; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+    kept = wave_sum_xor(kept);
     __syncthreads();
     if (t == 0) hist[0] = 0;
     __syncthreads();
@@ -1105,7 +1100,7 @@ __device__ __forceinline__ void rank_bin_wave0(const int *hist, int rank, int la
 {
     const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
     const int s4 = h0 + h1 + h2 + h3;
-    int inc = s4;
+    int inc = s4;      // (wave_incl_scan_shfl written out: as a call k_stereo_cut_one splits two v_and_or_b32)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
     const int exc = inc - s4;
@@ -1184,7 +1179,7 @@ __global__ __launch_bounds__(256) void k_stereo_cut_one(FeatDev Lf, const int32_
             else { uRight[i] = -1.0f; depth[i] = -1.0f; }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+        for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);      // (wave_sum_xor written out: as a call the scheduler reorders this kernel's tail)
         if (lane == 0) wsum[wv] = kept;
     }
     __threadfence_system();
@@ -1214,10 +1209,7 @@ extern "C" int orbx_matcher_create(int device, int max_features, int max_pairs, 
 {
     if (!out || max_features < 1 || max_features > 65535 || max_pairs < 1) { orbx_set_error("bad matcher arguments (1 <= max_features <= 65535)"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_matcher *m = new orbx_matcher();
     m->device = device; m->maxFeatures = max_features; m->maxPairs = max_pairs;
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

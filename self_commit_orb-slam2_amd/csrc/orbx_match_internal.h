@@ -26,13 +26,6 @@ struct FeatDev {   // orbx_feature_set with device pointers
     int cap;
 };
 
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
-
 __device__ __forceinline__ int hamming256(const unsigned long long a[4], unsigned long long b0, unsigned long long b1, unsigned long long b2,
                                           unsigned long long b3)
 {
@@ -50,7 +43,7 @@ __device__ __forceinline__ void three_maxima_wave(const int *hist, int lane, int
     uint32_t top[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        uint32_t v = key;
+        uint32_t v = key;      // (wave_max written out: as a call k_search_init and k_proj_last_greedy come out with other instructions)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(v, o); v = u > v ? u : v; }
         top[k] = v;
@@ -64,13 +57,6 @@ __device__ __forceinline__ void three_maxima_wave(const int *hist, int lane, int
 
 struct ProjFrameDev { const orbx_keypoint *kp; const uint8_t *desc; const float *uRight; const uint8_t *occupied; const int32_t *counts; int cap;
                       float minX, minY, gwInv, ghInv; };
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
 
 struct orbx_matcher {
     int device = 0, maxFeatures = 0, maxPairs = 0;

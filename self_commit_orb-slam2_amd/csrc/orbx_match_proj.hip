@@ -159,7 +159,7 @@ __device__ __forceinline__ void proj_topk_wave(const ProjFrameDev &F, size_t fba
     }
 #pragma unroll
     for (int k = 0; k < TOPK; k++) {
-        const unsigned long long mn = wave_min_u64(kk[0]);
+        const unsigned long long mn = wave_min(kk[0]);
         if (kk[0] == mn && mn != KEY64_EMPTY) {   // keys are unique: exactly one lane pops its head
 #pragma unroll
             for (int t = 0; t < TOPK - 1; t++) kk[t] = kk[t + 1];
@@ -311,9 +311,9 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_greedy(ProjFrameDe
                     const unsigned long long kx = proj_key(F, fbase, x, q);
                     if (kx < a) { b = a; a = kx; } else if (kx < b) b = kx;
                 }
-            const unsigned long long k1 = wave_min_u64(a);
+            const unsigned long long k1 = wave_min(a);
             if (a == k1) a = b;
-            const unsigned long long k2 = wave_min_u64(a);
+            const unsigned long long k2 = wave_min(a);
             const uint32_t nd = decide(k1, k2);
             if (lane == 0 && nd != dec[r]) { dec[r] = nd; sChangedP[par] = 1; }
         }
@@ -332,8 +332,7 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_greedy(ProjFrameDe
         const uint32_t d = dec[r];
         if (d != PROJ_NONE) { atomicMax(&owner[d], (uint32_t)r + 1u); total++; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+    total = wave_sum_xor(total);
     if (lane == 0 && total) atomicAdd(&sTotal, total);
     __syncthreads();
     for (int j = tid; j < n; j += PROJ_GREEDY_THREADS) if (owner[j]) aout[j] = (int32_t)owner[j] - 1;
@@ -512,7 +511,7 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_last_greedy(ProjFr
                     const unsigned long long kx = proj_key(F, fbase, x, q);
                     a = kx < a ? kx : a;
                 }
-            const unsigned long long k1 = wave_min_u64(a);
+            const unsigned long long k1 = wave_min(a);
             const uint32_t nd = (k1 != KEY64_EMPTY && (int)(k1 >> 32) <= TH_HIGH) ? (uint32_t)(k1 & 0xffff) : PROJ_NONE;
             if (lane == 0 && nd != dec[r]) { dec[r] = nd; sChangedP[par] = 1; }
         }
@@ -545,8 +544,7 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_last_greedy(ProjFr
             atomicAdd(&hist[bin], 1);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+    total = wave_sum_xor(total);
     if (lane == 0 && total) atomicAdd(&sTotal, total);
     __syncthreads();
     for (int j = tid; j < stride; j += PROJ_GREEDY_THREADS) aout[j] = (j < n && owner[j]) ? (int32_t)owner[j] - 1 : -1;
@@ -561,8 +559,7 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_last_greedy(ProjFr
             const int b = (int)(d >> 16);
             if (b != ind1 && b != ind2 && b != ind3) { aout[d & 0xffffu] = -2; removed++; }   // -2: assigned, then cleared (:1718)
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+        removed = wave_sum_xor(removed);
         if (lane == 0 && removed) atomicAdd(&sRemoved, removed);
     }
     __syncthreads();
@@ -633,7 +630,7 @@ __global__ __launch_bounds__(256) void k_fuse_best(ProjFrameDev F, FusePointsDev
             }
         }
     }
-    best = wave_min_u64(best);
+    best = wave_min(best);
     if (lane == 0) {
         const size_t o = (size_t)f * stride + i;
         bestIdx[o] = best == KEY64_EMPTY ? -1 : (int)(best & 0xffff);
@@ -786,7 +783,7 @@ __global__ __launch_bounds__(256) void k_area_topk(ProjFrameDev F, AreaQueriesDe
         }
 #pragma unroll
     for (int k = 0; k < TOPK; k++) {
-        const unsigned long long mn = wave_min_u64(kk[0]);
+        const unsigned long long mn = wave_min(kk[0]);
         if (kk[0] == mn && mn != KEY64_EMPTY) {   // keys are unique: exactly one lane pops its head
 #pragma unroll
             for (int t = 0; t < TOPK - 1; t++) kk[t] = kk[t + 1];
@@ -852,7 +849,7 @@ __global__ __launch_bounds__(256) void k_area_greedy(ProjFrameDev F, AreaQueries
                 const unsigned long long key = area_key(F, fbase, idx, q);
                 best = key < best ? key : best;
             }
-            best = wave_min_u64(best);
+            best = wave_min(best);
             uint32_t nd = KEY_EMPTY;
             if (best != KEY64_EMPTY && (int)(best >> 32) <= maxDist) nd = ((uint32_t)(best >> 32) << 16) | (uint32_t)(best & 0xffff);
             if (lane == 0 && nd != dec[r]) { dec[r] = nd; sChanged = 1; }
@@ -869,8 +866,7 @@ __global__ __launch_bounds__(256) void k_area_greedy(ProjFrameDev F, AreaQueries
         dout[r] = d == KEY_EMPTY ? 256 : (int)(d >> 16);
         total += d != KEY_EMPTY;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+    total = wave_sum_xor(total);
     if (lane == 0 && total) atomicAdd(&sTotal, total);
     __syncthreads();
     if (tid == 0) nmatches[f] = sTotal;
@@ -1033,7 +1029,7 @@ __global__ __launch_bounds__(256) void k_init_topk(FeatDev A, ProjFrameDev F2, c
         }
 #pragma unroll
     for (int k = 0; k < TOPK; k++) {
-        const unsigned long long mn = wave_min_u64(kk[0]);
+        const unsigned long long mn = wave_min(kk[0]);
         if (kk[0] == mn && mn != KEY64_EMPTY) {   // keys are unique: exactly one lane pops its head
 #pragma unroll
             for (int t = 0; t < TOPK - 1; t++) kk[t] = kk[t + 1];
@@ -1099,9 +1095,9 @@ __global__ __launch_bounds__(256) void k_search_init(FeatDev A, ProjFrameDev F2,
                             if (kx == KEY64_EMPTY || (int)holderDist[i2] <= (int)(kx >> 32)) continue;
                             if (kx < k0) { kk1 = k0; k0 = kx; } else if (kx < kk1) kk1 = kx;
                         }
-                    b = wave_min_u64(k0);
+                    b = wave_min(k0);
                     if (k0 == b) k0 = kk1;
-                    s2 = wave_min_u64(k0);
+                    s2 = wave_min(k0);
                 }
                 if (b == KEY64_EMPTY) continue;
                 const int bestDist = (int)(b >> 32), bestIdx2 = (int)(b & 0xffff);
@@ -1140,8 +1136,7 @@ __global__ __launch_bounds__(256) void k_search_init(FeatDev A, ProjFrameDev F2,
             const int b = bin12[i];
             if (b >= 0 && b != ind1 && b != ind2 && b != ind3 && m12[i] >= 0) { m12[i] = -1; removed++; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+        removed = wave_sum_xor(removed);
         if (lane == 0 && removed) atomicSub(&sTotal, removed);
     }
     __syncthreads();

@@ -86,44 +86,6 @@ __device__ __forceinline__ void os_huber(double delta, double e2, double &rho0, 
 
 __device__ __forceinline__ double os_chi2(const double (&e)[2], double w) { return w * (e[0] * e[0] + e[1] * e[1]); }
 
-// ---- fixed-order sums -------------------------------------------------------------------------------------------------------------------
-template <int CTRL> __device__ __forceinline__ double os_dpp(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u & 0xffffffffu), CTRL, 0xf, 0xf, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double os_readlane(double v, int src)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(u & 0xffffffffu), src), hi = (unsigned)__builtin_amdgcn_readlane((int)(u >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// the wave's sum in every lane: pairs, quads, half rows, rows (DPP butterflies), then the four rows' sums as scalar broadcasts
-__device__ __forceinline__ double os_wave_sum(double v)
-{
-    v += os_dpp<0xb1>(v);      // quad_perm [1,0,3,2]
-    v += os_dpp<0x4e>(v);      // quad_perm [2,3,0,1]
-    v += os_dpp<0x141>(v);     // row_half_mirror
-    v += os_dpp<0x140>(v);     // row_mirror
-    const double r0 = os_readlane(v, 0), r1 = os_readlane(v, 16), r2 = os_readlane(v, 32), r3 = os_readlane(v, 48);
-    return (r0 + r1) + (r2 + r3);
-}
-// v[0..N) per thread -> the sums over the workgroup in every thread.  One barrier; the caller keeps a barrier between two calls (red is reused).
-template <int N> __device__ __forceinline__ void os_block_sum(double (&v)[N], double (*red)[OS_NRED], int tid)
-{
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        const double x = os_wave_sum(v[k]);
-        if (lane == 0) red[wave][k] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-}
-
 struct OsShared {
     OsSim3 est, save, pert[14], pertInv[14];
     double red[4][OS_NRED];
@@ -296,7 +258,7 @@ __device__ __forceinline__ void os_run(const OsIn &I, uint8_t *__restrict__ out,
 #pragma unroll
             for (int k = 0; k < 28; k++) oj[28 * (size_t)i + k] = J[k];
         }
-        os_block_sum(acc, sh.red, tid);
+        block_sum_f64(acc, sh.red, tid);
         if (tid == 0) {
             double *oH = (double *)(blk + LL.H), *ob = (double *)(blk + LL.b);
             int k = 0;
@@ -343,7 +305,7 @@ __device__ __forceinline__ void os_run(const OsIn &I, uint8_t *__restrict__ out,
                     double J[28], chi[2];
                     os_pair_build(sh, S, Si, x1[j], x2[j], o1[j], o2[j], w1[j], w2[j], K1, K2, hub, er[j], J, chi, acc);
                 }
-                os_block_sum(acc, sh.red, tid);
+                block_sum_f64(acc, sh.red, tid);
                 if (tid == 0) {
                     int k = 0;
 #pragma unroll
@@ -444,7 +406,7 @@ __device__ __forceinline__ void os_run(const OsIn &I, uint8_t *__restrict__ out,
                         os_huber(hub, os_chi2(e21, (double)w2[j]), r0, r1);
                         cacc[0] += r0;
                     }
-                    os_block_sum(cacc, sh.red, tid);
+                    block_sum_f64(cacc, sh.red, tid);
                     if (tid == 0) {
                         double tempChi = cacc[0];
                         if (!sh.ok) tempChi = DBL_MAX;
@@ -615,10 +577,7 @@ extern "C" int orbx_sim3_optimizer_create(int device, int max_problems, int max_
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_sim3_optimizer *h = new orbx_sim3_optimizer();
     h->device = device; h->maxProblems = max_problems; h->maxPairs = max_pairs;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

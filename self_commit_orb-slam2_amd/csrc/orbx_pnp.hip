@@ -735,7 +735,7 @@ __global__ __launch_bounds__(64) void k_pnp_records(PnpDev D)
         const int it = base + tid;
         const int cnt = it < iters ? D.count[ib + it] : 0;
         const int v = cnt >= minInl ? cnt : 0;
-        int incl = v;
+        int incl = v;      // (inclusive maximum scan, written out here and in k_sim3_decide: as a shared helper both kernels come out with other instructions)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const int o = __shfl_up(incl, d);
@@ -944,10 +944,6 @@ int stage(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, int nc, const std::vec
 
 unsigned prepare_blocks(int maxN, int maxIt) { return (unsigned)std::max(1, (std::max(maxN, 4 * maxIt) + 255) / 256); }
 
-void expand_mask(const unsigned long long *row, int n, uint8_t *out)
-{
-    for (int i = 0; i < n; i++) out[i] = (uint8_t)((row[i >> 6] >> (i & 63)) & 1ull);
-}
 }  // namespace
 
 extern "C" int orbx_pnp_ransac_parameters(double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2, int n, int *min_inliers_out,
@@ -969,10 +965,7 @@ extern "C" int orbx_pnp_solver_create(int device, int max_candidates, int max_ma
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_pnp_solver *h = new orbx_pnp_solver();
     h->device = device; h->maxCands = max_candidates; h->maxMatches = max_matches; h->maxIters = max_iterations;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

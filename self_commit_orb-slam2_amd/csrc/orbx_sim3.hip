@@ -330,7 +330,7 @@ __global__ __launch_bounds__(SIM3_DECIDE_THREADS) void k_sim3_decide(Sim3Dev D, 
         for (int base = 0; base < iters; base += 64) {
             const int it = base + tid;
             const int v = it < iters ? D.count[ib + it] : -1;
-            int incl = v;
+            int incl = v;      // (inclusive maximum scan, written out here and in k_pnp_records: as a shared helper both kernels come out with other instructions)
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 const int o = __shfl_up(incl, d);
@@ -466,10 +466,6 @@ int stage(orbx_sim3_solver *h, const orbx_sim3_problem *Ps, int nc, const std::v
 
 unsigned prepare_blocks(int maxN, int maxIt) { return (unsigned)std::max(1, (std::max(maxN, 3 * maxIt) + 255) / 256); }
 
-void expand_mask(const unsigned long long *row, int n, uint8_t *out)
-{
-    for (int i = 0; i < n; i++) out[i] = (uint8_t)((row[i >> 6] >> (i & 63)) & 1ull);
-}
 }  // namespace
 
 extern "C" int orbx_sim3_ransac_iterations(double probability, int min_inliers, int max_iterations, int n)
@@ -493,10 +489,7 @@ extern "C" int orbx_sim3_solver_create(int device, int max_candidates, int max_m
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_sim3_solver *h = new orbx_sim3_solver();
     h->device = device; h->maxCands = max_candidates; h->maxMatches = max_matches; h->maxIters = max_iterations;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }

@@ -162,18 +162,6 @@ __global__ __launch_bounds__(256) void k_triangulate(TriArgs T, const int32_t *_
     x3d[3 * (size_t)j] = X[0]; x3d[3 * (size_t)j + 1] = X[1]; x3d[3 * (size_t)j + 2] = X[2];
 }
 
-// inclusive scan over the 64 lanes of a wave with DPP row shifts and row broadcasts (gfx9)
-__device__ __forceinline__ int wave_scan_incl(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);      // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);      // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);      // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);      // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
 #define COLLECT_THREADS 1024
 #define COLLECT_PER 8      /* status bytes per thread and round: one 8-byte load */
 // total = neighbours run * stride slots (stride a multiple of 8), slot s = neighbour * stride + idx1.  out: count | nmatches[K] | entries.
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(COLLECT_THREADS) void k_collect(const uint8_t *__re
         int mine = 0;
 #pragma unroll
         for (int b = 0; b < COLLECT_PER; b++) { const unsigned st = (unsigned)(w >> (8 * b)) & 0xffu; mine += (st >= ORBX_NP_TRIANGULATED && st <= ORBX_NP_STEREO2) ? 1 : 0; }
-        const int incl = wave_scan_incl(mine);
+        const int incl = wave_incl_scan_dpp(mine);
         if (lane == 63) waveSum[wave] = incl;
         __syncthreads();
         int before = 0, all = 0;

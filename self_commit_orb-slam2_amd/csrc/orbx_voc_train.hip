@@ -164,12 +164,13 @@ template <int MODE> __global__ __launch_bounds__(256) void k_scan_reduce(int N, 
     u64 v = 0;
     for (int i = 0; i < 4; i++)
         if (base + i < N) v += vt_val<MODE>(base + i, src, c0);
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);      // (not wave_sum_xor: as a call the scheduler orders this kernel's address arithmetic differently)
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) blockSum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+// (an LDS tree with two barriers per step, not a wave scan: kept here so that k_scan_blocks / k_scan_apply keep their instructions; orbx_wave.h has the wave forms)
 __device__ __forceinline__ u64 vt_block_exclusive(u64 mine, u64 *sh)      // exclusive sum of `mine` over the 256 threads of the workgroup
 {
     const int t = threadIdx.x;
@@ -742,10 +743,7 @@ extern "C" int orbx_voc_trainer_create(int device, int k, int L, int max_descrip
     if (!vt_tree_fits(k, L)) { orbx_set_error("a complete tree with k = %d, L = %d has 2^31 nodes or more", k, L); return ORBX_ERR_ARG; }
     if (max_descriptors < 1 || max_descriptors > (1 << 26)) { orbx_set_error("max_descriptors = %d outside 1..2^26", max_descriptors); return ORBX_ERR_ARG; }
     if (max_images < 1) { orbx_set_error("max_images = %d < 1", max_images); return ORBX_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { orbx_set_error("no HIP device available: liborbx has no CPU fallback"); return ORBX_ERR_NODEVICE; }
-    if (device < 0 || device >= ndev) { orbx_set_error("device %d out of range", device); return ORBX_ERR_ARG; }
-    ORBX_HIP_CHECK(hipSetDevice(device));
+    if (const int rc = orbx_select_device(device)) return rc;
     orbx_voc_trainer *h = new orbx_voc_trainer();
     h->device = device; h->k = k; h->L = L; h->maxDesc = max_descriptors; h->maxImg = max_images;
     int rc = ORBX_OK;
