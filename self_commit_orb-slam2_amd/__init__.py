@@ -133,13 +133,39 @@ def synth_sequence(first_seed, count, width, height, views_per_scene=16, step=(3
     return out
 
 
+class _Handle:
+    """What the wrappers of the C-ABI handles share: _L (the library), _h (the handle), close() / __del__ through the class's
+    destroy symbol, and the out-parameter plumbing of the *_last_timing calls."""
+    _destroy = None            # name of the class's *_destroy symbol
+    _keeps_pointer = False     # close() leaves an empty c_void_p in _h (the classes that always did), not None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = ctypes.c_void_p() if self._keeps_pointer else None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _timing(self, symbol, *types):
+        """symbol(handle, &out...) with one out-parameter per ctypes type -> the tuple of their values"""
+        out = [t() for t in types]
+        _check(getattr(self._L, symbol)(self._h, *[ctypes.byref(o) for o in out]))
+        return tuple(o.value for o in out)
+
+
 class HostPyramid(ctypes.Structure):
     """orbx_host_pyramid (include/orbx.h)."""
     _fields_ = [("level", ctypes.c_void_p * 12), ("width", ctypes.c_int * 12), ("height", ctypes.c_int * 12), ("stride", ctypes.c_int * 12), ("nlevels", ctypes.c_int)]
 
 
-class ORBextractor:
+class ORBextractor(_Handle):
     """Mirror of ORB_SLAM2::ORBextractor (reference include/ORBextractor.h:92-161)."""
+    _destroy = "orbx_extractor_destroy"
+    _keeps_pointer = True
 
     def __init__(self, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, max_width=1280, max_height=1024,
                  max_batch=1, device=0, gauss_taps=None):
@@ -155,17 +181,6 @@ class ORBextractor:
         self.max_batch = max_batch
         self.capacity = self._L.orbx_extractor_capacity(self._h)
         self._last_size = None
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbx_extractor_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # --- getters (ORBextractor.h:118-158) ---
     def _tables(self):
@@ -546,8 +561,10 @@ class TriangulationParams(ctypes.Structure):
                 ("scale_factors", ctypes.c_void_p), ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int), ("check_orientation", ctypes.c_int)]
 
 
-class ORBmatcher:
+class ORBmatcher(_Handle):
     """Mirror of the Hamming paths of ORB_SLAM2::ORBmatcher (reference include/ORBmatcher.h:57-215)."""
+    _destroy = "orbx_matcher_destroy"
+    _keeps_pointer = True
     TH_LOW = 50
     TH_HIGH = 100
     HISTO_LENGTH = 30
@@ -559,17 +576,6 @@ class ORBmatcher:
         self.max_features, self.max_pairs = max_features, max_pairs
         self._h = ctypes.c_void_p()
         _check(self._L.orbx_matcher_create(device, max_features, max_pairs, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbx_matcher_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- single pair, host arrays ----
     def SearchByBoW(self, kpsA, descA, kpsB, descB, groupsA=None, groupsB=None, validA=None, validB=None, mode=0):
@@ -701,10 +707,8 @@ class ORBmatcher:
 
     def new_points_last_timing(self):
         """(device ms of the last chain, kernel launches, ms inside k_triangulate - 0 unless profile_kernels)"""
-        ms, tri, n = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
         self._L.orbx_new_points_last_timing.argtypes = [ctypes.c_void_p] * 4
-        _check(self._L.orbx_new_points_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(tri)))
-        return ms.value, n.value, tri.value
+        return self._timing("orbx_new_points_last_timing", ctypes.c_float, ctypes.c_int, ctypes.c_float)
 
     def FuseSearch(self, kf, points, chi2_gate=True):
         """Steps 2-3 of ORBmatcher::Fuse (reference src/ORBmatcher.cc:1093-1146 / 1258-1276): per map point the KeyFrame
@@ -968,23 +972,20 @@ class ORBmatcher:
         return m, d, n
 
     def last_timing(self):
-        t = ctypes.c_float()
-        _check(self._L.orbx_matcher_last_timing(self._h, ctypes.byref(t)))
-        return t.value
+        return self._timing("orbx_matcher_last_timing", ctypes.c_float)[0]
 
     def last_kernel_timing(self):
         """(distance kernels ms, greedy replay ms) of the SearchByBoW calls averaged by the last last_timing()."""
-        a, b = ctypes.c_float(), ctypes.c_float()
-        _check(self._L.orbx_matcher_last_kernel_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._timing("orbx_matcher_last_kernel_timing", ctypes.c_float, ctypes.c_float)
 
 
 # =====================================================================================
 # Optimizer::LocalBundleAdjustment numerical core over the C ABI
 # =====================================================================================
-class Vocabulary:
+class Vocabulary(_Handle):
     """DBoW2 vocabulary tree on the device: transform() == TemplatedVocabulary::transform
     (reference Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1262), i.e. Frame::ComputeBoW."""
+    _destroy = "orbx_vocabulary_destroy"
 
     @staticmethod
     def _bind(L):
@@ -1014,15 +1015,7 @@ class Vocabulary:
         if getattr(self, "_job", None) is not None and self._job.value:      # (a job only reads the vocabulary and must go first)
             self._L.orbx_bow_job_destroy(self._job)
             self._job = None
-        if getattr(self, "_h", None):
-            self._L.orbx_vocabulary_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def size(self):
         return self._L.orbx_vocabulary_words(self._h)
@@ -1097,10 +1090,11 @@ class VocTrainSummary(ctypes.Structure):
     _fields_ = [("num_nodes", ctypes.c_int), ("num_words", ctypes.c_int), ("unconverged_nodes", ctypes.c_int), ("passes_per_level", ctypes.c_int * VOC_MAX_L)]
 
 
-class VocabularyTrainer:
+class VocabularyTrainer(_Handle):
     """TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the device (reference
     Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:557-996): hierarchical k-means++ over 256-bit descriptors and the IDF weights, with the three
     stated differences of include/orbx.h (counter-hash draws, an empty cluster keeps its centre, a cap on the assignment passes)."""
+    _destroy = "orbx_voc_trainer_destroy"
 
     def __init__(self, k, L, max_descriptors, max_images, device=0):
         self._L = load_library()
@@ -1123,17 +1117,6 @@ class VocabularyTrainer:
         self.k, self.L = int(k), int(L)
         self._h = vp()
         _check(L_.orbx_voc_trainer_create(device, int(k), int(L), int(max_descriptors), int(max_images), ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_voc_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add(self, images):
         """one uint8 array (n_i, 32) per image; an image may be empty"""
@@ -1252,9 +1235,10 @@ class RgbdFrame(ctypes.Structure):
                 ("n_valid", ctypes.c_int), ("n_close", ctypes.c_int)]
 
 
-class FrameOps:
+class FrameOps(_Handle):
     """Frame::UndistortKeyPoints, ComputeImageBounds and AssignFeaturesToGrid on the device
     (reference src/Frame.cc:899-1004, 460-491) for one camera (mK, mDistCoef)."""
+    _destroy = "orbx_frame_ops_destroy"
 
     def __init__(self, fx, fy, cx, cy, dist, device=0):
         self._L = load_library()
@@ -1282,17 +1266,6 @@ class FrameOps:
         cam.ndist = len(dist)
         self._h = vp()
         _check(L.orbx_frame_ops_create(device, ctypes.byref(cam), ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_frame_ops_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def ComputeImageBounds(self, cols, rows):
         """mnMinX, mnMaxX, mnMinY, mnMaxY."""
@@ -1434,8 +1407,9 @@ class PoseProblem(ctypes.Structure):
                 ("world_points", ctypes.c_void_p), ("observations", ctypes.c_void_p), ("inv_sigma2", ctypes.c_void_p)]
 
 
-class PoseOptimizer:
+class PoseOptimizer(_Handle):
     """Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:363-605) for a batch of independent frames."""
+    _destroy = "orbx_pose_optimizer_destroy"
 
     def __init__(self, max_frames=64, max_features=4096, device=0):
         self._L = load_library()
@@ -1447,17 +1421,6 @@ class PoseOptimizer:
         L.orbx_pose_optimization.argtypes = [vp, ctypes.POINTER(PoseProblem), vp, vp, vp, vp]
         self._h = vp()
         _check(L.orbx_pose_optimizer_create(device, max_frames, max_features, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_pose_optimizer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def PoseOptimization(self, frames):
         """frames: list of dict(pose (4x4), cam (fx,fy,cx,cy,bf), Xw (n,3), obs (n,3; uR<0 mono), inv_sigma2 (n)).
@@ -1480,9 +1443,11 @@ class PoseOptimizer:
         return [dict(pose=po[i].reshape(4, 4), outlier=outl[i, :counts[i]], inliers=int(inl[i]), stats=st[i]) for i in range(B)]
 
 
-class Optimizer:
+class Optimizer(_Handle):
     """Mirror of the static ORB_SLAM2::Optimizer::LocalBundleAdjustment (reference include/Optimizer.h:112)
     on a flat window (dict as produced by lba_synth.make_window)."""
+    _destroy = "orbx_lba_destroy"
+    _keeps_pointer = True
 
     def __init__(self, max_keyframes=256, max_points=20000, max_edges=400000, device=0):
         self._L = load_library()
@@ -1494,17 +1459,6 @@ class Optimizer:
         self._L.orbx_lba_last_timing.argtypes = [vp, vp, vp]
         self._h = vp()
         _check(self._L.orbx_lba_create(device, max_keyframes, max_points, max_edges, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbx_lba_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def LocalBundleAdjustment(self, w, stop_flag=None, iterations=None, robust=True):
         K, P, E = w["K"], w["P"], w["E"]
@@ -1529,16 +1483,15 @@ class Optimizer:
         return self.LocalBundleAdjustment(w, stop_flag, iterations=iterations, robust=robust)
 
     def last_timing(self):
-        ms = ctypes.c_float()
-        fl = ctypes.c_double()
-        _check(self._L.orbx_lba_last_timing(self._h, ctypes.byref(ms), ctypes.byref(fl)))
-        return ms.value, fl.value
+        return self._timing("orbx_lba_last_timing", ctypes.c_float, ctypes.c_double)
 
 
-class BatchOptimizer:
+class BatchOptimizer(_Handle):
     """Optimizer::LocalBundleAdjustment on many independent windows with ONE handle (orbx_lba_solve_batch): every kernel launch
     covers all windows of a call, and every window's result is bit-identical to Optimizer().LocalBundleAdjustment(w).
     Capacities are per window; max_keyframes <= 341."""
+    _destroy = "orbx_lba_batch_destroy"
+    _keeps_pointer = True
 
     def __init__(self, max_windows, max_keyframes, max_points, max_edges, device=0):
         self._L = load_library()
@@ -1550,17 +1503,6 @@ class BatchOptimizer:
         self._L.orbx_lba_batch_last_timing.argtypes = [vp, vp, vp]
         self._h = vp()
         _check(self._L.orbx_lba_batch_create(device, max_windows, max_keyframes, max_points, max_edges, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbx_lba_batch_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def LocalBundleAdjustment(self, windows, stop_flags=None):
         """windows: list of dicts as produced by lba_synth.make_window; stop_flags: None, or one uint8 array (or None) per window.
@@ -1589,10 +1531,7 @@ class BatchOptimizer:
         return outs
 
     def last_timing(self):
-        ms = ctypes.c_float()
-        fl = ctypes.c_double()
-        _check(self._L.orbx_lba_batch_last_timing(self._h, ctypes.byref(ms), ctypes.byref(fl)))
-        return ms.value, fl.value
+        return self._timing("orbx_lba_batch_last_timing", ctypes.c_float, ctypes.c_double)
 
 
 class MapPointBatch(ctypes.Structure):
@@ -1605,9 +1544,10 @@ class MapPointResult(ctypes.Structure):
                 ("updated", ctypes.c_void_p)]
 
 
-class MapPointOps:
+class MapPointOps(_Handle):
     """MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:359-439, 477-521) for a batch of
     points with ragged observation lists (orbx_mappoint_refresh): one launch chain, the observations of a point in the caller's order."""
+    _destroy = "orbx_mappoint_ops_destroy"
 
     def __init__(self, max_points, max_obs_total, device=0):
         self._L = load_library()
@@ -1620,17 +1560,6 @@ class MapPointOps:
         L.orbx_mappoint_last_timing.argtypes = [vp, vp, vp]
         self._h = vp()
         _check(L.orbx_mappoint_ops_create(device, max_points, max_obs_total, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_mappoint_ops_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def refresh(self, obs_offset, desc, cam_center, pos, ref_center, ref_scale, top_scale, desc_valid=None):
         """obs_offset (M+1) int32; desc (T,32) uint8; cam_center (T,3); pos, ref_center (M,3); ref_scale, top_scale (M); desc_valid (T) uint8 or
@@ -1655,10 +1584,7 @@ class MapPointOps:
 
     def last_timing(self):
         """(device ms of the last call's kernels, kernel launches)"""
-        ms = ctypes.c_float()
-        n = ctypes.c_int()
-        _check(self._L.orbx_mappoint_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_mappoint_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class InitMatches(ctypes.Structure):
@@ -1700,9 +1626,10 @@ def initializer_sets(n, iterations, randint):
     return out
 
 
-class Initializer:
+class Initializer(_Handle):
     """Initializer (reference include/Initializer.h, src/Initializer.cc) on the device: Initialize as one launch chain (orbx_initialize), and its
     two inner loops on explicit inputs (ScoreModels = CheckHomography / CheckFundamental, CheckRT)."""
+    _destroy = "orbx_initializer_destroy"
 
     def __init__(self, sigma=1.0, iterations=200, max_matches=4096, device=0):
         self._L = load_library()
@@ -1718,17 +1645,6 @@ class Initializer:
         self.sigma, self.iterations, self.max_matches = float(sigma), int(iterations), int(max_matches)
         self._h = vp()
         _check(L.orbx_initializer_create(device, self.max_matches, self.iterations, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_initializer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _matches(keys1, keys2, matches12):
@@ -1815,10 +1731,7 @@ class Initializer:
 
     def last_timing(self):
         """(device ms of the last Initialize chain, kernel launches)"""
-        ms = ctypes.c_float()
-        n = ctypes.c_int()
-        _check(self._L.orbx_initializer_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_initializer_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class Sim3Problem(ctypes.Structure):
@@ -1914,9 +1827,10 @@ class Sim3Candidate:
         return np.float32(self.s12[self._best])
 
 
-class Sim3Solver:
+class Sim3Solver(_Handle):
     """Sim3Solver (reference include/Sim3Solver.h, src/Sim3Solver.cc) on the device: every RANSAC iteration of every loop candidate in one launch
     chain (orbx_sim3_solve), and CheckInliers on explicit transformations (CheckModels)."""
+    _destroy = "orbx_sim3_solver_destroy"
 
     def __init__(self, max_candidates=8, max_matches=2048, max_iterations=300, device=0):
         self._L = load_library()
@@ -1932,17 +1846,6 @@ class Sim3Solver:
         self.max_candidates, self.max_matches, self.max_iterations = int(max_candidates), int(max_matches), int(max_iterations)
         self._h = vp()
         _check(L.orbx_sim3_solver_create(device, self.max_candidates, self.max_matches, self.max_iterations, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_sim3_solver_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _problem(c, keep):
@@ -2024,10 +1927,7 @@ class Sim3Solver:
 
     def last_timing(self):
         """(device ms of the last Solve chain, kernel launches)"""
-        ms = ctypes.c_float()
-        n = ctypes.c_int()
-        _check(self._L.orbx_sim3_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_sim3_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class Sim3OptProblem(ctypes.Structure):
@@ -2078,8 +1978,9 @@ def sim3_opt_problem(candidate, solved, matches, iteration=None):
     return p
 
 
-class Sim3Optimizer:
+class Sim3Optimizer(_Handle):
     """Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1364-1590) on the device: every problem of a call in one launch (orbx_optimize_sim3)."""
+    _destroy = "orbx_sim3_optimizer_destroy"
 
     def __init__(self, max_problems=8, max_pairs=1024, device=0):
         self._L = load_library()
@@ -2094,17 +1995,6 @@ class Sim3Optimizer:
         self.max_problems, self.max_pairs = int(max_problems), int(max_pairs)
         self._h = vp()
         _check(L.orbx_sim3_optimizer_create(device, self.max_problems, self.max_pairs, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_sim3_optimizer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _problem(c, keep, th2, fix_scale):
@@ -2175,10 +2065,7 @@ class Sim3Optimizer:
 
     def last_timing(self):
         """(device ms of the last OptimizeSim3 launch chain, kernel launches)"""
-        ms = ctypes.c_float()
-        n = ctypes.c_int()
-        _check(self._L.orbx_sim3_optimizer_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_sim3_optimizer_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class PnPProblem(ctypes.Structure):
@@ -2296,9 +2183,10 @@ class PnPCandidate:
         return T, vb, k
 
 
-class PnPsolver:
+class PnPsolver(_Handle):
     """PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc) on the device: every RANSAC iteration and every Refine of every relocalisation
     candidate in one launch chain (orbx_pnp_solve); CheckInliers on explicit poses (CheckModels) and compute_pose on explicit sets (EPnP)."""
+    _destroy = "orbx_pnp_solver_destroy"
 
     def __init__(self, max_candidates=8, max_matches=2048, max_iterations=300, device=0):
         self._L = load_library()
@@ -2315,17 +2203,6 @@ class PnPsolver:
         self.max_candidates, self.max_matches, self.max_iterations = int(max_candidates), int(max_matches), int(max_iterations)
         self._h = vp()
         _check(L.orbx_pnp_solver_create(device, self.max_candidates, self.max_matches, self.max_iterations, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_pnp_solver_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _problem(c, keep, params):
@@ -2451,10 +2328,7 @@ class PnPsolver:
 
     def last_timing(self):
         """(device ms of the last Solve chain, kernel launches)"""
-        ms = ctypes.c_float()
-        n = ctypes.c_int()
-        _check(self._L.orbx_pnp_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_pnp_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class EssentialGraphProblem(ctypes.Structure):
@@ -2560,8 +2434,9 @@ def essential_graph_edges(keyframes, loop_kf, cur_kf, corrected, non_corrected, 
     return dict(ids=np.array(ids, np.int64), est=est, meas=meas, fixed=index[loop_kf], edges=np.array(edges, np.int32).reshape(-1, 3))
 
 
-class EssentialGraphOptimizer:
+class EssentialGraphOptimizer(_Handle):
     """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1017-1339) on the device (orbx_optimize_essential_graph)."""
+    _destroy = "orbx_essential_graph_destroy"
 
     def __init__(self, max_keyframes, max_edges, max_points=0, max_fill_blocks=None, device=0):
         self._L = load_library()
@@ -2580,17 +2455,6 @@ class EssentialGraphOptimizer:
         self._n = 0
         self._h = vp()
         _check(L.orbx_essential_graph_create(device, self.max_keyframes, self.max_edges, self.max_points, self.max_fill_blocks, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_essential_graph_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _problem(g, keep, fix_scale, iterations, lambda_init):
@@ -2663,10 +2527,7 @@ class EssentialGraphOptimizer:
 
     def last_timing(self):
         """(device ms of the last OptimizeEssentialGraph chain, kernel launches, ms inside the solve kernel)"""
-        ms, sv = ctypes.c_float(), ctypes.c_float()
-        n = ctypes.c_int()
-        _check(self._L.orbx_essential_graph_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(sv)))
-        return ms.value, n.value, sv.value
+        return self._timing("orbx_essential_graph_last_timing", ctypes.c_float, ctypes.c_int, ctypes.c_float)
 
 
 KFDB_LOOP, KFDB_RELOC = 0, 1
@@ -2700,11 +2561,12 @@ def _kfdb_bow(bow):
     return w, v
 
 
-class KeyFrameDatabase:
+class KeyFrameDatabase(_Handle):
     """KeyFrameDatabase (reference src/KeyFrameDatabase.cc) on the device: add / erase / clear as there, set_covisibles pushes GetBestCovisibilityKeyFrames(10)
     of a keyframe (a query reads the covisibles as last pushed), DetectLoopCandidates / DetectRelocalizationCandidates return the candidate ids in the
     reference's order (full=True: every field of orbx_kfdb_result as a dict), query() runs several queries in one call.  A bow is (words, values) with ascending
     words, or a dict word -> value."""
+    _destroy = "orbx_kfdb_destroy"
 
     def __init__(self, n_words, max_keyframes, max_entries, max_queries=8, max_query_words=4096, device=0):
         self._L = load_library()
@@ -2724,17 +2586,6 @@ class KeyFrameDatabase:
         self.n_words, self.max_keyframes, self.max_entries = int(n_words), int(max_keyframes), int(max_entries)
         self._h = vp()
         _check(L.orbx_kfdb_create(device, self.n_words, self.max_keyframes, self.max_entries, int(max_queries), int(max_query_words), ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_kfdb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add(self, kf_id, bow):
         w, v = _kfdb_bow(bow)
@@ -2826,9 +2677,7 @@ class KeyFrameDatabase:
 
     def last_timing(self):
         """(device ms of the last query chain, kernel launches)"""
-        ms, n = ctypes.c_float(), ctypes.c_int()
-        _check(self._L.orbx_kfdb_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_kfdb_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class CovisSlice(ctypes.Structure):
@@ -2900,10 +2749,11 @@ def covis_marshal(map_slice, keep):
                       p["list_point"], p["list_octave"], p["list_close"]), a
 
 
-class Covisibility:
+class Covisibility(_Handle):
     """The counting of KeyFrame::UpdateConnections (reference src/KeyFrame.cc:386-507), Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1895-1955) and
     LocalMapping::KeyFrameCulling (src/LocalMapping.cc:873-956) on the device, over a slice of the map (covis_slice); keyframes are slot numbers, their
     std::map order is the slice's kf_rank.  Exact integers; AddConnection, the spanning tree and SetBadFlag stay with the caller."""
+    _destroy = "orbx_covis_destroy"
 
     def __init__(self, device=0):
         self._L = load_library()
@@ -2917,17 +2767,6 @@ class Covisibility:
         L.orbx_covis_last_timing.argtypes = [vp, vp, vp]
         self._h = vp()
         _check(L.orbx_covis_create(device, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_covis_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def UpdateConnections(self, map_slice, th=15, counter_capacity=None, conn_capacity=None):
         """All lists of the slice in one call -> dict(counter_offset, conn_offset (Q+1); counter_kf, counter_weight: KFcounter in ascending rank;
@@ -2974,9 +2813,7 @@ class Covisibility:
 
     def last_timing(self):
         """(device ms of the last call's chain, kernel launches)"""
-        ms, n = ctypes.c_float(), ctypes.c_int()
-        _check(self._L.orbx_covis_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_covis_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 class LoopSim3Problem(ctypes.Structure):
@@ -3037,12 +2874,13 @@ def _loop_outputs(fields, sizes):
     return o, (lambda: {k: o[k][:sizes[s]] for k, dt, s, w in fields})
 
 
-class LoopCorrection:
+class LoopCorrection(_Handle):
     """The two passes of the loop closer that move the map, on the device: CorrectLoop = the Sim3 propagation of LoopClosing::CorrectLoop (reference
     src/LoopClosing.cc:617-716: CorrectedSim3 / NonCorrectedSim3, every point of the group moved once by the first keyframe that reaches it, its
     UpdateNormalAndDepth, the SE3 poses), PropagateGBA = the map update after global BA (:930-1003: poses through the spanning tree, then every point).
     Keyframes are slot numbers; floats are bit for bit the reference's on the project's OpenCV stand-in.  Replace, AddObservation, UpdateConnections
     and the mutexes stay with the caller."""
+    _destroy = "orbx_loop_destroy"
 
     def __init__(self, device=0):
         self._L = load_library()
@@ -3056,17 +2894,6 @@ class LoopCorrection:
         L.orbx_loop_last_timing.argtypes = [vp, vp, vp]
         self._h = vp()
         _check(L.orbx_loop_create(device, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_loop_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def CorrectLoop(self, problem):
         """problem: dict(tcw (NK,12), ow (NK,3), group_kf (G), current, scw (8), list_offset (G+1), list_point, pos (M,3), point_bad, point_done, point_ref,
@@ -3095,9 +2922,7 @@ class LoopCorrection:
 
     def last_timing(self):
         """(device ms of the last call's launch chain, kernel launches)"""
-        ms, n = ctypes.c_float(), ctypes.c_int()
-        _check(self._L.orbx_loop_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_loop_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3143,11 +2968,13 @@ def rectify_maps(K, D, R, P, w, h):
     return mx, my
 
 
-class ImagePrep:
+class ImagePrep(_Handle):
     """What the reference does to a camera image in front of ORBextractor::operator(), on the device: cvtColor to grey (Tracking::GrabImage*,
     src/Tracking.cc:250-278, 311-326, 369-384) and cv::remap through the maps of cv::initUndistortRectifyMap (Examples/Stereo/stereo_euroc.cc:124-134,
     181-188).  The grey, rectified frames land in a device buffer in the padded layout ORBextractor.run_device prefers.  Colour frames that are also
     rectified are converted to grey first, then remapped (one launch).  Parity with OpenCV is unpinned; tests/imgprep_ref.py restates the arithmetic."""
+    _destroy = "orbx_image_prep_destroy"
+    _keeps_pointer = True
 
     def __init__(self, max_width, max_height, max_batch, gray_coef=None, gray_shift=0, device=0):
         self._L = _bind_image_prep(load_library())
@@ -3159,17 +2986,6 @@ class ImagePrep:
         self._h = ctypes.c_void_p()
         _check(self._L.orbx_image_prep_create(ctypes.byref(cfg), ctypes.byref(self._h)))
         self.max_batch = max_batch
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbx_image_prep_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_maps(self, side, mx, my):
         """The two CV_32FC1 maps of `side` (0 left, 1 right), converted once to fixed point on the device."""
@@ -3226,6 +3042,4 @@ class ImagePrep:
 
     def last_timing(self):
         """(device ms of the last call's kernel, kernel launches)"""
-        ms, n = ctypes.c_float(), ctypes.c_int()
-        _check(self._L.orbx_image_prep_last_timing(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+        return self._timing("orbx_image_prep_last_timing", ctypes.c_float, ctypes.c_int)

@@ -16,7 +16,7 @@
 
 #include <vector>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 
 namespace {
 
@@ -108,19 +108,18 @@ __global__ __launch_bounds__(256) void k_bow_ranks(const int32_t *__restrict__ w
 
 }  // namespace
 
-struct orbx_vocabulary {
-    int device = 0, k = 0, L = 0, numNodes = 0, numWords = 0;
-    hipStream_t stream = nullptr;   // host-array form only; the device form runs on the extractor's stream
-    OrbxDevBuf<VocNode> nodes;
-    OrbxDevBuf<int32_t> childList;
-    OrbxDevBuf<uint4> childDesc;
-    OrbxDevBuf<double> nodeWeight;
+struct orbx_vocabulary : OrbxHandle {      // (the stream: host-array form only; the device form runs on the extractor's stream)
+    int k = 0, L = 0, numNodes = 0, numWords = 0;
+    OrbxOwnedBuf<VocNode> nodes;
+    OrbxOwnedBuf<int32_t> childList;
+    OrbxOwnedBuf<uint4> childDesc;
+    OrbxOwnedBuf<double> nodeWeight;
     // results, double buffered in lockstep with the extractor's result buffers
-    OrbxDevBuf<int32_t> word[2], node[2];
-    OrbxDevBuf<double> weight[2];
+    OrbxOwnedBuf<int32_t> word[2], node[2];
+    OrbxOwnedBuf<double> weight[2];
     int cur = 0, lastBatch = 0, lastCap = 0;
     OrbxCallBox box;   // host-array form: descriptors in, word / node / weight out through mapped pinned memory
-    OrbxDevBuf<int32_t> hostWord, hostNode;   // host-array _sorted form: the device copy k_bow_ranks reads - its own, never the device form's word[] / node[] (a
+    OrbxOwnedBuf<int32_t> hostWord, hostNode;   // host-array _sorted form: the device copy k_bow_ranks reads - its own, never the device form's word[] / node[] (a
                                               // host call between two device calls must leave the last batch's results, and the pointers handed out, alone)
 };
 
@@ -149,12 +148,10 @@ extern "C" int orbx_vocabulary_create(int device, int k, int L, int num_nodes, c
     }
     std::vector<uint8_t> cdesc(childList.size() * 32);
     for (size_t c = 0; c < childList.size(); c++) memcpy(&cdesc[32 * c], descriptors + 32 * (size_t)childList[c], 32);
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_vocabulary *v = new orbx_vocabulary();
-    v->device = device; v->k = k; v->L = L; v->numNodes = num_nodes; v->numWords = words;
+    v->k = k; v->L = L; v->numNodes = num_nodes; v->numWords = words;
     int rc;
-    if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) { delete v; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    if ((rc = v->nodes.ensure(nodes.size())) || (rc = v->childList.ensure(childList.size())) || (rc = v->childDesc.ensure(childList.size() * 2)) ||
+    if ((rc = v->open(device)) || (rc = v->nodes.ensure(nodes.size())) || (rc = v->childList.ensure(childList.size())) || (rc = v->childDesc.ensure(childList.size() * 2)) ||
         (rc = v->nodeWeight.ensure((size_t)num_nodes))) {
         orbx_vocabulary_destroy(v);
         return rc;
@@ -167,15 +164,7 @@ extern "C" int orbx_vocabulary_create(int device, int k, int L, int num_nodes, c
     return ORBX_OK;
 }
 
-extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v)
-{
-    if (!v) return;
-    (void)hipSetDevice(v->device);
-    if (v->stream) { (void)hipStreamSynchronize(v->stream); (void)hipStreamDestroy(v->stream); }
-    v->nodes.release(); v->childList.release(); v->childDesc.release(); v->nodeWeight.release(); v->box.release(); v->hostWord.release(); v->hostNode.release();
-    for (int b = 0; b < 2; b++) { v->word[b].release(); v->node[b].release(); v->weight[b].release(); }
-    delete v;
-}
+extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v) { orbx_destroy_handle(v); }
 
 extern "C" int orbx_vocabulary_words(const orbx_vocabulary *v) { return v ? v->numWords : ORBX_ERR_ARG; }
 
@@ -188,8 +177,7 @@ static int launch_transform(orbx_vocabulary *v, hipStream_t stream, const uint8_
     if ((rc = v->word[b].ensure(n)) || (rc = v->node[b].ensure(n)) || (rc = v->weight[b].ensure(n))) return rc;
     hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((cap + 255) / 256), (unsigned)batch), dim3(256), 0, stream, v->nodes.p, v->childList.p, v->childDesc.p,
                        v->nodeWeight.p, v->L - levelsup, desc, counts, cap, v->word[b].p, v->node[b].p, v->weight[b].p, (int32_t *)nullptr, (int32_t *)nullptr, (unsigned *)nullptr, (unsigned long long *)nullptr, 0ull);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     v->lastBatch = batch; v->lastCap = cap;
     return ORBX_OK;
 }
@@ -255,8 +243,7 @@ static int bow_transform_host(orbx_vocabulary *v, const uint8_t *descriptors, in
     if (sorted)
         hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, v->stream, (const int32_t *)v->hostWord.p, (const int32_t *)v->hostNode.p, n, bx.outDev<int32_t>(offBW),
                            bx.outDev<int32_t>(offBN), bx.outDev<int32_t>(offF), bx.counter, bx.flagDev, seq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(v->stream)) != ORBX_OK) return rc;
     if (word) memcpy(word, bx.outHost<int32_t>(0), N * 4);
     if (node) memcpy(node, bx.outHost<int32_t>(offNode), N * 4);
@@ -283,12 +270,10 @@ extern "C" int orbx_bow_transform_sorted(orbx_vocabulary *v, const uint8_t *desc
 }
 
 // ---- the latency form (include/orbx.h: orbx_bow_job_*) ----
-struct orbx_bow_job {
+struct orbx_bow_job : OrbxHandle {      // (its own copy of the device: a job may be destroyed after its vocabulary - the shim does, when a vocabulary object was replaced at the same address)
     orbx_vocabulary *v = nullptr;
-    int device = 0;                 // (its own copy: a job may be destroyed after its vocabulary - the shim does, when a vocabulary object was replaced at the same address)
-    hipStream_t stream = nullptr;
     OrbxCallBox box;
-    OrbxDevBuf<int32_t> word, node;
+    OrbxOwnedBuf<int32_t> word, node;
     int pendingN = -1;      // -1: nothing begun
     size_t offNode = 0, offW = 0, offBW = 0, offBN = 0, offF = 0;
 };
@@ -297,22 +282,14 @@ extern "C" int orbx_bow_job_create(orbx_vocabulary *v, orbx_bow_job **out)
 {
     if (!v || !out) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    ORBX_HIP_CHECK(hipSetDevice(v->device));
     orbx_bow_job *j = new orbx_bow_job();
-    j->v = v; j->device = v->device;
-    if (hipStreamCreateWithFlags(&j->stream, hipStreamNonBlocking) != hipSuccess) { delete j; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
+    j->v = v;
+    if (const int rc = j->open(v->device)) { orbx_destroy_handle(j); return rc; }
     *out = j;
     return ORBX_OK;
 }
 
-extern "C" void orbx_bow_job_destroy(orbx_bow_job *j)
-{
-    if (!j) return;
-    (void)hipSetDevice(j->device);
-    if (j->stream) { (void)hipStreamSynchronize(j->stream); (void)hipStreamDestroy(j->stream); }
-    j->box.release(); j->word.release(); j->node.release();
-    delete j;
-}
+extern "C" void orbx_bow_job_destroy(orbx_bow_job *j) { orbx_destroy_handle(j); }
 
 extern "C" int orbx_bow_job_begin(orbx_bow_job *j, orbx_extractor *ext, int levelsup)
 {
@@ -341,8 +318,7 @@ extern "C" int orbx_bow_job_begin(orbx_bow_job *j, orbx_extractor *ext, int leve
                        (unsigned long long *)nullptr, seq);
     hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, j->stream, (const int32_t *)j->word.p, (const int32_t *)j->node.p, n, bx.outDev<int32_t>(j->offBW),
                        bx.outDev<int32_t>(j->offBN), bx.outDev<int32_t>(j->offF), bx.counter, bx.flagDev, seq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     j->pendingN = n;
     return ORBX_OK;
 }

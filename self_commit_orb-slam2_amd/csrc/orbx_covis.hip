@@ -29,7 +29,7 @@
 #include <numeric>
 #include <vector>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 
 #define COVIS_THREADS 256
 #define COVIS_LDS_NK ORBX_COVIS_LDS_KEYFRAMES      /* 12 bytes of LDS per slot: 48 KB per workgroup at the limit */
@@ -228,52 +228,27 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_cull_apply(CvDev D, int
 
 }  // namespace
 
-struct orbx_covis {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct orbx_covis : OrbxHandle {
+    OrbxCallTimer timer;
     OrbxCallBox box;
-    OrbxDevBuf<uint8_t> arena;              // the call's inputs in device memory
-    OrbxDevBuf<unsigned long long> work;    // keys | global histogram rows | culling state
+    OrbxOwnedBuf<uint8_t> arena;              // the call's inputs in device memory
+    OrbxOwnedBuf<unsigned long long> work;    // keys | global histogram rows | culling state
     std::vector<int32_t> order, pos, outOff;
     std::vector<uint8_t> seen;
-    bool timed = false;
-    int launches = 0;
 };
 
 extern "C" int orbx_covis_create(int device, orbx_covis **out)
 {
     if (!out) { orbx_set_error("orbx_covis_create: NULL argument"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_covis *h = new orbx_covis();
-    h->device = device;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-        orbx_set_error("covisibility: stream / event creation failed");
-        orbx_covis_destroy(h);
-        return ORBX_ERR_HIP;
-    }
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create())) { orbx_destroy_handle(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_covis_destroy(orbx_covis *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    h->box.release(); h->arena.release(); h->work.release();
-    delete h;
-}
-
-#define CV_LAUNCH_CHECK()                                                                                              \
-    do {                                                                                                               \
-        const hipError_t le_ = hipGetLastError();                                                                      \
-        if (le_ != hipSuccess) { orbx_set_error("covisibility kernel launch failed: %s", hipGetErrorString(le_)); return ORBX_ERR_HIP; } \
-        h->launches++;                                                                                                 \
-    } while (0)
+extern "C" void orbx_covis_destroy(orbx_covis *h) { orbx_destroy_handle(h); }
 
 namespace {
 
@@ -362,7 +337,7 @@ int cv_stage(orbx_covis *h, const orbx_covis_slice *s, bool culling, size_t outB
     }
     const size_t n16 = bx.used / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    CV_LAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     return ORBX_OK;
 }
 
@@ -375,7 +350,7 @@ extern "C" int orbx_covis_update_connections(orbx_covis *h, const orbx_covis_sli
     if ((rc = cv_validate(h, s, false, "orbx_covis_update_connections")) != ORBX_OK) return rc;
     if (out->counter_capacity < 0 || out->conn_capacity < 0) { orbx_set_error("orbx_covis_update_connections: negative capacity"); return ORBX_ERR_ARG; }
     const int NK = s->num_keyframes, Q = s->num_lists;
-    h->timed = false; h->launches = 0;
+    h->timer.timed = false;
     // a list's counter has at most min(NK, observations under its entries) keyframes (at least 1 pair: the below-threshold fallback writes one)
     h->outOff.resize((size_t)Q + 1);
     long long tot = 0;
@@ -394,7 +369,7 @@ extern "C" int orbx_covis_update_connections(orbx_covis *h, const orbx_covis_sli
     const size_t histWords = lds ? 0 : ((size_t)grid * (size_t)NK + 1) / 2;      // int32 rows inside the u64 work buffer
     if ((rc = h->work.ensure((lds ? 1 : P) + histWords)) != ORBX_OK) return rc;
     CvDev D = {};
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     if ((rc = cv_stage(h, s, false, outBytes, D)) != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
     D.th = th;
@@ -403,9 +378,8 @@ extern "C" int orbx_covis_update_connections(orbx_covis *h, const orbx_covis_sli
     const unsigned long long seq = bx.arm();
     if (lds) hipLaunchKernelGGL(k_covis_connect<true>, dim3(grid), dim3(COVIS_THREADS), 4 * (size_t)((NK + 1) & ~1) + 8 * (size_t)NK, h->stream, D, bx.counter, bx.flagDev, seq);
     else hipLaunchKernelGGL(k_covis_connect<false>, dim3(grid), dim3(COVIS_THREADS), 0, h->stream, D, bx.counter, bx.flagDev, seq);
-    CV_LAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
 
     const int32_t *head = bx.outHost<int32_t>(oHead), *cnt = bx.outHost<int32_t>(oCnt), *conn = bx.outHost<int32_t>(oConn);
@@ -444,7 +418,7 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
     if (!out) { orbx_set_error("orbx_covis_keyframe_culling: NULL argument"); return ORBX_ERR_ARG; }
     if ((rc = cv_validate(h, s, true, "orbx_covis_keyframe_culling")) != ORBX_OK) return rc;
     const int NK = s->num_keyframes, M = s->num_points, Q = s->num_lists;
-    h->timed = false; h->launches = 0;
+    h->timer.timed = false;
     h->outOff.assign((size_t)Q + 1, 0);
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     const size_t m = (size_t)M, oRec = 0, oRes = 256, oObs = oRes + OrbxCallBox::padded(12 * (size_t)Q), oBad = oObs + OrbxCallBox::padded(4 * m), outBytes = oBad + OrbxCallBox::padded(m);
@@ -452,7 +426,7 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
     const size_t wObs = 0, wFirst = OrbxCallBox::padded(4 * m), wState = wFirst + 256, wErased = wState + OrbxCallBox::padded(m), wBytes = wErased + OrbxCallBox::padded((size_t)NK);
     if ((rc = h->work.ensure(wBytes / 8)) != ORBX_OK) return rc;
     CvDev D = {};
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     if ((rc = cv_stage(h, s, true, outBytes, D)) != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
     uint8_t *W = (uint8_t *)h->work.p;
@@ -460,22 +434,21 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
     D.record = bx.outDev<int32_t>(oRec); D.res = bx.outDev<int32_t>(oRes); D.outObs = bx.outDev<int32_t>(oObs); D.outBad = bx.outDev<uint8_t>(oBad);
     const unsigned pointBlocks = (unsigned)((std::max(std::max(M, NK), 1) + COVIS_THREADS - 1) / COVIS_THREADS);
     hipLaunchKernelGGL(k_covis_cull_init, dim3(pointBlocks), dim3(COVIS_THREADS), 0, h->stream, D);
-    CV_LAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     for (int first = 0; first < Q;) {
         unsigned long long seq = bx.arm();
         hipLaunchKernelGGL(k_covis_cull_eval, dim3((unsigned)(Q - first)), dim3(COVIS_THREADS), 0, h->stream, D, first, bx.counter, bx.flagDev, seq);
-        CV_LAUNCH_CHECK();
-        ORBX_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-        h->timed = true;
+        ORBX_LAUNCH_COUNT(h->timer);
+        if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
         if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
         const int f = *bx.outHost<int32_t>(oRec);
         if (f < first || f >= Q) break;      // (INT_MAX: nothing behind `first` is culled and erasable)
         first = f + 1;
         seq = first < Q ? 0 : bx.arm();      // the last list: no round follows, the erase itself publishes
         hipLaunchKernelGGL(k_covis_cull_apply, dim3((unsigned)((std::max(M, 1) + COVIS_THREADS - 1) / COVIS_THREADS)), dim3(COVIS_THREADS), 0, h->stream, D, f, bx.counter, bx.flagDev, seq);
-        CV_LAUNCH_CHECK();
+        ORBX_LAUNCH_COUNT(h->timer);
         if (seq) {
-            ORBX_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+            if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
             if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
         }
     }
@@ -493,13 +466,5 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
 extern "C" int orbx_covis_last_timing(orbx_covis *h, float *kernel_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL covisibility handle"); return ORBX_ERR_ARG; }
-    float ms = 0.f;
-    if (h->timed) {
-        ORBX_HIP_CHECK(hipSetDevice(h->device));
-        ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
-        ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    }
-    if (kernel_ms) *kernel_ms = ms;
-    if (launches) *launches = h->timed ? h->launches : 0;
-    return ORBX_OK;
+    return h->timer.read(h->device, kernel_ms, launches, nullptr);
 }

@@ -28,7 +28,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "orbx_match_internal.h"
+#include "orbx_handle.h"
 #include "orbx_sim3_group.h"
 
 #define EG_THREADS 256
@@ -532,16 +532,14 @@ struct EgSymbolic {
     std::vector<int32_t> pos, order, colPtr, rowIdx, aPtr, aItem;
 };
 
-struct orbx_essential_graph {
-    int device = 0, maxKf = 0, maxEdges = 0, maxPoints = 0, maxFill = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false, linearized = false;
-    int launches = 0;
+struct orbx_essential_graph : OrbxHandle {
+    int maxKf = 0, maxEdges = 0, maxPoints = 0, maxFill = 0;
+    OrbxCallTimer timer;
+    bool linearized = false;
     double solveTicks = 0.0;
     OrbxCallBox box;
-    OrbxDevBuf<uint8_t> arena;       // the staged inputs on the device
-    OrbxDevBuf<double> work;         // every working array of a call
+    OrbxOwnedBuf<uint8_t> arena;       // the staged inputs on the device
+    OrbxOwnedBuf<double> work;         // every working array of a call
     EgSymbolic sym;                  // of the last call (orbx_essential_graph_solve runs on it)
     EgDev dev;
     std::vector<int32_t> edges;      // of the last linearisation
@@ -684,8 +682,7 @@ int eg_stage(orbx_essential_graph *h, const orbx_essential_graph_problem *P, con
     if (!S.aItem.empty()) memcpy(bx.in + oAi, S.aItem.data(), 4 * S.aItem.size());
     const size_t n16 = total / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    MLAUNCH_CHECK();
-    h->launches++;
+    ORBX_LAUNCH_COUNT(h->timer);
     // working arrays, in doubles (an OsSim3 is eight)
     size_t w = 0;
     auto take = [&](size_t n) { const size_t at0 = w; w += (n + 31) & ~(size_t)31; return at0; };
@@ -704,8 +701,7 @@ int eg_stage(orbx_essential_graph *h, const orbx_essential_graph_problem *P, con
     D.b = Wk + wb; D.y = Wk + wy; D.d = Wk + wd; D.xs = Wk + wxs; D.x = Wk + wx; D.dev = Wk + wdev;
     ORBX_HIP_CHECK(hipMemsetAsync(D.x, 0, 8 * (7 * nf + 32), h->stream));      // the solver's x and the solve record
     hipLaunchKernelGGL(k_eg_init, dim3((unsigned)eg_blocks(std::max(P->n, P->n_edges))), dim3(EG_THREADS), 0, h->stream, D);
-    MLAUNCH_CHECK();
-    h->launches++;
+    ORBX_LAUNCH_COUNT(h->timer);
     return ORBX_OK;
 }
 
@@ -714,21 +710,19 @@ int eg_chi(orbx_essential_graph *h, int buf, size_t recOff, int solved)
 {
     OrbxCallBox &bx = h->box;
     hipLaunchKernelGGL(k_eg_error, dim3((unsigned)eg_blocks(h->dev.E)), dim3(EG_THREADS), 0, h->stream, h->dev, buf);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(EG_THREADS), 0, h->stream, h->dev, bx.outDev<EgRecord>(recOff), solved, bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
-    h->launches += 2;
+    ORBX_LAUNCH_COUNT(h->timer);
     return ORBX_OK;
 }
 
 int eg_linearize(orbx_essential_graph *h, int buf)
 {
     hipLaunchKernelGGL(k_eg_linearize, dim3((unsigned)eg_blocks(16 * h->dev.E)), dim3(EG_THREADS), 0, h->stream, h->dev, buf);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)((h->dev.nf + h->dev.nOff + 3) / 4)), dim3(EG_THREADS), 0, h->stream, h->dev);
-    MLAUNCH_CHECK();
-    h->launches += 2;
+    ORBX_LAUNCH_COUNT(h->timer);
     return ORBX_OK;
 }
 }  // namespace
@@ -740,25 +734,15 @@ extern "C" int orbx_essential_graph_create(int device, int max_keyframes, int ma
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_essential_graph *h = new orbx_essential_graph();
-    h->device = device; h->maxKf = max_keyframes; h->maxEdges = max_edges; h->maxPoints = max_points; h->maxFill = max_fill_blocks;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev[0]); (void)hipEventCreate(&h->ev[1]);
+    h->maxKf = max_keyframes; h->maxEdges = max_edges; h->maxPoints = max_points; h->maxFill = max_fill_blocks;
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create())) { orbx_destroy_handle(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_essential_graph_destroy(orbx_essential_graph *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->box.release(); h->arena.release(); h->work.release();
-    for (int i = 0; i < 2; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void orbx_essential_graph_destroy(orbx_essential_graph *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx_essential_graph_problem *P, const orbx_essential_graph_result *R)
 {
@@ -773,10 +757,10 @@ extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx
     auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
     const size_t oRec = 0, oEst = padded(sizeof(EgRecord) * 2), oInv = oEst + padded(64 * N), oTiw = oInv + padded(64 * N), oPts = oTiw + padded(48 * N),
                  outBytes = oPts + padded(12 * M);
-    h->launches = 0; h->solveTicks = 0.0;
+    h->solveTicks = 0.0;
     OrbxCallBox &bx = h->box;
     if (bx.pending) { ORBX_HIP_CHECK(hipStreamSynchronize(h->stream)); bx.pending = false; }
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     if ((rc = eg_stage(h, P, nullptr, outBytes)) != ORBX_OK) return rc;
     const EgRecord *rec = bx.outHost<EgRecord>(oRec);
 
@@ -792,8 +776,7 @@ extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx
             int qmax = 0;
             do {
                 hipLaunchKernelGGL(k_eg_solve, dim3(1), dim3(EG_SOLVE_THREADS), 0, h->stream, h->dev, lambda, buf, 1);
-                MLAUNCH_CHECK();
-                h->launches++;
+                ORBX_LAUNCH_COUNT(h->timer);
                 if ((rc = eg_chi(h, buf ^ 1, oRec, 1)) != ORBX_OK) return rc;
                 if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
                 h->solveTicks += (double)rec->ticks;
@@ -831,10 +814,8 @@ extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx
     O.est = bx.outDev<OsSim3>(oEst); O.inv = bx.outDev<OsSim3>(oInv); O.tiw = bx.outDev<float>(oTiw); O.points = bx.outDev<float>(oPts);
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_eg_writeback, dim3((unsigned)eg_blocks(std::max(P->n, P->n_points))), dim3(EG_THREADS), 0, h->stream, h->dev, buf, O, bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
-    h->launches++;
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     if (R->est) memcpy(R->est, bx.out + oEst, 64 * N);
     if (R->inv) memcpy(R->inv, bx.out + oInv, 64 * N);
@@ -859,7 +840,7 @@ extern "C" int orbx_essential_graph_linearize(orbx_essential_graph *h, const orb
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     OrbxCallBox &bx = h->box;
     if (bx.pending) { ORBX_HIP_CHECK(hipStreamSynchronize(h->stream)); bx.pending = false; }
-    h->launches = 0;
+    h->timer.launches = 0;
     if ((rc = eg_stage(h, P, at, sizeof(EgRecord))) != ORBX_OK) return rc;
     const size_t N = (size_t)P->n, E = (size_t)P->n_edges;
     const EgSymbolic &S = h->sym;
@@ -915,7 +896,7 @@ extern "C" int orbx_essential_graph_solve(orbx_essential_graph *h, double lambda
     const EgSymbolic &S = h->sym;
     const EgDev &D = h->dev;
     hipLaunchKernelGGL(k_eg_solve, dim3(1), dim3(EG_SOLVE_THREADS), 0, h->stream, D, lambda, 0, 0);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     std::vector<double> xs(7 * (size_t)S.nf + 1), rec(4);
     ORBX_HIP_CHECK(hipMemcpy(xs.data(), D.xs, 56 * (size_t)S.nf, hipMemcpyDeviceToHost));
@@ -932,13 +913,7 @@ extern "C" int orbx_essential_graph_solve(orbx_essential_graph *h, double lambda
 extern "C" int orbx_essential_graph_last_timing(orbx_essential_graph *h, float *device_ms, int *launches, float *solve_ms)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no orbx_optimize_essential_graph call to report"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->launches;
+    if (const int rc = h->timer.read(h->device, device_ms, launches, "no orbx_optimize_essential_graph call to report")) return rc;
     if (solve_ms) *solve_ms = (float)(h->solveTicks / 1e5);      // wall_clock64: 100 MHz
     return ORBX_OK;
 }

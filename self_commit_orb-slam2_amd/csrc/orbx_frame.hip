@@ -24,7 +24,7 @@
 #include <atomic>
 #include <chrono>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 
 namespace {
 
@@ -289,17 +289,15 @@ __global__ __launch_bounds__(FT) void k_frame_finish(CamDev c, orbx_frame_grid g
 
 }  // namespace
 
-struct orbx_frame_ops {
-    int device = 0;
-    hipStream_t stream = nullptr;   // host-array forms and the corner pass; the device form runs on the extractor's stream
+struct orbx_frame_ops : OrbxHandle {      // (the stream: host-array forms and the corner pass; the device form runs on the extractor's stream)
     CamDev cam;
     // results, double buffered in lockstep with the extractor's result buffers
-    OrbxDevBuf<orbx_keypoint> kpUn[2];
-    OrbxDevBuf<int32_t> gridOff[2], gridIdx[2];
+    OrbxOwnedBuf<orbx_keypoint> kpUn[2];
+    OrbxOwnedBuf<int32_t> gridOff[2], gridIdx[2];
     int cur = 0, lastBatch = 0, lastCap = 0;
     // capacity word of the extractor batch behind result buffer b (device form only): COPIED into this handle's own memory on the
     // extractor's stream when the frame is finished - the extractor may grow, reuse or free its result buffers before the download
-    OrbxDevBuf<int> producerCopy;
+    OrbxOwnedBuf<int> producerCopy;
     bool producerValid[2] = {false, false};
     uint8_t *hostIO = nullptr, *hostIODev = nullptr;   // pinned: inputs and outputs of the host-array forms, read / written by the kernel itself
     size_t hostIOBytes = 0;
@@ -308,20 +306,25 @@ struct orbx_frame_ops {
     bool pendingUn = false, pendingGrid = false;
     size_t pendUn = 0, pendOff = 0, pendIdx = 0, pendFlag = 0;
     int pendSeq = 0;
-    OrbxDevBuf<orbx_keypoint> hostKp;
-    OrbxDevBuf<int32_t> hostCount;
-    OrbxDevBuf<float> corners;
+    OrbxOwnedBuf<orbx_keypoint> hostKp;
+    OrbxOwnedBuf<int32_t> hostCount;
+    OrbxOwnedBuf<float> corners;
     // the RGB-D step: results of the batch form (double buffered with the rest), the depth images of orbx_upload_depth, the latency form's
     // offsets inside hostIO and its pinned copy of the depth image (ORBX_RGBD_STAGE_IMAGE=1 only)
-    OrbxDevBuf<float> rDepth[2], rURight[2], rXyz[2];
-    OrbxDevBuf<int32_t> rOrder[2], rCounts[2];
+    OrbxOwnedBuf<float> rDepth[2], rURight[2], rXyz[2];
+    OrbxOwnedBuf<int32_t> rOrder[2], rCounts[2];
     bool rgbdValid[2] = {false, false};
-    OrbxDevBuf<uint8_t> depthDev;
+    OrbxOwnedBuf<uint8_t> depthDev;
     int depthDevFrames = 0;
     bool pendingRgbd = false;
     size_t pendDepth = 0, pendURight = 0, pendXyz = 0, pendOrder = 0, pendCounts = 0;
     uint8_t *depthStage = nullptr, *depthStageDev = nullptr;
     size_t depthStageBytes = 0;
+    ~orbx_frame_ops()
+    {
+        if (depthStage) (void)hipHostFree(depthStage);
+        if (hostIO) (void)hipHostFree(hostIO);
+    }
 };
 
 static size_t finish_lds_bytes(int cap, bool rgbd)
@@ -370,36 +373,22 @@ extern "C" int orbx_frame_ops_create(int device, const orbx_camera *cam, orbx_fr
     *out = nullptr;
     if (cam->ndist != 4 && cam->ndist != 5) { orbx_set_error("ndist must be 4 or 5 (k1 k2 p1 p2 [k3]), got %d", cam->ndist); return ORBX_ERR_ARG; }
     if (!(cam->fx != 0.0f) || !(cam->fy != 0.0f)) { orbx_set_error("focal length must be non-zero"); return ORBX_ERR_ARG; }
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_frame_ops *h = new orbx_frame_ops();
-    h->device = device;
     // (a plain stream: on a high-priority one - tried for the latency forms - the kernel shared a hardware queue with the combiner's second engines,
     // which are the other high-priority streams of the process: the stereo constructor went from 265 to 390 us once a second image size had been used)
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
+    int rc = h->open(device);
     CamDev &c = h->cam;
     c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy;
     for (int i = 0; i < 8; i++) c.k[i] = i < cam->ndist ? (double)cam->dist[i] : 0.0;
     c.distorted = cam->dist[0] != 0.0f;   // the reference's test, src/Frame.cc:901, 953
-    int rc = h->corners.ensure(8);
+    if (rc == ORBX_OK) rc = h->corners.ensure(8);
     if (rc == ORBX_OK) rc = h->hostCount.ensure(1);
     if (rc != ORBX_OK) { orbx_frame_ops_destroy(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_frame_ops_destroy(orbx_frame_ops *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (int b = 0; b < 2; b++) { h->kpUn[b].release(); h->gridOff[b].release(); h->gridIdx[b].release(); }
-    for (int b = 0; b < 2; b++) { h->rDepth[b].release(); h->rURight[b].release(); h->rXyz[b].release(); h->rOrder[b].release(); h->rCounts[b].release(); }
-    h->depthDev.release();
-    if (h->depthStage) (void)hipHostFree(h->depthStage);
-    h->hostKp.release(); h->hostCount.release(); h->corners.release(); h->producerCopy.release();
-    if (h->hostIO) (void)hipHostFree(h->hostIO);
-    delete h;
-}
+extern "C" void orbx_frame_ops_destroy(orbx_frame_ops *h) { orbx_destroy_handle(h); }
 
 // Frame::ComputeImageBounds, src/Frame.cc:950-1004
 extern "C" int orbx_frame_image_bounds(orbx_frame_ops *h, int cols, int rows, float *bounds)
@@ -451,8 +440,7 @@ static int launch_finish(orbx_frame_ops *h, hipStream_t stream, const orbx_frame
         hipLaunchKernelGGL(k_frame_finish<false>, dim3((unsigned)batch), dim3(FT), lds, stream, h->cam, g, undistort ? 1 : 0, grid ? 1 : 0, kp, counts, cap,
                            undistort ? h->kpUn[b].p : nullptr, grid ? h->gridOff[b].p : nullptr, grid ? h->gridIdx[b].p : nullptr, (int *)nullptr, 0, 0, RgbdDev());
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     h->lastBatch = batch; h->lastCap = cap;
     h->rgbdValid[b] = rgbd != nullptr;
     return ORBX_OK;
@@ -623,8 +611,7 @@ static int host_form(orbx_frame_ops *h, const orbx_frame_grid *grid, bool undist
     uint8_t *d = h->hostIODev;
     hipLaunchKernelGGL(k_frame_finish<false>, dim3(1), dim3(FT), lds, h->stream, h->cam, g, undistort ? 1 : 0, grid ? 1 : 0, (const orbx_keypoint *)(d + oIn), (const int32_t *)(d + oCnt), cap,
                        undistort ? (orbx_keypoint *)(d + oUn) : nullptr, grid ? (int32_t *)(d + oOff) : nullptr, grid ? (int32_t *)(d + oIdx) : nullptr, (int *)nullptr, 0, 1, RgbdDev());
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     if (undistort && n > 0 && kp_un) memcpy(kp_un, h->hostIO + oUn, (size_t)n * sizeof(orbx_keypoint));
     if (grid && grid_offsets) memcpy(grid_offsets, h->hostIO + oOff, (size_t)(NCELL + 1) * 4);
@@ -725,8 +712,7 @@ static int finish_begin(orbx_frame_ops *h, orbx_extractor *ext, const orbx_frame
         hipLaunchKernelGGL(k_frame_finish<false>, dim3(1), dim3(FT), lds, h->stream, h->cam, g, undist ? 1 : 0, grid ? 1 : 0, view.kp, view.counts, cap,
                            undist ? (orbx_keypoint *)(d + oUn) : nullptr, grid ? (int32_t *)(d + oOff) : nullptr, grid ? (int32_t *)(d + oIdx) : nullptr, (int *)(d + oFlag), seq, 1, RgbdDev());
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     h->pending = 2; h->pendingN = n; h->pendingUn = undist; h->pendingGrid = grid != nullptr;
     h->pendUn = oUn; h->pendOff = oOff; h->pendIdx = oIdx; h->pendFlag = oFlag;
     h->pendingRgbd = depth != nullptr;

@@ -694,18 +694,15 @@ __global__ __launch_bounds__(256) void k_init_decide(InitDecideArgs P)
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct orbx_initializer {
-    int device = 0, maxMatches = 0, maxIters = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false;
-    int launches = 0;
+struct orbx_initializer : OrbxHandle {
+    int maxMatches = 0, maxIters = 0;
+    OrbxCallTimer timer;
     OrbxCallBox box;                   // inputs and results of a call: mapped pinned memory + the sequence word
-    OrbxDevBuf<uint8_t> arena;         // the inputs on the device (k_stage_copy), same offsets as in box.in
-    OrbxDevBuf<float> hn, fpre, fn, h21, h12, f21, score, crtP3d, crtCos, rankCos;
-    OrbxDevBuf<uint8_t> inl, crtStatus;
-    OrbxDevBuf<int32_t> rankGood;
-    OrbxDevBuf<InitBest> best;
+    OrbxOwnedBuf<uint8_t> arena;         // the inputs on the device (k_stage_copy), same offsets as in box.in
+    OrbxOwnedBuf<float> hn, fpre, fn, h21, h12, f21, score, crtP3d, crtCos, rankCos;
+    OrbxOwnedBuf<uint8_t> inl, crtStatus;
+    OrbxOwnedBuf<int32_t> rankGood;
+    OrbxOwnedBuf<InitBest> best;
 };
 
 namespace {
@@ -806,7 +803,7 @@ int launch_stage_copy(orbx_initializer *h, size_t total)
     const size_t n16 = (total + 15) / 16;
     const unsigned blocks = (unsigned)std::min<size_t>((n16 + 255) / 256, 64);
     hipLaunchKernelGGL(k_stage_copy, dim3(blocks ? blocks : 1), dim3(256), 0, h->stream, (const uint4 *)h->box.inDev, (uint4 *)h->arena.p, n16);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }
 
@@ -830,29 +827,15 @@ extern "C" int orbx_initializer_create(int device, int max_matches, int max_iter
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_initializer *h = new orbx_initializer();
-    h->device = device; h->maxMatches = max_matches; h->maxIters = max_iterations;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev[0]); (void)hipEventCreate(&h->ev[1]);
-    const int rc = ensure_models(h);
-    if (rc != ORBX_OK) { orbx_initializer_destroy(h); return rc; }
+    h->maxMatches = max_matches; h->maxIters = max_iterations;
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create()) || (rc = ensure_models(h))) { orbx_destroy_handle(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_initializer_destroy(orbx_initializer *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->box.release(); h->arena.release();
-    h->hn.release(); h->fpre.release(); h->fn.release(); h->h21.release(); h->h12.release(); h->f21.release(); h->score.release(); h->crtP3d.release(); h->crtCos.release();
-    h->rankCos.release(); h->inl.release(); h->crtStatus.release(); h->rankGood.release(); h->best.release();
-    for (int i = 0; i < 2; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void orbx_initializer_destroy(orbx_initializer *h) { orbx_destroy_handle(h); }
 
 static void fill_model_args(orbx_initializer *h, const Staged &S, InitModelArgs &A)
 {
@@ -895,23 +878,23 @@ extern "C" int orbx_initialize(orbx_initializer *h, const orbx_init_problem *P, 
     A.invSigma2 = inv_sigma2(P->sigma);
 
     const unsigned long long seq = bx.arm();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     if ((rc = launch_stage_copy(h, S.total)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_init_models, dim3((unsigned)(2 * iters)), dim3(64), 0, h->stream, A);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_init_decompose, dim3(1), dim3(128), 0, h->stream, (const float *)h->score.p, iters, (const float *)h->h21.p, (const float *)h->f21.p, P->fx, P->fy, P->cx, P->cy,
                        h->best.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     InitRtArgs R;
     R.raw = A.raw; R.hypR = h->best.p->hypR; R.hypT = h->best.p->hypT; R.hypValid = h->best.p->hypValid; R.inlBase = h->inl.p; R.best = h->best.p; R.iters = iters; R.N = N;
     R.fx = P->fx; R.fy = P->fy; R.cx = P->cx; R.cy = P->cy;
     R.th2 = (float)(4.0 * (double)(P->sigma * P->sigma));      // 4.0 * mSigma2 (:1063)
     R.status = h->crtStatus.p; R.p3d = h->crtP3d.p; R.cosp = h->crtCos.p;
     hipLaunchKernelGGL(k_init_check_rt, dim3((unsigned)((N + 255) / 256), ORBX_INIT_HYPOTHESES), dim3(256), 0, h->stream, R);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_init_rank, dim3(ORBX_INIT_HYPOTHESES, RANK_SPLIT), dim3(RANK_THREADS), (size_t)((N + 3) & ~3) * 4, h->stream, (const uint8_t *)h->crtStatus.p, (const float *)h->crtCos.p, N,
                        h->best.p->hypGood, h->best.p->hypCos);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     InitDecideArgs D;
     D.best = h->best.p; D.inlBase = h->inl.p; D.iters = iters; D.N = N; D.n1 = P->n1;
     D.slot = (const int32_t *)(h->arena.p + S.slot); D.status = h->crtStatus.p; D.p3d = h->crtP3d.p;
@@ -920,9 +903,9 @@ extern "C" int orbx_initialize(orbx_initializer *h, const orbx_init_problem *P, 
     D.head = bx.outDev<InitHead>(0); D.outP3d = bx.outDev<float>(offP3d); D.outTri = bx.outDev<uint8_t>(offTri);
     D.counter = bx.counter; D.flag = bx.flagDev; D.seq = seq;
     hipLaunchKernelGGL(k_init_decide, dim3(1), dim3(256), 0, h->stream, D);
-    MLAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    h->launches = 6; h->timed = true;
+    ORBX_LAUNCH_CHECK();
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
+    h->timer.launches = 6;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
 
     const InitHead *H = bx.outHost<InitHead>(0);
@@ -989,7 +972,7 @@ extern "C" int orbx_init_score_models(orbx_initializer *h, const orbx_init_match
     A.invSigma2 = inv_sigma2(sigma);
     if ((rc = launch_stage_copy(h, S.total)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_init_models, dim3((unsigned)m), dim3(64), 0, h->stream, A);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     ORBX_HIP_CHECK(hipMemcpy(scores, h->score.p, (size_t)m * 4, hipMemcpyDeviceToHost));
     ORBX_HIP_CHECK(hipMemcpy(inliers, h->inl.p, (size_t)m * S.N, hipMemcpyDeviceToHost));
@@ -1019,10 +1002,10 @@ extern "C" int orbx_init_check_rt(orbx_initializer *h, const orbx_init_matches *
     R.status = h->crtStatus.p; R.p3d = h->crtP3d.p; R.cosp = h->crtCos.p;
     if ((rc = launch_stage_copy(h, S.total)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_init_check_rt, dim3((unsigned)((N + 255) / 256), (unsigned)m), dim3(256), 0, h->stream, R);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_init_rank, dim3((unsigned)m, RANK_SPLIT), dim3(RANK_THREADS), (size_t)((N + 3) & ~3) * 4, h->stream, (const uint8_t *)h->crtStatus.p, (const float *)h->crtCos.p, N, h->rankGood.p,
                        h->rankCos.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     std::vector<uint8_t> st((size_t)m * N);
     std::vector<float> pts((size_t)m * N * 3);
@@ -1048,12 +1031,5 @@ extern "C" int orbx_init_check_rt(orbx_initializer *h, const orbx_init_matches *
 extern "C" int orbx_initializer_last_timing(orbx_initializer *h, float *device_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no orbx_initialize call to report"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->launches;
-    return ORBX_OK;
+    return h->timer.read(h->device, device_ms, launches, "no orbx_initialize call to report");
 }

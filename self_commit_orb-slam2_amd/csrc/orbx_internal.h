@@ -264,6 +264,10 @@ struct OrbxHostStage {
         return ORBX_OK;
     }
     void release() { if (host) (void)hipHostFree(host); host = nullptr; hostBytes = 0; used = 0; dev.release(); }
+    OrbxHostStage() = default;
+    OrbxHostStage(const OrbxHostStage &) = delete;
+    OrbxHostStage &operator=(const OrbxHostStage &) = delete;
+    ~OrbxHostStage() { release(); }
 };
 
 /* One small synchronous host call WITHOUT a copy engine and WITHOUT a stream synchronisation.  Measured around an 11 us kernel
@@ -352,6 +356,10 @@ struct OrbxCallBox {
         if (counter) (void)hipFree(counter);
         in = out = nullptr; flag = nullptr; counter = nullptr; inBytes = outBytes = 0;
     }
+    OrbxCallBox() = default;
+    OrbxCallBox(const OrbxCallBox &) = delete;
+    OrbxCallBox &operator=(const OrbxCallBox &) = delete;
+    ~OrbxCallBox() { release(); }
 };
 
 #ifdef __HIPCC__

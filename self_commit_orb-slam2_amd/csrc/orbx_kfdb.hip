@@ -29,7 +29,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "orbx_match_internal.h"
+#include "orbx_handle.h"
 
 #define KF_THREADS 256
 #define KF_SLOTS_PER_BLOCK 16        /* four slots per wave behind one load of the query into LDS */
@@ -364,20 +364,19 @@ static __global__ __launch_bounds__(KF_THREADS) void k_kfdb_compact(const int4 *
     if (threadIdx.x == 0) dstR[blockIdx.x] = srcR[p.w];
 }
 
-struct orbx_kf_database {
-    int device = 0, nWords = 0, maxKf = 0, maxEntries = 0, maxQueries = 0, maxQueryWords = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+struct orbx_kf_database : OrbxHandle {
+    int nWords = 0, maxKf = 0, maxEntries = 0, maxQueries = 0, maxQueryWords = 0;
+    OrbxCallTimer timer;
     hipEvent_t pev[4] = {nullptr, nullptr, nullptr, nullptr};      // behind the staging, k_kfdb_intersect, k_kfdb_score, k_kfdb_commit (profiling only)
-    bool timed = false, profile = false, profiled = false;
-    int launches = 0;
+    bool profile = false, profiled = false;
     OrbxCallBox box;
-    OrbxDevBuf<uint8_t> arena;
-    OrbxDevBuf<int32_t> poolW, work;
-    OrbxDevBuf<double> poolV;
-    OrbxDevBuf<unsigned long long> key;
-    OrbxDevBuf<KfSlot> dslots;
-    OrbxDevBuf<float> reloc[2];
+    OrbxOwnedBuf<uint8_t> arena;
+    OrbxOwnedBuf<int32_t> poolW, work;
+    OrbxOwnedBuf<double> poolV;
+    OrbxOwnedBuf<unsigned long long> key;
+    OrbxOwnedBuf<KfSlot> dslots;
+    OrbxOwnedBuf<float> reloc[2];
+    ~orbx_kf_database() { for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e); }
     int cur = 0;                          // which reloc buffer holds the state
     std::vector<KfSlot> slots;            // host mirror, nslots entries in use
     std::vector<long long> covId;         // [slot][KF_COV] the ids as pushed
@@ -510,14 +509,14 @@ extern "C" int orbx_kfdb_create(int device, int n_words, int max_keyframes, int 
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_kf_database *h = new orbx_kf_database();
-    h->device = device; h->nWords = n_words; h->maxKf = max_keyframes; h->maxEntries = max_entries; h->maxQueries = max_queries; h->maxQueryWords = max_query_words;
+    h->nWords = n_words; h->maxKf = max_keyframes; h->maxEntries = max_entries; h->maxQueries = max_queries; h->maxQueryWords = max_query_words;
     h->slots.resize((size_t)max_keyframes);
     h->covId.resize((size_t)max_keyframes * KF_COV);
     const size_t per = (size_t)max_queries * (size_t)max_keyframes;
-    int rc = ORBX_OK;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { orbx_set_error("hipStreamCreate failed"); rc = ORBX_ERR_HIP; }
+    int rc = h->open(device);
+    if (rc == ORBX_OK) rc = h->timer.create();
+    for (int i = 0; i < 4 && rc == ORBX_OK; i++) rc = orbx_event_create(&h->pev[i]);
     if (rc == ORBX_OK) rc = h->poolW.ensure((size_t)max_entries);
     if (rc == ORBX_OK) rc = h->poolV.ensure((size_t)max_entries);
     if (rc == ORBX_OK) rc = h->dslots.ensure((size_t)max_keyframes);
@@ -526,24 +525,11 @@ extern "C" int orbx_kfdb_create(int device, int n_words, int max_keyframes, int 
     if (rc == ORBX_OK) rc = h->work.ensure(10 * per + 2 * (size_t)max_queries + 64);
     if (rc == ORBX_OK) rc = h->key.ensure(per);
     if (rc != ORBX_OK) { orbx_kfdb_destroy(h); return rc; }
-    (void)hipEventCreate(&h->ev[0]); (void)hipEventCreate(&h->ev[1]);
-    for (int i = 0; i < 4; i++) (void)hipEventCreate(&h->pev[i]);
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_kfdb_destroy(orbx_kf_database *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->box.release(); h->arena.release(); h->poolW.release(); h->poolV.release(); h->work.release(); h->key.release(); h->dslots.release();
-    h->reloc[0].release(); h->reloc[1].release();
-    for (int i = 0; i < 2; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    for (int i = 0; i < 4; i++) if (h->pev[i]) (void)hipEventDestroy(h->pev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void orbx_kfdb_destroy(orbx_kf_database *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_kfdb_add(orbx_kf_database *h, int64_t id, const int32_t *words, const double *values, int n)
 {
@@ -672,8 +658,7 @@ extern "C" int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *que
         if (queries[q].mode == ORBX_KFDB_LOOP) nc += (size_t)queries[q].n_connected;
     }
     const int Ns = h->nslots;
-    h->launches = 0;
-    h->timed = false;
+    h->timer.timed = false;
     if (Ns == 0) {      // an empty database: nothing is launched
         for (int q = 0; q < nq; q++) {
             const orbx_kfdb_query_t &Q = queries[q];
@@ -755,30 +740,29 @@ extern "C" int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *que
     D.key = h->key.p;
     D.out = bx.outDevP;
 
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     const size_t n16 = total / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipMemsetAsync(D.counters, 0, 8 * (size_t)nq, h->stream));
     h->profiled = false;
     if (h->profile) ORBX_HIP_CHECK(hipEventRecord(h->pev[0], h->stream));
     const dim3 grid((unsigned)((Ns + KF_SLOTS_PER_BLOCK - 1) / KF_SLOTS_PER_BLOCK), (unsigned)nq);
     const size_t lds = 4 * (size_t)std::max(maxn, 1);
     hipLaunchKernelGGL(k_kfdb_intersect, grid, dim3(KF_THREADS), lds, h->stream, D);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     if (h->profile) ORBX_HIP_CHECK(hipEventRecord(h->pev[1], h->stream));
     hipLaunchKernelGGL(k_kfdb_score, grid, dim3(KF_THREADS), lds, h->stream, D);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     if (h->profile) ORBX_HIP_CHECK(hipEventRecord(h->pev[2], h->stream));
     hipLaunchKernelGGL(k_kfdb_commit, dim3((unsigned)((Ns + KF_THREADS - 1) / KF_THREADS)), dim3(KF_THREADS), 0, h->stream, D);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     if (h->profile) ORBX_HIP_CHECK(hipEventRecord(h->pev[3], h->stream));
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_kfdb_select, dim3((unsigned)nq), dim3(KF_SEL_THREADS), 0, h->stream, D, bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
-    h->launches = 5;
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_CHECK();
+    h->timer.launches = 5;
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     h->profiled = h->profile;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     h->cur ^= 1;      // the scores of this call's relocalisation queries are the state now
@@ -824,28 +808,17 @@ extern "C" int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *que
 extern "C" int orbx_kfdb_last_timing(orbx_kf_database *h, float *device_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!h->timed) {      // no chain ran (no call yet, or an empty database)
-        if (device_ms) *device_ms = 0.f;
-        if (launches) *launches = 0;
-        return ORBX_OK;
-    }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->launches;
-    return ORBX_OK;
+    return h->timer.read(h->device, device_ms, launches, nullptr);      // zeros when no chain ran (no call yet, or an empty database)
 }
 
 extern "C" int orbx_kfdb_stage_timing(orbx_kf_database *h, int enable, float *stage_ms)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
     if (stage_ms) {
-        if (!h->timed || !h->profiled) { orbx_set_error("orbx_kfdb_stage_timing: the last query was not profiled"); return ORBX_ERR_STATE; }
+        if (!h->timer.timed || !h->profiled) { orbx_set_error("orbx_kfdb_stage_timing: the last query was not profiled"); return ORBX_ERR_STATE; }
         ORBX_HIP_CHECK(hipSetDevice(h->device));
-        ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-        hipEvent_t e[6] = {h->ev[0], h->pev[0], h->pev[1], h->pev[2], h->pev[3], h->ev[1]};
+        ORBX_HIP_CHECK(hipEventSynchronize(h->timer.ev[1]));
+        hipEvent_t e[6] = {h->timer.ev[0], h->pev[0], h->pev[1], h->pev[2], h->pev[3], h->timer.ev[1]};
         for (int i = 0; i < 5; i++) ORBX_HIP_CHECK(hipEventElapsedTime(&stage_ms[i], e[i], e[i + 1]));
     }
     h->profile = enable != 0;

@@ -35,7 +35,7 @@
 #include <limits>
 #include <vector>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 
 namespace {
 
@@ -2551,23 +2551,23 @@ namespace {
 
 // The device buffers of `windows` windows of the handle's capacities, window w at w times the per-window size.
 struct LbaBuffers {
-    OrbxDevBuf<DPose> pose, poseBak;
-    OrbxDevBuf<double> pt, ptBak, intr, obs, info, err, rchi, edgeBlk, Hpp, bp, Hll, bl, Dinv, Ddb, bs, xp, xl, red;
-    OrbxDevBuf<double> ywork, ysol, diagInv;   // multi-workgroup Cholesky: the two halves of the right-hand side, 1 / diagonal
-    OrbxDevBuf<double> spPart;                 // k_lin_sums: SP_SPLIT partial results per keyframe
-    OrbxDevBuf<double> partChi, partL;         // per-workgroup partial sums of k_errors / k_backsub_update
-    OrbxDevBuf<double> bsPart;                 // K x 32 x 6: the workgroups' shares of the reduced right-hand side
-    OrbxDevBuf<int> ep, ek, ptStart, ptEdges, kfStart, kfEdges, poseIdx, ptIdx, okFlag;
-    OrbxDevBuf<int> ptTmp, fillP, pActF, lActF, kfRowS0, kfRowN, ptPi;   // adjacency-list builder and stage preparation (device side)
-    OrbxDevBuf<uint8_t> stereo, active, fixedDev;
-    OrbxDevBuf<unsigned long long> scaleBits;  // max |Hpp[r][r]| over the free poses as bit patterns, r = 0..5: the fixed-point scale (k_schur_setup)
-    OrbxDevBuf<LmState> lm;                    // Levenberg-Marquardt state of the running stage (device side)
+    OrbxOwnedBuf<DPose> pose, poseBak;
+    OrbxOwnedBuf<double> pt, ptBak, intr, obs, info, err, rchi, edgeBlk, Hpp, bp, Hll, bl, Dinv, Ddb, bs, xp, xl, red;
+    OrbxOwnedBuf<double> ywork, ysol, diagInv;   // multi-workgroup Cholesky: the two halves of the right-hand side, 1 / diagonal
+    OrbxOwnedBuf<double> spPart;                 // k_lin_sums: SP_SPLIT partial results per keyframe
+    OrbxOwnedBuf<double> partChi, partL;         // per-workgroup partial sums of k_errors / k_backsub_update
+    OrbxOwnedBuf<double> bsPart;                 // K x 32 x 6: the workgroups' shares of the reduced right-hand side
+    OrbxOwnedBuf<int> ep, ek, ptStart, ptEdges, kfStart, kfEdges, poseIdx, ptIdx, okFlag;
+    OrbxOwnedBuf<int> ptTmp, fillP, pActF, lActF, kfRowS0, kfRowN, ptPi;   // adjacency-list builder and stage preparation (device side)
+    OrbxOwnedBuf<uint8_t> stereo, active, fixedDev;
+    OrbxOwnedBuf<unsigned long long> scaleBits;  // max |Hpp[r][r]| over the free poses as bit patterns, r = 0..5: the fixed-point scale (k_schur_setup)
+    OrbxOwnedBuf<LmState> lm;                    // Levenberg-Marquardt state of the running stage (device side)
     // sized by the call (grow-only): the reduced system, its factor and its fixed-point sums (all zero between trials) by the FREE keyframes,
     // the chunk counters of the adjacency-list builder, the device images of the input and result layouts (LbaLayout)
-    OrbxDevBuf<double> S, Lmat;
-    OrbxDevBuf<unsigned long long> Sacc;
-    OrbxDevBuf<int> csrCnt;
-    OrbxDevBuf<uint8_t> inArena, outArena;
+    OrbxOwnedBuf<double> S, Lmat;
+    OrbxOwnedBuf<unsigned long long> Sacc;
+    OrbxOwnedBuf<int> csrCnt;
+    OrbxOwnedBuf<uint8_t> inArena, outArena;
     size_t capK = 0, capP = 0, capE = 0, ebPerEdge = 0, okStride = 0;      // per-window strides (ensure)
 
     // splitForm: room for eb_rest, which only the launch-per-stage form (ORBX_LBA_SPLIT=1) writes; okStride: ints between the windows' okFlag
@@ -2589,16 +2589,6 @@ struct LbaBuffers {
 #undef LBA_ENSURE
         return rc;
     }
-    void release()
-    {
-        pose.release(); poseBak.release(); pt.release(); ptBak.release(); intr.release(); obs.release(); info.release(); err.release(); rchi.release(); edgeBlk.release();
-        Hpp.release(); bp.release(); Hll.release(); bl.release(); Dinv.release(); Ddb.release(); bs.release(); xp.release(); xl.release(); red.release();
-        ywork.release(); ysol.release(); diagInv.release(); spPart.release(); partChi.release(); partL.release(); bsPart.release();
-        ep.release(); ek.release(); ptStart.release(); ptEdges.release(); kfStart.release(); kfEdges.release(); poseIdx.release(); ptIdx.release(); okFlag.release();
-        ptTmp.release(); fillP.release(); pActF.release(); lActF.release(); kfRowS0.release(); kfRowN.release(); ptPi.release();
-        stereo.release(); active.release(); fixedDev.release(); scaleBits.release(); lm.release();
-        S.release(); Lmat.release(); Sacc.release(); csrCnt.release(); inArena.release(); outArena.release();
-    }
     // the by-value views of window w, for a problem of K keyframes, P points and E edges
     LbaDev views(size_t w, int K, int P, int E) const
     {
@@ -2613,12 +2603,10 @@ struct LbaBuffers {
 
 // What both handles are made of: the buffers, the stream and its timing events, the pinned I/O buffer of a call and, per window, the
 // mapped record the device mirrors the LM state into and the mapped stop word it reads.
-struct LbaCore : LbaBuffers {
-    int device = 0, maxW = 1, maxK = 0, maxP = 0, maxE = 0;
+struct LbaCore : OrbxHandle, LbaBuffers {      // (in this order: the buffers go before the stream does)
+    int maxW = 1, maxK = 0, maxP = 0, maxE = 0;
     int numCU = 256;                     // compute units of the device (residency of k_schur_rows)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    OrbxCallTimer timer;
     double flops = 0;
     double seq = 0;                      // last sequence number handed out (k_stage_index, k_lm_begin, k_lm_decide)
     uint8_t *hostIO = nullptr;           // pinned: the marshalled inputs of a call on their way up, flags / chi2 / estimates on their way down
@@ -2627,17 +2615,21 @@ struct LbaCore : LbaBuffers {
     // the sequence number at [15] stored last, so that ONE poll reads them back
     double *rec = nullptr, *recDev = nullptr;
     int *stopW = nullptr, *stopWDev = nullptr;      // mapped, 16 ints apart: the callers' stop flags as the device sees them (the waiting host keeps them current)
+    ~LbaCore()
+    {
+        if (hostIO) (void)hipHostFree(hostIO);
+        if (rec) (void)hipHostFree(rec);
+        if (stopW) (void)hipHostFree(stopW);
+    }
 };
 
-// device check, stream, events, CU count, the mapped words; lba_close() undoes whatever part of it was reached
+// device check, stream, events, CU count, the mapped words; the handle's destructors undo whatever part of it was reached
 int lba_open(LbaCore *h, int device, int maxW, int maxK, int maxP, int maxE)
 {
-    if (const int rc = orbx_select_device(device)) return rc;
-    h->device = device; h->maxW = maxW; h->maxK = maxK; h->maxP = maxP; h->maxE = maxE;
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create())) return rc;
+    h->maxW = maxW; h->maxK = maxK; h->maxP = maxP; h->maxE = maxE;
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev0);
-    (void)hipEventCreate(&h->ev1);
     const size_t W = (size_t)maxW;
     if (hipHostMalloc((void **)&h->rec, W * 16 * sizeof(double), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->recDev, h->rec, 0) != hipSuccess ||
         hipHostMalloc((void **)&h->stopW, W * 16 * sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&h->stopWDev, h->stopW, 0) != hipSuccess) {
@@ -2648,26 +2640,10 @@ int lba_open(LbaCore *h, int device, int maxW, int maxK, int maxP, int maxE)
     return ORBX_OK;
 }
 
-void lba_close(LbaCore *h)
-{
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->hostIO) (void)hipHostFree(h->hostIO);
-    if (h->rec) (void)hipHostFree(h->rec);
-    if (h->stopW) (void)hipHostFree(h->stopW);
-}
-
 int lba_last_timing(LbaCore *h, float *device_ms, double *flops)
 {
     if (!h) { orbx_set_error("NULL handle"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no solve yet"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
-    if (device_ms) ORBX_HIP_CHECK(hipEventElapsedTime(device_ms, h->ev0, h->ev1));
+    if (const int rc = h->timer.read(h->device, device_ms, nullptr, "no solve yet")) return rc;
     if (flops) *flops = h->flops;
     return ORBX_OK;
 }
@@ -2829,20 +2805,9 @@ extern "C" int orbx_lba_create(int device, int max_keyframes, int max_points, in
     return ORBX_OK;
 }
 
-extern "C" void orbx_lba_destroy(orbx_lba *h)
-{
-    if (!h) return;
-    lba_close(h);
-    delete h;
-}
+extern "C" void orbx_lba_destroy(orbx_lba *h) { orbx_destroy_handle(h); }
 
 namespace {
-
-#define LCHECK()                                                                                                   \
-    do {                                                                                                           \
-        hipError_t e_ = hipGetLastError();                                                                         \
-        if (e_ != hipSuccess) { orbx_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); return ORBX_ERR_HIP; } \
-    } while (0)
 
 // developer tap (tools/chol_phases.py; not part of include/orbx.h): a device array of 16 u64 the PROF instantiation of k_chol_step adds its phase cycles / passes to
 static unsigned long long *g_cholProf = nullptr;
@@ -2952,7 +2917,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
                            h->poseIdx.p, h->ptIdx.p, (const int *)h->csrCnt.p, (int)gM, h->recDev, seq);
         hipLaunchKernelGGL(k_stage_pairs, dim3(gM), dim3(256), 0, h->stream, E, (const int *)h->ek.p, (const int *)h->ptEdges.p, (const uint8_t *)h->active.p, (const int *)h->poseIdx.p,
                            h->ptPi.p);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         if (!c.stageFlags) { nPose = c.nPose0; nPt = c.nPt0; nAct = E; }      // nothing to wait for
         else {
             int rcw = wait_seq(h, seq, c.stop);
@@ -2985,15 +2950,15 @@ int optimize(Ctx &c, int iterations, double stats[4])
         if (!h->linSplit) {      // Jacobians inside the sums that consume them: one launch + the ordered add of the keyframe partials
             hipLaunchKernelGGL(k_lin_sums, dim3((unsigned)(K * c.spSplit + (P + 15) / 16)), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->ptStart.p, h->ptEdges.p, h->Hll.p,
                                h->bl.p, h->kfStart.p, h->kfEdges.p, h->spPart.p, c.spSplit, gLin, 1);
-            LCHECK();      // (the ordered add of the keyframe partials is the first part of the next k_schur_setup)
+            ORBX_LAUNCH_CHECK();      // (the ordered add of the keyframe partials is the first part of the next k_schur_setup)
             return ORBX_OK;
         }
         hipLaunchKernelGGL(k_linearize, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, gLin, 1);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_sum_points, dim3((unsigned)((P + 15) / 16)), dim3(256), 0, h->stream, c.d, h->ptStart.p, h->ptEdges.p, h->Hll.p, h->bl.p, gLin, 1);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_sum_poses, dim3((unsigned)K, (unsigned)c.spSplit), dim3(256), 0, h->stream, c.d, h->kfStart.p, h->kfEdges.p, h->spPart.p, c.spSplit, gLin, 1);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         return ORBX_OK;
     };
     // ---- start of the stage: errors and chi2 of the start, H and b, computeLambdaInit, the LM state (nothing is waited for)
@@ -3001,7 +2966,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
     {
         // (the state's `done` of the previous stage is still set: the first launches are not gated)
         hipLaunchKernelGGL(k_errors, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->partChi.p, (const int *)nullptr, 0);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         if (!h->linSplit) {
             hipLaunchKernelGGL(k_lin_sums, dim3((unsigned)(K * c.spSplit + (P + 15) / 16)), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->ptStart.p, h->ptEdges.p, h->Hll.p,
                                h->bl.p, h->kfStart.p, h->kfEdges.p, h->spPart.p, c.spSplit, (const int *)nullptr, 0);
@@ -3015,7 +2980,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
         const double seq = (h->seq += 1.0);
         hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(256), 0, h->stream, st, (const double *)h->partChi.p, (int)gE, (const double *)h->red.p, iterations, (const volatile int *)h->stopWDev,
                            h->recDev, seq, h->scaleBits.p);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
     }
     // ---- one Levenberg trial in two halves
     // the right-hand side of the reduced system is accumulated where the solver updates it in place (multi-workgroup Cholesky: ywork)
@@ -3027,7 +2992,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
             hipLaunchKernelGGL(k_schur_setup, dim3((unsigned)(nInit + (P + 3) / 4 + (nP6 > 0 ? (E + 255) / 256 : 0))), dim3(256), 0, h->stream, c.d, nInit, h->Hpp.p, h->bp.p, nPose, h->ptStart.p,
                                h->ptEdges.p, h->Hll.p, h->bl.p, 0.0, h->S.p, bsDev, h->Dinv.p, h->Ddb.p, h->okFlag.p, lam, h->scaleBits.p, (const double *)h->spPart.p, c.spSplit, h->Hpp.p, h->bp.p,
                                gDone, 0);
-            LCHECK();
+            ORBX_LAUNCH_CHECK();
         }
         if (nP6 > 0) {
             const size_t ldsRows = (size_t)(6 * nP6) * sizeof(unsigned long long);
@@ -3040,11 +3005,11 @@ int optimize(Ctx &c, int iterations, double stats[4])
                 if (ldsRows > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_schur_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsRows));
                 hipLaunchKernelGGL(k_schur_rows<false>, dim3((unsigned)K, (unsigned)ySplit), dim3(256), ldsRows, h->stream, c.d, h->kfStart.p, h->kfEdges.p, (const int *)h->kfRowS0.p, (const int *)h->kfRowN.p, h->ptEdges.p, (const int *)h->ptPi.p, nP6, h->Ddb.p, h->Sacc.p, h->bsPart.p, (const unsigned long long *)h->scaleBits.p, gDone, 0);
             }
-            LCHECK();
+            ORBX_LAUNCH_CHECK();
             // S and bs from the sums (and the accumulator cleared for the next trial)
             hipLaunchKernelGGL(k_schur_fin, dim3((unsigned)((nP6 + 255) / 256), (unsigned)(nPose + 1)), dim3(256), 0, h->stream, c.d, (const double *)h->Hpp.p, (const double *)h->bp.p, nPose, 0.0,
                                lam, h->Sacc.p, (const double *)h->bsPart.p, ys, (const unsigned long long *)h->scaleBits.p, h->S.p, bsDev, gDone, 0);
-            LCHECK();
+            ORBX_LAUNCH_CHECK();
         }
         return ORBX_OK;
     };
@@ -3086,7 +3051,7 @@ int optimize(Ctx &c, int iterations, double stats[4])
                     hipLaunchKernelGGL(k_chol_solve<4>, dim3(1), dim3(1024), lds, h->stream, h->S.p, h->bs.p, nP6, h->xp.p, h->okFlag.p, gDone, 0);
                 }
             }
-            LCHECK();
+            ORBX_LAUNCH_CHECK();
         }
         return ORBX_OK;
     };
@@ -3095,14 +3060,14 @@ int optimize(Ctx &c, int iterations, double stats[4])
         const unsigned gU = (unsigned)((std::max(K, 16 * P) + 255) / 256);
         hipLaunchKernelGGL(k_backsub_update, dim3(gU), dim3(256), 0, h->stream, c.d, h->ptStart.p, h->ptEdges.p, (const int *)h->ptPi.p, h->bl.p,
                            h->Dinv.p, h->xp.p, h->xl.p, h->poseBak.p, h->ptBak.p, 0.0, h->partL.p, lam, gDone, 0);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         const double seq = (h->seq += 1.0);
         hipLaunchKernelGGL(k_errors, dim3(gE), dim3(256), 0, h->stream, c.d, c.hub, c.robust, h->partChi.p, gDone, 0);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), 0, h->stream, st, (const double *)h->partChi.p, (int)gE, (const double *)h->partL.p, (int)gU, (const double *)h->xp.p,
                            (const double *)h->bp.p, nP6, nP6 > 0 ? (const int *)h->okFlag.p : (const int *)nullptr, (const volatile int *)h->stopWDev, h->recDev, seq, c.d,
                            (const DPose *)h->poseBak.p, (const double *)h->ptBak.p, h->scaleBits.p);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         // (a rejected update is taken back inside k_lm_decide); H and b at the new estimates behind an accepted trial
         int rcl = linearize();
         if (rcl) return rcl;
@@ -3168,13 +3133,13 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
     }
     c.d = h->views(0, K, P, E);
     hipStream_t s = h->stream;
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, s));
+    if (const int rc = h->timer.begin(s)) return rc;
     {
         ORBX_HIP_CHECK(hipMemcpyAsync(h->inArena.p, io, L.inEnd, hipMemcpyHostToDevice, s));
         UnpackSegs sg;
         lba_unpack_segs(L, c.d, h->ptStart.p, h->kfStart.p, h->fixedDev.p, h->fillP.p, h->pActF.p, h->lActF.p, sg);
         hipLaunchKernelGGL(k_unpack, dim3(256), dim3(256), 0, s, (const uint8_t *)h->inArena.p, sg);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         // adjacency lists
         if (csrLds > 48 * 1024) {
             ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_csr_kf_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)csrLds));
@@ -3186,7 +3151,7 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
         hipLaunchKernelGGL(k_csr_pt_fill, dim3(gE), dim3(256), 0, s, (const int *)h->ep.p, E, (const int *)h->ptStart.p, h->fillP.p, h->ptTmp.p);
         hipLaunchKernelGGL(k_csr_pt_rank, dim3(gE), dim3(256), 0, s, (const int *)h->ep.p, E, (const int *)h->ptStart.p, (const int *)h->ptTmp.p, h->ptEdges.p);
         hipLaunchKernelGGL(k_csr_rows, dim3(gE), dim3(256), 0, s, E, (const int *)h->ep.p, (const int *)h->kfEdges.p, (const int *)h->ptStart.p, h->kfRowS0.p, h->kfRowN.p);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
     }
     c.hub = lba_huber(secondStage ? 5.991 : 5.99);
     // classification on the device (k_classify); only the flags come back between the stages, the rest with the final results
@@ -3198,18 +3163,17 @@ static int lba_run(orbx_lba *h, const orbx_lba_problem *p, const volatile uint8_
         if (secondStage && !(stop && *stop)) {
             // :880-912: the outlier flags stay on the device, the second stage starts from them (k_stage_prep)
             hipLaunchKernelGGL(k_classify, dim3(gEc), dim3(256), 0, h->stream, c.d, oa + L.dFlag, (double *)nullptr, (DPose *)nullptr, (double *)nullptr);
-            LCHECK();
+            ORBX_LAUNCH_CHECK();
             c.stageFlags = oa + L.dFlag;
             c.robust = 0;
             if ((rc = optimize(c, 10, res->stats + 4)) != ORBX_OK) return rc;   // :916-917
         }
     }
-    ORBX_HIP_CHECK(hipEventRecord(h->ev1, s));
-    h->timed = true;
+    if (const int rc = h->timer.end(s)) return rc;
     // :921-958: final classification, chi2 and estimates in one kernel and one copy
     hipLaunchKernelGGL(k_classify, dim3(gEc), dim3(256), 0, h->stream, c.d, oa + L.dFlag, res->edge_chi2 ? (double *)(oa + L.dChi) : (double *)nullptr, (DPose *)(oa + L.dPose),
                        (double *)(oa + L.dPt));
-    LCHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipMemcpyAsync(io, oa, L.outEnd, hipMemcpyDeviceToHost, h->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     lba_write_result(io, L, K, P, E, res);
@@ -3230,9 +3194,8 @@ extern "C" int orbx_bundle_adjustment(orbx_lba *h, const orbx_lba_problem *p, in
 }
 
 // ---- PoseOptimization: its own small handle (stream + staging), batch of independent frames ----
-struct orbx_pose_optimizer {
-    int device = 0, maxFrames = 0, maxFeatures = 0;
-    hipStream_t stream = nullptr;
+struct orbx_pose_optimizer : OrbxHandle {
+    int maxFrames = 0, maxFeatures = 0;
     OrbxCallBox box;   // inputs of a call in mapped pinned memory (read in place), results written by the kernel into mapped pinned memory, sequence word
 };
 
@@ -3240,22 +3203,14 @@ extern "C" int orbx_pose_optimizer_create(int device, int max_frames, int max_fe
 {
     if (!out || max_frames < 1 || max_features < 1) { orbx_set_error("bad pose optimizer arguments"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_pose_optimizer *h = new orbx_pose_optimizer();
-    h->device = device; h->maxFrames = max_frames; h->maxFeatures = max_features;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
+    h->maxFrames = max_frames; h->maxFeatures = max_features;
+    if (const int rc = h->open(device)) { orbx_destroy_handle(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_pose_optimizer_destroy(orbx_pose_optimizer *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    h->box.release();
-    delete h;
-}
+extern "C" void orbx_pose_optimizer_destroy(orbx_pose_optimizer *h) { orbx_destroy_handle(h); }
 
 // developer tap (tools/pose_opt_phases.py; not part of include/orbx.h): a device array of 32 u64 the PROF instantiation of k_pose_opt adds its phase cycles / counts to
 static unsigned long long *g_poProf = nullptr;
@@ -3301,8 +3256,7 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
     else if (maxCount <= 256 * 8) hipLaunchKernelGGL((k_pose_opt<8, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
     else if (maxCount <= 256 * 16) hipLaunchKernelGGL((k_pose_opt<16, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
     else hipLaunchKernelGGL((k_pose_opt<32, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);      // up to 8192 correspondences: 32 per thread, one wave per SIMD
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { orbx_set_error("kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
+    ORBX_LAUNCH_CHECK();
     if ((rcs = bx.wait(st)) != ORBX_OK) return rcs;
     if (poses_out) memcpy(poses_out, o0, (size_t)B * 64);
     if (outlier)      // entries past a frame's count are not written by the kernel: they read 0
@@ -3319,10 +3273,10 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
 extern "C" int orbx_lba_last_timing(orbx_lba *h, float *device_ms, double *flops) { return lba_last_timing(h, device_ms, flops); }
 
 // ---- batched LocalBundleAdjustment: N independent windows, one launch chain ----
-struct orbx_lba_batch : LbaCore {
-    int launches = 0;                    // kernel launches of the last call (tools/lba_batch_rate.py)
-    OrbxDevBuf<uint8_t> descDev;         // LbaWin[2][maxW] | UnpackSegs[maxW] | route lists [2][7][maxW]
+struct orbx_lba_batch : LbaCore {      // (timer.launches: tools/lba_batch_rate.py reads it)
+    OrbxOwnedBuf<uint8_t> descDev;         // LbaWin[2][maxW] | UnpackSegs[maxW] | route lists [2][7][maxW]
     uint8_t *hostDesc = nullptr;         // pinned staging of descDev
+    ~orbx_lba_batch() { if (hostDesc) (void)hipHostFree(hostDesc); }
 };
 
 namespace {
@@ -3330,14 +3284,7 @@ const LbaDev D0 = {};      // the by-value views of a batch launch's arguments: 
 size_t batch_desc_bytes(int maxW) { return (size_t)2 * maxW * sizeof(LbaWin) + (size_t)maxW * sizeof(UnpackSegs) + (size_t)2 * RT_N * maxW * sizeof(int); }
 }
 
-extern "C" void orbx_lba_batch_destroy(orbx_lba_batch *h)
-{
-    if (!h) return;
-    lba_close(h);
-    h->descDev.release();
-    if (h->hostDesc) (void)hipHostFree(h->hostDesc);
-    delete h;
-}
+extern "C" void orbx_lba_batch_destroy(orbx_lba_batch *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_lba_batch_create(int device, int max_windows, int max_keyframes, int max_points, int max_edges, orbx_lba_batch **out)
 {
@@ -3366,7 +3313,7 @@ struct BatchWinHost {
     LbaLayout L;      // absolute offsets in the arenas of the batch
 };
 
-#define BLAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); h->launches++; } while (0)
+#define BLAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); h->timer.launches++; } while (0)
 
 // SparseOptimizer::optimize(iters) of every window with run = 1 in the descriptors `Wd` (optimize() of the single-window driver, from the
 // start of the stage on): the windows advance trial by trial together; the host waits for the decision of every window that is not done yet.
@@ -3395,7 +3342,7 @@ int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<Lb
     BLAUNCH(k_sum_poses_fin<true>, dim3((unsigned)((32 * maxK0 + 255) / 256), 1, Nz), dim3(256), 0, s, D0, nullptr, nullptr, nullptr, 0, nullptr, 0, Wd);
     BLAUNCH(k_diag_max<true>, dim3(1, 1, Nz), dim3(1024), 0, s, nullptr, 0, nullptr, 0, nullptr, Wd);
     BLAUNCH(k_lm_begin<true>, dim3(1, 1, Nz), dim3(256), 0, s, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, (h->seq += 1.0), nullptr, Wd);
-    LCHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t ldsRows = (size_t)(6 * maxNP6) * sizeof(unsigned long long);
     if (ldsRows > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_schur_rows<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsRows));
     auto trialSchur = [&]() -> int {
@@ -3407,7 +3354,7 @@ int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<Lb
             BLAUNCH(k_schur_fin<true>, dim3((unsigned)((maxNP6 + 255) / 256), (unsigned)(maxPose + 1), Nz), dim3(256), 0, s, D0, nullptr, nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0, nullptr,
                     nullptr, nullptr, nullptr, 0, Wd);
         }
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         return ORBX_OK;
     };
     auto trialChol = [&]() -> int {
@@ -3437,7 +3384,7 @@ int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<Lb
             if (nList[RT_REG10]) BLAUNCH((k_chol_backsub_reg<10, true>), dim3(1, 1, (unsigned)nList[RT_REG10]), dim3(1024), 0, s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_REG10 * mw);
             if (nList[RT_LDS]) BLAUNCH((k_chol_backsub<false, true>), dim3(1, 1, (unsigned)nList[RT_LDS]), dim3(1024), 0, s, nullptr, nullptr, 0, nullptr, nullptr, 0, Wd, L + RT_LDS * mw);
         }
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         return ORBX_OK;
     };
     auto trialRest = [&](double *seqOut) -> int {
@@ -3446,7 +3393,7 @@ int batch_stage(orbx_lba_batch *h, int N, const LbaWin *Wd, const std::vector<Lb
         const double seq = (h->seq += 1.0);
         BLAUNCH(k_lm_decide<true>, dim3(1, 1, Nz), dim3(256), 0, s, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, seq, D0, nullptr, nullptr, nullptr, Wd);
         BLAUNCH(k_lin_sums<true>, dim3((unsigned)maxLin, 1, Nz), dim3(256), 0, s, D0, Huber{}, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, Wd, 1);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         for (int w : live) h->flops += 650.0 * hw[w].d.E + (double)hw[w].nP6 * hw[w].nP6 * hw[w].nP6 / 3.0;
         *seqOut = seq;
         return ORBX_OK;
@@ -3505,7 +3452,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
     }
     // ---- from here on nothing fails for a reason of the input
     for (int w = 0; w < N; w++) for (int i = 0; i < 8; i++) res[w].stats[i] = 0;
-    h->flops = 0; h->launches = 0;
+    h->flops = 0; h->timer.launches = 0;
     const int mw = h->maxW;
     size_t nnStride = 1, cntStride = 1;
     int maxK0 = 1, maxP0 = 1, maxE0 = 1, maxChunk = 1;
@@ -3582,7 +3529,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
     buildLists(hw1, hL1, cnt1);
     for (int w = 0; w < N; w++) hD1[w] = hw1[w];
     hipStream_t s = h->stream;
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, s));
+    if (const int rc = h->timer.begin(s)) return rc;
     ORBX_HIP_CHECK(hipMemcpyAsync(h->inArena.p, io, inBytes, hipMemcpyHostToDevice, s));
     ORBX_HIP_CHECK(hipMemcpyAsync(h->descDev.p, h->hostDesc, batch_desc_bytes(mw), hipMemcpyHostToDevice, s));
     const unsigned Nz = (unsigned)N, gE = (unsigned)((maxE0 + 255) / 256);
@@ -3596,7 +3543,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         BLAUNCH(k_csr_pt_fill<true>, dim3(gE, 1, Nz), dim3(256), 0, s, nullptr, 0, nullptr, nullptr, nullptr, dD1);
         BLAUNCH(k_csr_pt_rank<true>, dim3(gE, 1, Nz), dim3(256), 0, s, nullptr, 0, nullptr, nullptr, nullptr, dD1);
         BLAUNCH(k_csr_rows<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dD1);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
     }
     std::vector<double> st1(4 * (size_t)N, 0.0), st2(4 * (size_t)N, 0.0);
     // ---- stage 1 (:863-864): initializeOptimization, then 5 robust iterations
@@ -3606,7 +3553,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         BLAUNCH(k_stage_mark<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dD1);
         BLAUNCH(k_stage_index<true>, dim3(1, 1, Nz), dim3(1024), 0, s, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, (h->seq += 1.0), dD1);
         BLAUNCH(k_stage_pairs<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dD1);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         ORBX_HIP_CHECK(hipMemsetAsync(h->Sacc.p, 0, (size_t)N * nnStride * sizeof(unsigned long long), s));
         int rc = batch_stage(h, N, dD1, hw1, dL1, cnt1, maxP0, maxK0, maxE0, stops, st1.data());
         if (rc) return rc;
@@ -3630,7 +3577,7 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         const double seq = (h->seq += 1.0);
         BLAUNCH(k_stage_index<true>, dim3(1, 1, Nz), dim3(1024), 0, s, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, seq, dD2);
         BLAUNCH(k_stage_pairs<true>, dim3(gE, 1, Nz), dim3(256), 0, s, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dD2);
-        LCHECK();
+        ORBX_LAUNCH_CHECK();
         std::vector<int> in2;
         for (int w = 0; w < N; w++) if (wh[w].stage2) in2.push_back(w);
         int rc = lba_wait(h, "LBA batch", in2.data(), (int)in2.size(), seq, stops);      // the stage's vertex counts, once for the whole batch
@@ -3653,11 +3600,10 @@ static int lba_run_batch(orbx_lba_batch *h, int N, const orbx_lba_problem *probs
         rc = batch_stage(h, N, dD2, hw2, dL2, cnt2, maxP0, maxK0, maxE0, stops, st2.data());
         if (rc) return rc;
     }
-    ORBX_HIP_CHECK(hipEventRecord(h->ev1, s));
-    h->timed = true;
+    if (const int rc = h->timer.end(s)) return rc;
     // :921-958: final classification, chi2 and estimates of every window in one launch, one copy back
     BLAUNCH(k_classify<true>, dim3((unsigned)((std::max(maxE0, std::max(maxK0, 3 * maxP0)) + 255) / 256), 1, Nz), dim3(256), 0, s, D0, nullptr, nullptr, nullptr, nullptr, dD1, 1);
-    LCHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipMemcpyAsync(io, oa, outBytes, hipMemcpyDeviceToHost, s));
     ORBX_HIP_CHECK(hipStreamSynchronize(s));
     for (int w = 0; w < N; w++) {
@@ -3678,4 +3624,4 @@ extern "C" int orbx_lba_solve_batch(orbx_lba_batch *h, int num_windows, const or
 extern "C" int orbx_lba_batch_last_timing(orbx_lba_batch *h, float *device_ms, double *flops) { return lba_last_timing(h, device_ms, flops); }
 
 // developer tap (tools/lba_batch_rate.py; not part of include/orbx.h): kernel launches of the handle's last batch call
-extern "C" int orbx_debug_lba_batch_launches(orbx_lba_batch *h) { return h ? h->launches : -1; }
+extern "C" int orbx_debug_lba_batch_launches(orbx_lba_batch *h) { return h ? h->timer.launches : -1; }

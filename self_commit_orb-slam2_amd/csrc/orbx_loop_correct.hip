@@ -32,7 +32,7 @@
 #include <cmath>
 #include <vector>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 #include "orbx_normal_depth.h"
 #include "orbx_sim3_group.h"
 
@@ -287,53 +287,28 @@ __global__ __launch_bounds__(LC_THREADS) void k_lg_points(LgDev D, unsigned *cou
 
 }  // namespace
 
-struct orbx_loop {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct orbx_loop : OrbxHandle {
+    OrbxCallTimer timer;
     OrbxCallBox box;
-    OrbxDevBuf<uint8_t> arena;      // the staged inputs in device memory
-    OrbxDevBuf<uint8_t> work;       // claim words, the group's Sim3s and centres, unit vectors | TcwGBA
-    OrbxDevBuf<uint8_t> results;    // orbx_loop_correct_sim3: the results before they cross to the host in one piece
+    OrbxOwnedBuf<uint8_t> arena;      // the staged inputs in device memory
+    OrbxOwnedBuf<uint8_t> work;       // claim words, the group's Sim3s and centres, unit vectors | TcwGBA
+    OrbxOwnedBuf<uint8_t> results;    // orbx_loop_correct_sim3: the results before they cross to the host in one piece
     std::vector<int32_t> groupPos, order, levelOff, level;
     std::vector<uint8_t> reached;
-    bool timed = false;
-    int launches = 0;
 };
 
 extern "C" int orbx_loop_create(int device, orbx_loop **out)
 {
     if (!out) { orbx_set_error("orbx_loop_create: NULL argument"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_loop *h = new orbx_loop();
-    h->device = device;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-        orbx_set_error("loop correction: stream / event creation failed");
-        orbx_loop_destroy(h);
-        return ORBX_ERR_HIP;
-    }
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create())) { orbx_destroy_handle(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_loop_destroy(orbx_loop *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    h->box.release(); h->arena.release(); h->work.release(); h->results.release();
-    delete h;
-}
-
-#define LC_LAUNCH_CHECK()                                                                                              \
-    do {                                                                                                               \
-        const hipError_t le_ = hipGetLastError();                                                                      \
-        if (le_ != hipSuccess) { orbx_set_error("loop correction kernel launch failed: %s", hipGetErrorString(le_)); return ORBX_ERR_HIP; } \
-        h->launches++;                                                                                                 \
-    } while (0)
+extern "C" void orbx_loop_destroy(orbx_loop *h) { orbx_destroy_handle(h); }
 
 namespace {
 
@@ -457,7 +432,7 @@ extern "C" int orbx_loop_correct_sim3(orbx_loop *h, const orbx_loop_sim3_problem
     if ((rc = lc_validate_sim3(p, groupPos)) != ORBX_OK) return rc;
     if (!h) { orbx_set_error("orbx_loop_correct_sim3: NULL handle"); return ORBX_ERR_ARG; }
     const size_t NK = (size_t)p->num_keyframes, G = (size_t)p->num_group, M = (size_t)p->num_points, S = (size_t)p->num_entries, T = (size_t)p->num_obs;
-    h->timed = false; h->launches = 0;
+    h->timer.timed = false;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     auto pd = [](size_t b) { return OrbxCallBox::padded(b); };
     const size_t inBytes = pd(48 * NK) + pd(12 * NK) + pd(4 * G) + pd(4 * NK) + pd(64) + pd(4 * (G + 1)) + pd(4 * S) + pd(12 * M) + 2 * pd(M) + 3 * pd(4 * M) + pd(4 * (M + 1)) + pd(4 * T);
@@ -494,27 +469,26 @@ extern "C" int orbx_loop_correct_sim3(orbx_loop *h, const orbx_loop_sim3_problem
     D.oNonc = (double *)(O + oNonc); D.oCorr = (double *)(O + oCorr); D.oTiw = (float *)(O + oTiw); D.oOwNew = (float *)(O + oOw); D.oScwMat = (float *)(O + oScw);
     D.oPos = (float *)(O + oPos); D.oBy = (int32_t *)(O + oBy); D.oNormal = (float *)(O + oNor); D.oMax = (float *)(O + oMax); D.oMin = (float *)(O + oMin);
     D.oUpd = O + oUpd;
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     const size_t n16 = bx.used / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    LC_LAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     hipLaunchKernelGGL(k_lc_sim3, dim3((unsigned)((std::max(G, M) + LC_THREADS - 1) / LC_THREADS)), dim3(LC_THREADS), 0, h->stream, D);
-    LC_LAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     if (S > 0 && M > 0) {
         hipLaunchKernelGGL(k_lc_claim, dim3((unsigned)std::min<size_t>(G, LC_CLAIM_BLOCKS)), dim3(LC_THREADS), 0, h->stream, D);
-        LC_LAUNCH_CHECK();
+        ORBX_LAUNCH_COUNT(h->timer);
     }
     if (M > 0) {
         hipLaunchKernelGGL(k_lc_move, dim3((unsigned)std::min<size_t>(M, (size_t)1 << 20)), dim3(LC_POINT_THREADS), 0, h->stream, D);
-        LC_LAUNCH_CHECK();
+        ORBX_LAUNCH_COUNT(h->timer);
     }
     const unsigned long long seq = bx.arm();
     const size_t o16 = outBytes / 16;
     hipLaunchKernelGGL(k_lc_results, dim3((unsigned)std::min<size_t>(256, (o16 + LC_THREADS - 1) / LC_THREADS)), dim3(LC_THREADS), 0, h->stream, (const uint4 *)h->results.p,
                        bx.outDev<uint4>(0), o16, bx.counter, bx.flagDev, seq);
-    LC_LAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     if (r) {
         if (r->noncorrected) memcpy(r->noncorrected, bx.outHost<uint8_t>(oNonc), 64 * G);
@@ -544,7 +518,7 @@ extern "C" int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem
     if ((rc = lc_validate_gba(p, reached, level, order, levelOff)) != ORBX_OK) return rc;
     if (!h) { orbx_set_error("orbx_loop_propagate_gba: NULL handle"); return ORBX_ERR_ARG; }
     const size_t n = (size_t)p->num_keyframes, M = (size_t)p->num_points, L = levelOff.size() - 1, C = order.size();
-    h->timed = false; h->launches = 0;
+    h->timer.timed = false;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     auto pd = [](size_t b) { return OrbxCallBox::padded(b); };
     const size_t kfBytes = 2 * pd(48 * n) + pd(4 * n) + pd(n) + pd(4 * C) + pd(4 * (L + 1));
@@ -572,16 +546,15 @@ extern "C" int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem
     D.ref = bx.put(p->point_ref, M);
     D.gba = (float *)h->work.p;
     D.oGba = bx.outDev<float>(oGba); D.oPos = bx.outDev<float>(oPos); D.oMoved = bx.outDev<uint8_t>(oMoved);
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    LC_LAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     hipLaunchKernelGGL(k_lg_chain, dim3(1), dim3(LC_THREADS), 0, h->stream, D);
-    LC_LAUNCH_CHECK();
+    ORBX_LAUNCH_COUNT(h->timer);
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_lg_points, dim3((unsigned)std::max<size_t>(1, (M + LC_THREADS - 1) / LC_THREADS)), dim3(LC_THREADS), 0, h->stream, D, bx.counter, bx.flagDev, seq);
-    LC_LAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     if (r) {
         if (r->tcw_gba) memcpy(r->tcw_gba, bx.outHost<uint8_t>(oGba), 48 * n);
@@ -597,13 +570,5 @@ extern "C" int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem
 extern "C" int orbx_loop_last_timing(orbx_loop *h, float *device_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL loop correction handle"); return ORBX_ERR_ARG; }
-    float ms = 0.f;
-    if (h->timed) {
-        ORBX_HIP_CHECK(hipSetDevice(h->device));
-        ORBX_HIP_CHECK(hipEventSynchronize(h->ev1));
-        ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    }
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->timed ? h->launches : 0;
-    return ORBX_OK;
+    return h->timer.read(h->device, device_ms, launches, nullptr);
 }

@@ -28,7 +28,7 @@
 #include <climits>
 #include <vector>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 #include "orbx_normal_depth.h"
 
 namespace {
@@ -224,49 +224,38 @@ __global__ __launch_bounds__(256) void k_mp_strided(MpDev D)
 
 #define MP_MAX_OBS 65535      /* per point: u16 bins and the 16-bit row index of the arg-min key */
 
-struct orbx_mappoint_ops {
-    int device = 0, maxPoints = 0, maxObs = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct orbx_mappoint_ops : OrbxHandle {
+    int maxPoints = 0, maxObs = 0;
+    OrbxCallTimer timer;
     OrbxHostStage stage;                 // inputs of a call: one pinned buffer, one copy
-    OrbxDevBuf<uint8_t> out;             // bestObs | bestMed | normal | maxD | minD
-    OrbxDevBuf<float> unit;
-    OrbxDevBuf<int32_t> comp;
+    OrbxOwnedBuf<uint8_t> out;             // bestObs | bestMed | normal | maxD | minD
+    OrbxOwnedBuf<float> unit;
+    OrbxOwnedBuf<int32_t> comp;
     uint8_t *hostOut = nullptr;          // pinned, sized for maxPoints
     std::vector<int32_t> lists[4];
-    float kernelMs = 0.0f;
-    int launches = 0;
+    float kernelMs = 0.0f;               // read inside the call, behind its synchronisation: what orbx_mappoint_last_timing returns
     bool ldsSet = false;
+    ~orbx_mappoint_ops() { if (hostOut) (void)hipHostFree(hostOut); }
 };
 
 extern "C" int orbx_mappoint_ops_create(int device, int max_points, int max_obs_total, orbx_mappoint_ops **out)
 {
     if (!out || max_points < 1 || max_obs_total < 1) { orbx_set_error("bad map point ops arguments"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_mappoint_ops *h = new orbx_mappoint_ops();
-    h->device = device; h->maxPoints = max_points; h->maxObs = max_obs_total;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-        hipHostMalloc((void **)&h->hostOut, (size_t)max_points * 28, hipHostMallocDefault) != hipSuccess) {
-        orbx_set_error("map point ops: stream / event / pinned memory creation failed");
-        orbx_mappoint_ops_destroy(h);
+    h->maxPoints = max_points; h->maxObs = max_obs_total;
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create())) { orbx_destroy_handle(h); return rc; }
+    if (hipHostMalloc((void **)&h->hostOut, (size_t)max_points * 28, hipHostMallocDefault) != hipSuccess) {
+        orbx_set_error("map point ops: pinned memory allocation failed");
+        orbx_destroy_handle(h);
         return ORBX_ERR_HIP;
     }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_mappoint_ops_destroy(orbx_mappoint_ops *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->hostOut) (void)hipHostFree(h->hostOut);
-    h->stage.release(); h->out.release(); h->unit.release(); h->comp.release();
-    delete h;
-}
+extern "C" void orbx_mappoint_ops_destroy(orbx_mappoint_ops *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_batch *b, const orbx_mappoint_result *r)
 {
@@ -274,7 +263,7 @@ extern "C" int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_b
     const int M = b->num_points, T = b->num_obs;
     if (M < 0 || T < 0) { orbx_set_error("negative batch size"); return ORBX_ERR_ARG; }
     if (M > h->maxPoints || T > h->maxObs) { orbx_set_error("batch (%d points, %d observations) exceeds the handle (%d, %d)", M, T, h->maxPoints, h->maxObs); return ORBX_ERR_ARG; }
-    h->kernelMs = 0.0f; h->launches = 0;
+    h->kernelMs = 0.0f; h->timer.launches = 0;
     if (M == 0) return ORBX_OK;
     if (!b->obs_offset || !b->pos || !b->ref_center || !b->ref_scale || !b->top_scale || (T > 0 && (!b->desc || !b->cam_center))) { orbx_set_error("NULL batch array"); return ORBX_ERR_ARG; }
     if (b->obs_offset[0] != 0) { orbx_set_error("obs_offset[0] must be 0"); return ORBX_ERR_ARG; }
@@ -322,7 +311,7 @@ extern "C" int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_b
 
     if ((rc = S.flush(st)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipMemsetAsync(h->out.p, 0, outBytes, st));      // points without observations read 0: the same bits on every call
-    ORBX_HIP_CHECK(hipEventRecord(h->ev0, st));
+    if ((rc = h->timer.begin(st)) != ORBX_OK) return rc;
     for (int c = 0; c < 4; c++) {
         const unsigned cnt = (unsigned)h->lists[c].size();
         if (!cnt) continue;
@@ -331,14 +320,12 @@ extern "C" int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_b
         else if (c == 1) hipLaunchKernelGGL((k_mp_block<128>), dim3(cnt), dim3(128), mp_block_lds(128), st, D);
         else if (c == 2) hipLaunchKernelGGL((k_mp_block<256>), dim3(cnt), dim3(256), mp_block_lds(256), st, D);
         else hipLaunchKernelGGL(k_mp_strided, dim3(cnt), dim3(256), mp_strided_lds(), st, D);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { orbx_set_error("map point kernel launch failed: %s", hipGetErrorString(e)); return ORBX_ERR_HIP; }
-        h->launches++;
+        ORBX_LAUNCH_COUNT(h->timer);
     }
-    ORBX_HIP_CHECK(hipEventRecord(h->ev1, st));
+    if ((rc = h->timer.end(st)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipMemcpyAsync(h->hostOut, h->out.p, outBytes, hipMemcpyDeviceToHost, st));
     ORBX_HIP_CHECK(hipStreamSynchronize(st));
-    ORBX_HIP_CHECK(hipEventElapsedTime(&h->kernelMs, h->ev0, h->ev1));
+    ORBX_HIP_CHECK(hipEventElapsedTime(&h->kernelMs, h->timer.ev[0], h->timer.ev[1]));
     if (r) {
         const uint8_t *o = h->hostOut;
         if (r->best_obs) memcpy(r->best_obs, o, m * 4);
@@ -356,6 +343,6 @@ extern "C" int orbx_mappoint_last_timing(orbx_mappoint_ops *h, float *kernel_ms,
 {
     if (!h) { orbx_set_error("NULL map point ops handle"); return ORBX_ERR_ARG; }
     if (kernel_ms) *kernel_ms = h->kernelMs;
-    if (launches) *launches = h->launches;
+    if (launches) *launches = h->timer.launches;
     return ORBX_OK;
 }

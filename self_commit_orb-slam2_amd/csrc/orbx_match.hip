@@ -1209,20 +1209,15 @@ extern "C" int orbx_matcher_create(int device, int max_features, int max_pairs, 
 {
     if (!out || max_features < 1 || max_features > 65535 || max_pairs < 1) { orbx_set_error("bad matcher arguments (1 <= max_features <= 65535)"); return ORBX_ERR_ARG; }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_matcher *m = new orbx_matcher();
-    m->device = device; m->maxFeatures = max_features; m->maxPairs = max_pairs;
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreateWithFlags(&m->evDep, hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&m->evDep2, hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&m->evPyr[0], hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&m->evPyr[1], hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&m->evDone[0], hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&m->evDone[1], hipEventDisableTiming);
-    for (int r = 0; r < MATCH_PROF_RING; r++) { (void)hipEventCreate(&m->ev0[r]); (void)hipEventCreate(&m->ev1[r]); (void)hipEventCreate(&m->evMid[r]); }
+    m->maxFeatures = max_features; m->maxPairs = max_pairs;
+    int rc = m->open(device);
+    hipEvent_t *const sync[] = {&m->evDep, &m->evDep2, &m->evPyr[0], &m->evPyr[1], &m->evDone[0], &m->evDone[1]};
+    for (hipEvent_t *e : sync) if (!rc) rc = orbx_event_create(e, hipEventDisableTiming);
+    for (int r = 0; r < MATCH_PROF_RING; r++)
+        for (hipEvent_t *e : {&m->ev0[r], &m->ev1[r], &m->evMid[r]}) if (!rc) rc = orbx_event_create(e);
     const size_t S = (size_t)max_features, P = (size_t)max_pairs;
-    int rc;
-    if ((rc = m->pairsA.ensure(P)) || (rc = m->pairsB.ensure(P)) || (rc = m->order.ensure(P * S)) || (rc = m->matches.ensure(P * S)) ||
+    if (rc || (rc = m->pairsA.ensure(P)) || (rc = m->pairsB.ensure(P)) || (rc = m->order.ensure(P * S)) || (rc = m->matches.ensure(P * S)) ||
         (rc = m->dists.ensure(P * S)) || (rc = m->nmatches.ensure(P)) || (rc = m->topk.ensure(P * S * TOPK)) || (rc = m->scales.ensure(128)) ||
         (rc = m->uright.ensure(P * S)) || (rc = m->depth.ensure(P * S)) || (rc = m->sad.ensure(P * S))) {
         orbx_matcher_destroy(m);
@@ -1232,29 +1227,7 @@ extern "C" int orbx_matcher_create(int device, int max_features, int max_pairs, 
     return ORBX_OK;
 }
 
-extern "C" void orbx_matcher_destroy(orbx_matcher *m)
-{
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    m->pairsA.release(); m->pairsB.release(); m->order.release(); m->matches.release(); m->dists.release(); m->nmatches.release();
-    m->hostStage.release(); m->projDec.release(); m->projQueue.release(); m->box.release(); m->arena.release();
-    m->topk.release(); m->scales.release(); m->uright.release(); m->depth.release(); m->sad.release(); m->stRowStart.release(); m->stRowList.release();
-    m->topk64.release(); m->pkp.release(); m->producerStatus.release();
-    for (int q = 0; q < 2; q++) { m->pf[q].release(); m->pb[q].release(); m->pi32[q].release(); }
-    if (m->evDep2) (void)hipEventDestroy(m->evDep2);
-    m->sfZero.release(); m->sfScalesDev.release();
-    if (m->sfHost) (void)hipHostFree(m->sfHost);
-    for (int i = 0; i < 2; i++) if (m->evPyr[i]) (void)hipEventDestroy(m->evPyr[i]);
-    for (int s = 0; s < 2; s++) { m->hk[s].release(); m->hd[s].release(); m->hv[s].release(); m->hc[s].release(); m->hg[s].release(); m->hs[s].release(); }
-    m->triGeom.release(); m->frProj.release(); m->frLevel.release(); m->frInView.release();
-    orbx_tri::release(m);
-    if (m->evDep) (void)hipEventDestroy(m->evDep);
-    for (int i = 0; i < 2; i++) if (m->evDone[i]) (void)hipEventDestroy(m->evDone[i]);
-    for (int r = 0; r < MATCH_PROF_RING; r++) { if (m->ev0[r]) (void)hipEventDestroy(m->ev0[r]); if (m->ev1[r]) (void)hipEventDestroy(m->ev1[r]); if (m->evMid[r]) (void)hipEventDestroy(m->evMid[r]); }
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
-}
+extern "C" void orbx_matcher_destroy(orbx_matcher *m) { orbx_destroy_handle(m); }
 
 // a consumer chained behind an extractor inherits its capacity word on the device (no host round trip); the consumer's download reports it
 // (`first` producer of a call overwrites the word - a consumer's status describes the call it belongs to, not its history -, a second one ORs)
@@ -1365,19 +1338,19 @@ extern "C" int orbx_search_by_bow_device(orbx_matcher *m, const orbx_feature_set
         if (mfma) hipLaunchKernelGGL(k_bow_topk_mfma, dim3((unsigned)((a->capacity + 255) / 256), (unsigned)npairs), dim3(256), 0, m->stream, A, B, m->pairsA.p, m->pairsB.p, dcut, m->topk.p, stride, dbg);
         else hipLaunchKernelGGL((k_bow_topk<false, false, TOPK_NROW>), gridTopk, dim3(256), 0, m->stream, A, B, m->pairsA.p, m->pairsB.p, params->mode, dcut, m->topk.p, stride, TriDev());
     }
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->evMid[slot], m->stream));
     m->midValid[slot] = true;
     // the processing order of the A features is an input of the replay only: behind the mid event, so that the first span of last_kernel_timing is
     // k_bow_topk alone (what a rocprofv3 kernel trace calls by that name) and the second the replay with its preparation
     hipLaunchKernelGGL(k_bow_order, dim3((unsigned)((a->capacity + 255) / 256), (unsigned)npairs), dim3(256), 0, m->stream, A, m->pairsA.p, m->order.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t ldsGreedy = (size_t)b->capacity * 4 + (size_t)a->capacity * 4 + (size_t)((a->capacity + 7) & ~7) * 2 * 2;
     if (ldsGreedy > 160 * 1024) { orbx_set_error("feature capacity %d too large for the LDS tile", a->capacity); return ORBX_ERR_CAPACITY; }
     if (ldsGreedy > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsGreedy));
     hipLaunchKernelGGL(k_bow_greedy, dim3((unsigned)npairs), dim3(GREEDY_THREADS), ldsGreedy, m->stream, A, B, m->pairsA.p, m->pairsB.p, params->mode, params->nn_ratio,
                        params->check_orientation, m->topk.p, m->order.p, m->matches.p, m->dists.p, m->nmatches.p, stride, TriDev(), (int32_t *)nullptr, (unsigned long long *)nullptr, 0ull);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = npairs; m->lastStride = stride;
@@ -1399,7 +1372,7 @@ extern "C" int orbx_stereo_match_device(orbx_matcher *m, const orbx_feature_set 
     m->midValid[slot] = false;
     hipLaunchKernelGGL(k_stereo, dim3((unsigned)((left->capacity + 3) / 4), (unsigned)npairs), dim3(256), 0, m->stream, to_dev(left), to_dev(right), m->pairsA.p,
                        m->pairsB.p, m->scales.p, max_disparity, m->matches.p, m->dists.p, m->nmatches.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = npairs; m->lastStride = stride;
@@ -1442,14 +1415,14 @@ extern "C" int orbx_compute_stereo_matches_device(orbx_matcher *m, orbx_extracto
         const size_t lds = (size_t)2 * (H + 1) * sizeof(int);
         if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_stereo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_stereo_rows, dim3((unsigned)npairs), dim3(256), lds, m->stream, to_dev(&fr), m->pairsB.p, m->scales.p, H, m->stRowStart.p, m->stRowList.p, listCap);
-        MLAUNCH_CHECK();
+        ORBX_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_stereo_full, dim3((unsigned)((vl.cap + 3) / 4), (unsigned)npairs), dim3(256), 0, m->stream, to_dev(&fl), to_dev(&fr), PL, PR, m->pairsA.p,
                        m->pairsB.p, m->scales.p, m->scales.p + 64, mbf, mb, m->matches.p, m->dists.p, m->uright.p, m->depth.p, m->sad.p, stride,
                        (const int32_t *)m->stRowStart.p, (const int32_t *)m->stRowList.p, H, listCap);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_stereo_cut, dim3((unsigned)npairs), dim3(256), 0, m->stream, to_dev(&fl), m->pairsA.p, m->sad.p, m->uright.p, m->depth.p, m->nmatches.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = npairs; m->lastStride = stride; m->lastStereoPairs = npairs;
@@ -1546,9 +1519,9 @@ extern "C" int orbx_stereo_frame_begin(orbx_matcher *m, orbx_extractor *left, or
             const int seq = ++m->sfSeq;
             hipLaunchKernelGGL(k_stereo_scan, dim3((unsigned)((vl.cap + 3) / 4)), dim3(256), lds1, st, to_dev(&fl), to_dev(&fr), PL, PR, sc, sc + 64, mbf, mb, m->matches.p, m->dists.p,
                                dU, dD, m->sad.p, stride, H, scanCap);
-            MLAUNCH_CHECK();
+            ORBX_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_stereo_cut_one, dim3(1), dim3(256), 0, st, to_dev(&fl), (const int32_t *)m->sad.p, dU, dD, m->nmatches.p, (int *)(m->sfHostDev + 2 * S), seq);
-            MLAUNCH_CHECK();
+            ORBX_LAUNCH_CHECK();
             m->sfFlagSeq = seq;
             m->lastPairs = 1; m->lastStride = stride;
             m->sfPending = 1;
@@ -1556,12 +1529,12 @@ extern "C" int orbx_stereo_frame_begin(orbx_matcher *m, orbx_extractor *left, or
         }
     }
     hipLaunchKernelGGL(k_stereo_rows, dim3(1), dim3(256), lds, st, to_dev(&fr), zero, sc, H, m->stRowStart.p, m->stRowList.p, listCap);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_stereo_full, dim3((unsigned)((vl.cap + 3) / 4), 1u), dim3(256), 0, st, to_dev(&fl), to_dev(&fr), PL, PR, zero, zero, sc, sc + 64, mbf, mb,
                        m->matches.p, m->dists.p, dU, dD, m->sad.p, stride, (const int32_t *)m->stRowStart.p, (const int32_t *)m->stRowList.p, H, listCap);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_stereo_cut, dim3(1), dim3(256), 0, st, to_dev(&fl), zero, m->sad.p, dU, dD, m->nmatches.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     m->sfPending = 1;
     return ORBX_OK;
@@ -1751,7 +1724,7 @@ static int search_by_bow_single(orbx_matcher *m, const orbx_feature_set *a, cons
     B.groups = b->groups ? (const int32_t *)dev(gb) : nullptr; B.valid = b->valid ? dev(vb) : nullptr; B.counts = dc + 1; B.cap = nB;
     const size_t n16 = bx.used / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, m->stream, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     uint32_t dcut = TH_LOW + 1;
     while (dcut < 257 && !(prm->nn_ratio * (float)dcut > (float)TH_LOW)) dcut++;
     const bool filter = b->groups != nullptr || (prm->mode == 1 && b->valid != nullptr);
@@ -1768,7 +1741,7 @@ static int search_by_bow_single(orbx_matcher *m, const orbx_feature_set *a, cons
         if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
         hipLaunchKernelGGL(k_bow_topk_pair<false>, grid, dim3(256), ldsPair, m->stream, A, B, prm->mode, dcut, nRowBlocks, per, m->topk.p, m->order.p);
     }
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t ldsGreedy = NB * 4 + NA * 4 + (size_t)((nA + 7) & ~7) * 2 * 2 + NB * 4 + std::max(NA, NB) * 4;      // (+ the B angles and the match list: k_bow_greedy with pubFlag)
     if (ldsGreedy > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile", nA); return ORBX_ERR_CAPACITY; }
     if (ldsGreedy > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsGreedy));
@@ -1780,7 +1753,7 @@ static int search_by_bow_single(orbx_matcher *m, const orbx_feature_set *a, cons
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_bow_greedy, dim3(1), dim3(GREEDY_THREADS), ldsGreedy, m->stream, A, B, (const int32_t *)m->sfZero.p, (const int32_t *)m->sfZero.p, prm->mode, prm->nn_ratio,
                        prm->check_orientation, m->topk.p, m->order.p, m->matches.p, m->dists.p, m->nmatches.p, stride, TriDev(), bx.outDev<int32_t>(0), bx.flagDev, seq);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(m->stream)) != ORBX_OK) return rc;
     const int32_t *res = bx.outHost<int32_t>(0);
@@ -1835,18 +1808,18 @@ extern "C" int orbx_search_for_triangulation_device(orbx_matcher *m, const orbx_
     const int slot = m->profCount % MATCH_PROF_RING;
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     hipLaunchKernelGGL(k_bow_order, dim3((unsigned)((a->capacity + 255) / 256), (unsigned)npairs), dim3(256), 0, m->stream, A, m->pairsA.p, m->order.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const dim3 gridTopk((unsigned)((a->capacity + TOPK_ROWS - 1) / TOPK_ROWS), (unsigned)npairs);
     // only dist <= TH_LOW can be accepted (:880) and there is no second-best test: cut at TH_LOW + 1
     hipLaunchKernelGGL((k_bow_topk<true, true, TOPK_NROW>), gridTopk, dim3(256), 0, m->stream, A, B, m->pairsA.p, m->pairsB.p, 2, (uint32_t)(TH_LOW + 1), m->topk.p, stride, T);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->midValid[slot] = false;
     const size_t ldsGreedy = (size_t)b->capacity * 4 + (size_t)a->capacity * 4 + (size_t)((a->capacity + 7) & ~7) * 2 * 2;
     if (ldsGreedy > 160 * 1024) { orbx_set_error("feature capacity %d too large for the LDS tile", a->capacity); return ORBX_ERR_CAPACITY; }
     if (ldsGreedy > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsGreedy));
     hipLaunchKernelGGL(k_bow_greedy, dim3((unsigned)npairs), dim3(GREEDY_THREADS), ldsGreedy, m->stream, A, B, m->pairsA.p, m->pairsB.p, 2, 0.0f, params->check_orientation,
                        m->topk.p, m->order.p, m->matches.p, m->dists.p, m->nmatches.p, stride, T, (int32_t *)nullptr, (unsigned long long *)nullptr, 0ull);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = npairs; m->lastStride = stride;

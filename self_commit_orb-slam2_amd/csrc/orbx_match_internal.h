@@ -3,7 +3,7 @@
 #ifndef ORBX_MATCH_INTERNAL_H
 #define ORBX_MATCH_INTERNAL_H
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 #include <vector>
 
 #define TH_HIGH 100       /* src/ORBmatcher.cc:49 */
@@ -58,9 +58,8 @@ __device__ __forceinline__ void three_maxima_wave(const int *hist, int lane, int
 struct ProjFrameDev { const orbx_keypoint *kp; const uint8_t *desc; const float *uRight; const uint8_t *occupied; const int32_t *counts; int cap;
                       float minX, minY, gwInv, ghInv; };
 
-struct orbx_matcher {
-    int device = 0, maxFeatures = 0, maxPairs = 0;
-    hipStream_t stream = nullptr;
+struct orbx_matcher : OrbxHandle {
+    int maxFeatures = 0, maxPairs = 0;
     hipEvent_t evDep = nullptr, evDone[2] = {nullptr, nullptr};
     int doneSlot = 0;
     hipEvent_t ev0[MATCH_PROF_RING] = {}, ev1[MATCH_PROF_RING] = {};   // one pair per *_device call (ring)
@@ -68,56 +67,62 @@ struct orbx_matcher {
     bool midValid[MATCH_PROF_RING] = {};
     float lastDistanceMs = 0.f, lastReplayMs = 0.f;
     int profCount = 0;
-    OrbxDevBuf<int32_t> pairsA, pairsB, order, matches, dists, nmatches;
-    OrbxDevBuf<uint32_t> topk;
-    OrbxDevBuf<float> scales, uright, depth, pf[2];          // pf: projection staging (floats)
-    OrbxDevBuf<unsigned long long> topk64;
-    OrbxDevBuf<uint8_t> pb[2];
-    OrbxDevBuf<int32_t> pi32[2];
-    OrbxDevBuf<orbx_keypoint> pkp;
-    OrbxDevBuf<uint32_t> projDec, projQueue;   // k_proj_greedy: chosen feature per map point, rescan queue
+    OrbxOwnedBuf<int32_t> pairsA, pairsB, order, matches, dists, nmatches;
+    OrbxOwnedBuf<uint32_t> topk;
+    OrbxOwnedBuf<float> scales, uright, depth, pf[2];          // pf: projection staging (floats)
+    OrbxOwnedBuf<unsigned long long> topk64;
+    OrbxOwnedBuf<uint8_t> pb[2];
+    OrbxOwnedBuf<int32_t> pi32[2];
+    OrbxOwnedBuf<orbx_keypoint> pkp;
+    OrbxOwnedBuf<uint32_t> projDec, projQueue;   // k_proj_greedy: chosen feature per map point, rescan queue
     OrbxHostStage hostStage;     // host-array entry points: all inputs of a call in one pinned buffer, one copy
     OrbxCallBox box;             // single-call host entry points of the tracking thread: mapped pinned inputs / results + sequence word (no copy engine, no stream sync)
-    OrbxDevBuf<uint8_t> arena;   // ... their inputs on the device, copied there once by k_stage_copy (same offsets as in box.in)
-    OrbxDevBuf<int32_t> sad;
-    OrbxDevBuf<int32_t> stRowStart, stRowList;   // ComputeStereoMatches: vRowIndices of the right frames (k_stereo_rows)
+    OrbxOwnedBuf<uint8_t> arena;   // ... their inputs on the device, copied there once by k_stage_copy (same offsets as in box.in)
+    OrbxOwnedBuf<int32_t> sad;
+    OrbxOwnedBuf<int32_t> stRowStart, stRowList;   // ComputeStereoMatches: vRowIndices of the right frames (k_stereo_rows)
     hipEvent_t evDep2 = nullptr, evPyr[2] = {nullptr, nullptr};
     int lastStereoPairs = 0;
     // orbx_stereo_frame (one stereo frame, host-synchronous): scale tables as last uploaded, a device zero for the pair arrays, pinned results
     float sfScales[128] = {};
     int sfLevels = 0;
-    OrbxDevBuf<int32_t> sfZero;
-    OrbxDevBuf<float> sfScalesDev;               // its own copy of the tables: the other calls overwrite `scales`
+    OrbxOwnedBuf<int32_t> sfZero;
+    OrbxOwnedBuf<float> sfScalesDev;               // its own copy of the tables: the other calls overwrite `scales`
     float *sfHost = nullptr, *sfHostDev = nullptr;   // pinned: uright | depth, written by the kernels across PCIe
     size_t sfHostFloats = 0;
     int sfSeq = 0, sfFlagSeq = 0;                 // k_stereo_one: call counter; the value the kernel of the pending call writes into the pinned completion word (0: none)
     int sfPending = 0;                            // orbx_stereo_frame_begin .. _end: 0 none, 1 launched (results land in sfHost), 2 the general path ran (download at the end)
     // staging for the host-array convenience calls
-    OrbxDevBuf<orbx_keypoint> hk[2];
-    OrbxDevBuf<uint8_t> hd[2], hv[2];
-    OrbxDevBuf<int32_t> hc[2], hg[2];
-    OrbxDevBuf<uint8_t> hs[2];                               // SearchForTriangulation: stereo flags (host form)
-    OrbxDevBuf<float> triGeom;                               // F12 + epipole per pair
+    OrbxOwnedBuf<orbx_keypoint> hk[2];
+    OrbxOwnedBuf<uint8_t> hd[2], hv[2];
+    OrbxOwnedBuf<int32_t> hc[2], hg[2];
+    OrbxOwnedBuf<uint8_t> hs[2];                               // SearchForTriangulation: stereo flags (host form)
+    OrbxOwnedBuf<float> triGeom;                               // F12 + epipole per pair
     // Frame::isInFrustum results (proj_x | proj_y | proj_xr | view_cos, level, in_view), orbx_projection_points layout
-    OrbxDevBuf<float> frProj;
-    OrbxDevBuf<int32_t> frLevel;
-    OrbxDevBuf<uint8_t> frInView;
+    OrbxOwnedBuf<float> frProj;
+    OrbxOwnedBuf<int32_t> frLevel;
+    OrbxOwnedBuf<uint8_t> frInView;
     size_t frCount = 0;
     int lastPairs = 0, lastStride = 0;
-    OrbxDevBuf<int> producerStatus;   // OR of the capacity words of the extractors this handle's calls were chained behind
+    OrbxOwnedBuf<int> producerStatus;   // OR of the capacity words of the extractors this handle's calls were chained behind
     // new map points (orbx_triangulate.hip): KF1 + the K neighbours staged once (pinned buffer, one copy), per-slot results of every neighbour
     OrbxHostStage npStage;
-    OrbxDevBuf<uint8_t> npStatus;     // [K * npStride]
-    OrbxDevBuf<float> npX3d;          // [K * npStride * 3]
-    OrbxDevBuf<int32_t> npMatches;    // [K * npStride]: the matches of each search (m->matches is overwritten by the next one)
-    OrbxDevBuf<int32_t> npNm;         // [K]
-    hipEvent_t npEv[2] = {nullptr, nullptr};
+    OrbxOwnedBuf<uint8_t> npStatus;     // [K * npStride]
+    OrbxOwnedBuf<float> npX3d;          // [K * npStride * 3]
+    OrbxOwnedBuf<int32_t> npMatches;    // [K * npStride]: the matches of each search (m->matches is overwritten by the next one)
+    OrbxOwnedBuf<int32_t> npNm;         // [K]
+    OrbxCallTimer npTimer;            // (its events are made by the first call)
     std::vector<hipEvent_t> npTriEv;  // profile_kernels: one pair per neighbour
-    int npTriTimed = 0, npLaunches = 0;
-    bool npTimed = false;
+    int npTriTimed = 0;
+    ~orbx_matcher()
+    {
+        hipEvent_t *const one[] = {&evDep, &evDep2, &evPyr[0], &evPyr[1], &evDone[0], &evDone[1]};
+        for (hipEvent_t *e : one) if (*e) (void)hipEventDestroy(*e);
+        for (int r = 0; r < MATCH_PROF_RING; r++)
+            for (hipEvent_t e : {ev0[r], ev1[r], evMid[r]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : npTriEv) if (e) (void)hipEventDestroy(e);
+        if (sfHost) (void)hipHostFree(sfHost);
+    }
 };
-
-namespace orbx_tri { void release(orbx_matcher *m); }   // orbx_triangulate.hip: called by orbx_matcher_destroy
 
 // ---- shared by orbx_triangulate.hip (CreateNewMapPoints) and orbx_initializer.hip (Initializer::Triangulate) ----
 // Sweeps of the one-sided Jacobi.  Chosen on the CPU with the same Jacobi restated in numpy float64 (tests/triangulate_ref.py::jacobi_null) over
@@ -181,12 +186,6 @@ __device__ __forceinline__ void jacobi_null(const float (&r0)[4], const float (&
     }
 }
 #endif
-
-#define MLAUNCH_CHECK()                                                                                              \
-    do {                                                                                                             \
-        hipError_t e_ = hipGetLastError();                                                                           \
-        if (e_ != hipSuccess) { orbx_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); return ORBX_ERR_HIP; } \
-    } while (0)
 
 // host helpers defined in orbx_match.hip
 namespace orbx_match {

@@ -653,7 +653,7 @@ static int fuse_launch(orbx_matcher *m, const ProjFrameDev &F, const FusePointsD
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     m->midValid[slot] = false;
     hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)((P.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, P, LV, chi2_gate, m->matches.p, m->dists.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = nframes; m->lastStride = stride;
@@ -886,13 +886,13 @@ static int area_launch(orbx_matcher *m, const ProjFrameDev &F, const AreaQueries
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     m->midValid[slot] = false;
     hipLaunchKernelGGL(k_area_topk, dim3((unsigned)((Q.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, Q, m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t lds = (size_t)F.cap * 4 + (size_t)Q.cap * 4 + (size_t)Q.cap * 2 + 16;
     if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
     if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_area_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_area_greedy, dim3((unsigned)nframes), dim3(256), lds, m->stream, F, Q, max_dist, m->topk64.p, m->matches.p, m->dists.p, m->nmatches.p,
                        stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = nframes; m->lastStride = stride;
@@ -1169,10 +1169,10 @@ extern "C" int orbx_search_for_initialization_device(orbx_matcher *m, const orbx
     m->midValid[slot] = false;
     hipLaunchKernelGGL(k_init_topk, dim3((unsigned)((f1->capacity + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, A, F, prev_matched_xy, (float)window_size, dcut,
                        m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_search_init, dim3((unsigned)nframes), dim3(256), lds, m->stream, A, F, prev_matched_xy, (float)window_size, nn_ratio, check_orientation,
                        m->topk64.p, m->matches.p, (int8_t *)m->pb[0].p, m->nmatches.p, stride);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = nframes; m->lastStride = stride;
@@ -1226,14 +1226,14 @@ static int proj_launch(orbx_matcher *m, const ProjFrameDev &F, const ProjPointsD
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     m->midValid[slot] = false;
     hipLaunchKernelGGL(k_proj_topk, dim3((unsigned)((P.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, P, m->scales.p, th, m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t lds = (size_t)F.cap * 6 + 16;
     if (lds > 160 * 1024) { orbx_set_error("feature capacity %d too large for the LDS tile of the projection replay", F.cap); return ORBX_ERR_CAPACITY; }
     if ((rc = m->projDec.ensure((size_t)nframes * P.cap)) != ORBX_OK || (rc = m->projQueue.ensure((size_t)nframes * P.cap)) != ORBX_OK) return rc;
     if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_proj_greedy, dim3((unsigned)nframes), dim3(PROJ_GREEDY_THREADS), lds, m->stream, F, P, m->scales.p, th, nnratio, m->topk64.p, m->matches.p,
                        m->nmatches.p, stride, m->projDec.p, m->projQueue.p, (int32_t *)nullptr, (unsigned long long *)nullptr, 0ull, 0);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = nframes; m->lastStride = stride;
@@ -1294,7 +1294,7 @@ extern "C" int orbx_search_by_projection(orbx_matcher *m, const orbx_projection_
     auto dev = [&](const void *boxAddr) { return ar + ((const uint8_t *)boxAddr - bx.inDev); };
     const size_t n16 = bx.used / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, st, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const int32_t *dCnt = (const int32_t *)dev(bCnt);
     const float *dScales = (const float *)dev(bSc);
     ProjFrameDev F = {(const orbx_keypoint *)dev(bKp), dev(bDesc), (const float *)dev(bUr), fr->occupied ? dev(bOcc) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
@@ -1303,7 +1303,7 @@ extern "C" int orbx_search_by_projection(orbx_matcher *m, const orbx_projection_
                        pt->has_observations ? dev(bObs) : nullptr, dev(bPd), dCnt + 1, mm};
     if ((rc = m->topk64.ensure(M * TOPK)) != ORBX_OK || (rc = m->projDec.ensure(M)) != ORBX_OK || (rc = m->projQueue.ensure(M)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_proj_topk, dim3((unsigned)((mm + 3) / 4), 1u), dim3(256), 0, st, F, P, dScales, th, m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     size_t lds = (size_t)n * 6 + 16;
     if (lds > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile of the projection replay", n); return ORBX_ERR_CAPACITY; }
     int decLds = 0;      // dec[mm] + the observation flags behind the feature tile, when they fit (k_proj_greedy)
@@ -1313,7 +1313,7 @@ extern "C" int orbx_search_by_projection(orbx_matcher *m, const orbx_projection_
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_proj_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, P, dScales, th, nn_ratio, m->topk64.p, m->matches.p, m->nmatches.p, stride, m->projDec.p,
                        m->projQueue.p, bx.outDev<int32_t>(0), bx.flagDev, seq, decLds);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     const int32_t *as = bx.outHost<int32_t>(0);
@@ -1336,14 +1336,14 @@ static int proj_last_launch(orbx_matcher *m, const ProjFrameDev &F, const ProjLa
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     m->midValid[slot] = false;
     hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((L.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, L, m->scales.p, th, b_mono, m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t lds = (size_t)F.cap * 5 + 16;
     if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
     if ((rc = m->projDec.ensure((size_t)nframes * L.cap)) != ORBX_OK || (rc = m->projQueue.ensure((size_t)nframes * L.cap)) != ORBX_OK) return rc;
     if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_last_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_proj_last_greedy, dim3((unsigned)nframes), dim3(PROJ_GREEDY_THREADS), lds, m->stream, F, L, m->scales.p, th, b_mono, check_ori, m->topk64.p,
                        m->matches.p, m->nmatches.p, stride, m->projDec.p, m->projQueue.p, (int32_t *)nullptr, (unsigned long long *)nullptr, 0ull);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = nframes; m->lastStride = stride;
@@ -1401,7 +1401,7 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
     auto dev = [&](const void *boxAddr) { return ar + ((const uint8_t *)boxAddr - bx.inDev); };
     const size_t n16 = bx.used / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, st, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const int32_t *dCnt = (const int32_t *)dev(bCnt);
     const float *dScales = (const float *)dev(bSc);
     ProjFrameDev F = {(const orbx_keypoint *)dev(bKp), dev(bDesc), (const float *)dev(bUr), fr->occupied ? dev(bOcc) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
@@ -1410,7 +1410,7 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
                      (const float *)dev(bTc), (const float *)dev(bTl), ls->fx, ls->fy, ls->cx, ls->cy, ls->mbf, ls->mb, ls->max_x, ls->max_y};
     if ((rc = m->topk64.ensure(NL * TOPK)) != ORBX_OK || (rc = m->projDec.ensure(NL)) != ORBX_OK || (rc = m->projQueue.ensure(NL)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((nl + 3) / 4), 1u), dim3(256), 0, st, F, L, dScales, th, b_mono, m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     const size_t lds = (size_t)n * 5 + 16;
     if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
     if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_last_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1418,7 +1418,7 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_proj_last_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, L, dScales, th, b_mono, check_orientation, m->topk64.p, m->matches.p, m->nmatches.p, stride,
                        m->projDec.p, m->projQueue.p, bx.outDev<int32_t>(0), bx.flagDev, seq);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     const int32_t *as = bx.outHost<int32_t>(0);
@@ -1584,7 +1584,7 @@ extern "C" int orbx_is_in_frustum_device(orbx_matcher *m, const orbx_frustum_fra
     MapPointsDev M = {points->world_pos, points->normal, points->max_distance, points->min_distance, points->counts, points->capacity};
     hipLaunchKernelGGL(k_is_in_frustum, dim3((unsigned)((points->capacity + 255) / 256), (unsigned)frame->nframes), dim3(256), 0, m->stream, Fr, M, m->frProj.p,
                        m->frProj.p + n, m->frProj.p + 2 * n, m->frLevel.p, m->frProj.p + 3 * n, m->frInView.p, (unsigned *)nullptr, (unsigned long long *)nullptr, 0ull);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->frCount = n;
     return ORBX_OK;
 }
@@ -1639,7 +1639,7 @@ extern "C" int orbx_is_in_frustum(orbx_matcher *m, const orbx_frustum_frame *fra
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_is_in_frustum, dim3((unsigned)((mm + 255) / 256), 1u), dim3(256), 0, st, Fr, M, bx.outDev<float>(0), bx.outDev<float>(oY), bx.outDev<float>(oXr), bx.outDev<int32_t>(oL),
                        bx.outDev<float>(oVc), bx.outDev<uint8_t>(oIn), bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     memcpy(in_view, bx.outHost<uint8_t>(oIn), n);
     // (the mTrack* values of a point that is not in view are not written by the kernel: the caller's arrays keep what they held, as the reference's members do)
@@ -1710,7 +1710,7 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
     const uint8_t *zDesc = dev(bPd);
     const size_t n16 = staged / 16;
     hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, st, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     if ((rc = m->frProj.ensure(4 * M)) || (rc = m->frLevel.ensure(M)) || (rc = m->frInView.ensure(M)) || (rc = m->topk64.ensure(M * TOPK)) || (rc = m->projDec.ensure(M)) ||
         (rc = m->projQueue.ensure(M))) return rc;
     const int32_t *dCnt = (const int32_t *)dev(bCnt);
@@ -1725,7 +1725,7 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
     FrustumHostOut Ho = {bx.outDev<float>(0), bx.outDev<float>(offPy), bx.outDev<float>(offPxr), bx.outDev<float>(offVc), bx.outDev<int32_t>(offLvl), bx.outDev<uint8_t>(offIn)};
     hipLaunchKernelGGL(k_frustum_topk, dim3((unsigned)((mm + 3) / 4)), dim3(256), 0, st, Fr, Mp, F, zDesc, dScales, th, m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p,
                        m->frProj.p + 3 * M, m->frInView.p, Ho, m->topk64.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->frCount = M;
     ProjPointsDev P = {m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p, m->frProj.p + 3 * M, m->frInView.p, pt->has_observations ? dev(bObs) : nullptr, zDesc, dCnt + 1, mm};
     size_t lds = (size_t)n * 6 + 16;
@@ -1737,7 +1737,7 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_proj_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, P, dScales, th, nn_ratio, m->topk64.p, m->matches.p, m->nmatches.p, stride, m->projDec.p,
                        m->projQueue.p, bx.outDev<int32_t>(offAs), bx.flagDev, seq, decLds);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     memcpy(in_view, bx.outHost<uint8_t>(offIn), M);

@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "orbx_match_internal.h"
+#include "orbx_handle.h"
 #include "orbx_sim3_group.h"
 
 #define OS_THREADS 256
@@ -496,12 +496,9 @@ __global__ __launch_bounds__(OS_THREADS) void k_optsim3(OsIn I, uint8_t *__restr
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct orbx_sim3_optimizer {
-    int device = 0, maxProblems = 0, maxPairs = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false;
-    int launches = 0;
+struct orbx_sim3_optimizer : OrbxHandle {
+    int maxProblems = 0, maxPairs = 0;
+    OrbxCallTimer timer;
     OrbxCallBox box;
 };
 
@@ -577,25 +574,15 @@ extern "C" int orbx_sim3_optimizer_create(int device, int max_problems, int max_
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_sim3_optimizer *h = new orbx_sim3_optimizer();
-    h->device = device; h->maxProblems = max_problems; h->maxPairs = max_pairs;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev[0]); (void)hipEventCreate(&h->ev[1]);
+    h->maxProblems = max_problems; h->maxPairs = max_pairs;
+    int rc;
+    if ((rc = h->open(device)) || (rc = h->timer.create())) { orbx_destroy_handle(h); return rc; }
     *out = h;
     return ORBX_OK;
 }
 
-extern "C" void orbx_sim3_optimizer_destroy(orbx_sim3_optimizer *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->box.release();
-    for (int i = 0; i < 2; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void orbx_sim3_optimizer_destroy(orbx_sim3_optimizer *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_optimize_sim3(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *Ps, int np, const orbx_sim3_opt_result *Rs)
 {
@@ -612,12 +599,10 @@ extern "C" int orbx_optimize_sim3(orbx_sim3_optimizer *h, const orbx_sim3_opt_pr
     if ((rc = os_stage(h, Ps, np, false, nullptr, probs, I)) != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
     const unsigned long long seq = bx.arm();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     os_launch<false>(h, maxN, np, I, seq);
-    MLAUNCH_CHECK();
-    h->launches = 1;
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
 
     for (int c = 0; c < np; c++) {
@@ -661,7 +646,7 @@ extern "C" int orbx_optimize_sim3_linearize(orbx_sim3_optimizer *h, const orbx_s
     OrbxCallBox &bx = h->box;
     const unsigned long long seq = bx.arm();
     os_launch<true>(h, P->n, 1, I, seq);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     const size_t n = (size_t)P->n;
     const OsLinBlock B(P->n);
@@ -676,12 +661,5 @@ extern "C" int orbx_optimize_sim3_linearize(orbx_sim3_optimizer *h, const orbx_s
 extern "C" int orbx_sim3_optimizer_last_timing(orbx_sim3_optimizer *h, float *device_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no orbx_optimize_sim3 call to report"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->launches;
-    return ORBX_OK;
+    return h->timer.read(h->device, device_ms, launches, "no orbx_optimize_sim3 call to report");
 }

@@ -33,7 +33,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "orbx_match_internal.h"
+#include "orbx_handle.h"
 
 #define PNP_SWEEPS12 ORBX_PNP_JACOBI_SWEEPS
 #define PNP_SWEEPS_SMALL ORBX_PNP_SMALL_SWEEPS
@@ -818,19 +818,17 @@ __global__ __launch_bounds__(PNP_DECIDE_THREADS) void k_pnp_decide(PnpDev D, uin
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct orbx_pnp_solver {
-    int device = 0, maxCands = 0, maxMatches = 0, maxIters = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false, solved = false;
-    int launches = 0;
+struct orbx_pnp_solver : OrbxHandle {
+    int maxCands = 0, maxMatches = 0, maxIters = 0;
+    OrbxCallTimer timer;
+    bool solved = false;
     OrbxCallBox box;
-    OrbxDevBuf<float> pts;                // 6 floats per match
-    OrbxDevBuf<double> models;            // 26 doubles per iteration
-    OrbxDevBuf<int32_t> sets, ints, nrec, cmCount, epSets;
-    OrbxDevBuf<PnpCand> cand;
-    OrbxDevBuf<unsigned long long> mask, cmMask;
-    OrbxDevBuf<double> epOut, epFull, epAlphas;
+    OrbxOwnedBuf<float> pts;                // 6 floats per match
+    OrbxOwnedBuf<double> models;            // 26 doubles per iteration
+    OrbxOwnedBuf<int32_t> sets, ints, nrec, cmCount, epSets;
+    OrbxOwnedBuf<PnpCand> cand;
+    OrbxOwnedBuf<unsigned long long> mask, cmMask;
+    OrbxOwnedBuf<double> epOut, epFull, epAlphas;
     std::vector<PnpCand> last;            // the candidates of the last solve (orbx_pnp_inliers)
 };
 
@@ -965,14 +963,11 @@ extern "C" int orbx_pnp_solver_create(int device, int max_candidates, int max_ma
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_pnp_solver *h = new orbx_pnp_solver();
-    h->device = device; h->maxCands = max_candidates; h->maxMatches = max_matches; h->maxIters = max_iterations;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev[0]); (void)hipEventCreate(&h->ev[1]);
+    h->maxCands = max_candidates; h->maxMatches = max_matches; h->maxIters = max_iterations;
     const size_t P = (size_t)max_candidates * max_matches, I = (size_t)max_candidates * max_iterations, W = (size_t)(max_matches + 63) / 64;
     int rc;
-    if ((rc = h->pts.ensure(6 * P)) || (rc = h->models.ensure(26 * I)) || (rc = h->sets.ensure(4 * I)) || (rc = h->ints.ensure(4 * I)) || (rc = h->nrec.ensure((size_t)max_candidates)) ||
+    if ((rc = h->open(device)) || (rc = h->timer.create()) || (rc = h->pts.ensure(6 * P)) || (rc = h->models.ensure(26 * I)) || (rc = h->sets.ensure(4 * I)) || (rc = h->ints.ensure(4 * I)) || (rc = h->nrec.ensure((size_t)max_candidates)) ||
         (rc = h->cmCount.ensure((size_t)max_iterations)) || (rc = h->cand.ensure((size_t)max_candidates)) || (rc = h->mask.ensure(2 * I * W)) ||
         (rc = h->cmMask.ensure((size_t)max_iterations * W))) {
         orbx_pnp_solver_destroy(h);
@@ -982,18 +977,7 @@ extern "C" int orbx_pnp_solver_create(int device, int max_candidates, int max_ma
     return ORBX_OK;
 }
 
-extern "C" void orbx_pnp_solver_destroy(orbx_pnp_solver *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->box.release();
-    h->pts.release(); h->models.release(); h->sets.release(); h->ints.release(); h->nrec.release(); h->cmCount.release(); h->epSets.release(); h->cand.release();
-    h->mask.release(); h->cmMask.release(); h->epOut.release(); h->epFull.release(); h->epAlphas.release();
-    for (int i = 0; i < 2; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void orbx_pnp_solver_destroy(orbx_pnp_solver *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, int nc, const orbx_pnp_result *Rs)
 {
@@ -1017,34 +1001,30 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
     h->solved = false;
 
     const unsigned long long seq = bx.arm();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_pnp_prepare, dim3(prepare_blocks(maxN, maxIt), (unsigned)nc), dim3(256), 0, h->stream, I, D, 1);
-    MLAUNCH_CHECK();
-    h->launches = 2;
+    ORBX_LAUNCH_COUNT(h->timer);
     if (maxIt > 0) {
         const unsigned teams = 64 / PNP_TEAM;
         hipLaunchKernelGGL(k_pnp_models, dim3((unsigned)((maxIt + teams - 1) / teams), (unsigned)nc), dim3(64), 0, h->stream, D, (const int32_t *)D.sets, 4, D.r, D.t, D.err, (double *)nullptr,
                            (double *)nullptr);
-        MLAUNCH_CHECK();
+        ORBX_LAUNCH_COUNT(h->timer);
         hipLaunchKernelGGL(k_pnp_check, dim3((unsigned)((maxIt + PNP_CHECK_WAVES - 1) / PNP_CHECK_WAVES), (unsigned)nc), dim3(64 * PNP_CHECK_WAVES), 0, h->stream, D, (const double *)D.r,
                            (const double *)D.t, (const int32_t *)nullptr, D.count, D.mask);
-        MLAUNCH_CHECK();
+        ORBX_LAUNCH_COUNT(h->timer);
         hipLaunchKernelGGL(k_pnp_records, dim3((unsigned)nc), dim3(64), 0, h->stream, D);
-        MLAUNCH_CHECK();
-        h->launches = 5;
+        ORBX_LAUNCH_COUNT(h->timer);
         if (maxRec > 0) {
             hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)maxRec, (unsigned)nc), dim3(PNP_REFINE_THREADS), 0, h->stream, D);
-            MLAUNCH_CHECK();
+            ORBX_LAUNCH_COUNT(h->timer);
             hipLaunchKernelGGL(k_pnp_check, dim3((unsigned)((maxRec + PNP_CHECK_WAVES - 1) / PNP_CHECK_WAVES), (unsigned)nc), dim3(64 * PNP_CHECK_WAVES), 0, h->stream, D,
                                (const double *)D.refR, (const double *)D.refT, (const int32_t *)D.nrec, D.refCount, D.refMask);
-            MLAUNCH_CHECK();
-            h->launches = 7;
-        }
+            ORBX_LAUNCH_COUNT(h->timer);
+            }
     }
     hipLaunchKernelGGL(k_pnp_decide, dim3((unsigned)nc), dim3(PNP_DECIDE_THREADS), 0, h->stream, D, bx.outDevP, bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
     h->last = cands; h->solved = true;
 
@@ -1126,10 +1106,10 @@ extern "C" int orbx_pnp_check_models(orbx_pnp_solver *h, const orbx_pnp_problem 
     // the last solve's matches on the device are overwritten, its masks are not: orbx_pnp_inliers keeps working
     const PnpDev D = dev_view(h);
     hipLaunchKernelGGL(k_pnp_prepare, dim3(prepare_blocks(P->n, 0), 1), dim3(256), 0, h->stream, I, D, 0);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_pnp_check, dim3((unsigned)((m + PNP_CHECK_WAVES - 1) / PNP_CHECK_WAVES), 1), dim3(64 * PNP_CHECK_WAVES), 0, h->stream, D, (const double *)(bx.inDev + L.extraA),
                        (const double *)(bx.inDev + L.extraB), (const int32_t *)nullptr, h->cmCount.p, h->cmMask.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     ORBX_HIP_CHECK(hipMemcpy(count, h->cmCount.p, (size_t)m * 4, hipMemcpyDeviceToHost));
     if (inliers && P->n > 0) {
@@ -1174,12 +1154,12 @@ extern "C" int orbx_pnp_epnp(orbx_pnp_solver *h, const orbx_pnp_problem *P, cons
     const PnpDev D = dev_view(h);
     double *o = h->epOut.p;
     hipLaunchKernelGGL(k_pnp_prepare, dim3(prepare_blocks(P->n, 0), 1), dim3(256), 0, h->stream, I, D, 0);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipMemcpyAsync(h->epSets.p, sets, nsets * 4, hipMemcpyHostToDevice, h->stream));
     const unsigned teams = 64 / PNP_TEAM;
     hipLaunchKernelGGL(k_pnp_models, dim3((unsigned)((m + teams - 1) / teams), 1), dim3(64), 0, h->stream, D, (const int32_t *)h->epSets.p, set_size, o, o + 9 * (size_t)m, o + 12 * (size_t)m,
                        full ? h->epFull.p : (double *)nullptr, alphas ? h->epAlphas.p : (double *)nullptr);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     ORBX_HIP_CHECK(hipMemcpy(R, o, (size_t)m * 72, hipMemcpyDeviceToHost));
     ORBX_HIP_CHECK(hipMemcpy(t, o + 9 * (size_t)m, (size_t)m * 24, hipMemcpyDeviceToHost));
@@ -1192,12 +1172,5 @@ extern "C" int orbx_pnp_epnp(orbx_pnp_solver *h, const orbx_pnp_problem *P, cons
 extern "C" int orbx_pnp_last_timing(orbx_pnp_solver *h, float *device_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no orbx_pnp_solve call to report"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->launches;
-    return ORBX_OK;
+    return h->timer.read(h->device, device_ms, launches, "no orbx_pnp_solve call to report");
 }

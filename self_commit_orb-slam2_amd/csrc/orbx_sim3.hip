@@ -27,7 +27,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "orbx_match_internal.h"
+#include "orbx_handle.h"
 
 // Sweeps of the 4x4 Jacobi: ORBX_SIM3_JACOBI_SWEEPS of include/orbx.h, where the choice is recorded
 #define SIM3_SWEEPS ORBX_SIM3_JACOBI_SWEEPS
@@ -367,17 +367,15 @@ __global__ __launch_bounds__(SIM3_DECIDE_THREADS) void k_sim3_decide(Sim3Dev D, 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------------------
-struct orbx_sim3_solver {
-    int device = 0, maxCands = 0, maxMatches = 0, maxIters = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false, solved = false;
-    int launches = 0;
+struct orbx_sim3_solver : OrbxHandle {
+    int maxCands = 0, maxMatches = 0, maxIters = 0;
+    OrbxCallTimer timer;
+    bool solved = false;
     OrbxCallBox box;
-    OrbxDevBuf<float> pairs, models;      // 12 floats per pair; 56 floats per iteration
-    OrbxDevBuf<int32_t> sets, count, cmCount;
-    OrbxDevBuf<Sim3Cand> cand;
-    OrbxDevBuf<unsigned long long> mask, cmMask;
+    OrbxOwnedBuf<float> pairs, models;      // 12 floats per pair; 56 floats per iteration
+    OrbxOwnedBuf<int32_t> sets, count, cmCount;
+    OrbxOwnedBuf<Sim3Cand> cand;
+    OrbxOwnedBuf<unsigned long long> mask, cmMask;
     std::vector<Sim3Cand> last;           // the candidates of the last solve (orbx_sim3_inliers)
 };
 
@@ -489,14 +487,11 @@ extern "C" int orbx_sim3_solver_create(int device, int max_candidates, int max_m
         return ORBX_ERR_ARG;
     }
     *out = nullptr;
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_sim3_solver *h = new orbx_sim3_solver();
-    h->device = device; h->maxCands = max_candidates; h->maxMatches = max_matches; h->maxIters = max_iterations;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; orbx_set_error("hipStreamCreate failed"); return ORBX_ERR_HIP; }
-    (void)hipEventCreate(&h->ev[0]); (void)hipEventCreate(&h->ev[1]);
+    h->maxCands = max_candidates; h->maxMatches = max_matches; h->maxIters = max_iterations;
     const size_t P = (size_t)max_candidates * max_matches, I = (size_t)max_candidates * max_iterations, W = (size_t)(max_matches + 63) / 64;
     int rc;
-    if ((rc = h->pairs.ensure(12 * P)) || (rc = h->models.ensure(65 * I)) || (rc = h->sets.ensure(3 * I)) || (rc = h->count.ensure(I)) || (rc = h->cmCount.ensure((size_t)max_iterations)) ||
+    if ((rc = h->open(device)) || (rc = h->timer.create()) || (rc = h->pairs.ensure(12 * P)) || (rc = h->models.ensure(65 * I)) || (rc = h->sets.ensure(3 * I)) || (rc = h->count.ensure(I)) || (rc = h->cmCount.ensure((size_t)max_iterations)) ||
         (rc = h->cand.ensure((size_t)max_candidates)) || (rc = h->mask.ensure(I * W)) || (rc = h->cmMask.ensure((size_t)max_iterations * W))) {
         orbx_sim3_solver_destroy(h);
         return rc;
@@ -505,17 +500,7 @@ extern "C" int orbx_sim3_solver_create(int device, int max_candidates, int max_m
     return ORBX_OK;
 }
 
-extern "C" void orbx_sim3_solver_destroy(orbx_sim3_solver *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->box.release();
-    h->pairs.release(); h->models.release(); h->sets.release(); h->count.release(); h->cmCount.release(); h->cand.release(); h->mask.release(); h->cmMask.release();
-    for (int i = 0; i < 2; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void orbx_sim3_solver_destroy(orbx_sim3_solver *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_sim3_solve(orbx_sim3_solver *h, const orbx_sim3_problem *Ps, int nc, const orbx_sim3_result *Rs)
 {
@@ -537,22 +522,19 @@ extern "C" int orbx_sim3_solve(orbx_sim3_solver *h, const orbx_sim3_problem *Ps,
     h->solved = false;
 
     const unsigned long long seq = bx.arm();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_sim3_prepare, dim3(prepare_blocks(maxN, maxIt), (unsigned)nc), dim3(256), 0, h->stream, I, D, 1);
-    MLAUNCH_CHECK();
-    h->launches = 2;
+    ORBX_LAUNCH_COUNT(h->timer);
     if (maxIt > 0) {
         hipLaunchKernelGGL(k_sim3_models, dim3((unsigned)((maxIt + 63) / 64), (unsigned)nc), dim3(64), 0, h->stream, D);
-        MLAUNCH_CHECK();
+        ORBX_LAUNCH_COUNT(h->timer);
         hipLaunchKernelGGL(k_sim3_check, dim3((unsigned)((maxIt + SIM3_CHECK_WAVES - 1) / SIM3_CHECK_WAVES), (unsigned)nc), dim3(64 * SIM3_CHECK_WAVES), 0, h->stream, D, (const float *)D.t12m,
                            (const float *)D.t21m, D.count, D.mask);
-        MLAUNCH_CHECK();
-        h->launches = 4;
+        ORBX_LAUNCH_COUNT(h->timer);
     }
     hipLaunchKernelGGL(k_sim3_decide, dim3((unsigned)nc), dim3(SIM3_DECIDE_THREADS), 0, h->stream, D, bx.outDevP, bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    h->timed = true;
+    ORBX_LAUNCH_COUNT(h->timer);
+    if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
     h->last = cands; h->solved = true;
 
@@ -628,10 +610,10 @@ extern "C" int orbx_sim3_check_models(orbx_sim3_solver *h, const orbx_sim3_probl
     // the last solve's pairs on the device are overwritten, its masks are not: orbx_sim3_inliers keeps working
     const Sim3Dev D = dev_view(h);
     hipLaunchKernelGGL(k_sim3_prepare, dim3(prepare_blocks(P->n, 0), 1), dim3(256), 0, h->stream, I, D, 0);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sim3_check, dim3((unsigned)((m + SIM3_CHECK_WAVES - 1) / SIM3_CHECK_WAVES), 1), dim3(64 * SIM3_CHECK_WAVES), 0, h->stream, D, (const float *)(bx.inDev + L.extraA),
                        (const float *)(bx.inDev + L.extraB), h->cmCount.p, h->cmMask.p);
-    MLAUNCH_CHECK();
+    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     ORBX_HIP_CHECK(hipMemcpy(count, h->cmCount.p, (size_t)m * 4, hipMemcpyDeviceToHost));
     if (inliers && P->n > 0) {
@@ -646,12 +628,5 @@ extern "C" int orbx_sim3_check_models(orbx_sim3_solver *h, const orbx_sim3_probl
 extern "C" int orbx_sim3_last_timing(orbx_sim3_solver *h, float *device_ms, int *launches)
 {
     if (!h) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!h->timed) { orbx_set_error("no orbx_sim3_solve call to report"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(h->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = h->launches;
-    return ORBX_OK;
+    return h->timer.read(h->device, device_ms, launches, "no orbx_sim3_solve call to report");
 }

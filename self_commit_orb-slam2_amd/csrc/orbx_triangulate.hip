@@ -212,14 +212,6 @@ __global__ __launch_bounds__(COLLECT_THREADS) void k_collect(const uint8_t *__re
 }
 
 namespace orbx_tri {
-void release(orbx_matcher *m)
-{
-    m->npStage.release(); m->npStatus.release(); m->npX3d.release(); m->npMatches.release(); m->npNm.release();
-    for (int i = 0; i < 2; i++) if (m->npEv[i]) (void)hipEventDestroy(m->npEv[i]);
-    for (hipEvent_t e : m->npTriEv) if (e) (void)hipEventDestroy(e);
-    m->npTriEv.clear();
-}
-
 static int check_geom(const orbx_keyframe_geom *g, const char *what, int idx)
 {
     if (!g->scale_factors || !g->level_sigma2) { orbx_set_error("%s %d: NULL scale tables", what, idx); return ORBX_ERR_ARG; }
@@ -302,7 +294,7 @@ extern "C" int orbx_triangulate_matches(orbx_matcher *m, const orbx_triangulate_
         if (n == 0) continue;
         hipLaunchKernelGGL(k_triangulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, args[(size_t)p], d2 + off, d1 + off, n, n, (uint8_t *)nullptr,
                            m->npStatus.p + off, m->npX3d.p + 3 * (size_t)off, (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
-        MLAUNCH_CHECK();
+        ORBX_LAUNCH_CHECK();
     }
     ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));
     ORBX_HIP_CHECK(hipMemcpy(status, m->npStatus.p, (size_t)M, hipMemcpyDeviceToHost));
@@ -346,7 +338,7 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     if ((rc = hs.begin(bytes)) != ORBX_OK || (rc = ensure_slots(m, (size_t)K * stride, (size_t)K)) != ORBX_OK) return rc;
     if (prm->profile_kernels)
         while (m->npTriEv.size() < 2 * (size_t)K) { hipEvent_t e = nullptr; ORBX_HIP_CHECK(hipEventCreate(&e)); m->npTriEv.push_back(e); }
-    for (int i = 0; i < 2; i++) if (!m->npEv[i]) ORBX_HIP_CHECK(hipEventCreate(&m->npEv[i]));
+    if ((rc = m->npTimer.create()) != ORBX_OK) return rc;
     auto host_of = [&](const void *dev) { return hs.host + ((const uint8_t *)dev - hs.dev.p); };
 
     orbx_feature_set da = *kf1, db = *nb;
@@ -381,8 +373,8 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     for (int k = 0; k < K; k++) ((int32_t *)host_of(pairIdx))[k] = k;
     const float *f12 = hs.put(prm->f12, (size_t)K * 9), *epi = hs.put(prm->epipole, (size_t)K * 2);
     if (hs.used > bytes) { orbx_set_error("internal: staging layout exceeds its size"); return ORBX_ERR_STATE; }
-    m->npTimed = false; m->npTriTimed = 0; m->npLaunches = 0;
-    ORBX_HIP_CHECK(hipEventRecord(m->npEv[0], m->stream));
+    m->npTimer.timed = false; m->npTriTimed = 0;
+    if ((rc = m->npTimer.begin(m->stream)) != ORBX_OK) return rc;
     if ((rc = hs.flush(m->stream)) != ORBX_OK) return rc;
 
     // ---- the chain: search k, triangulate k, (mask), search k+1 ... all on m->stream ----
@@ -409,7 +401,7 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
         if (prm->profile_kernels) ORBX_HIP_CHECK(hipEventRecord(m->npTriEv[2 * (size_t)k], m->stream));
         hipLaunchKernelGGL(k_triangulate, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, m->stream, T, (const int32_t *)m->matches.p, (const int32_t *)nullptr, n1, stride, mask,
                            m->npStatus.p + so, m->npX3d.p + 3 * so, m->npMatches.p + so, (const int32_t *)m->nmatches.p, m->npNm.p + k);
-        MLAUNCH_CHECK();
+        ORBX_LAUNCH_CHECK();
         if (prm->profile_kernels) ORBX_HIP_CHECK(hipEventRecord(m->npTriEv[2 * (size_t)k + 1], m->stream));
         done++;
     }
@@ -420,10 +412,10 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     orbx_new_point *outList = bx.outDev<orbx_new_point>(listOff);
     hipLaunchKernelGGL(k_collect, dim3(1), dim3(COLLECT_THREADS), 0, m->stream, (const uint8_t *)m->npStatus.p, (const int32_t *)m->npMatches.p, (const float *)m->npX3d.p,
                        (const int32_t *)m->npNm.p, K, done, stride, res->created_capacity, outHead, outList, bx.counter, bx.flagDev, seq);
-    MLAUNCH_CHECK();
-    ORBX_HIP_CHECK(hipEventRecord(m->npEv[1], m->stream));
-    m->npLaunches = 4 * done + 1;      // k_bow_order, k_bow_topk, k_bow_greedy, k_triangulate per neighbour; k_collect
-    m->npTimed = true; m->npTriTimed = prm->profile_kernels ? done : 0;
+    ORBX_LAUNCH_CHECK();
+    if ((rc = m->npTimer.end(m->stream)) != ORBX_OK) return rc;
+    m->npTimer.launches = 4 * done + 1;      // k_bow_order, k_bow_topk, k_bow_greedy, k_triangulate per neighbour; k_collect
+    m->npTriTimed = prm->profile_kernels ? done : 0;
     if ((rc = bx.wait(m->stream)) != ORBX_OK) return rc;      // the one synchronisation
     const int32_t *head = bx.outHost<int32_t>(0);
     const int cnt = head[0];
@@ -451,19 +443,13 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
 extern "C" int orbx_new_points_last_timing(orbx_matcher *m, float *device_ms, int *launches, float *triangulate_ms)
 {
     if (!m) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
-    if (!m->npTimed) { orbx_set_error("no orbx_create_new_map_points call to report"); return ORBX_ERR_STATE; }
-    ORBX_HIP_CHECK(hipSetDevice(m->device));
-    ORBX_HIP_CHECK(hipEventSynchronize(m->npEv[1]));
-    float ms = 0.f;
-    ORBX_HIP_CHECK(hipEventElapsedTime(&ms, m->npEv[0], m->npEv[1]));
+    if (const int rc = m->npTimer.read(m->device, device_ms, launches, "no orbx_create_new_map_points call to report")) return rc;
     float tri = 0.f;
     for (int k = 0; k < m->npTriTimed; k++) {
         float t = 0.f;
         ORBX_HIP_CHECK(hipEventElapsedTime(&t, m->npTriEv[2 * (size_t)k], m->npTriEv[2 * (size_t)k + 1]));
         tri += t;
     }
-    if (device_ms) *device_ms = ms;
-    if (launches) *launches = m->npLaunches;
     if (triangulate_ms) *triangulate_ms = tri;
     return ORBX_OK;
 }

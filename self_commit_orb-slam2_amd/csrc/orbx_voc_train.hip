@@ -40,7 +40,7 @@
 #include <chrono>
 #include <vector>
 
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 
 namespace {
 
@@ -506,23 +506,22 @@ __global__ void k_append_commit(const int32_t *__restrict__ counts, int batch, i
 
 }  // namespace
 
-struct orbx_voc_trainer {
-    int device = 0, k = 0, L = 0, maxDesc = 0, maxImg = 0;
-    hipStream_t stream = nullptr;
+struct orbx_voc_trainer : OrbxHandle {
+    int k = 0, L = 0, maxDesc = 0, maxImg = 0;
     hipEvent_t extEvent = nullptr;
     // the training set: descriptors in training order, features per image, {descriptors, images, overflow} (authoritative on the device while
     // `dirty`: add_extracted appends without a download)
-    OrbxDevBuf<uint4> desc;
-    OrbxDevBuf<int32_t> imgCount, state;
+    OrbxOwnedBuf<uint4> desc;
+    OrbxOwnedBuf<int32_t> imgCount, state;
     int nDesc = 0, nImg = 0;
     bool dirty = false;
     // work arrays (grow-only, sized by the call)
-    OrbxDevBuf<uint4> stageDesc, centres, nodeDesc;
-    OrbxDevBuf<int32_t> perm[2], segOf, assoc, md, nc, changedPass, cursor, chosen, counts, xSeg, imgStart, word, ni, childStart, childCount, nodeWord;
-    OrbxDevBuf<u64> G, blockSum, table;
-    OrbxDevBuf<VtSeg> segs;
-    OrbxDevBuf<unsigned> cntG, sizeG, devCount;
-    OrbxDevBuf<uint8_t> flags;
+    OrbxOwnedBuf<uint4> stageDesc, centres, nodeDesc;
+    OrbxOwnedBuf<int32_t> perm[2], segOf, assoc, md, nc, changedPass, cursor, chosen, counts, xSeg, imgStart, word, ni, childStart, childCount, nodeWord;
+    OrbxOwnedBuf<u64> G, blockSum, table;
+    OrbxOwnedBuf<VtSeg> segs;
+    OrbxOwnedBuf<unsigned> cntG, sizeG, devCount;
+    OrbxOwnedBuf<uint8_t> flags;
     OrbxCallBox box;
     // the last result, flat arrays in orbx_vocabulary_create's layout
     bool trained = false;
@@ -537,6 +536,11 @@ struct orbx_voc_trainer {
     size_t evUsed = 0;
     float totalMs = 0, levelMs[ORBX_VOC_MAX_L] = {0}, stageMs[5] = {0};
     int launches = 0;
+    ~orbx_voc_trainer()      // (add_extracted's work on the extractor's stream ends before the members free what it writes)
+    {
+        if (extEvent) { (void)hipEventSynchronize(extEvent); (void)hipEventDestroy(extEvent); }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -743,14 +747,10 @@ extern "C" int orbx_voc_trainer_create(int device, int k, int L, int max_descrip
     if (!vt_tree_fits(k, L)) { orbx_set_error("a complete tree with k = %d, L = %d has 2^31 nodes or more", k, L); return ORBX_ERR_ARG; }
     if (max_descriptors < 1 || max_descriptors > (1 << 26)) { orbx_set_error("max_descriptors = %d outside 1..2^26", max_descriptors); return ORBX_ERR_ARG; }
     if (max_images < 1) { orbx_set_error("max_images = %d < 1", max_images); return ORBX_ERR_ARG; }
-    if (const int rc = orbx_select_device(device)) return rc;
     orbx_voc_trainer *h = new orbx_voc_trainer();
-    h->device = device; h->k = k; h->L = L; h->maxDesc = max_descriptors; h->maxImg = max_images;
-    int rc = ORBX_OK;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->extEvent, hipEventDisableTiming) != hipSuccess) {
-        orbx_set_error("hipStreamCreate / hipEventCreate failed");
-        rc = ORBX_ERR_HIP;
-    }
+    h->k = k; h->L = L; h->maxDesc = max_descriptors; h->maxImg = max_images;
+    int rc = h->open(device);
+    if (!rc) rc = orbx_event_create(&h->extEvent, hipEventDisableTiming);
     if (!rc) rc = h->desc.ensure(2 * (size_t)max_descriptors);
     if (!rc) rc = h->imgCount.ensure((size_t)max_images);
     if (!rc) rc = h->state.ensure(4);
@@ -761,20 +761,7 @@ extern "C" int orbx_voc_trainer_create(int device, int k, int L, int max_descrip
     return ORBX_OK;
 }
 
-extern "C" void orbx_voc_trainer_destroy(orbx_voc_trainer *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->extEvent) { (void)hipEventSynchronize(h->extEvent); (void)hipEventDestroy(h->extEvent); }
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    h->desc.release(); h->imgCount.release(); h->state.release(); h->stageDesc.release(); h->centres.release(); h->nodeDesc.release();
-    h->perm[0].release(); h->perm[1].release(); h->segOf.release(); h->assoc.release(); h->md.release(); h->nc.release(); h->changedPass.release();
-    h->cursor.release(); h->chosen.release(); h->counts.release(); h->xSeg.release(); h->imgStart.release(); h->word.release(); h->ni.release();
-    h->childStart.release(); h->childCount.release(); h->nodeWord.release(); h->G.release(); h->blockSum.release(); h->table.release(); h->segs.release();
-    h->cntG.release(); h->sizeG.release(); h->devCount.release(); h->flags.release(); h->box.release();
-    delete h;
-}
+extern "C" void orbx_voc_trainer_destroy(orbx_voc_trainer *h) { orbx_destroy_handle(h); }
 
 extern "C" int orbx_voc_trainer_add(orbx_voc_trainer *h, const uint8_t *descriptors, const int32_t *counts, int num_images)
 {
