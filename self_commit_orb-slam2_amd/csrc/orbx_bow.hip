@@ -218,6 +218,17 @@ extern "C" int orbx_bow_download(orbx_vocabulary *v, orbx_extractor *ext, int ba
     return ORBX_OK;
 }
 
+// The results of one transform in the call box: word / node / weight per feature, the features ranked by word and by node, the number filed.
+struct BowSlots {
+    OrbxSlot<int32_t, ORBX_STAGE_OUT> word, node, byWord, byNode, filed;
+    OrbxSlot<double, ORBX_STAGE_OUT> weight;
+    BowSlots(OrbxOutPlan &po, size_t N)
+    {
+        word = po.hole<int32_t>(N); node = po.hole<int32_t>(N); weight = po.hole<double>(N);
+        byWord = po.hole<int32_t>(N); byNode = po.hole<int32_t>(N); filed = po.hole<int32_t>(1);
+    }
+};
+
 // Host-array form (Frame::ComputeBoW / KeyFrame::ComputeBoW through shim/BoW_hip.cc): the descent kernel reads the descriptors from mapped pinned memory
 // (32 bytes per thread, each once) and writes word / node / weight into mapped pinned memory (and word / node into device memory for the ranking
 // kernel of the _sorted form); no copy engine, no stream synchronisation (OrbxCallBox).
@@ -230,29 +241,32 @@ static int bow_transform_host(orbx_vocabulary *v, const uint8_t *descriptors, in
     ORBX_HIP_CHECK(hipSetDevice(v->device));
     OrbxCallBox &bx = v->box;
     const bool sorted = by_word && by_node && filed;
-    const size_t N = (size_t)n, offNode = bx.padded(N * 4), offW = offNode + bx.padded(N * 4), offBW = offW + bx.padded(N * 8), offBN = offBW + bx.padded(N * 4),
-                 offF = offBN + bx.padded(N * 4);
-    int rc = bx.begin(bx.padded(N * 32), offF + bx.padded(4), v->stream);
+    const size_t N = (size_t)n;
+    auto [pin, pout] = bx.plan();
+    const auto sDesc = pin.add(descriptors, N * 32);
+    const BowSlots R(pout, N);
+    int rc;
+    const OrbxStaged sg = bx.begin(v->stream, &rc);
     if (rc != ORBX_OK) return rc;
-    const uint8_t *dDesc = bx.put(descriptors, N * 32);
+    const uint8_t *dDesc = sg.dev(sDesc);
     const unsigned long long seq = bx.arm();
     if (sorted && ((rc = v->hostWord.ensure(N)) || (rc = v->hostNode.ensure(N)))) return rc;
     hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((n + 255) / 256), 1u), dim3(256), 0, v->stream, v->nodes.p, v->childList.p, v->childDesc.p, v->nodeWeight.p, v->L - levelsup,
-                       dDesc, (const int32_t *)nullptr, n, bx.outDev<int32_t>(0), bx.outDev<int32_t>(offNode), bx.outDev<double>(offW), sorted ? v->hostWord.p : (int32_t *)nullptr,
+                       dDesc, (const int32_t *)nullptr, n, sg.dev(R.word), sg.dev(R.node), sg.dev(R.weight), sorted ? v->hostWord.p : (int32_t *)nullptr,
                        sorted ? v->hostNode.p : (int32_t *)nullptr, bx.counter, sorted ? (unsigned long long *)nullptr : bx.flagDev, seq);
     if (sorted)
-        hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, v->stream, (const int32_t *)v->hostWord.p, (const int32_t *)v->hostNode.p, n, bx.outDev<int32_t>(offBW),
-                           bx.outDev<int32_t>(offBN), bx.outDev<int32_t>(offF), bx.counter, bx.flagDev, seq);
+        hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, v->stream, (const int32_t *)v->hostWord.p, (const int32_t *)v->hostNode.p, n, sg.dev(R.byWord),
+                           sg.dev(R.byNode), sg.dev(R.filed), bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(v->stream)) != ORBX_OK) return rc;
-    if (word) memcpy(word, bx.outHost<int32_t>(0), N * 4);
-    if (node) memcpy(node, bx.outHost<int32_t>(offNode), N * 4);
-    if (weight) memcpy(weight, bx.outHost<double>(offW), N * 8);
+    if (word) memcpy(word, sg.host(R.word), N * 4);
+    if (node) memcpy(node, sg.host(R.node), N * 4);
+    if (weight) memcpy(weight, sg.host(R.weight), N * 8);
     if (sorted) {
-        const int nf = *bx.outHost<int32_t>(offF);
+        const int nf = *sg.host(R.filed);
         *filed = nf;
-        memcpy(by_word, bx.outHost<int32_t>(offBW), (size_t)nf * 4);
-        memcpy(by_node, bx.outHost<int32_t>(offBN), (size_t)nf * 4);
+        memcpy(by_word, sg.host(R.byWord), (size_t)nf * 4);
+        memcpy(by_node, sg.host(R.byNode), (size_t)nf * 4);
     }
     return ORBX_OK;
 }
@@ -275,7 +289,8 @@ struct orbx_bow_job : OrbxHandle {      // (its own copy of the device: a job ma
     OrbxCallBox box;
     OrbxOwnedBuf<int32_t> word, node;
     int pendingN = -1;      // -1: nothing begun
-    size_t offNode = 0, offW = 0, offBW = 0, offBN = 0, offF = 0;
+    const int32_t *hWord = nullptr, *hNode = nullptr, *hByWord = nullptr, *hByNode = nullptr, *hFiled = nullptr;      // the pending job's results in the box (host side)
+    const double *hWeight = nullptr;
 };
 
 extern "C" int orbx_bow_job_create(orbx_vocabulary *v, orbx_bow_job **out)
@@ -308,16 +323,20 @@ extern "C" int orbx_bow_job_begin(orbx_bow_job *j, orbx_extractor *ext, int leve
     if (n == 0) { j->pendingN = 0; return ORBX_OK; }
     OrbxCallBox &bx = j->box;
     const size_t N = (size_t)n;
-    j->offNode = bx.padded(N * 4); j->offW = j->offNode + bx.padded(N * 4); j->offBW = j->offW + bx.padded(N * 8); j->offBN = j->offBW + bx.padded(N * 4); j->offF = j->offBN + bx.padded(N * 4);
-    if ((rc = bx.begin(0, j->offF + bx.padded(4), j->stream)) != ORBX_OK) return rc;
+    auto [pin, pout] = bx.plan();
+    (void)pin;      // (the descriptors are the extractor's, on the device)
+    const BowSlots R(pout, N);
+    const OrbxStaged sg = bx.begin(j->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    j->hWord = sg.host(R.word); j->hNode = sg.host(R.node); j->hWeight = sg.host(R.weight); j->hByWord = sg.host(R.byWord); j->hByNode = sg.host(R.byNode); j->hFiled = sg.host(R.filed);
     if ((rc = j->word.ensure(N)) || (rc = j->node.ensure(N))) return rc;
     const unsigned long long seq = bx.arm();
     // (frame 0 of the view, n features: `cap` = n for the kernel's indexing - one frame, feature i at i)
     hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((n + 255) / 256), 1u), dim3(256), 0, j->stream, v->nodes.p, v->childList.p, v->childDesc.p, v->nodeWeight.p, v->L - levelsup,
-                       view.desc, (const int32_t *)nullptr, n, bx.outDev<int32_t>(0), bx.outDev<int32_t>(j->offNode), bx.outDev<double>(j->offW), j->word.p, j->node.p, bx.counter,
+                       view.desc, (const int32_t *)nullptr, n, sg.dev(R.word), sg.dev(R.node), sg.dev(R.weight), j->word.p, j->node.p, bx.counter,
                        (unsigned long long *)nullptr, seq);
-    hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, j->stream, (const int32_t *)j->word.p, (const int32_t *)j->node.p, n, bx.outDev<int32_t>(j->offBW),
-                       bx.outDev<int32_t>(j->offBN), bx.outDev<int32_t>(j->offF), bx.counter, bx.flagDev, seq);
+    hipLaunchKernelGGL(k_bow_ranks, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, j->stream, (const int32_t *)j->word.p, (const int32_t *)j->node.p, n, sg.dev(R.byWord),
+                       sg.dev(R.byNode), sg.dev(R.filed), bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
     j->pendingN = n;
     return ORBX_OK;
@@ -335,12 +354,11 @@ extern "C" int orbx_bow_job_end(orbx_bow_job *j, const int32_t **word, const int
     ORBX_HIP_CHECK(hipSetDevice(j->device));
     int rc = j->box.wait(j->stream);
     if (rc != ORBX_OK) return rc;
-    const OrbxCallBox &bx = j->box;
-    if (word) *word = bx.outHost<int32_t>(0);
-    if (node) *node = bx.outHost<int32_t>(j->offNode);
-    if (weight) *weight = bx.outHost<double>(j->offW);
-    if (by_word) *by_word = bx.outHost<int32_t>(j->offBW);
-    if (by_node) *by_node = bx.outHost<int32_t>(j->offBN);
-    *filed = *bx.outHost<int32_t>(j->offF);
+    if (word) *word = j->hWord;
+    if (node) *node = j->hNode;
+    if (weight) *weight = j->hWeight;
+    if (by_word) *by_word = j->hByWord;
+    if (by_node) *by_node = j->hByNode;
+    *filed = *j->hFiled;
     return ORBX_OK;
 }

@@ -233,6 +233,7 @@ struct orbx_covis : OrbxHandle {
     OrbxCallBox box;
     OrbxOwnedBuf<uint8_t> arena;              // the call's inputs in device memory
     OrbxOwnedBuf<unsigned long long> work;    // keys | global histogram rows | culling state
+    OrbxWorkPlan workPlan;                    // layout of the culling state inside `work`
     std::vector<int32_t> order, pos, outOff;
     std::vector<uint8_t> seen;
 };
@@ -304,40 +305,42 @@ int cv_validate(orbx_covis *h, const orbx_covis_slice *s, bool culling, const ch
     return ORBX_OK;
 }
 
-// the slice into the call box and, by k_stage_copy, into the arena; D's input pointers address the arena
-int cv_stage(orbx_covis *h, const orbx_covis_slice *s, bool culling, size_t outBytes, CvDev &D)
-{
-    const size_t NK = (size_t)s->num_keyframes, M = (size_t)s->num_points, T = (size_t)s->num_obs, Q = (size_t)s->num_lists, S = (size_t)s->num_entries;
-    auto pd = [](size_t b) { return OrbxCallBox::padded(b); };
-    size_t total = 2 * pd(4 * NK) + pd(NK) + pd(4 * (M + 1)) + pd(4 * T) + pd(M) + 2 * pd(4 * (Q + 1)) + pd(4 * Q) + pd(4 * S);
-    if (culling) total += 2 * pd(T) + 2 * pd(S);
-    OrbxCallBox &bx = h->box;
-    int rc;
-    if ((rc = bx.begin(total, outBytes, h->stream)) != ORBX_OK) return rc;
-    if ((rc = h->arena.ensure(total)) != ORBX_OK) return rc;
-    const uint8_t *A = h->arena.p;
-    auto dev = [&](const void *boxAddr) { return A + ((const uint8_t *)boxAddr - bx.inDev); };
-    D.NK = (int)NK; D.M = (int)M; D.Q = (int)Q;
-    D.pos = (const int32_t *)dev(bx.put(h->pos.data(), NK));
-    D.slotAt = (const int32_t *)dev(bx.put(h->order.data(), NK));
-    D.flags = dev(bx.put(s->kf_flags, NK));
-    D.obsOff = (const int32_t *)dev(bx.put(s->obs_offset, M + 1));
-    D.obsKf = (const int32_t *)dev(bx.put(s->obs_kf, T));
-    D.ptBad = dev(bx.put(s->point_bad, M));
-    D.listOff = (const int32_t *)dev(bx.put(s->list_offset, Q + 1));
-    D.outOff = (const int32_t *)dev(bx.put(h->outOff.data(), Q + 1));
-    D.listKf = (const int32_t *)dev(bx.put(s->list_kf, Q));
-    D.listPt = (const int32_t *)dev(bx.put(s->list_point, S));
-    D.obsOct = D.obsSt = D.listOct = D.listClose = nullptr;
-    if (culling) {
-        D.obsOct = dev(bx.put(s->obs_octave, T));
-        D.obsSt = dev(bx.put(s->obs_stereo, T));
-        D.listOct = dev(bx.put(s->list_octave, S));
-        D.listClose = dev(bx.put(s->list_close, S));
+// the slice's place in the call box: planned before the box's begin() ...
+struct CvSlots {
+    OrbxSlot<int32_t, ORBX_STAGE_IN> pos, slotAt, obsOff, obsKf, listOff, outOff, listKf, listPt;
+    OrbxSlot<uint8_t, ORBX_STAGE_IN> flags, ptBad, obsOct, obsSt, listOct, listClose;
+    CvSlots(OrbxInPlan &pin, const orbx_covis *h, const orbx_covis_slice *s, bool culling)
+    {
+        const size_t NK = (size_t)s->num_keyframes, M = (size_t)s->num_points, T = (size_t)s->num_obs, Q = (size_t)s->num_lists, S = (size_t)s->num_entries;
+        pos = pin.add(h->pos.data(), NK);
+        slotAt = pin.add(h->order.data(), NK);
+        flags = pin.add(s->kf_flags, NK);
+        obsOff = pin.add(s->obs_offset, M + 1);
+        obsKf = pin.add(s->obs_kf, T);
+        ptBad = pin.add(s->point_bad, M);
+        listOff = pin.add(s->list_offset, Q + 1);
+        outOff = pin.add(h->outOff.data(), Q + 1);
+        listKf = pin.add(s->list_kf, Q);
+        listPt = pin.add(s->list_point, S);
+        obsOct = pin.add(s->obs_octave, culling ? T : 0);
+        obsSt = pin.add(s->obs_stereo, culling ? T : 0);
+        listOct = pin.add(s->list_octave, culling ? S : 0);
+        listClose = pin.add(s->list_close, culling ? S : 0);
     }
-    const size_t n16 = bx.used / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
+};
+
+// ... and behind it copied into the arena by k_stage_copy; D's input pointers address the arena
+int cv_stage(orbx_covis *h, const orbx_covis_slice *s, bool culling, const CvSlots &I, CvDev &D)
+{
+    int rc;
+    uint8_t *A;
+    if ((rc = orbx_stage_to_arena(h->box, h->arena, h->stream, 256, &A)) != ORBX_OK) return rc;
     ORBX_LAUNCH_COUNT(h->timer);
+    D.NK = s->num_keyframes; D.M = s->num_points; D.Q = s->num_lists;
+    D.pos = I.pos.in(A); D.slotAt = I.slotAt.in(A); D.flags = I.flags.in(A); D.obsOff = I.obsOff.in(A); D.obsKf = I.obsKf.in(A); D.ptBad = I.ptBad.in(A);
+    D.listOff = I.listOff.in(A); D.outOff = I.outOff.in(A); D.listKf = I.listKf.in(A); D.listPt = I.listPt.in(A);
+    D.obsOct = D.obsSt = D.listOct = D.listClose = nullptr;
+    if (culling) { D.obsOct = I.obsOct.in(A); D.obsSt = I.obsSt.in(A); D.listOct = I.listOct.in(A); D.listClose = I.listClose.in(A); }
     return ORBX_OK;
 }
 
@@ -363,18 +366,22 @@ extern "C" int orbx_covis_update_connections(orbx_covis *h, const orbx_covis_sli
     }
     h->outOff[(size_t)Q] = (int32_t)tot;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
-    const size_t P = (size_t)tot, oHead = 0, oCnt = OrbxCallBox::padded(16 * (size_t)Q), oConn = oCnt + OrbxCallBox::padded(8 * P), outBytes = oConn + OrbxCallBox::padded(8 * P);
+    const size_t P = (size_t)tot;
     const bool lds = NK <= COVIS_LDS_NK;
     const unsigned grid = (unsigned)std::min(Q, lds ? COVIS_MAX_BLOCKS : COVIS_GLOBAL_BLOCKS);
     const size_t histWords = lds ? 0 : ((size_t)grid * (size_t)NK + 1) / 2;      // int32 rows inside the u64 work buffer
     if ((rc = h->work.ensure((lds ? 1 : P) + histWords)) != ORBX_OK) return rc;
     CvDev D = {};
-    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    if ((rc = cv_stage(h, s, false, outBytes, D)) != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
+    auto [pin, pout] = bx.plan();
+    const CvSlots I(pin, h, s, false);
+    const auto rHead = pout.hole<int32_t>(4 * (size_t)Q), rCnt = pout.hole<int32_t>(2 * P), rConn = pout.hole<int32_t>(2 * P);
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK || (rc = cv_stage(h, s, false, I, D)) != ORBX_OK) return rc;
     D.th = th;
     D.keys = h->work.p; D.hist = (int32_t *)(h->work.p + (lds ? 1 : P));
-    D.head = bx.outDev<int32_t>(oHead); D.cnt = bx.outDev<int32_t>(oCnt); D.conn = bx.outDev<int32_t>(oConn);
+    D.head = sg.dev(rHead); D.cnt = sg.dev(rCnt); D.conn = sg.dev(rConn);
     const unsigned long long seq = bx.arm();
     if (lds) hipLaunchKernelGGL(k_covis_connect<true>, dim3(grid), dim3(COVIS_THREADS), 4 * (size_t)((NK + 1) & ~1) + 8 * (size_t)NK, h->stream, D, bx.counter, bx.flagDev, seq);
     else hipLaunchKernelGGL(k_covis_connect<false>, dim3(grid), dim3(COVIS_THREADS), 0, h->stream, D, bx.counter, bx.flagDev, seq);
@@ -382,7 +389,7 @@ extern "C" int orbx_covis_update_connections(orbx_covis *h, const orbx_covis_sli
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
 
-    const int32_t *head = bx.outHost<int32_t>(oHead), *cnt = bx.outHost<int32_t>(oCnt), *conn = bx.outHost<int32_t>(oConn);
+    const int32_t *head = sg.host(rHead), *cnt = sg.host(rCnt), *conn = sg.host(rConn);
     long long nc = 0, nn = 0;
     for (int q = 0; q < Q; q++) { nc += head[4 * q]; nn += head[4 * q + 3]; }
     if (((out->counter_kf || out->counter_weight) && nc > out->counter_capacity) || ((out->conn_kf || out->conn_weight) && nn > out->conn_capacity)) {      // nothing is written
@@ -421,17 +428,26 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
     h->timer.timed = false;
     h->outOff.assign((size_t)Q + 1, 0);
     ORBX_HIP_CHECK(hipSetDevice(h->device));
-    const size_t m = (size_t)M, oRec = 0, oRes = 256, oObs = oRes + OrbxCallBox::padded(12 * (size_t)Q), oBad = oObs + OrbxCallBox::padded(4 * m), outBytes = oBad + OrbxCallBox::padded(m);
+    const size_t m = (size_t)M;
     // device state: nobs [M] int32 | firstCull (16 bytes) | state [M] | erased [NK]
-    const size_t wObs = 0, wFirst = OrbxCallBox::padded(4 * m), wState = wFirst + 256, wErased = wState + OrbxCallBox::padded(m), wBytes = wErased + OrbxCallBox::padded((size_t)NK);
+    OrbxWorkPlan &work = h->workPlan;
+    work.reset();
+    const auto wObs = work.hole<int32_t>(m), wFirst = work.hole<int32_t>(4);
+    const auto wState = work.hole<uint8_t>(m), wErased = work.hole<uint8_t>((size_t)NK);
+    const size_t wBytes = work.total();
     if ((rc = h->work.ensure(wBytes / 8)) != ORBX_OK) return rc;
     CvDev D = {};
-    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    if ((rc = cv_stage(h, s, true, outBytes, D)) != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
-    uint8_t *W = (uint8_t *)h->work.p;
-    D.nobs = (int32_t *)(W + wObs); D.firstCull = (int32_t *)(W + wFirst); D.state = W + wState; D.erased = W + wErased;
-    D.record = bx.outDev<int32_t>(oRec); D.res = bx.outDev<int32_t>(oRes); D.outObs = bx.outDev<int32_t>(oObs); D.outBad = bx.outDev<uint8_t>(oBad);
+    auto [pin, pout] = bx.plan();
+    const CvSlots I(pin, h, s, true);
+    const auto rRec = pout.hole<int32_t>(1), rRes = pout.hole<int32_t>(3 * (size_t)Q), rObs = pout.hole<int32_t>(m);
+    const auto rBad = pout.hole<uint8_t>(m);
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK || (rc = cv_stage(h, s, true, I, D)) != ORBX_OK) return rc;
+    void *W = h->work.p;
+    D.nobs = wObs.in(W); D.firstCull = wFirst.in(W); D.state = wState.in(W); D.erased = wErased.in(W);
+    D.record = sg.dev(rRec); D.res = sg.dev(rRes); D.outObs = sg.dev(rObs); D.outBad = sg.dev(rBad);
     const unsigned pointBlocks = (unsigned)((std::max(std::max(M, NK), 1) + COVIS_THREADS - 1) / COVIS_THREADS);
     hipLaunchKernelGGL(k_covis_cull_init, dim3(pointBlocks), dim3(COVIS_THREADS), 0, h->stream, D);
     ORBX_LAUNCH_COUNT(h->timer);
@@ -441,7 +457,7 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
         ORBX_LAUNCH_COUNT(h->timer);
         if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
         if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
-        const int f = *bx.outHost<int32_t>(oRec);
+        const int f = *sg.host(rRec);
         if (f < first || f >= Q) break;      // (INT_MAX: nothing behind `first` is culled and erasable)
         first = f + 1;
         seq = first < Q ? 0 : bx.arm();      // the last list: no round follows, the erase itself publishes
@@ -452,14 +468,14 @@ extern "C" int orbx_covis_keyframe_culling(orbx_covis *h, const orbx_covis_slice
             if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
         }
     }
-    const int32_t *res = bx.outHost<int32_t>(oRes);
+    const int32_t *res = sg.host(rRes);
     for (int q = 0; q < Q; q++) {
         if (out->n_mps) out->n_mps[q] = res[3 * q];
         if (out->n_redundant) out->n_redundant[q] = res[3 * q + 1];
         if (out->culled) out->culled[q] = (uint8_t)res[3 * q + 2];
     }
-    if (out->point_obs && M) memcpy(out->point_obs, bx.outHost<uint8_t>(oObs), 4 * m);
-    if (out->point_bad && M) memcpy(out->point_bad, bx.outHost<uint8_t>(oBad), m);
+    if (out->point_obs && M) memcpy(out->point_obs, sg.host(rObs), 4 * m);
+    if (out->point_bad && M) memcpy(out->point_bad, sg.host(rBad), m);
     return ORBX_OK;
 }
 

@@ -647,41 +647,30 @@ int eg_symbolic(const orbx_essential_graph *h, const orbx_essential_graph_proble
     return ORBX_OK;
 }
 
-// stage the call's inputs (mapped pinned), copy them to the device once, lay the working arrays out
-int eg_stage(orbx_essential_graph *h, const orbx_essential_graph_problem *P, const double *at, size_t outBytes)
+// the call's inputs in the call box (mapped pinned): planned before the box's begin() ...
+struct EgSlots {
+    OrbxSlot<double, ORBX_STAGE_IN> est, meas, at;
+    OrbxSlot<int32_t, ORBX_STAGE_IN> edges, ref, pos, colPtr, rowIdx, aPtr, aItem;
+    OrbxSlot<float, ORBX_STAGE_IN> points;
+    EgSlots(OrbxInPlan &pin, const EgSymbolic &S, const orbx_essential_graph_problem *P, const double *at0)
+    {
+        const size_t N = (size_t)P->n, E = (size_t)P->n_edges, M = (size_t)P->n_points, nf = (size_t)S.nf, nOff = (size_t)S.nOff, nL = nf + nOff;
+        est = pin.add(P->est, 8 * N); meas = pin.add(P->meas ? P->meas : P->est, 8 * N); at = pin.add(at0 ? at0 : P->est, 8 * N);
+        edges = pin.add(P->edges, 3 * E);
+        points = pin.add(P->points, 3 * M); ref = pin.add(P->point_ref, M);
+        pos = pin.add(S.pos.data(), N); colPtr = pin.add(S.colPtr.data(), nf + 1); rowIdx = pin.add(S.rowIdx.data(), nOff);
+        aPtr = pin.add(S.aPtr.data(), nL + 1); aItem = pin.add(S.aItem.data(), S.aItem.size());
+    }
+};
+
+// ... and behind it copied to the device once; lays the working arrays out
+int eg_stage(orbx_essential_graph *h, const orbx_essential_graph_problem *P, const EgSlots &I)
 {
     const EgSymbolic &S = h->sym;
-    const size_t N = (size_t)P->n, E = (size_t)P->n_edges, M = (size_t)P->n_points, nf = (size_t)S.nf, nOff = (size_t)S.nOff, nL = nf + nOff;
-    auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
-    size_t o = 0;
-    const size_t oEst = o; o += padded(64 * N);
-    const size_t oMeas = o; o += padded(64 * N);
-    const size_t oAt = o; o += padded(64 * N);
-    const size_t oEdges = o; o += padded(12 * E);
-    const size_t oPts = o; o += padded(12 * M);
-    const size_t oRef = o; o += padded(4 * M);
-    const size_t oPos = o; o += padded(4 * N);
-    const size_t oCol = o; o += padded(4 * (nf + 1));
-    const size_t oRow = o; o += padded(4 * nOff);
-    const size_t oAp = o; o += padded(4 * (nL + 1));
-    const size_t oAi = o; o += padded(4 * S.aItem.size());
-    const size_t total = o;
+    const size_t N = (size_t)P->n, E = (size_t)P->n_edges, nf = (size_t)S.nf, nOff = (size_t)S.nOff, nL = nf + nOff;
     int rc;
-    OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(total, outBytes, h->stream)) != ORBX_OK) return rc;
-    if ((rc = h->arena.ensure(total)) != ORBX_OK) return rc;
-    memcpy(bx.in + oEst, P->est, 64 * N);
-    memcpy(bx.in + oMeas, P->meas ? P->meas : P->est, 64 * N);
-    memcpy(bx.in + oAt, at ? at : P->est, 64 * N);
-    if (E) memcpy(bx.in + oEdges, P->edges, 12 * E);
-    if (M) { memcpy(bx.in + oPts, P->points, 12 * M); memcpy(bx.in + oRef, P->point_ref, 4 * M); }
-    memcpy(bx.in + oPos, S.pos.data(), 4 * N);
-    memcpy(bx.in + oCol, S.colPtr.data(), 4 * (nf + 1));
-    if (nOff) memcpy(bx.in + oRow, S.rowIdx.data(), 4 * nOff);
-    memcpy(bx.in + oAp, S.aPtr.data(), 4 * (nL + 1));
-    if (!S.aItem.empty()) memcpy(bx.in + oAi, S.aItem.data(), 4 * S.aItem.size());
-    const size_t n16 = total / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
+    uint8_t *A;
+    if ((rc = orbx_stage_to_arena(h->box, h->arena, h->stream, 256, &A)) != ORBX_OK) return rc;
     ORBX_LAUNCH_COUNT(h->timer);
     // working arrays, in doubles (an OsSim3 is eight)
     size_t w = 0;
@@ -690,12 +679,11 @@ int eg_stage(orbx_essential_graph *h, const orbx_essential_graph_problem *P, con
                  wW = take(49 * nOff), wb = take(7 * nf), wy = take(7 * nf), wd = take(7 * nf), wxs = take(7 * nf), wx = take(7 * nf), wdev = take(4);
     if ((rc = h->work.ensure(w)) != ORBX_OK) return rc;
     EgDev &D = h->dev;
-    const uint8_t *A = h->arena.p;
     double *Wk = h->work.p;
     D.N = P->n; D.E = P->n_edges; D.M = P->n_points; D.nf = S.nf; D.nOff = S.nOff; D.fixScale = P->fix_scale ? 1 : 0;
-    D.est0 = (const OsSim3 *)(A + oEst); D.meas0 = (const OsSim3 *)(A + oMeas); D.at = (const OsSim3 *)(A + oAt);
-    D.edges = (const int32_t *)(A + oEdges); D.points = (const float *)(A + oPts); D.ref = (const int32_t *)(A + oRef); D.pos = (const int32_t *)(A + oPos);
-    D.colPtr = (const int32_t *)(A + oCol); D.rowIdx = (const int32_t *)(A + oRow); D.aPtr = (const int32_t *)(A + oAp); D.aItem = (const int32_t *)(A + oAi);
+    D.est0 = (const OsSim3 *)I.est.in(A); D.meas0 = (const OsSim3 *)I.meas.in(A); D.at = (const OsSim3 *)I.at.in(A);
+    D.edges = I.edges.in(A); D.points = I.points.in(A); D.ref = I.ref.in(A); D.pos = I.pos.in(A);
+    D.colPtr = I.colPtr.in(A); D.rowIdx = I.rowIdx.in(A); D.aPtr = I.aPtr.in(A); D.aItem = I.aItem.in(A);
     D.est[0] = (OsSim3 *)(Wk + wE0); D.est[1] = (OsSim3 *)(Wk + wE1); D.meas = (OsSim3 *)(Wk + wMeas);
     D.J = Wk + wJ; D.err = Wk + wErr; D.chiE = Wk + wChi; D.H = Wk + wH; D.L = Wk + wL; D.W = Wk + wW;
     D.b = Wk + wb; D.y = Wk + wy; D.d = Wk + wd; D.xs = Wk + wxs; D.x = Wk + wx; D.dev = Wk + wdev;
@@ -706,13 +694,13 @@ int eg_stage(orbx_essential_graph *h, const orbx_essential_graph_problem *P, con
 }
 
 // errors + chi2 of est[buf] into record `rec` of the result buffer; the caller waits
-int eg_chi(orbx_essential_graph *h, int buf, size_t recOff, int solved)
+int eg_chi(orbx_essential_graph *h, int buf, EgRecord *rec, int solved)
 {
     OrbxCallBox &bx = h->box;
     hipLaunchKernelGGL(k_eg_error, dim3((unsigned)eg_blocks(h->dev.E)), dim3(EG_THREADS), 0, h->stream, h->dev, buf);
     ORBX_LAUNCH_COUNT(h->timer);
     const unsigned long long seq = bx.arm();
-    hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(EG_THREADS), 0, h->stream, h->dev, bx.outDev<EgRecord>(recOff), solved, bx.counter, bx.flagDev, seq);
+    hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(EG_THREADS), 0, h->stream, h->dev, rec, solved, bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_COUNT(h->timer);
     return ORBX_OK;
 }
@@ -754,20 +742,24 @@ extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     const int iterations = P->iterations > 0 ? P->iterations : 20;
     const size_t N = (size_t)P->n, M = (size_t)P->n_points;
-    auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
-    const size_t oRec = 0, oEst = padded(sizeof(EgRecord) * 2), oInv = oEst + padded(64 * N), oTiw = oInv + padded(64 * N), oPts = oTiw + padded(48 * N),
-                 outBytes = oPts + padded(12 * M);
     h->solveTicks = 0.0;
     OrbxCallBox &bx = h->box;
     if (bx.pending) { ORBX_HIP_CHECK(hipStreamSynchronize(h->stream)); bx.pending = false; }
+    auto [pin, pout] = bx.plan();
+    const EgSlots I(pin, h->sym, P, nullptr);
+    const auto rRec = pout.hole<EgRecord>(2);
+    const auto rEst = pout.hole<OsSim3>(N), rInv = pout.hole<OsSim3>(N);
+    const auto rTiw = pout.hole<float>(12 * N), rPts = pout.hole<float>(3 * M);
     if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    if ((rc = eg_stage(h, P, nullptr, outBytes)) != ORBX_OK) return rc;
-    const EgRecord *rec = bx.outHost<EgRecord>(oRec);
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK || (rc = eg_stage(h, P, I)) != ORBX_OK) return rc;
+    const EgRecord *rec = sg.host(rRec);
+    EgRecord *const recDev = sg.dev(rRec);
 
     double chi0 = 0.0, cur = 0.0, lambda = P->lambda_init > 0.0 ? P->lambda_init : 1e-16, ni = 2.0, rho = 0.0;
     int buf = 0, done = 0, ended = ORBX_EG_END_ITERATIONS, nBad = 0;
     if (P->n_edges > 0) {
-        if ((rc = eg_chi(h, buf, oRec, 0)) != ORBX_OK) return rc;
+        if ((rc = eg_chi(h, buf, recDev, 0)) != ORBX_OK) return rc;
         if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
         chi0 = cur = rec->chi;
         for (int it = 0; it < iterations; it++) {
@@ -777,7 +769,7 @@ extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx
             do {
                 hipLaunchKernelGGL(k_eg_solve, dim3(1), dim3(EG_SOLVE_THREADS), 0, h->stream, h->dev, lambda, buf, 1);
                 ORBX_LAUNCH_COUNT(h->timer);
-                if ((rc = eg_chi(h, buf ^ 1, oRec, 1)) != ORBX_OK) return rc;
+                if ((rc = eg_chi(h, buf ^ 1, recDev, 1)) != ORBX_OK) return rc;
                 if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
                 h->solveTicks += (double)rec->ticks;
                 const double temp = rec->ok ? rec->chi : DBL_MAX, scale = rec->scale + 1e-3;
@@ -811,16 +803,16 @@ extern "C" int orbx_optimize_essential_graph(orbx_essential_graph *h, const orbx
         }
     }
     EgOut O;
-    O.est = bx.outDev<OsSim3>(oEst); O.inv = bx.outDev<OsSim3>(oInv); O.tiw = bx.outDev<float>(oTiw); O.points = bx.outDev<float>(oPts);
+    O.est = sg.dev(rEst); O.inv = sg.dev(rInv); O.tiw = sg.dev(rTiw); O.points = sg.dev(rPts);
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_eg_writeback, dim3((unsigned)eg_blocks(std::max(P->n, P->n_points))), dim3(EG_THREADS), 0, h->stream, h->dev, buf, O, bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_COUNT(h->timer);
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
-    if (R->est) memcpy(R->est, bx.out + oEst, 64 * N);
-    if (R->inv) memcpy(R->inv, bx.out + oInv, 64 * N);
-    if (R->tiw) memcpy(R->tiw, bx.out + oTiw, 48 * N);
-    if (R->points && M) memcpy(R->points, bx.out + oPts, 12 * M);
+    if (R->est) memcpy(R->est, sg.host(rEst), 64 * N);
+    if (R->inv) memcpy(R->inv, sg.host(rInv), 64 * N);
+    if (R->tiw) memcpy(R->tiw, sg.host(rTiw), 48 * N);
+    if (R->points && M) memcpy(R->points, sg.host(rPts), 12 * M);
     if (R->chi2) { R->chi2[0] = chi0; R->chi2[1] = cur; }
     if (R->iterations) *R->iterations = done;
     if (R->ended) *R->ended = ended;
@@ -841,17 +833,21 @@ extern "C" int orbx_essential_graph_linearize(orbx_essential_graph *h, const orb
     OrbxCallBox &bx = h->box;
     if (bx.pending) { ORBX_HIP_CHECK(hipStreamSynchronize(h->stream)); bx.pending = false; }
     h->timer.launches = 0;
-    if ((rc = eg_stage(h, P, at, sizeof(EgRecord))) != ORBX_OK) return rc;
+    auto [pin, pout] = bx.plan();
+    const EgSlots I(pin, h->sym, P, at);
+    const auto rRec = pout.hole<EgRecord>(1);
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK || (rc = eg_stage(h, P, I)) != ORBX_OK) return rc;
     const size_t N = (size_t)P->n, E = (size_t)P->n_edges;
     const EgSymbolic &S = h->sym;
     const EgDev &D = h->dev;
     double chi = 0.0;
     std::vector<double> Hh, bh;
     if (E) {
-        if ((rc = eg_chi(h, 0, 0, 0)) != ORBX_OK) return rc;
+        if ((rc = eg_chi(h, 0, sg.dev(rRec), 0)) != ORBX_OK) return rc;
         if ((rc = eg_linearize(h, 0)) != ORBX_OK) return rc;
         if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
-        chi = bx.outHost<EgRecord>(0)->chi;
+        chi = sg.host(rRec)->chi;
     }
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));      // (a tap: plain copies)
     if (E) {

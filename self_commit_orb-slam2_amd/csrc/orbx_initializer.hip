@@ -746,8 +746,9 @@ float cos_bound(float minParallax, bool strict)
     return lo;
 }
 
-struct Staged {      // offsets into box.in / the arena
-    size_t raw = 0, nrm = 0, slot = 0, sets = 0, extra = 0, extra2 = 0, extra3 = 0, total = 0;
+struct Staged {      // the matches in box.in / the arena
+    OrbxSlot<float, ORBX_STAGE_IN> raw, nrm;
+    OrbxSlot<int32_t, ORBX_STAGE_IN> slot;
     int N = 0;
     float t1[9], t2[9];
 };
@@ -760,31 +761,25 @@ int check_matches(const orbx_init_matches *M)
     return ORBX_OK;
 }
 
-// vMatches12 compacted in i1 order (:96-109) into the mapped input buffer; with `normalise`, Normalize of both frames too.  extra* = bytes the
-// caller appends behind (sets, models, motions ...).
-int stage_matches(orbx_initializer *h, const orbx_init_matches *M, bool normalise, size_t extra, size_t extra2, size_t extra3, size_t outBytes, Staged &S)
+// vMatches12 compacted in i1 order (:96-109) into the mapped input buffer; with `normalise`, Normalize of both frames too.  plan_matches reserves the
+// three arrays at the head of the box's input plan (the caller adds its own - sets, models, motions ... - behind them), fill_matches writes them
+// after the box's begin().
+int plan_matches(orbx_initializer *h, const orbx_init_matches *M, OrbxInPlan &pin, Staged &S)
 {
     int N = 0;
     for (int i = 0; i < M->n1; i++) N += M->matches12[i] >= 0 ? 1 : 0;
     if (N > h->maxMatches) { orbx_set_error("%d matches, the initializer was created for %d", N, h->maxMatches); return ORBX_ERR_CAPACITY; }
     S.N = N;
-    const size_t pad = 256;
-    auto padded = [&](size_t b) { return (b + pad - 1) & ~(pad - 1); };
-    S.raw = 0;
-    S.nrm = S.raw + padded((size_t)N * 16);
-    S.slot = S.nrm + padded((size_t)N * 16);
-    S.sets = S.slot + padded((size_t)M->n1 * 4);
-    S.extra = S.sets;      // the caller lays out `extra` itself, starting here
-    S.extra2 = S.extra + padded(extra);
-    S.extra3 = S.extra2 + padded(extra2);
-    S.total = S.extra3 + padded(extra3);
-    int rc;
-    OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(S.total, outBytes, h->stream)) != ORBX_OK || (rc = h->arena.ensure(S.total + 256)) != ORBX_OK) return rc;
+    S.raw = pin.hole<float>((size_t)N * 4); S.nrm = pin.hole<float>((size_t)N * 4); S.slot = pin.hole<int32_t>((size_t)M->n1);
+    return ORBX_OK;
+}
+
+void fill_matches(const orbx_init_matches *M, bool normalise, const OrbxStaged &sg, Staged &S)
+{
     std::vector<float> pn1, pn2;
     if (normalise) { normalize_host(M->keys1_xy, M->n1, pn1, S.t1); normalize_host(M->keys2_xy, M->n2, pn2, S.t2); }
-    float *raw = (float *)(bx.in + S.raw), *nrm = (float *)(bx.in + S.nrm);
-    int32_t *slot = (int32_t *)(bx.in + S.slot);
+    float *raw = sg.host(S.raw), *nrm = sg.host(S.nrm);
+    int32_t *slot = sg.host(S.slot);
     int m = 0;
     for (int i = 0; i < M->n1; i++) {
         const int j = M->matches12[i];
@@ -795,14 +790,13 @@ int stage_matches(orbx_initializer *h, const orbx_init_matches *M, bool normalis
         else nrm[4 * m] = nrm[4 * m + 1] = nrm[4 * m + 2] = nrm[4 * m + 3] = 0.0f;
         m++;
     }
-    return ORBX_OK;
 }
 
-int launch_stage_copy(orbx_initializer *h, size_t total)
+// the box's inputs into the arena (every later kernel reads them many times); the arena keeps 256 bytes behind them
+int stage_to_arena(orbx_initializer *h, uint8_t **ar)
 {
-    const size_t n16 = (total + 15) / 16;
-    const unsigned blocks = (unsigned)std::min<size_t>((n16 + 255) / 256, 64);
-    hipLaunchKernelGGL(k_stage_copy, dim3(blocks ? blocks : 1), dim3(256), 0, h->stream, (const uint4 *)h->box.inDev, (uint4 *)h->arena.p, n16);
+    const int rc = orbx_stage_to_arena(h->box, h->arena, h->stream, 64, ar, h->box.inPlan.total() + 256);
+    if (rc != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }
@@ -837,9 +831,9 @@ extern "C" int orbx_initializer_create(int device, int max_matches, int max_iter
 
 extern "C" void orbx_initializer_destroy(orbx_initializer *h) { orbx_destroy_handle(h); }
 
-static void fill_model_args(orbx_initializer *h, const Staged &S, InitModelArgs &A)
+static void fill_model_args(orbx_initializer *h, const Staged &S, const uint8_t *ar, InitModelArgs &A)
 {
-    A.nrm = (const float4 *)(h->arena.p + S.nrm); A.raw = (const float4 *)(h->arena.p + S.raw);
+    A.nrm = (const float4 *)S.nrm.in(ar); A.raw = (const float4 *)S.raw.in(ar);
     A.sets = nullptr; A.explicitModels = nullptr; A.kind = 0; A.N = S.N; A.iters = 0; A.nmodels = 0;
     A.hn = h->hn.p; A.fpre = h->fpre.p; A.fn = h->fn.p; A.h21 = h->h21.p; A.h12 = h->h12.p; A.f21 = h->f21.p; A.score = h->score.p; A.inl = h->inl.p;
     for (int j = 0; j < 9; j++) A.t1[j] = A.t2inv[j] = A.t2t[j] = 0.0f;
@@ -863,23 +857,29 @@ extern "C" int orbx_initialize(orbx_initializer *h, const orbx_init_problem *P, 
         if (P->sets[i] < 0 || P->sets[i] >= N) { orbx_set_error("sets[%d][%d] = %d is outside the %d matches", i / 8, i % 8, P->sets[i], N); return ORBX_ERR_ARG; }
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     const size_t n1 = (size_t)P->n1;
-    const size_t offP3d = OrbxCallBox::padded(sizeof(InitHead)), offTri = offP3d + OrbxCallBox::padded(n1 * 12), outBytes = offTri + OrbxCallBox::padded(n1);
     Staged S;
-    if ((rc = stage_matches(h, &M, true, (size_t)iters * 32, 0, 0, outBytes, S)) != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
-    memcpy(bx.in + S.sets, P->sets, (size_t)iters * 32);
+    auto [pin, pout] = bx.plan();
+    if ((rc = plan_matches(h, &M, pin, S)) != ORBX_OK) return rc;
+    const auto sSets = pin.add(P->sets, (size_t)iters * 8);
+    const auto rHead = pout.hole<InitHead>(1);
+    const auto rP3d = pout.hole<float>(n1 * 3);
+    const auto rTri = pout.hole<uint8_t>(n1);
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    fill_matches(&M, true, sg, S);
 
+    const unsigned long long seq = bx.arm();
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
+    uint8_t *ar;
+    if ((rc = stage_to_arena(h, &ar)) != ORBX_OK) return rc;
     InitModelArgs A;
-    fill_model_args(h, S, A);
-    A.sets = (const int32_t *)(h->arena.p + S.sets); A.iters = iters; A.nmodels = 2 * iters;
+    fill_model_args(h, S, ar, A);
+    A.sets = sSets.in(ar); A.iters = iters; A.nmodels = 2 * iters;
     memcpy(A.t1, S.t1, sizeof(A.t1));
     inv3(S.t2, A.t2inv);                                   // T2.inv() (:260)
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) A.t2t[3 * i + j] = S.t2[3 * j + i];      // T2.t() (:354)
     A.invSigma2 = inv_sigma2(P->sigma);
-
-    const unsigned long long seq = bx.arm();
-    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    if ((rc = launch_stage_copy(h, S.total)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_init_models, dim3((unsigned)(2 * iters)), dim3(64), 0, h->stream, A);
     ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_init_decompose, dim3(1), dim3(128), 0, h->stream, (const float *)h->score.p, iters, (const float *)h->h21.p, (const float *)h->f21.p, P->fx, P->fy, P->cx, P->cy,
@@ -897,10 +897,10 @@ extern "C" int orbx_initialize(orbx_initializer *h, const orbx_init_problem *P, 
     ORBX_LAUNCH_CHECK();
     InitDecideArgs D;
     D.best = h->best.p; D.inlBase = h->inl.p; D.iters = iters; D.N = N; D.n1 = P->n1;
-    D.slot = (const int32_t *)(h->arena.p + S.slot); D.status = h->crtStatus.p; D.p3d = h->crtP3d.p;
+    D.slot = S.slot.in(ar); D.status = h->crtStatus.p; D.p3d = h->crtP3d.p;
     D.cosGt = cos_bound(P->min_parallax, true); D.cosGe = cos_bound(P->min_parallax, false);
     D.minTriangulated = P->min_triangulated;
-    D.head = bx.outDev<InitHead>(0); D.outP3d = bx.outDev<float>(offP3d); D.outTri = bx.outDev<uint8_t>(offTri);
+    D.head = sg.dev(rHead); D.outP3d = sg.dev(rP3d); D.outTri = sg.dev(rTri);
     D.counter = bx.counter; D.flag = bx.flagDev; D.seq = seq;
     hipLaunchKernelGGL(k_init_decide, dim3(1), dim3(256), 0, h->stream, D);
     ORBX_LAUNCH_CHECK();
@@ -908,14 +908,14 @@ extern "C" int orbx_initialize(orbx_initializer *h, const orbx_init_problem *P, 
     h->timer.launches = 6;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
 
-    const InitHead *H = bx.outHost<InitHead>(0);
+    const InitHead *H = sg.host(rHead);
     if (res->success) *res->success = H->success;
     if (res->model) *res->model = H->model;
     if (res->hyp) *res->hyp = H->hyp;
     if (res->r21) memcpy(res->r21, H->r21, sizeof(H->r21));
     if (res->t21) memcpy(res->t21, H->t21, sizeof(H->t21));
-    if (res->p3d) memcpy(res->p3d, bx.outHost<float>(offP3d), n1 * 12);
-    if (res->triangulated) memcpy(res->triangulated, bx.outHost<uint8_t>(offTri), n1);
+    if (res->p3d) memcpy(res->p3d, sg.host(rP3d), n1 * 12);
+    if (res->triangulated) memcpy(res->triangulated, sg.host(rTri), n1);
     if (res->n_matches) *res->n_matches = N;
     if (res->t1) memcpy(res->t1, S.t1, sizeof(S.t1));
     if (res->t2) memcpy(res->t2, S.t2, sizeof(S.t2));
@@ -963,14 +963,20 @@ extern "C" int orbx_init_score_models(orbx_initializer *h, const orbx_init_match
     if (m > 2 * h->maxIters) { orbx_set_error("%d models, the initializer holds %d", m, 2 * h->maxIters); return ORBX_ERR_CAPACITY; }
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     Staged S;
-    if ((rc = stage_matches(h, M, false, (size_t)m * 36, 0, 0, 0, S)) != ORBX_OK) return rc;
+    auto [pin, pout] = h->box.plan();
+    (void)pout;
+    if ((rc = plan_matches(h, M, pin, S)) != ORBX_OK) return rc;
+    const auto sModels = pin.add(models, (size_t)m * 9);
+    const OrbxStaged sg = h->box.begin(h->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    fill_matches(M, false, sg, S);
     if (S.N < 1) { orbx_set_error("no matches"); return ORBX_ERR_ARG; }
-    memcpy(h->box.in + S.extra, models, (size_t)m * 36);
+    uint8_t *ar;
+    if ((rc = stage_to_arena(h, &ar)) != ORBX_OK) return rc;
     InitModelArgs A;
-    fill_model_args(h, S, A);
-    A.explicitModels = (const float *)(h->arena.p + S.extra); A.kind = kind; A.nmodels = m; A.iters = m;
+    fill_model_args(h, S, ar, A);
+    A.explicitModels = sModels.in(ar); A.kind = kind; A.nmodels = m; A.iters = m;
     A.invSigma2 = inv_sigma2(sigma);
-    if ((rc = launch_stage_copy(h, S.total)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_init_models, dim3((unsigned)m), dim3(64), 0, h->stream, A);
     ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -991,16 +997,21 @@ extern "C" int orbx_init_check_rt(orbx_initializer *h, const orbx_init_matches *
     int N = 0;
     for (int i = 0; i < M->n1; i++) N += M->matches12[i] >= 0 ? 1 : 0;
     if (N < 1) { orbx_set_error("no matches"); return ORBX_ERR_ARG; }
-    if ((rc = stage_matches(h, M, false, (size_t)N, (size_t)m * 36, (size_t)m * 12, 0, S)) != ORBX_OK) return rc;
-    memcpy(h->box.in + S.extra, inliers, (size_t)N);
-    memcpy(h->box.in + S.extra2, r, (size_t)m * 36);
-    memcpy(h->box.in + S.extra3, t, (size_t)m * 12);
+    auto [pin, pout] = h->box.plan();
+    (void)pout;
+    if ((rc = plan_matches(h, M, pin, S)) != ORBX_OK) return rc;
+    const auto sInl = pin.add(inliers, (size_t)N);
+    const auto sR = pin.add(r, (size_t)m * 9), sT = pin.add(t, (size_t)m * 3);
+    const OrbxStaged sg = h->box.begin(h->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    fill_matches(M, false, sg, S);
+    uint8_t *ar;
+    if ((rc = stage_to_arena(h, &ar)) != ORBX_OK) return rc;
     InitRtArgs R;
-    R.raw = (const float4 *)(h->arena.p + S.raw); R.hypR = (const float *)(h->arena.p + S.extra2); R.hypT = (const float *)(h->arena.p + S.extra3); R.hypValid = nullptr;
-    R.inlBase = h->arena.p + S.extra; R.best = nullptr; R.iters = 0; R.N = N;
+    R.raw = (const float4 *)S.raw.in(ar); R.hypR = sR.in(ar); R.hypT = sT.in(ar); R.hypValid = nullptr;
+    R.inlBase = sInl.in(ar); R.best = nullptr; R.iters = 0; R.N = N;
     R.fx = fx; R.fy = fy; R.cx = cx; R.cy = cy; R.th2 = th2;
     R.status = h->crtStatus.p; R.p3d = h->crtP3d.p; R.cosp = h->crtCos.p;
-    if ((rc = launch_stage_copy(h, S.total)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_init_check_rt, dim3((unsigned)((N + 255) / 256), (unsigned)m), dim3(256), 0, h->stream, R);
     ORBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_init_rank, dim3((unsigned)m, RANK_SPLIT), dim3(RANK_THREADS), (size_t)((N + 3) & ~3) * 4, h->stream, (const uint8_t *)h->crtStatus.p, (const float *)h->crtCos.p, N, h->rankGood.p,
@@ -1014,7 +1025,7 @@ extern "C" int orbx_init_check_rt(orbx_initializer *h, const orbx_init_matches *
     if (good) ORBX_HIP_CHECK(hipMemcpy(good, h->rankGood.p, (size_t)m * 4, hipMemcpyDeviceToHost));
     if (cos_parallax) ORBX_HIP_CHECK(hipMemcpy(cos_parallax, h->rankCos.p, (size_t)m * 4, hipMemcpyDeviceToHost));
     if (status) memcpy(status, st.data(), st.size());
-    const int32_t *slot = (const int32_t *)(h->box.in + S.slot);
+    const int32_t *slot = sg.host(S.slot);
     const size_t n1 = (size_t)M->n1;
     for (int k = 0; k < m; k++)
         for (size_t i = 0; i < n1; i++) {

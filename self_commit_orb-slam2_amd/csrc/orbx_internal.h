@@ -8,6 +8,7 @@
 
 #include "../../include/orbx.h"
 #include "orbx_wave.h"
+#include "orbx_stage.h"
 
 #define ORBX_MAX_LEVELS 12
 #define ORBX_EDGE 19          /* EDGE_THRESHOLD, reference src/ORBextractor.cc:93 */
@@ -230,17 +231,26 @@ template <typename T> struct OrbxDevBuf {
 
 /* Host arrays of one call packed into ONE pinned buffer and moved with ONE copy: a dozen small
  * hipMemcpyAsync calls from pageable memory cost more than the kernels of a single-frame call.
- * begin(total) sizes both sides, put() copies a host array in and returns where it will live on the
- * device, flush() issues the copy.  The caller synchronises the stream before the next begin()
- * (every host-array entry point ends with a synchronous download). */
+ * plan() hands out the (emptied) layout plan, the caller add()s every array once in buffer order
+ * (orbx_stage.h), begin() sizes both sides from the plan, copies the listed arrays into the pinned
+ * side and returns the view that resolves the slots, flush() issues the copy.  The caller
+ * synchronises the stream before the next begin() (every host-array entry point ends with a
+ * synchronous download). */
 struct OrbxHostStage {
     uint8_t *host = nullptr;
-    size_t hostBytes = 0, used = 0;
+    size_t hostBytes = 0;
     OrbxDevBuf<uint8_t> dev;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    int begin(size_t total)
+    OrbxInPlan layout;
+    OrbxInPlan &plan() { layout.reset(); return layout; }
+    OrbxStaged begin(int *rc, size_t reserve = 0)      /* reserve: what the largest call will need, so that no later call reallocates */
     {
-        used = 0;
+        const size_t total = layout.total();
+        if ((*rc = grow(total > reserve ? total : reserve)) != ORBX_OK) return OrbxStaged(nullptr, nullptr, nullptr, nullptr);
+        layout.fill(host);
+        return OrbxStaged(host, dev.p, nullptr, nullptr);
+    }
+    int grow(size_t total)
+    {
         int rc = dev.ensure(total ? total : 256);
         if (rc != ORBX_OK) return rc;
         if (total > hostBytes) {
@@ -251,19 +261,12 @@ struct OrbxHostStage {
         }
         return ORBX_OK;
     }
-    template <typename T> T *put(const T *src, size_t count)
-    {
-        T *d = (T *)(dev.p + used);
-        if (src && count) memcpy(host + used, src, count * sizeof(T));
-        used += padded(count * sizeof(T));
-        return d;
-    }
     int flush(hipStream_t st)
     {
-        if (used) ORBX_HIP_CHECK(hipMemcpyAsync(dev.p, host, used, hipMemcpyHostToDevice, st));
+        if (layout.total()) ORBX_HIP_CHECK(hipMemcpyAsync(dev.p, host, layout.total(), hipMemcpyHostToDevice, st));
         return ORBX_OK;
     }
-    void release() { if (host) (void)hipHostFree(host); host = nullptr; hostBytes = 0; used = 0; dev.release(); }
+    void release() { if (host) (void)hipHostFree(host); host = nullptr; hostBytes = 0; dev.release(); }
     OrbxHostStage() = default;
     OrbxHostStage(const OrbxHostStage &) = delete;
     OrbxHostStage &operator=(const OrbxHostStage &) = delete;
@@ -274,36 +277,46 @@ struct OrbxHostStage {
  * (tools/ubench_call.hip, profiles/r06_call_floor.txt): pageable upload + hipStreamSynchronize + two hipMemcpy downloads = 63 us; inputs in MAPPED pinned
  * memory read in place by the kernel, results written by the kernel into mapped pinned memory, a sequence word raised behind them by the last workgroup
  * and polled by the host = 22 us.  (hipMemcpyAsync from pinned memory alone costs 17 us of stream time before the kernel starts.)
- *   begin(in, out) sizes the two mapped buffers (grow-only) and waits for a call that was abandoned half way;
- *   put(src, n)    copies a host array into the input buffer and returns the address the DEVICE reads it at (each byte should be read once: inputs that
- *                  several workgroups read again and again are copied to device memory by the first kernel of the chain);
- *   outDev / outHost(off) address the result buffer from both sides;
+ *   plan()         hands out the two (emptied) layout plans; the caller add()s every input array and every result region once, in buffer order
+ *                  (orbx_stage.h);
+ *   begin()        waits for a call that was abandoned half way, sizes the two mapped buffers (grow-only) from the plans, copies the listed inputs in
+ *                  and returns the view that resolves a slot to its host address and to the address the DEVICE reads or writes it at (each input byte
+ *                  should be read once: inputs that several workgroups read again and again go to device memory first, orbx_stage_to_arena());
  *   arm() hands out the sequence number the chain's last kernel publishes with orbx_publish(); wait() spins until it shows up. */
 struct OrbxCallBox {
     uint8_t *in = nullptr, *inDev = nullptr;
-    size_t inBytes = 0, used = 0;
+    size_t inBytes = 0;
     uint8_t *out = nullptr, *outDevP = nullptr;
     size_t outBytes = 0;
     unsigned long long *flag = nullptr, *flagDev = nullptr;      /* mapped: the last published sequence number */
     unsigned *counter = nullptr;                                 /* device: arrivals of the publishing kernel's workgroups (0 between calls) */
     unsigned long long seq = 0;
     bool pending = false;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    OrbxInPlan inPlan;
+    OrbxOutPlan outPlan;
+    struct Plans { OrbxInPlan &in; OrbxOutPlan &out; };
+    Plans plan() { inPlan.reset(); outPlan.reset(); return Plans{inPlan, outPlan}; }
     int grow(uint8_t **host, uint8_t **dev, size_t *have, size_t want)
     {
         if (want <= *have) return ORBX_OK;
         if (*host) (void)hipHostFree(*host);
         *host = nullptr; *dev = nullptr; *have = 0;
-        want = padded(want + want / 2);
+        want = OrbxInPlan::padded(want + want / 2);
         ORBX_HIP_CHECK(hipHostMalloc((void **)host, want, hipHostMallocMapped));
         ORBX_HIP_CHECK(hipHostGetDevicePointer((void **)dev, *host, 0));
         *have = want;
         return ORBX_OK;
     }
-    int begin(size_t inTotal, size_t outTotal, hipStream_t st)
+    OrbxStaged begin(hipStream_t st, int *rc)
+    {
+        if ((*rc = size(st)) != ORBX_OK) return OrbxStaged(nullptr, nullptr, nullptr, nullptr);
+        inPlan.fill(in);
+        return OrbxStaged(in, inDev, out, outDevP);
+    }
+    int size(hipStream_t st)
     {
         if (pending) { ORBX_HIP_CHECK(hipStreamSynchronize(st)); pending = false; }      /* (a call that returned an error before its wait()) */
-        used = 0;
+        const size_t inTotal = inPlan.total(), outTotal = outPlan.total();
         int rc;
         if ((rc = grow(&in, &inDev, &inBytes, inTotal ? inTotal : 256)) != ORBX_OK) return rc;
         if ((rc = grow(&out, &outDevP, &outBytes, outTotal ? outTotal : 256)) != ORBX_OK) return rc;
@@ -316,16 +329,6 @@ struct OrbxCallBox {
         }
         return ORBX_OK;
     }
-    template <typename T> const T *put(const T *src, size_t count)
-    {
-        const T *d = (const T *)(inDev + used);
-        if (src && count) memcpy(in + used, src, count * sizeof(T));
-        used += padded(count * sizeof(T));
-        return d;
-    }
-    template <typename T> T *hostIn(const T *devAddr) { return (T *)(in + ((const uint8_t *)devAddr - inDev)); }      /* where put() placed an array, host side */
-    template <typename T> T *outDev(size_t off) { return (T *)(outDevP + off); }
-    template <typename T> const T *outHost(size_t off) const { return (const T *)(out + off); }
     unsigned long long arm() { pending = true; return ++seq; }
     /* spins on the sequence word; the stream is queried now and then so that a failed launch becomes an error instead of a hang */
     int wait(hipStream_t st)
@@ -362,6 +365,13 @@ struct OrbxCallBox {
     ~OrbxCallBox() { release(); }
 };
 
+/* Sim3Solver / PnPsolver stage one array per candidate, concatenated: the region is planned as a hole and candidate c's `count` elements go to element
+ * `first` of it after begin(). */
+template <typename T> static inline void orbx_put_at(const OrbxStaged &sg, OrbxSlot<T, ORBX_STAGE_IN> region, size_t first, const T *src, size_t count)
+{
+    if (count) memcpy(sg.host(region) + first, src, count * sizeof(T));
+}
+
 #ifdef __HIPCC__
 /* End of the LAST kernel of an OrbxCallBox chain, called by every thread of every workgroup after its last store of results (to mapped host memory):
  * the workgroup that arrives last raises the sequence word with system scope behind everybody's stores (agent-scope release per workgroup, acquire +
@@ -382,6 +392,19 @@ __device__ __forceinline__ void orbx_publish(unsigned *counter, unsigned long lo
 static __global__ __launch_bounds__(256) void k_stage_copy(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16)
 {
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+}
+/* ... the launch: grows `arena` to the planned input bytes (or to arenaBytes, if that is more), copies the box's inputs there with at most maxBlocks
+ * workgroups and sets *base; the arrays keep their offsets (slot.in(base)).  headBytes: only the arrays in front of that offset are copied (the rest
+ * is read in place).  The caller checks / counts the launch. */
+template <typename Arena>
+static inline int orbx_stage_to_arena(OrbxCallBox &box, Arena &arena, hipStream_t st, size_t maxBlocks, uint8_t **base, size_t arenaBytes = 0, size_t headBytes = ~(size_t)0)
+{
+    const size_t bytes = box.inPlan.total() < headBytes ? box.inPlan.total() : headBytes, n16 = bytes / 16, blocks = (n16 + 255) / 256;
+    const int rc = arena.ensure(bytes > arenaBytes ? bytes : arenaBytes);
+    if (rc != ORBX_OK) return rc;
+    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)(blocks > maxBlocks ? maxBlocks : blocks ? blocks : 1)), dim3(256), 0, st, (const uint4 *)box.inDev, (uint4 *)arena.p, n16);
+    *base = (uint8_t *)arena.p;
+    return ORBX_OK;
 }
 #endif
 

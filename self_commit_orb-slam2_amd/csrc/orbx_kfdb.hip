@@ -705,45 +705,42 @@ extern "C" int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *que
             wo += (size_t)Q.n; co += (size_t)K.nconn;
         }
     }
-    auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
-    const size_t oQs = 0, oW = oQs + padded(sizeof(KfQuery) * (size_t)nq), oV = oW + padded(4 * nw), oCs = oV + padded(8 * nw), oCc = oCs + padded(4 * nc),
-                 oSo = oCc + padded(4 * nc), total = oSo + padded(4 * nsorted);
     OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(total, outTotal, h->stream)) != ORBX_OK) return rc;
-    if ((rc = h->arena.ensure(total)) != ORBX_OK) return rc;
-    memcpy(bx.in + oQs, qs.data(), sizeof(KfQuery) * (size_t)nq);
+    auto [pin, pout] = bx.plan();
+    const auto sQs = pin.add(qs.data(), (size_t)nq);
+    const auto sW = pin.hole<int32_t>(nw);      // the queries' words and values, concatenated: filled below
+    const auto sV = pin.hole<double>(nw);
+    const auto sCs = pin.add(connSlot.data(), nc), sCc = pin.add(connCount.data(), nc), sSo = pin.add(connSorted.data(), nsorted);
+    const auto rOut = pout.hole<uint8_t>(outTotal);      // the queries' kf_out_layout blocks
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK) return rc;
     {
         size_t wo = 0;
         for (int q = 0; q < nq; q++) {
-            if (queries[q].n) {
-                memcpy(bx.in + oW + 4 * wo, queries[q].words, 4 * (size_t)queries[q].n);
-                memcpy(bx.in + oV + 8 * wo, queries[q].values, 8 * (size_t)queries[q].n);
-            }
+            orbx_put_at(sg, sW, wo, queries[q].words, (size_t)queries[q].n);
+            orbx_put_at(sg, sV, wo, queries[q].values, (size_t)queries[q].n);
             wo += (size_t)queries[q].n;
         }
     }
-    if (nc) { memcpy(bx.in + oCs, connSlot.data(), 4 * nc); memcpy(bx.in + oCc, connCount.data(), 4 * nc); }
-    if (nsorted) memcpy(bx.in + oSo, connSorted.data(), 4 * nsorted);
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
+    uint8_t *A;
+    if ((rc = orbx_stage_to_arena(bx, h->arena, h->stream, 256, &A)) != ORBX_OK) return rc;
+    ORBX_LAUNCH_CHECK();
 
     KfDev D;
     const size_t per = (size_t)nq * (size_t)Ns;
-    const uint8_t *A = h->arena.p;
     D.Ns = Ns; D.nq = nq;
     D.slots = h->dslots.p; D.poolW = h->poolW.p; D.poolV = h->poolV.p;
     D.relocOld = h->reloc[h->cur].p; D.relocNew = h->reloc[h->cur ^ 1].p;
-    D.qs = (const KfQuery *)(A + oQs); D.qwords = (const int32_t *)(A + oW); D.qvalues = (const double *)(A + oV);
-    D.connSlot = (const int32_t *)(A + oCs); D.connCount = (const int32_t *)(A + oCc); D.connSorted = (const int32_t *)(A + oSo);
+    D.qs = sQs.in(A); D.qwords = sW.in(A); D.qvalues = sV.in(A);
+    D.connSlot = sCs.in(A); D.connCount = sCc.in(A); D.connSorted = sSo.in(A);
     int32_t *W = h->work.p;
     D.words = W; D.first = W + per; D.flag = W + 2 * per; D.firstocc = W + 3 * per; D.score = (float *)(W + 4 * per);
     D.list = W + 5 * per; D.order = W + 6 * per; D.lsm = W + 7 * per; D.best = W + 8 * per; D.acc = (float *)(W + 9 * per);
     D.counters = W + 10 * (size_t)h->maxQueries * (size_t)h->maxKf;
     D.key = h->key.p;
-    D.out = bx.outDevP;
+    D.out = sg.dev(rOut);
 
-    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    const size_t n16 = total / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipMemsetAsync(D.counters, 0, 8 * (size_t)nq, h->stream));
     h->profiled = false;
     if (h->profile) ORBX_HIP_CHECK(hipEventRecord(h->pev[0], h->stream));
@@ -768,7 +765,7 @@ extern "C" int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *que
     h->cur ^= 1;      // the scores of this call's relocalisation queries are the state now
 
     for (int q = 0; q < nq; q++) {      // nothing is written when one list does not fit
-        const int32_t *hi = (const int32_t *)(bx.out + qs[(size_t)q].outOff);
+        const int32_t *hi = (const int32_t *)(sg.host(rOut) + qs[(size_t)q].outOff);
         const orbx_kfdb_result &R = results[q];
         const int cap = queries[q].capacity;
         if (((R.scored_id || R.scored_words || R.scored_score) && hi[3] > cap) || ((R.kept || R.acc_score || R.best_id) && hi[4] > cap) || (R.candidates && hi[5] > cap)) {
@@ -779,7 +776,7 @@ extern "C" int orbx_kfdb_query(orbx_kf_database *h, const orbx_kfdb_query_t *que
     }
     for (int q = 0; q < nq; q++) {
         const KfQuery &K = qs[(size_t)q];
-        const uint8_t *o = bx.out + K.outOff;
+        const uint8_t *o = sg.host(rOut) + K.outOff;
         const int32_t *hi = (const int32_t *)o;
         const float *hf = (const float *)o;
         const KfOutOff O = kf_out_layout(Ns, K.nconn);

@@ -3227,15 +3227,19 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
     // No copy engine, no stream synchronisation (OrbxCallBox): every input is read exactly once, into the registers of the thread that owns the edge, straight
     // from mapped pinned memory; pose / flags / inlier count / statistics are written into mapped pinned memory and the last workgroup raises the sequence word.
     OrbxCallBox &bx = h->box;
-    const size_t inBytes = bx.padded((size_t)B * 64) + bx.padded((size_t)B * 20) + bx.padded((size_t)B * 4) + 2 * bx.padded(N * 12) + bx.padded(N * 4);
-    const size_t q1 = bx.padded((size_t)B * 64), q2 = q1 + bx.padded(N), q3 = q2 + bx.padded((size_t)B * 4), outBytes = q3 + bx.padded((size_t)B * 64);
-    int rcs = bx.begin(inBytes, outBytes, st);
+    auto [pin, pout] = bx.plan();
+    const auto sPose = pin.add(p->poses, (size_t)B * 16), sCam = pin.add(p->cameras, (size_t)B * 5);
+    const auto sCnt = pin.add(p->counts, (size_t)B);
+    const auto sXw = pin.add(p->world_points, N * 3), sObs = pin.add(p->observations, N * 3), sInv = pin.add(p->inv_sigma2, N);
+    const auto rPose = pout.hole<float>((size_t)B * 16);
+    const auto rOutlier = pout.hole<uint8_t>(N);
+    const auto rInliers = pout.hole<int32_t>((size_t)B);
+    const auto rStats = pout.hole<double>((size_t)B * 8);
+    int rcs;
+    const OrbxStaged sg = bx.begin(st, &rcs);
     if (rcs != ORBX_OK) return rcs;
-    const float *dPose = bx.put(p->poses, (size_t)B * 16), *dCam = bx.put(p->cameras, (size_t)B * 5);
-    const int32_t *dCnt = bx.put(p->counts, (size_t)B);
-    const float *dXw = bx.put(p->world_points, N * 3), *dObs = bx.put(p->observations, N * 3), *dInv = bx.put(p->inv_sigma2, N);
-    const uint8_t *o0 = bx.outHost<uint8_t>(0), *o1 = bx.outHost<uint8_t>(q1), *o2 = bx.outHost<uint8_t>(q2), *o3 = bx.outHost<uint8_t>(q3);
-    PoseOptDev D = {dPose, dCam, dXw, dObs, dInv, dCnt, cap, bx.outDev<float>(0), bx.outDev<uint8_t>(q1), bx.outDev<int32_t>(q2), bx.outDev<double>(q3), bx.counter, bx.flagDev, bx.arm(), g_poProf,
+    const uint8_t *o1 = sg.host(rOutlier);
+    PoseOptDev D = {sg.dev(sPose), sg.dev(sCam), sg.dev(sXw), sg.dev(sObs), sg.dev(sInv), sg.dev(sCnt), cap, sg.dev(rPose), sg.dev(rOutlier), sg.dev(rInliers), sg.dev(rStats), bx.counter, bx.flagDev, bx.arm(), g_poProf,
                     B == 1 ? 1 : 0, p->counts[0], {}, {}};
     if (B == 1) { memcpy(D.cam0, p->cameras, sizeof D.cam0); memcpy(D.pose00, p->poses, sizeof D.pose00); }
     const float thMono = (float)sqrt(5.991), thStereo = (float)sqrt(7.815);   // deltaMono / deltaStereo are floats (:389-390)
@@ -3258,15 +3262,15 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
     else hipLaunchKernelGGL((k_pose_opt<32, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);      // up to 8192 correspondences: 32 per thread, one wave per SIMD
     ORBX_LAUNCH_CHECK();
     if ((rcs = bx.wait(st)) != ORBX_OK) return rcs;
-    if (poses_out) memcpy(poses_out, o0, (size_t)B * 64);
+    if (poses_out) memcpy(poses_out, sg.host(rPose), (size_t)B * 64);
     if (outlier)      // entries past a frame's count are not written by the kernel: they read 0
         for (int f = 0; f < B; f++) {
             const size_t c = (size_t)std::min(std::max((int)p->counts[f], 0), cap);
             memcpy(outlier + (size_t)f * cap, o1 + (size_t)f * cap, c);
             memset(outlier + (size_t)f * cap + c, 0, (size_t)cap - c);
         }
-    if (inliers) memcpy(inliers, o2, (size_t)B * 4);
-    if (stats) memcpy(stats, o3, (size_t)B * 64);
+    if (inliers) memcpy(inliers, sg.host(rInliers), (size_t)B * 4);
+    if (stats) memcpy(stats, sg.host(rStats), (size_t)B * 64);
     return ORBX_OK;
 }
 

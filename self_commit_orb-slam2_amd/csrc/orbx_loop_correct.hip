@@ -292,6 +292,7 @@ struct orbx_loop : OrbxHandle {
     OrbxCallBox box;
     OrbxOwnedBuf<uint8_t> arena;      // the staged inputs in device memory
     OrbxOwnedBuf<uint8_t> work;       // claim words, the group's Sim3s and centres, unit vectors | TcwGBA
+    OrbxWorkPlan workPlan;            // ... their layout
     OrbxOwnedBuf<uint8_t> results;    // orbx_loop_correct_sim3: the results before they cross to the host in one piece
     std::vector<int32_t> groupPos, order, levelOff, level;
     std::vector<uint8_t> reached;
@@ -434,45 +435,49 @@ extern "C" int orbx_loop_correct_sim3(orbx_loop *h, const orbx_loop_sim3_problem
     const size_t NK = (size_t)p->num_keyframes, G = (size_t)p->num_group, M = (size_t)p->num_points, S = (size_t)p->num_entries, T = (size_t)p->num_obs;
     h->timer.timed = false;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
-    auto pd = [](size_t b) { return OrbxCallBox::padded(b); };
-    const size_t inBytes = pd(48 * NK) + pd(12 * NK) + pd(4 * G) + pd(4 * NK) + pd(64) + pd(4 * (G + 1)) + pd(4 * S) + pd(12 * M) + 2 * pd(M) + 3 * pd(4 * M) + pd(4 * (M + 1)) + pd(4 * T);
-    const size_t oNonc = 0, oCorr = oNonc + pd(64 * G), oTiw = oCorr + pd(64 * G), oOw = oTiw + pd(48 * G), oScw = oOw + pd(12 * G), oPos = oScw + pd(48 * G), oBy = oPos + pd(12 * M),
-                 oNor = oBy + pd(4 * M), oMax = oNor + pd(12 * M), oMin = oMax + pd(4 * M), oUpd = oMin + pd(4 * M), outBytes = oUpd + pd(M);
-    const size_t wClaim = 0, wNonc = wClaim + pd(4 * M), wSwi = wNonc + pd(64 * G), wOw = wSwi + pd(64 * G), wUnit = wOw + pd(12 * G), wBytes = wUnit + pd(12 * T);
     OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(inBytes, outBytes, h->stream)) != ORBX_OK) return rc;
-    if ((rc = h->arena.ensure(inBytes)) != ORBX_OK) return rc;
-    if ((rc = h->work.ensure(wBytes ? wBytes : 256)) != ORBX_OK) return rc;
+    auto [pin, pout] = bx.plan();
+    const auto sTcw = pin.add(p->tcw, 12 * NK), sOw = pin.add(p->ow, 3 * NK);
+    const auto sGroupKf = pin.add(p->group_kf, G), sGroupPos = pin.add((const int32_t *)groupPos.data(), NK);
+    const auto sScw = pin.add(p->scw, (size_t)8);
+    const auto sListOff = pin.add(p->list_offset, G + 1), sListPt = pin.add(p->list_point, S);
+    const auto sPos = pin.add(p->pos, 3 * M);
+    const auto sBad = pin.add(p->point_bad, M), sDone = pin.add(p->point_done, M);
+    const auto sRef = pin.add(p->point_ref, M);
+    const auto sRsc = pin.add(p->ref_scale, M), sTsc = pin.add(p->top_scale, M);
+    const auto sObsOff = pin.add(p->obs_offset, M + 1), sObsKf = pin.add(p->obs_kf, T);
+    // the results: built in device memory (h->results) in this layout, then copied to the box in one pass
+    const auto rNonc = pout.hole<double>(8 * G), rCorr = pout.hole<double>(8 * G);
+    const auto rTiw = pout.hole<float>(12 * G), rOw = pout.hole<float>(3 * G), rScw = pout.hole<float>(12 * G), rPos = pout.hole<float>(3 * M);
+    const auto rBy = pout.hole<int32_t>(M);
+    const auto rNor = pout.hole<float>(3 * M), rMax = pout.hole<float>(M), rMin = pout.hole<float>(M);
+    const auto rUpd = pout.hole<uint8_t>(M);
+    const size_t outBytes = pout.total();
+    OrbxWorkPlan &work = h->workPlan;
+    work.reset();
+    const auto wClaim = work.hole<int32_t>(M);
+    const auto wNonc = work.hole<double>(8 * G), wSwi = work.hole<double>(8 * G);
+    const auto wOw = work.hole<float>(3 * G), wUnit = work.hole<float>(3 * T);
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    if ((rc = h->work.ensure(work.total() ? work.total() : 256)) != ORBX_OK) return rc;
     if ((rc = h->results.ensure(outBytes)) != ORBX_OK) return rc;
-    const uint8_t *A = h->arena.p;
-    auto dev = [&](const void *boxAddr) { return A + ((const uint8_t *)boxAddr - bx.inDev); };
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
+    uint8_t *A;
+    if ((rc = orbx_stage_to_arena(bx, h->arena, h->stream, 256, &A)) != ORBX_OK) return rc;
+    ORBX_LAUNCH_COUNT(h->timer);
     LcDev D = {};
     D.NK = (int)NK; D.G = (int)G; D.M = (int)M; D.cur = p->current;
-    D.tcw = (const float *)dev(bx.put(p->tcw, 12 * NK));
-    D.ow = (const float *)dev(bx.put(p->ow, 3 * NK));
-    D.groupKf = (const int32_t *)dev(bx.put(p->group_kf, G));
-    D.groupPos = (const int32_t *)dev(bx.put(groupPos.data(), NK));
-    D.scw = (const double *)dev(bx.put(p->scw, (size_t)8));
-    D.listOff = (const int32_t *)dev(bx.put(p->list_offset, G + 1));
-    D.listPt = (const int32_t *)dev(bx.put(p->list_point, S));
-    D.pos = (const float *)dev(bx.put(p->pos, 3 * M));
-    D.bad = dev(bx.put(p->point_bad, M));
-    D.done = dev(bx.put(p->point_done, M));
-    D.ref = (const int32_t *)dev(bx.put(p->point_ref, M));
-    D.rsc = (const float *)dev(bx.put(p->ref_scale, M));
-    D.tsc = (const float *)dev(bx.put(p->top_scale, M));
-    D.obsOff = (const int32_t *)dev(bx.put(p->obs_offset, M + 1));
-    D.obsKf = (const int32_t *)dev(bx.put(p->obs_kf, T));
-    uint8_t *W = h->work.p;
-    D.claim = (int32_t *)(W + wClaim); D.wNonc = (double *)(W + wNonc); D.wSwi = (double *)(W + wSwi); D.wOwNew = (float *)(W + wOw); D.unit = (float *)(W + wUnit);
-    uint8_t *O = h->results.p;
-    D.oNonc = (double *)(O + oNonc); D.oCorr = (double *)(O + oCorr); D.oTiw = (float *)(O + oTiw); D.oOwNew = (float *)(O + oOw); D.oScwMat = (float *)(O + oScw);
-    D.oPos = (float *)(O + oPos); D.oBy = (int32_t *)(O + oBy); D.oNormal = (float *)(O + oNor); D.oMax = (float *)(O + oMax); D.oMin = (float *)(O + oMin);
-    D.oUpd = O + oUpd;
-    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    const size_t n16 = bx.used / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    ORBX_LAUNCH_COUNT(h->timer);
+    D.tcw = sTcw.in(A); D.ow = sOw.in(A); D.groupKf = sGroupKf.in(A); D.groupPos = sGroupPos.in(A); D.scw = sScw.in(A);
+    D.listOff = sListOff.in(A); D.listPt = sListPt.in(A);
+    D.pos = sPos.in(A); D.bad = sBad.in(A); D.done = sDone.in(A); D.ref = sRef.in(A); D.rsc = sRsc.in(A); D.tsc = sTsc.in(A);
+    D.obsOff = sObsOff.in(A); D.obsKf = sObsKf.in(A);
+    void *W = h->work.p;
+    D.claim = wClaim.in(W); D.wNonc = wNonc.in(W); D.wSwi = wSwi.in(W); D.wOwNew = wOw.in(W); D.unit = wUnit.in(W);
+    void *O = h->results.p;
+    D.oNonc = rNonc.in(O); D.oCorr = rCorr.in(O); D.oTiw = rTiw.in(O); D.oOwNew = rOw.in(O); D.oScwMat = rScw.in(O);
+    D.oPos = rPos.in(O); D.oBy = rBy.in(O); D.oNormal = rNor.in(O); D.oMax = rMax.in(O); D.oMin = rMin.in(O);
+    D.oUpd = rUpd.in(O);
     hipLaunchKernelGGL(k_lc_sim3, dim3((unsigned)((std::max(G, M) + LC_THREADS - 1) / LC_THREADS)), dim3(LC_THREADS), 0, h->stream, D);
     ORBX_LAUNCH_COUNT(h->timer);
     if (S > 0 && M > 0) {
@@ -486,23 +491,23 @@ extern "C" int orbx_loop_correct_sim3(orbx_loop *h, const orbx_loop_sim3_problem
     const unsigned long long seq = bx.arm();
     const size_t o16 = outBytes / 16;
     hipLaunchKernelGGL(k_lc_results, dim3((unsigned)std::min<size_t>(256, (o16 + LC_THREADS - 1) / LC_THREADS)), dim3(LC_THREADS), 0, h->stream, (const uint4 *)h->results.p,
-                       bx.outDev<uint4>(0), o16, bx.counter, bx.flagDev, seq);
+                       (uint4 *)sg.dev(rNonc), o16, bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_COUNT(h->timer);
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     if (r) {
-        if (r->noncorrected) memcpy(r->noncorrected, bx.outHost<uint8_t>(oNonc), 64 * G);
-        if (r->corrected) memcpy(r->corrected, bx.outHost<uint8_t>(oCorr), 64 * G);
-        if (r->tiw) memcpy(r->tiw, bx.outHost<uint8_t>(oTiw), 48 * G);
-        if (r->ow_new) memcpy(r->ow_new, bx.outHost<uint8_t>(oOw), 12 * G);
-        if (r->scw_mat) memcpy(r->scw_mat, bx.outHost<uint8_t>(oScw), 48 * G);
+        if (r->noncorrected) memcpy(r->noncorrected, sg.host(rNonc), 64 * G);
+        if (r->corrected) memcpy(r->corrected, sg.host(rCorr), 64 * G);
+        if (r->tiw) memcpy(r->tiw, sg.host(rTiw), 48 * G);
+        if (r->ow_new) memcpy(r->ow_new, sg.host(rOw), 12 * G);
+        if (r->scw_mat) memcpy(r->scw_mat, sg.host(rScw), 48 * G);
         if (M) {
-            if (r->pos) memcpy(r->pos, bx.outHost<uint8_t>(oPos), 12 * M);
-            if (r->corrected_by) memcpy(r->corrected_by, bx.outHost<uint8_t>(oBy), 4 * M);
-            if (r->normal) memcpy(r->normal, bx.outHost<uint8_t>(oNor), 12 * M);
-            if (r->max_dist) memcpy(r->max_dist, bx.outHost<uint8_t>(oMax), 4 * M);
-            if (r->min_dist) memcpy(r->min_dist, bx.outHost<uint8_t>(oMin), 4 * M);
-            if (r->updated) memcpy(r->updated, bx.outHost<uint8_t>(oUpd), M);
+            if (r->pos) memcpy(r->pos, sg.host(rPos), 12 * M);
+            if (r->corrected_by) memcpy(r->corrected_by, sg.host(rBy), 4 * M);
+            if (r->normal) memcpy(r->normal, sg.host(rNor), 12 * M);
+            if (r->max_dist) memcpy(r->max_dist, sg.host(rMax), 4 * M);
+            if (r->min_dist) memcpy(r->min_dist, sg.host(rMin), 4 * M);
+            if (r->updated) memcpy(r->updated, sg.host(rUpd), M);
         }
     }
     return ORBX_OK;
@@ -520,35 +525,35 @@ extern "C" int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem
     const size_t n = (size_t)p->num_keyframes, M = (size_t)p->num_points, L = levelOff.size() - 1, C = order.size();
     h->timer.timed = false;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
-    auto pd = [](size_t b) { return OrbxCallBox::padded(b); };
-    const size_t kfBytes = 2 * pd(48 * n) + pd(4 * n) + pd(n) + pd(4 * C) + pd(4 * (L + 1));
-    const size_t inBytes = kfBytes + 2 * pd(12 * M) + 2 * pd(M) + pd(4 * M);
-    const size_t oGba = 0, oPos = oGba + pd(48 * n), oMoved = oPos + pd(12 * M), outBytes = oMoved + pd(M);
     OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(inBytes, outBytes, h->stream)) != ORBX_OK) return rc;
-    if ((rc = h->arena.ensure(kfBytes)) != ORBX_OK) return rc;
-    if ((rc = h->work.ensure(pd(48 * n))) != ORBX_OK) return rc;
-    const uint8_t *A = h->arena.p;
-    auto dev = [&](const void *boxAddr) { return A + ((const uint8_t *)boxAddr - bx.inDev); };
+    auto [pin, pout] = bx.plan();
+    // the keyframe arrays: staged to the arena; the point arrays behind them are read in place
+    const auto sTcw = pin.add(p->tcw, 12 * n), sGba = pin.add(p->tcw_gba, 12 * n);
+    const auto sParent = pin.add(p->parent, n);
+    const auto sReached = pin.add((const uint8_t *)reached.data(), n);
+    const auto sOrder = pin.add((const int32_t *)order.data(), C), sLevelOff = pin.add((const int32_t *)levelOff.data(), L + 1);
+    const size_t kfBytes = pin.total();
+    const auto sPos = pin.add(p->pos, 3 * M), sPosGba = pin.add(p->pos_gba, 3 * M);
+    const auto sPtIn = pin.add(p->point_in_gba, M), sPtBad = pin.add(p->point_bad, M);
+    const auto sRef = pin.add(p->point_ref, M);
+    const auto rGba = pout.hole<float>(12 * n), rPos = pout.hole<float>(3 * M);
+    const auto rMoved = pout.hole<uint8_t>(M);
+    const OrbxStaged sg = bx.begin(h->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    OrbxWorkPlan &work = h->workPlan;
+    work.reset();
+    const auto wGba = work.hole<float>(12 * n);
+    if ((rc = h->work.ensure(work.total())) != ORBX_OK) return rc;
+    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
+    uint8_t *A;
+    if ((rc = orbx_stage_to_arena(bx, h->arena, h->stream, 256, &A, 0, kfBytes)) != ORBX_OK) return rc;
+    ORBX_LAUNCH_COUNT(h->timer);
     LgDev D = {};
     D.n = (int)n; D.M = (int)M; D.L = (int)L;
-    D.tcw = (const float *)dev(bx.put(p->tcw, 12 * n));
-    D.gbaIn = (const float *)dev(bx.put(p->tcw_gba, 12 * n));
-    D.parent = (const int32_t *)dev(bx.put(p->parent, n));
-    D.reached = dev(bx.put(reached.data(), n));
-    D.order = (const int32_t *)dev(bx.put(order.data(), C));
-    D.levelOff = (const int32_t *)dev(bx.put(levelOff.data(), L + 1));
-    const size_t n16 = bx.used / 16;      // the keyframe arrays: staged; the point arrays behind them are read in place
-    D.pos = bx.put(p->pos, 3 * M);
-    D.posGba = bx.put(p->pos_gba, 3 * M);
-    D.ptIn = bx.put(p->point_in_gba, M);
-    D.ptBad = bx.put(p->point_bad, M);
-    D.ref = bx.put(p->point_ref, M);
-    D.gba = (float *)h->work.p;
-    D.oGba = bx.outDev<float>(oGba); D.oPos = bx.outDev<float>(oPos); D.oMoved = bx.outDev<uint8_t>(oMoved);
-    if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(256, (n16 + 255) / 256)), dim3(256), 0, h->stream, (const uint4 *)bx.inDev, (uint4 *)h->arena.p, n16);
-    ORBX_LAUNCH_COUNT(h->timer);
+    D.tcw = sTcw.in(A); D.gbaIn = sGba.in(A); D.parent = sParent.in(A); D.reached = sReached.in(A); D.order = sOrder.in(A); D.levelOff = sLevelOff.in(A);
+    D.pos = sg.dev(sPos); D.posGba = sg.dev(sPosGba); D.ptIn = sg.dev(sPtIn); D.ptBad = sg.dev(sPtBad); D.ref = sg.dev(sRef);
+    D.gba = wGba.in((void *)h->work.p);
+    D.oGba = sg.dev(rGba); D.oPos = sg.dev(rPos); D.oMoved = sg.dev(rMoved);
     hipLaunchKernelGGL(k_lg_chain, dim3(1), dim3(LC_THREADS), 0, h->stream, D);
     ORBX_LAUNCH_COUNT(h->timer);
     const unsigned long long seq = bx.arm();
@@ -557,11 +562,11 @@ extern "C" int orbx_loop_propagate_gba(orbx_loop *h, const orbx_loop_gba_problem
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     if (r) {
-        if (r->tcw_gba) memcpy(r->tcw_gba, bx.outHost<uint8_t>(oGba), 48 * n);
+        if (r->tcw_gba) memcpy(r->tcw_gba, sg.host(rGba), 48 * n);
         if (r->reached) memcpy(r->reached, reached.data(), n);
         if (M) {
-            if (r->pos) memcpy(r->pos, bx.outHost<uint8_t>(oPos), 12 * M);
-            if (r->moved) memcpy(r->moved, bx.outHost<uint8_t>(oMoved), M);
+            if (r->pos) memcpy(r->pos, sg.host(rPos), 12 * M);
+            if (r->moved) memcpy(r->moved, sg.host(rMoved), M);
         }
     }
     return ORBX_OK;

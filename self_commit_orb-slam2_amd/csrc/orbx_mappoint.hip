@@ -289,21 +289,31 @@ extern "C" int orbx_mappoint_refresh(orbx_mappoint_ops *h, const orbx_mappoint_b
     }
     OrbxHostStage &S = h->stage;
     const size_t m = (size_t)M, t = (size_t)T;
-    int rc = S.begin(S.padded((m + 1) * 4) + S.padded(t * 32) + S.padded(t) + S.padded(t * 12) + 2 * S.padded(m * 12) + 2 * S.padded(m * 4) + 4 * S.padded(m * 4));
+    OrbxInPlan &pl = S.plan();
+    const auto sOff = pl.add(b->obs_offset, m + 1);
+    const auto sDesc = pl.add(b->desc, t * 32);
+    const auto sValid = pl.add(b->desc_valid, b->desc_valid ? t : 0);
+    const auto sCam = pl.add(b->cam_center, t * 3);
+    const auto sPos = pl.add(b->pos, m * 3), sRefc = pl.add(b->ref_center, m * 3);
+    const auto sRsc = pl.add(b->ref_scale, m), sTsc = pl.add(b->top_scale, m);
+    OrbxSlot<int32_t, ORBX_STAGE_IN> sList[4];
+    for (int c = 0; c < 4; c++) sList[c] = pl.add((const int32_t *)h->lists[c].data(), h->lists[c].size());
+    int rc;
+    const OrbxStaged sg = S.begin(&rc);
     if (rc != ORBX_OK) return rc;
     const size_t outBytes = m * 28;
     if ((rc = h->out.ensure(outBytes)) != ORBX_OK) return rc;
     if (!h->lists[3].empty() && ((rc = h->unit.ensure(t * 3)) != ORBX_OK || (rc = h->comp.ensure(t)) != ORBX_OK)) return rc;
 
     MpDev D;
-    D.off = S.put(b->obs_offset, m + 1);
-    D.desc = (const uint32_t *)S.put(b->desc, t * 32);
-    D.valid = b->desc_valid ? S.put(b->desc_valid, t) : nullptr;
-    D.cam = S.put(b->cam_center, t * 3);
-    D.pos = S.put(b->pos, m * 3); D.refc = S.put(b->ref_center, m * 3);
-    D.rsc = S.put(b->ref_scale, m); D.tsc = S.put(b->top_scale, m);
+    D.off = sg.dev(sOff);
+    D.desc = (const uint32_t *)sg.dev(sDesc);
+    D.valid = b->desc_valid ? sg.dev(sValid) : nullptr;
+    D.cam = sg.dev(sCam);
+    D.pos = sg.dev(sPos); D.refc = sg.dev(sRefc);
+    D.rsc = sg.dev(sRsc); D.tsc = sg.dev(sTsc);
     const int32_t *lists[4];
-    for (int c = 0; c < 4; c++) lists[c] = S.put(h->lists[c].data(), h->lists[c].size());
+    for (int c = 0; c < 4; c++) lists[c] = sg.dev(sList[c]);
     D.bestObs = (int32_t *)h->out.p; D.bestMed = D.bestObs + m;
     D.normal = (float *)(D.bestMed + m); D.maxD = D.normal + 3 * m; D.minD = D.maxD + m;
     D.unit = h->unit.p; D.comp = h->comp.p;

@@ -1667,32 +1667,43 @@ extern "C" int orbx_matcher_last_kernel_timing(orbx_matcher *m, float *distance_
 
 // ---- host-array convenience: stage one frame per side, run, download ----
 namespace orbx_match {
-int stage_host(orbx_matcher *m, int side, const orbx_feature_set *h, orbx_feature_set *d)
+int stage_host(orbx_matcher *m, const orbx_feature_set *const *h, orbx_feature_set *const *d, int nsides)
 {
-    // the five arrays of a side go through the pinned staging buffer and ONE copy (ten small copies from pageable memory
-    // cost more than the kernels of a single-pair call): side 0 opens the buffer, sized for two full feature sets
-    if (!h || !h->keypoints || !h->descriptors || !h->counts) { orbx_set_error("NULL feature arrays"); return ORBX_ERR_ARG; }
-    const int n = h->counts[0];
-    if (n < 0 || n > m->maxFeatures) { orbx_set_error("feature count %d exceeds max_features %d", n, m->maxFeatures); return ORBX_ERR_CAPACITY; }
-    OrbxHostStage &hs = m->hostStage;
-    const size_t cap = (size_t)m->maxFeatures;
-    int rc;
-    if (side == 0) {
-        const size_t perSide = hs.padded(cap * sizeof(orbx_keypoint)) + hs.padded(cap * 32) + hs.padded(4) + hs.padded(cap * 4) + hs.padded(cap);
-        ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));   // the previous call's copy has left the pinned buffer
-        if ((rc = hs.begin(2 * perSide)) != ORBX_OK) return rc;
+    // the five arrays of each side go through the pinned staging buffer and ONE copy (ten small copies from pageable memory
+    // cost more than the kernels of a single-pair call); the buffer is sized once, for two full feature sets
+    int32_t cnt[2] = {0, 0};
+    for (int sd = 0; sd < nsides; sd++) {
+        if (!h[sd] || !h[sd]->keypoints || !h[sd]->descriptors || !h[sd]->counts) { orbx_set_error("NULL feature arrays"); return ORBX_ERR_ARG; }
+        cnt[sd] = h[sd]->counts[0];
+        if (cnt[sd] < 0 || cnt[sd] > m->maxFeatures) { orbx_set_error("feature count %d exceeds max_features %d", cnt[sd], m->maxFeatures); return ORBX_ERR_CAPACITY; }
     }
-    const size_t first = hs.used;
-    const int32_t cnt = n;
-    d->keypoints = hs.put(h->keypoints, (size_t)n);
-    d->descriptors = hs.put(h->descriptors, (size_t)n * 32);
-    d->counts = hs.put(&cnt, 1);
-    const int32_t *g = hs.put(h->groups, h->groups ? (size_t)n : 0);
-    const uint8_t *v = hs.put(h->valid, h->valid ? (size_t)n : 0);
-    d->groups = h->groups ? g : nullptr; d->valid = h->valid ? v : nullptr;
-    d->capacity = m->maxFeatures; d->nframes = 1;
-    ORBX_HIP_CHECK(hipMemcpyAsync(hs.dev.p + first, hs.host + first, hs.used - first, hipMemcpyHostToDevice, m->stream));
-    return ORBX_OK;
+    OrbxHostStage &hs = m->hostStage;
+    OrbxInPlan &pl = hs.plan();
+    const size_t cap = (size_t)m->maxFeatures;
+    for (int sd = 0; sd < 2; sd++) { pl.hole<orbx_keypoint>(cap); pl.hole<uint8_t>(cap * 32); pl.hole<int32_t>(1); pl.hole<int32_t>(cap); pl.hole<uint8_t>(cap); }
+    const size_t reserve = pl.total();      // two full feature sets: no later call reallocates the pinned buffer
+    pl.reset();
+    OrbxSlot<orbx_keypoint, ORBX_STAGE_IN> sKp[2];
+    OrbxSlot<uint8_t, ORBX_STAGE_IN> sDesc[2], sValid[2];
+    OrbxSlot<int32_t, ORBX_STAGE_IN> sCnt[2], sGroups[2];
+    for (int sd = 0; sd < nsides; sd++) {
+        const size_t n = (size_t)cnt[sd];
+        sKp[sd] = pl.add(h[sd]->keypoints, n);
+        sDesc[sd] = pl.add(h[sd]->descriptors, n * 32);
+        sCnt[sd] = pl.add(&cnt[sd], 1);
+        sGroups[sd] = pl.add(h[sd]->groups, h[sd]->groups ? n : 0);
+        sValid[sd] = pl.add(h[sd]->valid, h[sd]->valid ? n : 0);
+    }
+    ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));   // the previous call's copy has left the pinned buffer
+    int rc;
+    const OrbxStaged sg = hs.begin(&rc, reserve);
+    if (rc != ORBX_OK) return rc;
+    for (int sd = 0; sd < nsides; sd++) {
+        d[sd]->keypoints = sg.dev(sKp[sd]); d[sd]->descriptors = sg.dev(sDesc[sd]); d[sd]->counts = sg.dev(sCnt[sd]);
+        d[sd]->groups = h[sd]->groups ? sg.dev(sGroups[sd]) : nullptr; d[sd]->valid = h[sd]->valid ? sg.dev(sValid[sd]) : nullptr;
+        d[sd]->capacity = m->maxFeatures; d[sd]->nframes = 1;
+    }
+    return hs.flush(m->stream);
 }
 }  // namespace orbx_match
 
@@ -1706,25 +1717,28 @@ static int search_by_bow_single(orbx_matcher *m, const orbx_feature_set *a, cons
     OrbxCallBox &bx = m->box;
     const size_t NA = (size_t)nA, NB = (size_t)nB;
     const int nOut = prm->mode == 0 ? nB : nA;
-    const size_t inBytes = bx.padded(NA * sizeof(orbx_keypoint)) + bx.padded(NA * 32) + bx.padded(NA * 4) + bx.padded(NA) + bx.padded(NB * sizeof(orbx_keypoint)) + bx.padded(NB * 32) +
-                           bx.padded(NB * 4) + bx.padded(NB) + bx.padded(8);
-    int rc = bx.begin(inBytes, bx.padded(((size_t)nOut + 1) * 4), m->stream);
-    if (rc != ORBX_OK) return rc;
-    if ((rc = m->arena.ensure(inBytes)) != ORBX_OK) return rc;
-    uint8_t *const ar = m->arena.p;
-    auto dev = [&](const void *boxAddr) { return ar + ((const uint8_t *)boxAddr - bx.inDev); };      // the same offsets in the device arena
     const int32_t cnt[2] = {nA, nB};
-    FeatDev A, B;
-    A.kp = (const orbx_keypoint *)dev(bx.put(a->keypoints, NA)); A.desc = dev(bx.put(a->descriptors, NA * 32));
-    const void *ga = bx.put(a->groups, a->groups ? NA : 0), *va = bx.put(a->valid, a->valid ? NA : 0);
-    B.kp = (const orbx_keypoint *)dev(bx.put(b->keypoints, NB)); B.desc = dev(bx.put(b->descriptors, NB * 32));
-    const void *gb = bx.put(b->groups, b->groups ? NB : 0), *vb = bx.put(b->valid, b->valid ? NB : 0);
-    const int32_t *dc = (const int32_t *)dev(bx.put(cnt, 2));
-    A.groups = a->groups ? (const int32_t *)dev(ga) : nullptr; A.valid = a->valid ? dev(va) : nullptr; A.counts = dc; A.cap = nA;
-    B.groups = b->groups ? (const int32_t *)dev(gb) : nullptr; B.valid = b->valid ? dev(vb) : nullptr; B.counts = dc + 1; B.cap = nB;
-    const size_t n16 = bx.used / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, m->stream, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
+    auto [pin, pout] = bx.plan();
+    const auto sKpA = pin.add(a->keypoints, NA);
+    const auto sDescA = pin.add(a->descriptors, NA * 32);
+    const auto sGrA = pin.add(a->groups, a->groups ? NA : 0);
+    const auto sValA = pin.add(a->valid, a->valid ? NA : 0);
+    const auto sKpB = pin.add(b->keypoints, NB);
+    const auto sDescB = pin.add(b->descriptors, NB * 32);
+    const auto sGrB = pin.add(b->groups, b->groups ? NB : 0);
+    const auto sValB = pin.add(b->valid, b->valid ? NB : 0);
+    const auto sCnt = pin.add(cnt, 2);
+    const auto rRes = pout.hole<int32_t>((size_t)nOut + 1);
+    int rc;
+    const OrbxStaged sg = bx.begin(m->stream, &rc);
+    if (rc != ORBX_OK) return rc;
+    uint8_t *ar;      // the same offsets in the device arena
+    if ((rc = orbx_stage_to_arena(bx, m->arena, m->stream, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
+    const int32_t *dc = sCnt.in(ar);
+    FeatDev A, B;
+    A.kp = sKpA.in(ar); A.desc = sDescA.in(ar); A.groups = a->groups ? sGrA.in(ar) : nullptr; A.valid = a->valid ? sValA.in(ar) : nullptr; A.counts = dc; A.cap = nA;
+    B.kp = sKpB.in(ar); B.desc = sDescB.in(ar); B.groups = b->groups ? sGrB.in(ar) : nullptr; B.valid = b->valid ? sValB.in(ar) : nullptr; B.counts = dc + 1; B.cap = nB;
     uint32_t dcut = TH_LOW + 1;
     while (dcut < 257 && !(prm->nn_ratio * (float)dcut > (float)TH_LOW)) dcut++;
     const bool filter = b->groups != nullptr || (prm->mode == 1 && b->valid != nullptr);
@@ -1752,11 +1766,11 @@ static int search_by_bow_single(orbx_matcher *m, const orbx_feature_set *a, cons
     const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_bow_greedy, dim3(1), dim3(GREEDY_THREADS), ldsGreedy, m->stream, A, B, (const int32_t *)m->sfZero.p, (const int32_t *)m->sfZero.p, prm->mode, prm->nn_ratio,
-                       prm->check_orientation, m->topk.p, m->order.p, m->matches.p, m->dists.p, m->nmatches.p, stride, TriDev(), bx.outDev<int32_t>(0), bx.flagDev, seq);
+                       prm->check_orientation, m->topk.p, m->order.p, m->matches.p, m->dists.p, m->nmatches.p, stride, TriDev(), sg.dev(rRes), bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(m->stream)) != ORBX_OK) return rc;
-    const int32_t *res = bx.outHost<int32_t>(0);
+    const int32_t *res = sg.host(rRes);
     if (nOut > 0) memcpy(matches, res, (size_t)nOut * 4);
     *nmatches = res[nOut];
     return ORBX_OK;
@@ -1773,8 +1787,10 @@ extern "C" int orbx_search_by_bow(orbx_matcher *m, const orbx_feature_set *a_hos
         a_host->counts[0] > 0 && b_host->counts[0] > 0 && a_host->counts[0] <= m->maxFeatures && b_host->counts[0] <= std::min(m->maxFeatures, 4000))      // (B in LDS: 36 bytes per feature)
         return search_by_bow_single(m, a_host, b_host, params, matches, nmatches);
     orbx_feature_set da, db;
+    const orbx_feature_set *const hostSets[2] = {a_host, b_host};
+    orbx_feature_set *const devSets[2] = {&da, &db};
     int rc;
-    if ((rc = stage_host(m, 0, a_host, &da)) != ORBX_OK || (rc = stage_host(m, 1, b_host, &db)) != ORBX_OK) return rc;
+    if ((rc = stage_host(m, hostSets, devSets, 2)) != ORBX_OK) return rc;
     const int32_t zero = 0;
     if ((rc = orbx_search_by_bow_device(m, &da, &db, &zero, &zero, 1, params, nullptr)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -1832,8 +1848,10 @@ extern "C" int orbx_search_for_triangulation(orbx_matcher *m, const orbx_feature
     if (!m || !params_host || !matches12 || !nmatches) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
     ORBX_HIP_CHECK(hipSetDevice(m->device));
     orbx_feature_set da, db;
+    const orbx_feature_set *const hostSets[2] = {a_host, b_host};
+    orbx_feature_set *const devSets[2] = {&da, &db};
     int rc;
-    if ((rc = stage_host(m, 0, a_host, &da)) != ORBX_OK || (rc = stage_host(m, 1, b_host, &db)) != ORBX_OK) return rc;
+    if ((rc = stage_host(m, hostSets, devSets, 2)) != ORBX_OK) return rc;
     orbx_triangulation_params P = *params_host;
     const uint8_t *hostFlags[2] = {params_host->stereo_a, params_host->stereo_b};
     const int cnt[2] = {a_host->counts[0], b_host->counts[0]};
@@ -1859,8 +1877,10 @@ extern "C" int orbx_stereo_match(orbx_matcher *m, const orbx_feature_set *left_h
     if (!m || !best_dist || !best_idx) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
     ORBX_HIP_CHECK(hipSetDevice(m->device));
     orbx_feature_set dl, dr;
+    const orbx_feature_set *const hostSets[2] = {left_host, right_host};
+    orbx_feature_set *const devSets[2] = {&dl, &dr};
     int rc;
-    if ((rc = stage_host(m, 0, left_host, &dl)) != ORBX_OK || (rc = stage_host(m, 1, right_host, &dr)) != ORBX_OK) return rc;
+    if ((rc = stage_host(m, hostSets, devSets, 2)) != ORBX_OK) return rc;
     const int32_t zero = 0;
     if ((rc = orbx_stereo_match_device(m, &dl, &dr, &zero, &zero, 1, scale_factors, nlevels, max_disparity, nullptr)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));

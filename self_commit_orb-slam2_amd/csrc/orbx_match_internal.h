@@ -194,8 +194,8 @@ int chain_back(orbx_matcher *m, orbx_extractor *after);
 int inherit_status(orbx_matcher *m, orbx_extractor *after, bool first = true);
 int check_producer_status(orbx_matcher *m);
 FeatDev to_dev(const orbx_feature_set *s);
-/* stage one frame of host features into the matcher's staging buffers (side 0 / 1) */
-int stage_host(orbx_matcher *m, int side, const orbx_feature_set *h, orbx_feature_set *d);
+/* stage one frame of host features per side (nsides = 1 or 2) into the matcher's staging buffer; d[side] receives the device view */
+int stage_host(orbx_matcher *m, const orbx_feature_set *const *h, orbx_feature_set *const *d, int nsides);
 }  // namespace orbx_match
 
 #endif

@@ -1194,8 +1194,9 @@ extern "C" int orbx_search_for_initialization(orbx_matcher *m, const orbx_featur
     if (n2 > m->maxFeatures) { orbx_set_error("%d features exceed the matcher's max_features %d", n2, m->maxFeatures); return ORBX_ERR_CAPACITY; }
     ORBX_HIP_CHECK(hipSetDevice(m->device));
     orbx_feature_set d1;
+    orbx_feature_set *const devSet = &d1;
     int rc;
-    if ((rc = stage_host(m, 0, f1_host, &d1)) != ORBX_OK) return rc;
+    if ((rc = stage_host(m, &f1_host, &devSet, 1)) != ORBX_OK) return rc;
     if ((rc = m->pkp.ensure((size_t)n2)) || (rc = m->hd[1].ensure((size_t)n2 * 32)) || (rc = m->pi32[0].ensure(2)) || (rc = m->pf[1].ensure((size_t)m->maxFeatures * 2)))
         return rc;
     hipStream_t st = m->stream;
@@ -1275,32 +1276,34 @@ extern "C" int orbx_search_by_projection(orbx_matcher *m, const orbx_projection_
     hipStream_t st = m->stream;
     OrbxCallBox &bx = m->box;
     const size_t N = (size_t)n, M = (size_t)mm;
-    const size_t total = bx.padded(N * sizeof(orbx_keypoint)) + bx.padded(N * 32) + bx.padded(N * 4) + bx.padded(N) + bx.padded(8) + 5 * bx.padded(M * 4) +
-                         bx.padded(M * 32) + 2 * bx.padded(M) + bx.padded(64 * 4);
     if (!scale_factors || nlevels < 1 || nlevels > 64) { orbx_set_error("bad scale factor table"); return ORBX_ERR_ARG; }
     if (!fr->keypoints_un || !fr->descriptors || !fr->u_right || !pt->proj_x || !pt->proj_y || !pt->proj_xr || !pt->scale_level || !pt->view_cos || !pt->in_view || !pt->descriptors) {
         orbx_set_error("NULL array in the projection arguments");
         return ORBX_ERR_ARG;
     }
-    if ((rc = bx.begin(total, bx.padded((N + 1) * 4), st)) != ORBX_OK) return rc;
     const int32_t cnt[2] = {n, mm};
-    const void *bKp = bx.put(fr->keypoints_un, N), *bDesc = bx.put(fr->descriptors, N * 32), *bUr = bx.put(fr->u_right, N), *bOcc = bx.put(fr->occupied, fr->occupied ? N : 0);
-    const void *bCnt = bx.put(cnt, 2);
-    const void *bPx = bx.put(pt->proj_x, M), *bPy = bx.put(pt->proj_y, M), *bPxr = bx.put(pt->proj_xr, M), *bCos = bx.put(pt->view_cos, M), *bLvl = bx.put(pt->scale_level, M);
-    const void *bPd = bx.put(pt->descriptors, M * 32), *bIn = bx.put(pt->in_view, M), *bObs = bx.put(pt->has_observations, pt->has_observations ? M : 0);
-    const void *bSc = bx.put(scale_factors, (size_t)nlevels);
-    if ((rc = m->arena.ensure(bx.used)) != ORBX_OK) return rc;
-    uint8_t *const ar = m->arena.p;
-    auto dev = [&](const void *boxAddr) { return ar + ((const uint8_t *)boxAddr - bx.inDev); };
-    const size_t n16 = bx.used / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, st, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
+    auto [pin, pout] = bx.plan();
+    const auto sKp = pin.add(fr->keypoints_un, N);
+    const auto sDesc = pin.add(fr->descriptors, N * 32);
+    const auto sUr = pin.add(fr->u_right, N);
+    const auto sOcc = pin.add(fr->occupied, fr->occupied ? N : 0);
+    const auto sCnt = pin.add(cnt, 2);
+    const auto sPx = pin.add(pt->proj_x, M), sPy = pin.add(pt->proj_y, M), sPxr = pin.add(pt->proj_xr, M), sCos = pin.add(pt->view_cos, M);
+    const auto sLvl = pin.add(pt->scale_level, M);
+    const auto sPd = pin.add(pt->descriptors, M * 32), sIn = pin.add(pt->in_view, M), sObs = pin.add(pt->has_observations, pt->has_observations ? M : 0);
+    const auto sSc = pin.add(scale_factors, (size_t)nlevels);
+    const auto rAs = pout.hole<int32_t>(N + 1);
+    const OrbxStaged sg = bx.begin(st, &rc);
+    if (rc != ORBX_OK) return rc;
+    uint8_t *ar;
+    if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
-    const int32_t *dCnt = (const int32_t *)dev(bCnt);
-    const float *dScales = (const float *)dev(bSc);
-    ProjFrameDev F = {(const orbx_keypoint *)dev(bKp), dev(bDesc), (const float *)dev(bUr), fr->occupied ? dev(bOcc) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
+    const int32_t *dCnt = sCnt.in(ar);
+    const float *dScales = sSc.in(ar);
+    ProjFrameDev F = {sKp.in(ar), sDesc.in(ar), sUr.in(ar), fr->occupied ? sOcc.in(ar) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
                       fr->grid_height_inv};
-    ProjPointsDev P = {(const float *)dev(bPx), (const float *)dev(bPy), (const float *)dev(bPxr), (const int32_t *)dev(bLvl), (const float *)dev(bCos), dev(bIn),
-                       pt->has_observations ? dev(bObs) : nullptr, dev(bPd), dCnt + 1, mm};
+    ProjPointsDev P = {sPx.in(ar), sPy.in(ar), sPxr.in(ar), sLvl.in(ar), sCos.in(ar), sIn.in(ar),
+                       pt->has_observations ? sObs.in(ar) : nullptr, sPd.in(ar), dCnt + 1, mm};
     if ((rc = m->topk64.ensure(M * TOPK)) != ORBX_OK || (rc = m->projDec.ensure(M)) != ORBX_OK || (rc = m->projQueue.ensure(M)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_proj_topk, dim3((unsigned)((mm + 3) / 4), 1u), dim3(256), 0, st, F, P, dScales, th, m->topk64.p);
     ORBX_LAUNCH_CHECK();
@@ -1312,11 +1315,11 @@ extern "C" int orbx_search_by_projection(orbx_matcher *m, const orbx_projection_
     const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_proj_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, P, dScales, th, nn_ratio, m->topk64.p, m->matches.p, m->nmatches.p, stride, m->projDec.p,
-                       m->projQueue.p, bx.outDev<int32_t>(0), bx.flagDev, seq, decLds);
+                       m->projQueue.p, sg.dev(rAs), bx.flagDev, seq, decLds);
     ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
-    const int32_t *as = bx.outHost<int32_t>(0);
+    const int32_t *as = sg.host(rAs);
     memcpy(assigned, as, N * 4);
     if (nmatches) *nmatches = as[n];
     return ORBX_OK;
@@ -1386,28 +1389,31 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
     hipStream_t st = m->stream;
     OrbxCallBox &bx = m->box;
     const size_t N = (size_t)n, NL = (size_t)nl;
-    const size_t inBytes = bx.padded(N * sizeof(orbx_keypoint)) + bx.padded(N * 32) + bx.padded(N * 4) + bx.padded(N) + bx.padded(8) + bx.padded(NL * 12) + bx.padded(NL * 4) + 2 * bx.padded(64) +
-                           bx.padded(NL * 4) + bx.padded(NL * 32) + 2 * bx.padded(NL) + bx.padded(64 * 4);
     if (!scale_factors || nlevels < 1 || nlevels > 64) { orbx_set_error("bad scale factor table"); return ORBX_ERR_ARG; }
     if (nl > 65535) { orbx_set_error("bad capacities (features %d, last %d)", n, nl); return ORBX_ERR_CAPACITY; }
-    if ((rc = bx.begin(inBytes, bx.padded((N + 1) * 4), st)) != ORBX_OK) return rc;
     const int32_t cnt[2] = {n, nl};
-    const void *bKp = bx.put(fr->keypoints_un, N), *bDesc = bx.put(fr->descriptors, N * 32), *bUr = bx.put(fr->u_right, N), *bOcc = bx.put(fr->occupied, fr->occupied ? N : 0);
-    const void *bCnt = bx.put(cnt, 2), *bPos = bx.put(ls->world_pos, NL * 3), *bAng = bx.put(ls->angle, NL), *bTc = bx.put(ls->tcw_current, 16), *bTl = bx.put(ls->tcw_last, 16);
-    const void *bOct = bx.put(ls->octave, NL), *bLd = bx.put(ls->descriptors, NL * 32), *bVal = bx.put(ls->valid, NL), *bObs = bx.put(ls->has_observations, ls->has_observations ? NL : 0);
-    const void *bSc = bx.put(scale_factors, (size_t)nlevels);
-    if ((rc = m->arena.ensure(bx.used)) != ORBX_OK) return rc;
-    uint8_t *const ar = m->arena.p;
-    auto dev = [&](const void *boxAddr) { return ar + ((const uint8_t *)boxAddr - bx.inDev); };
-    const size_t n16 = bx.used / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, st, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
+    auto [pin, pout] = bx.plan();
+    const auto sKp = pin.add(fr->keypoints_un, N);
+    const auto sDesc = pin.add(fr->descriptors, N * 32);
+    const auto sUr = pin.add(fr->u_right, N);
+    const auto sOcc = pin.add(fr->occupied, fr->occupied ? N : 0);
+    const auto sCnt = pin.add(cnt, 2);
+    const auto sPos = pin.add(ls->world_pos, NL * 3), sAng = pin.add(ls->angle, NL), sTc = pin.add(ls->tcw_current, 16), sTl = pin.add(ls->tcw_last, 16);
+    const auto sOct = pin.add(ls->octave, NL);
+    const auto sLd = pin.add(ls->descriptors, NL * 32), sVal = pin.add(ls->valid, NL), sObs = pin.add(ls->has_observations, ls->has_observations ? NL : 0);
+    const auto sSc = pin.add(scale_factors, (size_t)nlevels);
+    const auto rAs = pout.hole<int32_t>(N + 1);
+    const OrbxStaged sg = bx.begin(st, &rc);
+    if (rc != ORBX_OK) return rc;
+    uint8_t *ar;
+    if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
-    const int32_t *dCnt = (const int32_t *)dev(bCnt);
-    const float *dScales = (const float *)dev(bSc);
-    ProjFrameDev F = {(const orbx_keypoint *)dev(bKp), dev(bDesc), (const float *)dev(bUr), fr->occupied ? dev(bOcc) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
+    const int32_t *dCnt = sCnt.in(ar);
+    const float *dScales = sSc.in(ar);
+    ProjFrameDev F = {sKp.in(ar), sDesc.in(ar), sUr.in(ar), fr->occupied ? sOcc.in(ar) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
                       fr->grid_height_inv};
-    ProjLastDev L = {dev(bVal), (const float *)dev(bPos), dev(bLd), ls->has_observations ? dev(bObs) : nullptr, (const int32_t *)dev(bOct), (const float *)dev(bAng), dCnt + 1, nl,
-                     (const float *)dev(bTc), (const float *)dev(bTl), ls->fx, ls->fy, ls->cx, ls->cy, ls->mbf, ls->mb, ls->max_x, ls->max_y};
+    ProjLastDev L = {sVal.in(ar), sPos.in(ar), sLd.in(ar), ls->has_observations ? sObs.in(ar) : nullptr, sOct.in(ar), sAng.in(ar), dCnt + 1, nl,
+                     sTc.in(ar), sTl.in(ar), ls->fx, ls->fy, ls->cx, ls->cy, ls->mbf, ls->mb, ls->max_x, ls->max_y};
     if ((rc = m->topk64.ensure(NL * TOPK)) != ORBX_OK || (rc = m->projDec.ensure(NL)) != ORBX_OK || (rc = m->projQueue.ensure(NL)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((nl + 3) / 4), 1u), dim3(256), 0, st, F, L, dScales, th, b_mono, m->topk64.p);
     ORBX_LAUNCH_CHECK();
@@ -1417,11 +1423,11 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
     const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_proj_last_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, L, dScales, th, b_mono, check_orientation, m->topk64.p, m->matches.p, m->nmatches.p, stride,
-                       m->projDec.p, m->projQueue.p, bx.outDev<int32_t>(0), bx.flagDev, seq);
+                       m->projDec.p, m->projQueue.p, sg.dev(rAs), bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
-    const int32_t *as = bx.outHost<int32_t>(0);
+    const int32_t *as = sg.host(rAs);
     memcpy(assigned, as, N * 4);
     if (nmatches) *nmatches = as[n];
     return ORBX_OK;
@@ -1623,28 +1629,35 @@ extern "C" int orbx_is_in_frustum(orbx_matcher *m, const orbx_frustum_frame *fra
     hipStream_t st = m->stream;
     OrbxCallBox &bx = m->box;
     const size_t n = (size_t)mm;
-    const size_t inBytes = bx.padded(64) + 2 * bx.padded(n * 12) + 2 * bx.padded(n * 4) + bx.padded(4);
-    const size_t oY = bx.padded(n * 4), oXr = 2 * oY, oVc = 3 * oY, oL = 4 * oY, oIn = oL + bx.padded(n * 4), outBytes = oIn + bx.padded(n);
-    if ((rc = bx.begin(inBytes, outBytes, st)) != ORBX_OK) return rc;
     const int32_t cnt = mm;
+    auto [pin, pout] = bx.plan();
+    const auto sTcw = pin.add(frame_host->tcw, 16);
+    const auto sPos = pin.add(points_host->world_pos, n * 3), sNrm = pin.add(points_host->normal, n * 3);
+    const auto sMax = pin.add(points_host->max_distance, n), sMin = pin.add(points_host->min_distance, n);
+    const auto sCnt = pin.add(&cnt, 1);
+    const auto rX = pout.hole<float>(n), rY = pout.hole<float>(n), rXr = pout.hole<float>(n), rVc = pout.hole<float>(n);
+    const auto rL = pout.hole<int32_t>(n);
+    const auto rIn = pout.hole<uint8_t>(n);
+    const OrbxStaged sg = bx.begin(st, &rc);
+    if (rc != ORBX_OK) return rc;
     FrustumDev Fr;
-    Fr.tcw = bx.put(frame_host->tcw, 16);
+    Fr.tcw = sg.dev(sTcw);
     Fr.fx = frame_host->fx; Fr.fy = frame_host->fy; Fr.cx = frame_host->cx; Fr.cy = frame_host->cy; Fr.mbf = frame_host->mbf;
     Fr.minX = frame_host->min_x; Fr.maxX = frame_host->max_x; Fr.minY = frame_host->min_y; Fr.maxY = frame_host->max_y; Fr.cosLimit = viewing_cos_limit; Fr.nlevels = frame_host->nlevels;
     for (int k = 0; k < ORBX_MAX_LEVELS; k++) Fr.ratioTh[k] = k + 1 < frame_host->nlevels ? frame_host->ratio_thresholds[k] : 0.0f;
     MapPointsDev M;
-    M.pos = bx.put(points_host->world_pos, n * 3); M.normal = bx.put(points_host->normal, n * 3);
-    M.maxDist = bx.put(points_host->max_distance, n); M.minDist = bx.put(points_host->min_distance, n);
-    M.counts = bx.put(&cnt, 1); M.cap = mm;
+    M.pos = sg.dev(sPos); M.normal = sg.dev(sNrm);
+    M.maxDist = sg.dev(sMax); M.minDist = sg.dev(sMin);
+    M.counts = sg.dev(sCnt); M.cap = mm;
     const unsigned long long seq = bx.arm();
-    hipLaunchKernelGGL(k_is_in_frustum, dim3((unsigned)((mm + 255) / 256), 1u), dim3(256), 0, st, Fr, M, bx.outDev<float>(0), bx.outDev<float>(oY), bx.outDev<float>(oXr), bx.outDev<int32_t>(oL),
-                       bx.outDev<float>(oVc), bx.outDev<uint8_t>(oIn), bx.counter, bx.flagDev, seq);
+    hipLaunchKernelGGL(k_is_in_frustum, dim3((unsigned)((mm + 255) / 256), 1u), dim3(256), 0, st, Fr, M, sg.dev(rX), sg.dev(rY), sg.dev(rXr), sg.dev(rL),
+                       sg.dev(rVc), sg.dev(rIn), bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
-    memcpy(in_view, bx.outHost<uint8_t>(oIn), n);
+    memcpy(in_view, sg.host(rIn), n);
     // (the mTrack* values of a point that is not in view are not written by the kernel: the caller's arrays keep what they held, as the reference's members do)
-    const float *hx = bx.outHost<float>(0), *hy = bx.outHost<float>(oY), *hxr = bx.outHost<float>(oXr), *hvc = bx.outHost<float>(oVc);
-    const int32_t *hl = bx.outHost<int32_t>(oL);
+    const float *hx = sg.host(rX), *hy = sg.host(rY), *hxr = sg.host(rXr), *hvc = sg.host(rVc);
+    const int32_t *hl = sg.host(rL);
     for (int k = 0; k < mm; k++)
         if (in_view[k]) {
             if (proj_x) proj_x[k] = hx[k];
@@ -1691,43 +1704,45 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
     hipStream_t st = m->stream;
     OrbxCallBox &bx = m->box;
     const size_t N = (size_t)n, M = (size_t)mm;
-    const size_t inBytes = bx.padded(N * sizeof(orbx_keypoint)) + bx.padded(N * 32) + bx.padded(N * 4) + bx.padded(N) + bx.padded(8) + bx.padded(64) + bx.padded(M) + bx.padded(64 * 4) +
-                           2 * bx.padded(M * 12) + 2 * bx.padded(M * 4) + bx.padded(M * 32);
-    const size_t offPy = bx.padded(M * 4), offPxr = 2 * offPy, offVc = 3 * offPy, offLvl = 4 * offPy, offIn = offLvl + bx.padded(M * 4), offAs = offIn + bx.padded(M),
-                 outBytes = offAs + bx.padded((N + 1) * 4);
-    if ((rc = bx.begin(inBytes, outBytes, st)) != ORBX_OK) return rc;
     const int32_t cnt[2] = {n, mm};
-    // --- staged part (first in the buffer)
-    const void *bKp = bx.put(fr->keypoints_un, N), *bDesc = bx.put(fr->descriptors, N * 32), *bUr = bx.put(fr->u_right, N), *bOcc = bx.put(fr->occupied, fr->occupied ? N : 0);
-    const void *bCnt = bx.put(cnt, 2), *bTcw = bx.put(pose->tcw, 16), *bObs = bx.put(pt->has_observations, pt->has_observations ? M : 0), *bSc = bx.put(scale_factors, (size_t)nlevels);
-    const float *bPos = bx.put(pt->world_pos, M * 3), *bNrm = bx.put(pt->normal, M * 3), *bMax = bx.put(pt->max_distance, M), *bMin = bx.put(pt->min_distance, M);
-    const uint8_t *bPd = bx.put(pt->descriptors, M * 32);
-    const size_t staged = bx.used;
-    if ((rc = m->arena.ensure(staged)) != ORBX_OK) return rc;
-    uint8_t *const ar = m->arena.p;
-    auto dev = [&](const void *boxAddr) { return ar + ((const uint8_t *)boxAddr - bx.inDev); };
-    const float *zPos = (const float *)dev(bPos), *zNrm = (const float *)dev(bNrm), *zMax = (const float *)dev(bMax), *zMin = (const float *)dev(bMin);
-    const uint8_t *zDesc = dev(bPd);
-    const size_t n16 = staged / 16;
-    hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, st, (const uint4 *)bx.inDev, (uint4 *)ar, n16);
+    auto [pin, pout] = bx.plan();
+    const auto sKp = pin.add(fr->keypoints_un, N);
+    const auto sDesc = pin.add(fr->descriptors, N * 32);
+    const auto sUr = pin.add(fr->u_right, N);
+    const auto sOcc = pin.add(fr->occupied, fr->occupied ? N : 0);
+    const auto sCnt = pin.add(cnt, 2);
+    const auto sTcw = pin.add(pose->tcw, 16);
+    const auto sObs = pin.add(pt->has_observations, pt->has_observations ? M : 0);
+    const auto sSc = pin.add(scale_factors, (size_t)nlevels);
+    const auto sPos = pin.add(pt->world_pos, M * 3), sNrm = pin.add(pt->normal, M * 3), sMax = pin.add(pt->max_distance, M), sMin = pin.add(pt->min_distance, M);
+    const auto sPd = pin.add(pt->descriptors, M * 32);
+    const auto rPx = pout.hole<float>(M), rPy = pout.hole<float>(M), rPxr = pout.hole<float>(M), rVc = pout.hole<float>(M);
+    const auto rLvl = pout.hole<int32_t>(M);
+    const auto rIn = pout.hole<uint8_t>(M);
+    const auto rAs = pout.hole<int32_t>(N + 1);
+    const OrbxStaged sg = bx.begin(st, &rc);
+    if (rc != ORBX_OK) return rc;
+    uint8_t *ar;
+    if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
+    const uint8_t *zDesc = sPd.in(ar);
     if ((rc = m->frProj.ensure(4 * M)) || (rc = m->frLevel.ensure(M)) || (rc = m->frInView.ensure(M)) || (rc = m->topk64.ensure(M * TOPK)) || (rc = m->projDec.ensure(M)) ||
         (rc = m->projQueue.ensure(M))) return rc;
-    const int32_t *dCnt = (const int32_t *)dev(bCnt);
+    const int32_t *dCnt = sCnt.in(ar);
     FrustumDev Fr;
-    Fr.tcw = (const float *)dev(bTcw); Fr.fx = pose->fx; Fr.fy = pose->fy; Fr.cx = pose->cx; Fr.cy = pose->cy; Fr.mbf = pose->mbf;
+    Fr.tcw = sTcw.in(ar); Fr.fx = pose->fx; Fr.fy = pose->fy; Fr.cx = pose->cx; Fr.cy = pose->cy; Fr.mbf = pose->mbf;
     Fr.minX = pose->min_x; Fr.maxX = pose->max_x; Fr.minY = pose->min_y; Fr.maxY = pose->max_y; Fr.cosLimit = viewing_cos_limit; Fr.nlevels = pose->nlevels;
     for (int k = 0; k < ORBX_MAX_LEVELS; k++) Fr.ratioTh[k] = k + 1 < pose->nlevels ? pose->ratio_thresholds[k] : 0.0f;
-    MapPointsDev Mp = {zPos, zNrm, zMax, zMin, dCnt + 1, mm};
-    ProjFrameDev F = {(const orbx_keypoint *)dev(bKp), dev(bDesc), (const float *)dev(bUr), fr->occupied ? dev(bOcc) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
+    MapPointsDev Mp = {sPos.in(ar), sNrm.in(ar), sMax.in(ar), sMin.in(ar), dCnt + 1, mm};
+    ProjFrameDev F = {sKp.in(ar), sDesc.in(ar), sUr.in(ar), fr->occupied ? sOcc.in(ar) : nullptr, dCnt, n, fr->min_x, fr->min_y, fr->grid_width_inv,
                       fr->grid_height_inv};
-    const float *dScales = (const float *)dev(bSc);
-    FrustumHostOut Ho = {bx.outDev<float>(0), bx.outDev<float>(offPy), bx.outDev<float>(offPxr), bx.outDev<float>(offVc), bx.outDev<int32_t>(offLvl), bx.outDev<uint8_t>(offIn)};
+    const float *dScales = sSc.in(ar);
+    FrustumHostOut Ho = {sg.dev(rPx), sg.dev(rPy), sg.dev(rPxr), sg.dev(rVc), sg.dev(rLvl), sg.dev(rIn)};
     hipLaunchKernelGGL(k_frustum_topk, dim3((unsigned)((mm + 3) / 4)), dim3(256), 0, st, Fr, Mp, F, zDesc, dScales, th, m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p,
                        m->frProj.p + 3 * M, m->frInView.p, Ho, m->topk64.p);
     ORBX_LAUNCH_CHECK();
     m->frCount = M;
-    ProjPointsDev P = {m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p, m->frProj.p + 3 * M, m->frInView.p, pt->has_observations ? dev(bObs) : nullptr, zDesc, dCnt + 1, mm};
+    ProjPointsDev P = {m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p, m->frProj.p + 3 * M, m->frInView.p, pt->has_observations ? sObs.in(ar) : nullptr, zDesc, dCnt + 1, mm};
     size_t lds = (size_t)n * 6 + 16;
     if (lds > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile of the projection replay", n); return ORBX_ERR_CAPACITY; }
     int decLds = 0;      // dec[mm] + the observation flags behind the feature tile, when they fit (k_proj_greedy)
@@ -1736,14 +1751,14 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
     const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_proj_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, P, dScales, th, nn_ratio, m->topk64.p, m->matches.p, m->nmatches.p, stride, m->projDec.p,
-                       m->projQueue.p, bx.outDev<int32_t>(offAs), bx.flagDev, seq, decLds);
+                       m->projQueue.p, sg.dev(rAs), bx.flagDev, seq, decLds);
     ORBX_LAUNCH_CHECK();
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
-    memcpy(in_view, bx.outHost<uint8_t>(offIn), M);
+    memcpy(in_view, sg.host(rIn), M);
     // (the mTrack* values of a point that is not in view are not written by the kernel: the caller's arrays keep what they held, as with the reference's members)
-    const float *hx = bx.outHost<float>(0), *hy = bx.outHost<float>(offPy), *hxr = bx.outHost<float>(offPxr), *hvc = bx.outHost<float>(offVc);
-    const int32_t *hl = bx.outHost<int32_t>(offLvl);
+    const float *hx = sg.host(rPx), *hy = sg.host(rPy), *hxr = sg.host(rPxr), *hvc = sg.host(rVc);
+    const int32_t *hl = sg.host(rLvl);
     for (int k = 0; k < mm; k++)
         if (in_view[k]) {
             if (proj_x) proj_x[k] = hx[k];
@@ -1752,7 +1767,7 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
             if (view_cos) view_cos[k] = hvc[k];
             if (scale_level) scale_level[k] = hl[k];
         }
-    const int32_t *as = bx.outHost<int32_t>(offAs);
+    const int32_t *as = sg.host(rAs);
     memcpy(assigned, as, N * 4);
     if (nmatches) *nmatches = as[n];
     return ORBX_OK;

@@ -518,7 +518,8 @@ int os_check_problem(const orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *
 }
 
 // headers + arrays of `np` problems into the mapped input buffer; offs[c] = the problem's result block (lin: OsLinBlock)
-int os_stage(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *Ps, int np, bool lin, const uint8_t *active, std::vector<OsProb> &probs, OsIn &I)
+struct OsStaged { OrbxStaged sg; OrbxSlot<uint8_t, ORBX_STAGE_OUT> res; };      // res: the problems' result blocks
+OsStaged os_stage(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *Ps, int np, bool lin, const uint8_t *active, std::vector<OsProb> &probs, OsIn &I, int *rc)
 {
     size_t totN = 0, off = 0;
     probs.assign((size_t)np, OsProb());
@@ -532,38 +533,40 @@ int os_stage(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *Ps, int np, bo
         totN += (size_t)P.n;
         off += lin ? OsLinBlock(P.n).total : OsBlock(P.n).total;
     }
-    auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
-    const size_t oProb = 0, oW1 = padded(sizeof(OsProb) * (size_t)np), oW2 = oW1 + padded(totN * 12), oO1 = oW2 + padded(totN * 12), oO2 = oO1 + padded(totN * 8),
-                 oI1 = oO2 + padded(totN * 8), oI2 = oI1 + padded(totN * 4), oAct = oI2 + padded(totN * 4), total = oAct + padded(active ? totN : 0);
-    int rc;
     OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(total, off, h->stream)) != ORBX_OK) return rc;
-    memcpy(bx.in + oProb, probs.data(), sizeof(OsProb) * (size_t)np);
+    auto [pin, pout] = bx.plan();
+    // the problems' arrays lie concatenated, problem c's at element mb of its region: holes, filled below
+    const auto sProb = pin.add(probs.data(), (size_t)np);
+    const auto sW1 = pin.hole<float>(totN * 3), sW2 = pin.hole<float>(totN * 3), sO1 = pin.hole<float>(totN * 2), sO2 = pin.hole<float>(totN * 2);
+    const auto sI1 = pin.hole<float>(totN), sI2 = pin.hole<float>(totN);
+    const auto sAct = pin.hole<uint8_t>(active ? totN : 0);
+    const auto rRes = pout.hole<uint8_t>(off);
+    const OsStaged S = {bx.begin(h->stream, rc), rRes};
+    if (*rc != ORBX_OK) return S;
     for (int c = 0; c < np; c++) {
         const orbx_sim3_opt_problem &P = Ps[c];
         const size_t n = (size_t)P.n, mb = (size_t)probs[c].mb;
-        if (!n) continue;
-        memcpy(bx.in + oW1 + 12 * mb, P.world1, 12 * n); memcpy(bx.in + oW2 + 12 * mb, P.world2, 12 * n);
-        memcpy(bx.in + oO1 + 8 * mb, P.obs1, 8 * n); memcpy(bx.in + oO2 + 8 * mb, P.obs2, 8 * n);
-        memcpy(bx.in + oI1 + 4 * mb, P.inv_sigma2_1, 4 * n); memcpy(bx.in + oI2 + 4 * mb, P.inv_sigma2_2, 4 * n);
-        if (active) memcpy(bx.in + oAct + mb, active, n);
+        orbx_put_at(S.sg, sW1, 3 * mb, P.world1, 3 * n); orbx_put_at(S.sg, sW2, 3 * mb, P.world2, 3 * n);
+        orbx_put_at(S.sg, sO1, 2 * mb, P.obs1, 2 * n); orbx_put_at(S.sg, sO2, 2 * mb, P.obs2, 2 * n);
+        orbx_put_at(S.sg, sI1, mb, P.inv_sigma2_1, n); orbx_put_at(S.sg, sI2, mb, P.inv_sigma2_2, n);
+        if (active) orbx_put_at(S.sg, sAct, mb, active, n);
     }
-    I.prob = (const OsProb *)(bx.inDev + oProb);
-    I.world1 = (const float *)(bx.inDev + oW1); I.world2 = (const float *)(bx.inDev + oW2);
-    I.obs1 = (const float *)(bx.inDev + oO1); I.obs2 = (const float *)(bx.inDev + oO2);
-    I.inv1 = (const float *)(bx.inDev + oI1); I.inv2 = (const float *)(bx.inDev + oI2);
-    I.active = active ? bx.inDev + oAct : nullptr;
+    I.prob = S.sg.dev(sProb);
+    I.world1 = S.sg.dev(sW1); I.world2 = S.sg.dev(sW2);
+    I.obs1 = S.sg.dev(sO1); I.obs2 = S.sg.dev(sO2);
+    I.inv1 = S.sg.dev(sI1); I.inv2 = S.sg.dev(sI2);
+    I.active = active ? S.sg.dev(sAct) : nullptr;
     memset(&I.lin, 0, sizeof(I.lin));
-    return ORBX_OK;
+    return S;
 }
 
-template <bool LIN> void os_launch(orbx_sim3_optimizer *h, int maxN, int np, const OsIn &I, unsigned long long seq)
+template <bool LIN> void os_launch(orbx_sim3_optimizer *h, int maxN, int np, const OsIn &I, uint8_t *res, unsigned long long seq)
 {
     OrbxCallBox &bx = h->box;
     const dim3 g((unsigned)np), b(OS_THREADS);
-    if (maxN <= OS_THREADS) hipLaunchKernelGGL((k_optsim3<1, LIN>), g, b, 0, h->stream, I, bx.outDevP, bx.counter, bx.flagDev, seq);
-    else if (maxN <= 2 * OS_THREADS) hipLaunchKernelGGL((k_optsim3<2, LIN>), g, b, 0, h->stream, I, bx.outDevP, bx.counter, bx.flagDev, seq);
-    else hipLaunchKernelGGL((k_optsim3<4, LIN>), g, b, 0, h->stream, I, bx.outDevP, bx.counter, bx.flagDev, seq);
+    if (maxN <= OS_THREADS) hipLaunchKernelGGL((k_optsim3<1, LIN>), g, b, 0, h->stream, I, res, bx.counter, bx.flagDev, seq);
+    else if (maxN <= 2 * OS_THREADS) hipLaunchKernelGGL((k_optsim3<2, LIN>), g, b, 0, h->stream, I, res, bx.counter, bx.flagDev, seq);
+    else hipLaunchKernelGGL((k_optsim3<4, LIN>), g, b, 0, h->stream, I, res, bx.counter, bx.flagDev, seq);
 }
 }  // namespace
 
@@ -596,11 +599,12 @@ extern "C" int orbx_optimize_sim3(orbx_sim3_optimizer *h, const orbx_sim3_opt_pr
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     std::vector<OsProb> probs;
     OsIn I;
-    if ((rc = os_stage(h, Ps, np, false, nullptr, probs, I)) != ORBX_OK) return rc;
+    const OsStaged S = os_stage(h, Ps, np, false, nullptr, probs, I, &rc);
+    if (rc != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
     const unsigned long long seq = bx.arm();
     if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    os_launch<false>(h, maxN, np, I, seq);
+    os_launch<false>(h, maxN, np, I, S.sg.dev(S.res), seq);
     ORBX_LAUNCH_COUNT(h->timer);
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
@@ -609,7 +613,7 @@ extern "C" int orbx_optimize_sim3(orbx_sim3_optimizer *h, const orbx_sim3_opt_pr
         const orbx_sim3_opt_result &R = Rs[c];
         const size_t n = (size_t)probs[c].n;
         const OsBlock B(probs[c].n);
-        const uint8_t *blk = bx.out + probs[c].outOff;
+        const uint8_t *blk = S.sg.host(S.res) + probs[c].outOff;
         const int32_t *head = (const int32_t *)blk;
         const double *est = (const double *)(blk + B.est);
         if (R.n_inliers) *R.n_inliers = head[0];
@@ -639,22 +643,24 @@ extern "C" int orbx_optimize_sim3_linearize(orbx_sim3_optimizer *h, const orbx_s
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     std::vector<OsProb> probs;
     OsIn I;
-    if ((rc = os_stage(h, P, 1, true, P->n > 0 ? active : nullptr, probs, I)) != ORBX_OK) return rc;
+    const OsStaged S = os_stage(h, P, 1, true, P->n > 0 ? active : nullptr, probs, I, &rc);
+    if (rc != ORBX_OK) return rc;
     for (int j = 0; j < 4; j++) I.lin.q[j] = quat[j];
     for (int j = 0; j < 3; j++) I.lin.t[j] = t[j];
     I.lin.s = s;
     OrbxCallBox &bx = h->box;
     const unsigned long long seq = bx.arm();
-    os_launch<true>(h, P->n, 1, I, seq);
+    os_launch<true>(h, P->n, 1, I, S.sg.dev(S.res), seq);
     ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     const size_t n = (size_t)P->n;
     const OsLinBlock B(P->n);
-    if (errors && n) memcpy(errors, bx.out + B.err, 32 * n);
-    if (chi2 && n) memcpy(chi2, bx.out + B.chi, 16 * n);
-    if (jac && n) memcpy(jac, bx.out + B.jac, 224 * n);
-    if (H) memcpy(H, bx.out + B.H, 49 * 8);
-    if (b) memcpy(b, bx.out + B.b, 56);
+    const uint8_t *blk = S.sg.host(S.res);
+    if (errors && n) memcpy(errors, blk + B.err, 32 * n);
+    if (chi2 && n) memcpy(chi2, blk + B.chi, 16 * n);
+    if (jac && n) memcpy(jac, blk + B.jac, 224 * n);
+    if (H) memcpy(H, blk + B.H, 49 * 8);
+    if (b) memcpy(b, blk + B.b, 56);
     return ORBX_OK;
 }
 

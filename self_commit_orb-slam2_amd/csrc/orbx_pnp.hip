@@ -870,7 +870,7 @@ PnpParams ransac_parameters(double probability, int minInliers, int maxIteration
     return o;
 }
 
-struct PnpLayout { size_t cand, world, uv, sigma, sets, extraA, extraB, total; };
+struct PnpStaged { OrbxStaged sg; OrbxSlot<double, ORBX_STAGE_IN> extraA, extraB; OrbxSlot<uint8_t, ORBX_STAGE_OUT> res; };      // res: the candidates' PnpBlocks
 
 int check_problem(const orbx_pnp_solver *h, const orbx_pnp_problem *P, int c, bool withSets, int &iters, int &minInl)
 {
@@ -896,9 +896,10 @@ int check_problem(const orbx_pnp_solver *h, const orbx_pnp_problem *P, int c, bo
     return ORBX_OK;
 }
 
-// headers + arrays of `nc` candidates into the mapped input buffer; iters[c] = iterations to run (sets are staged when withSets)
-int stage(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, int nc, const std::vector<int> &iters, const std::vector<int> &minInl, bool withSets, size_t extraA, size_t extraB,
-          size_t outBytes, std::vector<PnpCand> &cands, PnpLayout &L, PnpIn &I)
+// headers + arrays of `nc` candidates into the mapped input buffer; iters[c] = iterations to run (sets are staged when withSets); extraA / extraB doubles of
+// room for the caller behind them; outBytes of results, 0 = the candidates' PnpBlocks
+PnpStaged stage(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, int nc, const std::vector<int> &iters, const std::vector<int> &minInl, bool withSets, size_t extraA, size_t extraB,
+                size_t outBytes, std::vector<PnpCand> &cands, PnpIn &I, int *rc)
 {
     size_t totN = 0, totIt = 0, totW = 0, off = 0;
     cands.assign((size_t)nc, PnpCand());
@@ -911,33 +912,27 @@ int stage(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, int nc, const std::vec
         totN += (size_t)P.n; totIt += (size_t)iters[c]; totW += (size_t)H.words * (size_t)iters[c];
         off += PnpBlock(P.n, iters[c]).total;
     }
-    auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
-    L.cand = 0;
-    L.world = padded(sizeof(PnpCand) * (size_t)nc);
-    L.uv = L.world + padded(totN * 12);
-    L.sigma = L.uv + padded(totN * 8);
-    L.sets = L.sigma + padded(totN * 4);
-    L.extraA = L.sets + padded(withSets ? totIt * 16 : 0);
-    L.extraB = L.extraA + padded(extraA);
-    L.total = L.extraB + padded(extraB);
-    int rc;
     OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(L.total, outBytes ? outBytes : off, h->stream)) != ORBX_OK) return rc;
-    memcpy(bx.in + L.cand, cands.data(), sizeof(PnpCand) * (size_t)nc);
+    auto [pin, pout] = bx.plan();
+    // the candidates' arrays lie concatenated, candidate c's at element mb (matches) / ib (sets) of its region: holes, filled below
+    const auto sCand = pin.add(cands.data(), (size_t)nc);
+    const auto sWorld = pin.hole<float>(totN * 3), sUv = pin.hole<float>(totN * 2), sSigma = pin.hole<float>(totN);
+    const auto sSets = pin.hole<int32_t>(withSets ? totIt * 4 : 0);
+    const auto sA = pin.hole<double>(extraA), sB = pin.hole<double>(extraB);
+    const auto rRes = pout.hole<uint8_t>(outBytes ? outBytes : off);
+    const PnpStaged S = {bx.begin(h->stream, rc), sA, sB, rRes};
+    if (*rc != ORBX_OK) return S;
     for (int c = 0; c < nc; c++) {
         const orbx_pnp_problem &P = Ps[c];
         const PnpCand &H = cands[c];
-        const size_t n = (size_t)P.n;
-        if (n) {
-            memcpy(bx.in + L.world + 12 * (size_t)H.mb, P.p3dw, 12 * n); memcpy(bx.in + L.uv + 8 * (size_t)H.mb, P.p2d, 8 * n);
-            memcpy(bx.in + L.sigma + 4 * (size_t)H.mb, P.sigma2, 4 * n);
-        }
-        if (withSets && H.iters) memcpy(bx.in + L.sets + 16 * (size_t)H.ib, P.sets, 16 * (size_t)H.iters);
+        const size_t n = (size_t)P.n, mb = (size_t)H.mb;
+        orbx_put_at(S.sg, sWorld, 3 * mb, P.p3dw, 3 * n); orbx_put_at(S.sg, sUv, 2 * mb, P.p2d, 2 * n); orbx_put_at(S.sg, sSigma, mb, P.sigma2, n);
+        if (withSets) orbx_put_at(S.sg, sSets, 4 * (size_t)H.ib, P.sets, 4 * (size_t)H.iters);
     }
-    I.cand = (const PnpCand *)(bx.inDev + L.cand);
-    I.world = (const float *)(bx.inDev + L.world); I.uv = (const float *)(bx.inDev + L.uv); I.sigma = (const float *)(bx.inDev + L.sigma);
-    I.sets = (const int32_t *)(bx.inDev + L.sets);
-    return ORBX_OK;
+    I.cand = S.sg.dev(sCand);
+    I.world = S.sg.dev(sWorld); I.uv = S.sg.dev(sUv); I.sigma = S.sg.dev(sSigma);
+    I.sets = S.sg.dev(sSets);
+    return S;
 }
 
 unsigned prepare_blocks(int maxN, int maxIt) { return (unsigned)std::max(1, (std::max(maxN, 4 * maxIt) + 255) / 256); }
@@ -993,9 +988,9 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
     }
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     std::vector<PnpCand> cands;
-    PnpLayout L;
     PnpIn I;
-    if ((rc = stage(h, Ps, nc, iters, minInl, true, 0, 0, 0, cands, L, I)) != ORBX_OK) return rc;
+    const PnpStaged S = stage(h, Ps, nc, iters, minInl, true, 0, 0, 0, cands, I, &rc);
+    if (rc != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
     const PnpDev D = dev_view(h);
     h->solved = false;
@@ -1022,7 +1017,7 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
             ORBX_LAUNCH_COUNT(h->timer);
             }
     }
-    hipLaunchKernelGGL(k_pnp_decide, dim3((unsigned)nc), dim3(PNP_DECIDE_THREADS), 0, h->stream, D, bx.outDevP, bx.counter, bx.flagDev, seq);
+    hipLaunchKernelGGL(k_pnp_decide, dim3((unsigned)nc), dim3(PNP_DECIDE_THREADS), 0, h->stream, D, S.sg.dev(S.res), bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_COUNT(h->timer);
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
@@ -1034,7 +1029,7 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
         const PnpCand &H = cands[c];
         const size_t it = (size_t)H.iters, n = (size_t)H.n;
         const PnpBlock B(H.n, H.iters);
-        const uint8_t *blk = bx.out + H.outOff;
+        const uint8_t *blk = S.sg.host(S.res) + H.outOff;
         const int32_t *head = (const int32_t *)blk;
         if (R.first_event) *R.first_event = head[0];
         if (R.best_iteration) *R.best_iteration = head[1];
@@ -1097,18 +1092,17 @@ extern "C" int orbx_pnp_check_models(orbx_pnp_solver *h, const orbx_pnp_problem 
     if ((rc = check_problem(h, P, 0, false, unused, minInl)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     std::vector<PnpCand> cands;
-    PnpLayout L;
     PnpIn I;
     const std::vector<int> iters(1, m), mins(1, minInl);
-    if ((rc = stage(h, P, 1, iters, mins, false, (size_t)m * 72, (size_t)m * 24, 256, cands, L, I)) != ORBX_OK) return rc;
-    OrbxCallBox &bx = h->box;
-    memcpy(bx.in + L.extraA, R, (size_t)m * 72); memcpy(bx.in + L.extraB, t, (size_t)m * 24);
+    const PnpStaged S = stage(h, P, 1, iters, mins, false, (size_t)m * 9, (size_t)m * 3, 256, cands, I, &rc);
+    if (rc != ORBX_OK) return rc;
+    orbx_put_at(S.sg, S.extraA, 0, R, (size_t)m * 9); orbx_put_at(S.sg, S.extraB, 0, t, (size_t)m * 3);
     // the last solve's matches on the device are overwritten, its masks are not: orbx_pnp_inliers keeps working
     const PnpDev D = dev_view(h);
     hipLaunchKernelGGL(k_pnp_prepare, dim3(prepare_blocks(P->n, 0), 1), dim3(256), 0, h->stream, I, D, 0);
     ORBX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_pnp_check, dim3((unsigned)((m + PNP_CHECK_WAVES - 1) / PNP_CHECK_WAVES), 1), dim3(64 * PNP_CHECK_WAVES), 0, h->stream, D, (const double *)(bx.inDev + L.extraA),
-                       (const double *)(bx.inDev + L.extraB), (const int32_t *)nullptr, h->cmCount.p, h->cmMask.p);
+    hipLaunchKernelGGL(k_pnp_check, dim3((unsigned)((m + PNP_CHECK_WAVES - 1) / PNP_CHECK_WAVES), 1), dim3(64 * PNP_CHECK_WAVES), 0, h->stream, D, (const double *)S.sg.dev(S.extraA),
+                       (const double *)S.sg.dev(S.extraB), (const int32_t *)nullptr, h->cmCount.p, h->cmMask.p);
     ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     ORBX_HIP_CHECK(hipMemcpy(count, h->cmCount.p, (size_t)m * 4, hipMemcpyDeviceToHost));
@@ -1147,10 +1141,10 @@ extern "C" int orbx_pnp_epnp(orbx_pnp_solver *h, const orbx_pnp_problem *P, cons
         (alphas && (rc = h->epAlphas.ensure(nsets * 4))))
         return rc;
     std::vector<PnpCand> cands;
-    PnpLayout L;
     PnpIn I;
     const std::vector<int> iters(1, m), mins(1, minInl);
-    if ((rc = stage(h, P, 1, iters, mins, false, 0, 0, 256, cands, L, I)) != ORBX_OK) return rc;
+    stage(h, P, 1, iters, mins, false, 0, 0, 256, cands, I, &rc);
+    if (rc != ORBX_OK) return rc;
     const PnpDev D = dev_view(h);
     double *o = h->epOut.p;
     hipLaunchKernelGGL(k_pnp_prepare, dim3(prepare_blocks(P->n, 0), 1), dim3(256), 0, h->stream, I, D, 0);

@@ -392,7 +392,7 @@ Sim3Dev dev_view(orbx_sim3_solver *h)
     return D;
 }
 
-struct Sim3Layout { size_t cand, world1, world2, sigma1, sigma2, sets, extraA, extraB, total; };
+struct Sim3Staged { OrbxStaged sg; OrbxSlot<float, ORBX_STAGE_IN> extraA, extraB; OrbxSlot<uint8_t, ORBX_STAGE_OUT> res; };      // res: the candidates' Sim3Blocks
 
 int check_problem(const orbx_sim3_solver *h, const orbx_sim3_problem *P, int c, bool withSets, int &iters)
 {
@@ -415,9 +415,10 @@ int check_problem(const orbx_sim3_solver *h, const orbx_sim3_problem *P, int c, 
     return ORBX_OK;
 }
 
-// headers + arrays of `nc` candidates into the mapped input buffer; iters[c] = iterations to run (sets are staged when withSets)
-int stage(orbx_sim3_solver *h, const orbx_sim3_problem *Ps, int nc, const std::vector<int> &iters, bool withSets, size_t extraA, size_t extraB, size_t outBytes,
-          std::vector<Sim3Cand> &cands, Sim3Layout &L, Sim3In &I)
+// headers + arrays of `nc` candidates into the mapped input buffer; iters[c] = iterations to run (sets are staged when withSets); extraA / extraB floats of
+// room for the caller behind them; outBytes of results, 0 = the candidates' Sim3Blocks
+Sim3Staged stage(orbx_sim3_solver *h, const orbx_sim3_problem *Ps, int nc, const std::vector<int> &iters, bool withSets, size_t extraA, size_t extraB, size_t outBytes,
+                 std::vector<Sim3Cand> &cands, Sim3In &I, int *rc)
 {
     size_t totN = 0, totIt = 0, totW = 0, off = 0;
     cands.assign((size_t)nc, Sim3Cand());
@@ -431,35 +432,29 @@ int stage(orbx_sim3_solver *h, const orbx_sim3_problem *Ps, int nc, const std::v
         totN += (size_t)P.n; totIt += (size_t)iters[c]; totW += (size_t)H.words * (size_t)iters[c];
         off += Sim3Block(P.n, iters[c]).total;
     }
-    auto padded = [](size_t b) { return OrbxCallBox::padded(b); };
-    L.cand = 0;
-    L.world1 = padded(sizeof(Sim3Cand) * (size_t)nc);
-    L.world2 = L.world1 + padded(totN * 12);
-    L.sigma1 = L.world2 + padded(totN * 12);
-    L.sigma2 = L.sigma1 + padded(totN * 4);
-    L.sets = L.sigma2 + padded(totN * 4);
-    L.extraA = L.sets + padded(withSets ? totIt * 12 : 0);
-    L.extraB = L.extraA + padded(extraA);
-    L.total = L.extraB + padded(extraB);
-    int rc;
     OrbxCallBox &bx = h->box;
-    if ((rc = bx.begin(L.total, outBytes ? outBytes : off, h->stream)) != ORBX_OK) return rc;
-    memcpy(bx.in + L.cand, cands.data(), sizeof(Sim3Cand) * (size_t)nc);
+    auto [pin, pout] = bx.plan();
+    // the candidates' arrays lie concatenated, candidate c's at element mb (matches) / ib (sets) of its region: holes, filled below
+    const auto sCand = pin.add(cands.data(), (size_t)nc);
+    const auto sW1 = pin.hole<float>(totN * 3), sW2 = pin.hole<float>(totN * 3), sS1 = pin.hole<float>(totN), sS2 = pin.hole<float>(totN);
+    const auto sSets = pin.hole<int32_t>(withSets ? totIt * 3 : 0);
+    const auto sA = pin.hole<float>(extraA), sB = pin.hole<float>(extraB);
+    const auto rRes = pout.hole<uint8_t>(outBytes ? outBytes : off);
+    const Sim3Staged S = {bx.begin(h->stream, rc), sA, sB, rRes};
+    if (*rc != ORBX_OK) return S;
     for (int c = 0; c < nc; c++) {
         const orbx_sim3_problem &P = Ps[c];
         const Sim3Cand &H = cands[c];
-        const size_t n = (size_t)P.n;
-        if (n) {
-            memcpy(bx.in + L.world1 + 12 * (size_t)H.mb, P.world1, 12 * n); memcpy(bx.in + L.world2 + 12 * (size_t)H.mb, P.world2, 12 * n);
-            memcpy(bx.in + L.sigma1 + 4 * (size_t)H.mb, P.sigma2_1, 4 * n); memcpy(bx.in + L.sigma2 + 4 * (size_t)H.mb, P.sigma2_2, 4 * n);
-        }
-        if (withSets && H.iters) memcpy(bx.in + L.sets + 12 * (size_t)H.ib, P.sets, 12 * (size_t)H.iters);
+        const size_t n = (size_t)P.n, mb = (size_t)H.mb;
+        orbx_put_at(S.sg, sW1, 3 * mb, P.world1, 3 * n); orbx_put_at(S.sg, sW2, 3 * mb, P.world2, 3 * n);
+        orbx_put_at(S.sg, sS1, mb, P.sigma2_1, n); orbx_put_at(S.sg, sS2, mb, P.sigma2_2, n);
+        if (withSets) orbx_put_at(S.sg, sSets, 3 * (size_t)H.ib, P.sets, 3 * (size_t)H.iters);
     }
-    I.cand = (const Sim3Cand *)(bx.inDev + L.cand);
-    I.world1 = (const float *)(bx.inDev + L.world1); I.world2 = (const float *)(bx.inDev + L.world2);
-    I.sigma1 = (const float *)(bx.inDev + L.sigma1); I.sigma2 = (const float *)(bx.inDev + L.sigma2);
-    I.sets = (const int32_t *)(bx.inDev + L.sets);
-    return ORBX_OK;
+    I.cand = S.sg.dev(sCand);
+    I.world1 = S.sg.dev(sW1); I.world2 = S.sg.dev(sW2);
+    I.sigma1 = S.sg.dev(sS1); I.sigma2 = S.sg.dev(sS2);
+    I.sets = S.sg.dev(sSets);
+    return S;
 }
 
 unsigned prepare_blocks(int maxN, int maxIt) { return (unsigned)std::max(1, (std::max(maxN, 3 * maxIt) + 255) / 256); }
@@ -514,9 +509,9 @@ extern "C" int orbx_sim3_solve(orbx_sim3_solver *h, const orbx_sim3_problem *Ps,
     }
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     std::vector<Sim3Cand> cands;
-    Sim3Layout L;
     Sim3In I;
-    if ((rc = stage(h, Ps, nc, iters, true, 0, 0, 0, cands, L, I)) != ORBX_OK) return rc;
+    const Sim3Staged S = stage(h, Ps, nc, iters, true, 0, 0, 0, cands, I, &rc);
+    if (rc != ORBX_OK) return rc;
     OrbxCallBox &bx = h->box;
     const Sim3Dev D = dev_view(h);
     h->solved = false;
@@ -532,7 +527,7 @@ extern "C" int orbx_sim3_solve(orbx_sim3_solver *h, const orbx_sim3_problem *Ps,
                            (const float *)D.t21m, D.count, D.mask);
         ORBX_LAUNCH_COUNT(h->timer);
     }
-    hipLaunchKernelGGL(k_sim3_decide, dim3((unsigned)nc), dim3(SIM3_DECIDE_THREADS), 0, h->stream, D, bx.outDevP, bx.counter, bx.flagDev, seq);
+    hipLaunchKernelGGL(k_sim3_decide, dim3((unsigned)nc), dim3(SIM3_DECIDE_THREADS), 0, h->stream, D, S.sg.dev(S.res), bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_COUNT(h->timer);
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
@@ -544,7 +539,7 @@ extern "C" int orbx_sim3_solve(orbx_sim3_solver *h, const orbx_sim3_problem *Ps,
         const Sim3Cand &H = cands[c];
         const size_t it = (size_t)H.iters, n = (size_t)H.n;
         const Sim3Block B(H.n, H.iters);
-        const uint8_t *blk = bx.out + H.outOff;
+        const uint8_t *blk = S.sg.host(S.res) + H.outOff;
         const int32_t *head = (const int32_t *)blk;
         if (R.first_event) *R.first_event = head[0];
         if (R.best_iteration) *R.best_iteration = head[1];
@@ -601,18 +596,17 @@ extern "C" int orbx_sim3_check_models(orbx_sim3_solver *h, const orbx_sim3_probl
     if ((rc = check_problem(h, P, 0, false, unused)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipSetDevice(h->device));
     std::vector<Sim3Cand> cands;
-    Sim3Layout L;
     Sim3In I;
     const std::vector<int> iters(1, m);
-    if ((rc = stage(h, P, 1, iters, false, (size_t)m * 64, (size_t)m * 64, 256, cands, L, I)) != ORBX_OK) return rc;
-    OrbxCallBox &bx = h->box;
-    memcpy(bx.in + L.extraA, t12, (size_t)m * 64); memcpy(bx.in + L.extraB, t21, (size_t)m * 64);
+    const Sim3Staged S = stage(h, P, 1, iters, false, (size_t)m * 16, (size_t)m * 16, 256, cands, I, &rc);
+    if (rc != ORBX_OK) return rc;
+    orbx_put_at(S.sg, S.extraA, 0, t12, (size_t)m * 16); orbx_put_at(S.sg, S.extraB, 0, t21, (size_t)m * 16);
     // the last solve's pairs on the device are overwritten, its masks are not: orbx_sim3_inliers keeps working
     const Sim3Dev D = dev_view(h);
     hipLaunchKernelGGL(k_sim3_prepare, dim3(prepare_blocks(P->n, 0), 1), dim3(256), 0, h->stream, I, D, 0);
     ORBX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sim3_check, dim3((unsigned)((m + SIM3_CHECK_WAVES - 1) / SIM3_CHECK_WAVES), 1), dim3(64 * SIM3_CHECK_WAVES), 0, h->stream, D, (const float *)(bx.inDev + L.extraA),
-                       (const float *)(bx.inDev + L.extraB), h->cmCount.p, h->cmMask.p);
+    hipLaunchKernelGGL(k_sim3_check, dim3((unsigned)((m + SIM3_CHECK_WAVES - 1) / SIM3_CHECK_WAVES), 1), dim3(64 * SIM3_CHECK_WAVES), 0, h->stream, D, (const float *)S.sg.dev(S.extraA),
+                       (const float *)S.sg.dev(S.extraB), h->cmCount.p, h->cmMask.p);
     ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipStreamSynchronize(h->stream));
     ORBX_HIP_CHECK(hipMemcpy(count, h->cmCount.p, (size_t)m * 4, hipMemcpyDeviceToHost));

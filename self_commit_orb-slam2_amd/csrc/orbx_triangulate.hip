@@ -247,8 +247,6 @@ extern "C" int orbx_triangulate_matches(orbx_matcher *m, const orbx_triangulate_
     if (P->match_offset[0] != 0) { orbx_set_error("match_offset[0] must be 0"); return ORBX_ERR_ARG; }
     const int M = P->match_offset[K];
     if (M > 0 && (!P->idx1 || !P->idx2)) { orbx_set_error("NULL match lists"); return ORBX_ERR_ARG; }
-    const OrbxHostStage &H = m->npStage;
-    size_t bytes = 2 * H.padded((size_t)std::max(M, 0) * 4);
     int rc;
     for (int p = 0; p < K; p++) {
         if (P->match_offset[p + 1] < P->match_offset[p]) { orbx_set_error("match_offset decreases at pair %d", p); return ORBX_ERR_ARG; }
@@ -259,7 +257,6 @@ extern "C" int orbx_triangulate_matches(orbx_matcher *m, const orbx_triangulate_
             if (n < 0) { orbx_set_error("pair %d: negative feature count %d", p, n); return ORBX_ERR_ARG; }      // (nothing here is sized by max_features)
             if (n > 0 && !ob[sd]->keys_un) { orbx_set_error("pair %d: NULL keys_un", p); return ORBX_ERR_ARG; }
             if ((ob[sd]->u_right == nullptr) != (ob[sd]->depth == nullptr)) { orbx_set_error("pair %d: u_right and depth go together", p); return ORBX_ERR_ARG; }
-            bytes += H.padded((size_t)n * sizeof(orbx_keypoint)) + H.padded((size_t)n * 8) + 2 * H.padded((size_t)n * 4);
         }
         for (int j = P->match_offset[p]; j < P->match_offset[p + 1]; j++)
             if (P->idx1[j] < 0 || P->idx1[j] >= P->obs1[p].count || P->idx2[j] < 0 || P->idx2[j] >= P->obs2[p].count) {
@@ -270,8 +267,23 @@ extern "C" int orbx_triangulate_matches(orbx_matcher *m, const orbx_triangulate_
     if (M == 0) return ORBX_OK;
     ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));      // an earlier call's copy has left the pinned buffer
     OrbxHostStage &hs = m->npStage;
-    if ((rc = hs.begin(bytes)) != ORBX_OK || (rc = ensure_slots(m, (size_t)M, 1)) != ORBX_OK) return rc;
-    const int32_t *d1 = hs.put(P->idx1, (size_t)M), *d2 = hs.put(P->idx2, (size_t)M);
+    OrbxInPlan &pl = hs.plan();
+    const auto s1 = pl.add(P->idx1, (size_t)M), s2 = pl.add(P->idx2, (size_t)M);
+    struct SideSlots { OrbxSlot<orbx_keypoint, ORBX_STAGE_IN> kp; OrbxSlot<float, ORBX_STAGE_IN> raw, ur, dp; };
+    std::vector<SideSlots> slots(2 * (size_t)K);
+    for (int p = 0; p < K; p++) {
+        const orbx_keyframe_obs *ob[2] = {&P->obs1[p], &P->obs2[p]};
+        for (int sd = 0; sd < 2; sd++) {
+            const size_t n = (size_t)ob[sd]->count;
+            SideSlots &S = slots[2 * (size_t)p + sd];
+            S.kp = pl.add(ob[sd]->keys_un, n);
+            S.raw = pl.add(ob[sd]->keys_raw, ob[sd]->keys_raw ? 2 * n : 0);
+            S.ur = pl.add(ob[sd]->u_right, ob[sd]->u_right ? n : 0); S.dp = pl.add(ob[sd]->depth, ob[sd]->depth ? n : 0);
+        }
+    }
+    const OrbxStaged sg = hs.begin(&rc);
+    if (rc != ORBX_OK || (rc = ensure_slots(m, (size_t)M, 1)) != ORBX_OK) return rc;
+    const int32_t *d1 = sg.dev(s1), *d2 = sg.dev(s2);
     std::vector<TriArgs> args((size_t)K);
     for (int p = 0; p < K; p++) {
         TriArgs &T = args[(size_t)p];
@@ -280,12 +292,10 @@ extern "C" int orbx_triangulate_matches(orbx_matcher *m, const orbx_triangulate_
         const orbx_keyframe_obs *ob[2] = {&P->obs1[p], &P->obs2[p]};
         TriCam *cam[2] = {&T.c1, &T.c2};
         for (int sd = 0; sd < 2; sd++) {
-            const size_t n = (size_t)ob[sd]->count;
-            cam[sd]->kp = hs.put(ob[sd]->keys_un, n);
-            const float *raw = hs.put(ob[sd]->keys_raw, ob[sd]->keys_raw ? 2 * n : 0);
-            const float *ur = hs.put(ob[sd]->u_right, ob[sd]->u_right ? n : 0), *dp = hs.put(ob[sd]->depth, ob[sd]->depth ? n : 0);
-            cam[sd]->raw = ob[sd]->keys_raw ? raw : nullptr; cam[sd]->ur = ob[sd]->u_right ? ur : nullptr; cam[sd]->depth = ob[sd]->depth ? dp : nullptr;
-            cam[sd]->n = (int)n;
+            const SideSlots &S = slots[2 * (size_t)p + sd];
+            cam[sd]->kp = sg.dev(S.kp);
+            cam[sd]->raw = ob[sd]->keys_raw ? sg.dev(S.raw) : nullptr; cam[sd]->ur = ob[sd]->u_right ? sg.dev(S.ur) : nullptr; cam[sd]->depth = ob[sd]->depth ? sg.dev(S.dp) : nullptr;
+            cam[sd]->n = ob[sd]->count;
         }
     }
     if ((rc = hs.flush(m->stream)) != ORBX_OK) return rc;
@@ -327,52 +337,62 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     // ---- stage KF1 and the K neighbours once: one pinned buffer, one copy ----
     OrbxHostStage &hs = m->npStage;
     const size_t C1 = (size_t)cap1, N1 = (size_t)n1, A2 = (size_t)K * cap2;
-    const size_t bytes = hs.padded(C1 * sizeof(orbx_keypoint)) + hs.padded(C1 * 32) + 3 * hs.padded(C1 * 4) + 2 * hs.padded(C1) + hs.padded(C1 * 8) + hs.padded(8) +
-                         hs.padded(A2 * sizeof(orbx_keypoint)) + hs.padded(A2 * 32) + 3 * hs.padded(A2 * 4) + 2 * hs.padded(A2) + hs.padded(A2 * 8) + 2 * hs.padded((size_t)K * 4) +
-                         hs.padded((size_t)K * 9 * 4) + hs.padded((size_t)K * 2 * 4);
     const int stride = (cap1 + 7) & ~7;
-    const size_t outBytes = OrbxCallBox::padded(((size_t)K + 1) * 4) + (size_t)res->created_capacity * sizeof(orbx_new_point);
+    // KF1's arrays hold n1 elements on the host and capacity elements on the device
+    OrbxInPlan &pl = hs.plan();
+    const auto sKp1 = pl.add(kf1->keypoints, N1, C1);
+    const auto sDesc1 = pl.add(kf1->descriptors, N1 * 32, C1 * 32);
+    const int32_t heads[2] = {n1, 0};
+    const auto sHeads = pl.add(heads, 2);
+    const auto sG1 = pl.add(kf1->groups, kf1->groups ? N1 : 0, kf1->groups ? C1 : 0);
+    const auto sMask = pl.add(kf1->valid, kf1->valid ? N1 : 0, C1);      // (no valid flags: a hole, all ones below)
+    const auto sSt1 = pl.hole<uint8_t>(C1);
+    const auto sRaw1 = pl.add(prm->keys_raw1, prm->keys_raw1 ? 2 * N1 : 0, prm->keys_raw1 ? 2 * C1 : 0);
+    const auto sUr1 = pl.add(prm->u_right1, prm->u_right1 ? N1 : 0, prm->u_right1 ? C1 : 0), sDp1 = pl.add(prm->depth1, prm->depth1 ? N1 : 0, prm->depth1 ? C1 : 0);
+    const auto sKp2 = pl.add(nb->keypoints, A2);
+    const auto sDesc2 = pl.add(nb->descriptors, A2 * 32);
+    const auto sCnt2 = pl.add(nb->counts, (size_t)K);
+    const auto sG2 = pl.add(nb->groups, nb->groups ? A2 : 0);
+    const auto sV2 = pl.add(nb->valid, nb->valid ? A2 : 0);
+    const auto sSt2 = pl.hole<uint8_t>(A2);
+    const auto sRaw2 = pl.add(prm->keys_raw2, prm->keys_raw2 ? 2 * A2 : 0), sUr2 = pl.add(prm->u_right2, prm->u_right2 ? A2 : 0), sDp2 = pl.add(prm->depth2, prm->depth2 ? A2 : 0);
+    const auto sPair = pl.hole<int32_t>((size_t)K);
+    const auto sF12 = pl.add(prm->f12, (size_t)K * 9), sEpi = pl.add(prm->epipole, (size_t)K * 2);
     OrbxCallBox &bx = m->box;
-    if ((rc = bx.begin(0, outBytes, m->stream)) != ORBX_OK) return rc;      // (waits for a call that was abandoned half way)
-    ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));                         // an earlier call's copy has left the pinned buffer
-    if ((rc = hs.begin(bytes)) != ORBX_OK || (rc = ensure_slots(m, (size_t)K * stride, (size_t)K)) != ORBX_OK) return rc;
+    auto [pin, pout] = bx.plan();
+    (void)pin;
+    const auto rHead = pout.hole<int32_t>((size_t)K + 1);
+    const auto rList = pout.hole<orbx_new_point>((size_t)res->created_capacity);
+    const OrbxStaged bg = bx.begin(m->stream, &rc);      // (waits for a call that was abandoned half way)
+    if (rc != ORBX_OK) return rc;
+    ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));      // an earlier call's copy has left the pinned buffer
+    const OrbxStaged sg = hs.begin(&rc);
+    if (rc != ORBX_OK || (rc = ensure_slots(m, (size_t)K * stride, (size_t)K)) != ORBX_OK) return rc;
     if (prm->profile_kernels)
         while (m->npTriEv.size() < 2 * (size_t)K) { hipEvent_t e = nullptr; ORBX_HIP_CHECK(hipEventCreate(&e)); m->npTriEv.push_back(e); }
     if ((rc = m->npTimer.create()) != ORBX_OK) return rc;
-    auto host_of = [&](const void *dev) { return hs.host + ((const uint8_t *)dev - hs.dev.p); };
 
     orbx_feature_set da = *kf1, db = *nb;
     TriCam cam1, cam2;
     fill_cam(cam1, prm->geom1);
-    // KF1's arrays hold n1 elements on the host and capacity elements on the device
-    auto put1 = [&](auto *src, size_t per, bool present) { auto *d = hs.put(src, present ? N1 * per : 0); hs.used += present ? hs.padded(C1 * per * sizeof(*src)) - hs.padded(N1 * per * sizeof(*src)) : 0; return d; };
-    da.keypoints = put1(kf1->keypoints, 1, true);
-    da.descriptors = put1(kf1->descriptors, 32, true);
-    const int32_t heads[2] = {n1, 0};
-    const int32_t *dHeads = hs.put(heads, 2);
-    da.counts = dHeads;
-    const int32_t *g1 = put1(kf1->groups, 1, kf1->groups != nullptr);
-    da.groups = kf1->groups ? g1 : nullptr;
-    uint8_t *mask = hs.put((const uint8_t *)nullptr, C1);
-    if (kf1->valid) memcpy(host_of(mask), kf1->valid, N1); else memset(host_of(mask), 1, N1);
+    da.keypoints = sg.dev(sKp1);
+    da.descriptors = sg.dev(sDesc1);
+    da.counts = sg.dev(sHeads);
+    da.groups = kf1->groups ? sg.dev(sG1) : nullptr;
+    uint8_t *const mask = sg.dev(sMask);
+    if (!kf1->valid) memset(sg.host(sMask), 1, N1);
     da.valid = mask;
-    uint8_t *st1 = hs.put((const uint8_t *)nullptr, C1);
-    for (size_t i = 0; i < N1; i++) host_of(st1)[i] = prm->u_right1 ? (prm->u_right1[i] >= 0 ? 1 : 0) : 0;
-    const float *raw1 = put1(prm->keys_raw1, 2, prm->keys_raw1 != nullptr), *ur1 = put1(prm->u_right1, 1, prm->u_right1 != nullptr), *dp1 = put1(prm->depth1, 1, prm->depth1 != nullptr);
-    cam1.kp = da.keypoints; cam1.raw = prm->keys_raw1 ? raw1 : nullptr; cam1.ur = prm->u_right1 ? ur1 : nullptr; cam1.depth = prm->depth1 ? dp1 : nullptr; cam1.n = n1;
+    uint8_t *const st1 = sg.dev(sSt1);
+    for (size_t i = 0; i < N1; i++) sg.host(sSt1)[i] = prm->u_right1 ? (prm->u_right1[i] >= 0 ? 1 : 0) : 0;
+    cam1.kp = da.keypoints; cam1.raw = prm->keys_raw1 ? sg.dev(sRaw1) : nullptr; cam1.ur = prm->u_right1 ? sg.dev(sUr1) : nullptr; cam1.depth = prm->depth1 ? sg.dev(sDp1) : nullptr; cam1.n = n1;
 
-    db.keypoints = hs.put(nb->keypoints, A2); db.descriptors = hs.put(nb->descriptors, A2 * 32);
-    db.counts = hs.put(nb->counts, (size_t)K);
-    const int32_t *g2 = hs.put(nb->groups, nb->groups ? A2 : 0);
-    const uint8_t *v2 = hs.put(nb->valid, nb->valid ? A2 : 0);
-    db.groups = nb->groups ? g2 : nullptr; db.valid = nb->valid ? v2 : nullptr;
-    uint8_t *st2 = hs.put((const uint8_t *)nullptr, A2);
-    for (size_t i = 0; i < A2; i++) host_of(st2)[i] = prm->u_right2 ? (prm->u_right2[i] >= 0 ? 1 : 0) : 0;
-    const float *raw2 = hs.put(prm->keys_raw2, prm->keys_raw2 ? 2 * A2 : 0), *ur2 = hs.put(prm->u_right2, prm->u_right2 ? A2 : 0), *dp2 = hs.put(prm->depth2, prm->depth2 ? A2 : 0);
-    int32_t *pairIdx = hs.put((const int32_t *)nullptr, (size_t)K);
-    for (int k = 0; k < K; k++) ((int32_t *)host_of(pairIdx))[k] = k;
-    const float *f12 = hs.put(prm->f12, (size_t)K * 9), *epi = hs.put(prm->epipole, (size_t)K * 2);
-    if (hs.used > bytes) { orbx_set_error("internal: staging layout exceeds its size"); return ORBX_ERR_STATE; }
+    db.keypoints = sg.dev(sKp2); db.descriptors = sg.dev(sDesc2);
+    db.counts = sg.dev(sCnt2);
+    db.groups = nb->groups ? sg.dev(sG2) : nullptr; db.valid = nb->valid ? sg.dev(sV2) : nullptr;
+    uint8_t *const st2 = sg.dev(sSt2);
+    for (size_t i = 0; i < A2; i++) sg.host(sSt2)[i] = prm->u_right2 ? (prm->u_right2[i] >= 0 ? 1 : 0) : 0;
+    const float *raw2 = sg.dev(sRaw2), *ur2 = sg.dev(sUr2), *dp2 = sg.dev(sDp2);
+    for (int k = 0; k < K; k++) sg.host(sPair)[k] = k;
     m->npTimer.timed = false; m->npTriTimed = 0;
     if ((rc = m->npTimer.begin(m->stream)) != ORBX_OK) return rc;
     if ((rc = hs.flush(m->stream)) != ORBX_OK) return rc;
@@ -380,8 +400,8 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     // ---- the chain: search k, triangulate k, (mask), search k+1 ... all on m->stream ----
     const unsigned long long seq = bx.arm();      // before the first launch: an error below leaves the box pending and the next begin() drains the stream
     // the pair indices, F12 and the epipole are read by the search from the PINNED copy: its uploads stay asynchronous
-    const int32_t *hostZero = (const int32_t *)host_of(dHeads) + 1, *hostPair = (const int32_t *)host_of(pairIdx);
-    const float *hostF12 = (const float *)host_of(f12), *hostEpi = (const float *)host_of(epi);
+    const int32_t *hostZero = sg.host(sHeads) + 1, *hostPair = sg.host(sPair);
+    const float *hostF12 = sg.host(sF12), *hostEpi = sg.host(sEpi);
     int done = 0;
     for (int k = 0; k < K; k++) {
         if (k > 0 && stop_flag && *stop_flag) break;      // :353
@@ -407,9 +427,8 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     }
     // Results: k_collect writes them into mapped pinned memory and raises the sequence word.  (A device list fetched with one copy behind a
     // stream synchronisation measured 9 - 17 us slower per call at every shape of profiles/new_points_latency.txt and was removed.)
-    const size_t listOff = OrbxCallBox::padded(((size_t)K + 1) * 4);
-    int32_t *outHead = bx.outDev<int32_t>(0);
-    orbx_new_point *outList = bx.outDev<orbx_new_point>(listOff);
+    int32_t *outHead = bg.dev(rHead);
+    orbx_new_point *outList = bg.dev(rList);
     hipLaunchKernelGGL(k_collect, dim3(1), dim3(COLLECT_THREADS), 0, m->stream, (const uint8_t *)m->npStatus.p, (const int32_t *)m->npMatches.p, (const float *)m->npX3d.p,
                        (const int32_t *)m->npNm.p, K, done, stride, res->created_capacity, outHead, outList, bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
@@ -417,11 +436,11 @@ extern "C" int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_se
     m->npTimer.launches = 4 * done + 1;      // k_bow_order, k_bow_topk, k_bow_greedy, k_triangulate per neighbour; k_collect
     m->npTriTimed = prm->profile_kernels ? done : 0;
     if ((rc = bx.wait(m->stream)) != ORBX_OK) return rc;      // the one synchronisation
-    const int32_t *head = bx.outHost<int32_t>(0);
+    const int32_t *head = bg.host(rHead);
     const int cnt = head[0];
     *res->count = cnt; *res->pairs_done = done;
     memcpy(res->nmatches, head + 1, (size_t)K * 4);
-    if (cnt > 0) memcpy(res->created, bx.outHost<orbx_new_point>(OrbxCallBox::padded(((size_t)K + 1) * 4)), (size_t)cnt * sizeof(orbx_new_point));
+    if (cnt > 0) memcpy(res->created, bg.host(rList), (size_t)cnt * sizeof(orbx_new_point));
     if (res->status || res->matches || res->x3d) {      // the optional per-slot arrays (tests, diagnostics): copies of their own
         ORBX_HIP_CHECK(hipStreamSynchronize(m->stream));
         for (int k = 0; k < K; k++) {

@@ -523,6 +523,8 @@ struct orbx_voc_trainer : OrbxHandle {
     OrbxOwnedBuf<unsigned> cntG, sizeG, devCount;
     OrbxOwnedBuf<uint8_t> flags;
     OrbxCallBox box;
+    int32_t *changedDev = nullptr;            // the box's one result, planned once at creation: a pass's changed-assignment count
+    const int32_t *changedHost = nullptr;
     // the last result, flat arrays in orbx_vocabulary_create's layout
     bool trained = false;
     std::vector<int32_t> parent, ni_;
@@ -687,12 +689,12 @@ int vt_assign(orbx_voc_trainer *h, const uint4 *desc, int N, int pass, int cur, 
     const u64 seq = bx.arm();
     hipLaunchKernelGGL(k_assign, dim3(std::min(vt_blocks((size_t)N), (unsigned)VT_ASSIGN_BLOCKS)), dim3(256), 0, h->stream, (const VtSeg *)h->segs.p, (const int32_t *)h->segOf.p, N, pass,
                        (const int32_t *)h->perm[cur].p, desc, (const uint4 *)h->centres.p, (const int32_t *)h->nc.p, h->assoc.p, h->changedPass.p, h->devCount.p, bx.counter,
-                       bx.outDev<int32_t>(0), bx.flagDev, seq);
+                       h->changedDev, bx.flagDev, seq);
     h->launches++;
     int rc = vt_launch_check("k_assign");
     if (rc) return rc;
     if ((rc = bx.wait(h->stream))) return rc;
-    *changed = *bx.outHost<int32_t>(0);
+    *changed = *h->changedHost;
     return ORBX_OK;
 }
 
@@ -755,7 +757,13 @@ extern "C" int orbx_voc_trainer_create(int device, int k, int L, int max_descrip
     if (!rc) rc = h->imgCount.ensure((size_t)max_images);
     if (!rc) rc = h->state.ensure(4);
     if (!rc) rc = vt_push_state(h);
-    if (!rc) rc = h->box.begin(0, 256, h->stream);
+    if (!rc) {
+        auto [pin, pout] = h->box.plan();
+        (void)pin;
+        const auto rChanged = pout.hole<int32_t>(1);
+        const OrbxStaged sg = h->box.begin(h->stream, &rc);
+        if (!rc) { h->changedDev = sg.dev(rChanged); h->changedHost = sg.host(rChanged); }
+    }
     if (rc) { orbx_voc_trainer_destroy(h); return rc; }
     *out = h;
     return ORBX_OK;
