@@ -974,6 +974,142 @@ int orbx_create_new_map_points(orbx_matcher *m, const orbx_feature_set *kf1_host
 int orbx_new_points_last_timing(orbx_matcher *m, float *device_ms, int *launches, float *triangulate_ms);
 
 /* ----------------------------------------------------------------------------------
+ * LocalMapping::SearchInNeighbors, steps 2 and 3 (reference src/LocalMapping.cc:666-713): the T + 1 complete calls of
+ * ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1020-1174) - one per target keyframe on the current
+ * keyframe's points, then one of the current keyframe on the targets' points - as ONE chain on the matcher's stream.
+ * The state that couples the calls (isBad, the observation maps and Observations(), mvpMapPoints of the searchable
+ * keyframes, the descriptor that Replace -> ComputeDistinctiveDescriptors rewrites) lives on the device; the host
+ * waits once.  Integers and bytes: every result equals the sequential loop.
+ *
+ * The slice (host arrays).  Keyframes are slots 0..num_keyframes-1: the current keyframe, the targets and every other
+ * keyframe that observes a point of the slice; kf_rank = the iteration order of std::map<KeyFrame*, size_t> (distinct),
+ * kf_bad = isBad().  The SEARCHABLE keyframes (the current keyframe and every target, each once) carry their
+ * features, pose and calibration (orbx_fuse_keyframe).  Points 0..num_points-1: every point a searchable keyframe
+ * holds; observations as CSR in ascending rank, each with the keyframe slot, the feature index, the stereo byte
+ * (mvuRight[idx] >= 0) and the 32 descriptor bytes of that feature.  Observations() is derived: 1 per observation,
+ * 2 where it is stereo.  For a searchable keyframe, kf_point[f] == p exactly when p has the observation
+ * (that keyframe, f).
+ *
+ * One Fuse call (keyframe k, list of point ids, -1 = NULL):
+ *   prepare  on the state at the start of the call, per entry: skip -1, bad points and points observed by k; the gates
+ *            and values of :1040-1086 in the reference's precisions (3x3 * 3x1 left to right in float, cv::norm and
+ *            Mat::dot in double, the viewing gate a double comparison, the level from the ratio thresholds of
+ *            orbx_predict_scale_thresholds);
+ *   search   the search of orbx_fuse_search with chi2_gate = 1 on the point's current descriptor;
+ *   apply    strictly in list order; an entry whose point has meanwhile gone bad or entered k is skipped.  With
+ *            bestDist <= TH_LOW (the entry counts for nFused) and q = kf_point[k][bestIdx]:
+ *              q < 0             ORBX_FUSE_ADDED: the point gains the observation (k, bestIdx), kf_point[k][bestIdx] = p
+ *              q bad             ORBX_FUSE_HOLDER_BAD: nothing changes
+ *              Obs(q) > Obs(p)   ORBX_FUSE_REPLACED_BY_HOLDER: p->Replace(q)
+ *              else              ORBX_FUSE_REPLACED_HOLDER: q->Replace(p)
+ *            a->Replace(b) (src/MapPoint.cc:244-307): a goes bad, replaced[a] = b; a's observations in ascending rank
+ *            move to b (kf_point of a searchable keyframe follows) or, where b is observed by that keyframe already,
+ *            are dropped (kf_point = -1); found / visible of a are added to b's; b's descriptor is recomputed over
+ *            its observations whose keyframe is not bad (median of the Hamming distances at sorted position
+ *            (N - 1) / 2, first strictly smallest median; kept when N = 0).  Observations() of a is left as it was.
+ * The chain: the forward list is kf_point of the current keyframe at the start (the same for every target), targets in
+ * the caller's order (a slot may repeat); the candidates of the reverse pass are gathered on the device (targets in
+ * order, features in order, every point held NOW that is not bad and not yet listed).
+ * ---------------------------------------------------------------------------------- */
+#define ORBX_FUSE_ADDED 0
+#define ORBX_FUSE_REPLACED_BY_HOLDER 1   /* the list point went bad, replaced by the holder */
+#define ORBX_FUSE_REPLACED_HOLDER 2      /* the holder went bad, replaced by the list point  */
+#define ORBX_FUSE_HOLDER_BAD 3
+
+typedef struct orbx_fuse_keyframe {      /* host memory: one searchable keyframe */
+    int slot;                            /* its keyframe slot                                                         */
+    int num_features;                    /* N, 0..65535                                                               */
+    const orbx_keypoint *keys_un;        /* mvKeysUn                                                                  */
+    const uint8_t *descriptors;          /* mDescriptors, 32 bytes each                                               */
+    const float *u_right;                /* mvuRight                                                                  */
+    const int32_t *kf_point;             /* mvpMapPoints: a point id or -1                                            */
+    float tcw[12];                       /* the first three rows of Tcw: Rcw | tcw                                    */
+    float ow[3];                         /* GetCameraCenter()                                                         */
+    float fx, fy, cx, cy, mbf;
+    float grid_min_x, grid_min_y;        /* Frame::mnMinX / mnMinY, the float bounds mGrid was filed with             */
+    float grid_width_inv, grid_height_inv;
+    int min_x, max_x, min_y, max_y;      /* KeyFrame::mnMinX .. mnMaxY (int): IsInImage and the cell window           */
+    const float *scale_factors;          /* mvScaleFactors[nlevels]                                                   */
+    const float *inv_level_sigma2;       /* mvInvLevelSigma2[nlevels]                                                 */
+    float log_scale_factor;              /* mfLogScaleFactor                                                          */
+    int nlevels;                         /* mnScaleLevels                                                             */
+} orbx_fuse_keyframe;
+
+typedef struct orbx_fuse_slice {         /* host memory */
+    int num_keyframes;
+    const int32_t *kf_rank;              /* [num_keyframes] distinct                                                  */
+    const uint8_t *kf_bad;               /* [num_keyframes]                                                           */
+    int num_searchable;
+    const orbx_fuse_keyframe *searchable;/* [num_searchable], every slot at most once                                 */
+    int num_points, num_obs;
+    const float *pos, *normal;           /* [3*num_points] mWorldPos, mNormalVector                                   */
+    const float *min_distance;           /* GetMinDistanceInvariance()                                                */
+    const float *max_distance;           /* GetMaxDistanceInvariance()                                                */
+    const float *raw_max_distance;       /* mfMaxDistance (PredictScale reads this one)                               */
+    const uint8_t *descriptors;          /* [32*num_points] mDescriptor                                               */
+    const uint8_t *point_bad;
+    const int32_t *visible, *found;      /* mnVisible, mnFound                                                        */
+    const int32_t *obs_offset;           /* [num_points + 1]                                                          */
+    const int32_t *obs_kf, *obs_idx;     /* [num_obs] keyframe slot (ascending rank inside a point), feature index    */
+    const uint8_t *obs_stereo;           /* [num_obs]                                                                 */
+    const uint8_t *obs_descriptors;      /* [32*num_obs]                                                              */
+    float th;                            /* 3.0 in SearchInNeighbors                                                  */
+    int profile_kernels;                 /* 1: time every apply launch with events of its own                         */
+} orbx_fuse_slice;
+
+typedef struct orbx_fuse_decision {
+    int32_t call;                        /* 0..T-1 the forward pass, T the reverse pass (orbx_fuse_apply: 0)           */
+    int32_t position;                    /* index in that call's list                                                 */
+    int32_t point, feature;              /* the list point and bestIdx                                                */
+    int32_t kind;                        /* ORBX_FUSE_*                                                               */
+    int32_t other;                       /* the holder, -1 for ORBX_FUSE_ADDED                                        */
+} orbx_fuse_decision;
+
+typedef struct orbx_fuse_result {        /* host memory; every pointer may be NULL */
+    orbx_fuse_decision *log;             /* [log_capacity] in execution order                                         */
+    int log_capacity;
+    int32_t *log_count;
+    int32_t *nfused;                     /* [T + 1] (orbx_fuse_apply: [1])                                             */
+    int32_t *candidates;                 /* [candidates_capacity] the list of the reverse pass                        */
+    int candidates_capacity;
+    int32_t *candidates_count;
+    int32_t *kf_point;                   /* the searchable keyframes' kf_point one behind the other, in their order   */
+    uint8_t *point_bad;                  /* [num_points]                                                              */
+    int32_t *replaced;                   /* [num_points] -1 = none                                                    */
+    int32_t *point_obs;                  /* [num_points] Observations()                                               */
+    int32_t *visible, *found;            /* [num_points]                                                              */
+    uint8_t *descriptors;                /* [32*num_points]                                                           */
+    int32_t *obs_offset;                 /* [num_points + 1] the observations after the call, ascending rank          */
+    int32_t *obs_kf, *obs_idx;           /* [obs_capacity]                                                            */
+    uint8_t *obs_stereo;                 /* [obs_capacity]                                                            */
+    int obs_capacity;
+    /* per call c and list position i at c*full_stride + i (orbx_search_in_neighbors only; positions behind a list's end
+     * are not written): the prepare and search results */
+    int full_stride;
+    uint8_t *active;
+    float *u, *v, *ur;
+    int32_t *level;
+    float *radius;
+    int32_t *best_idx, *best_dist;
+} orbx_fuse_result;
+
+/* The chain.  current = the slot of the current keyframe, targets = vpTargetKFs as slots (searchable, not `current`).
+ * ORBX_ERR_ARG before anything is launched: a NULL array, an index, offset or rank that the kernels would trip over,
+ * observations of a point not in ascending rank, kf_point and the observations of a searchable keyframe that disagree,
+ * a target that is not searchable.  ORBX_ERR_CAPACITY before anything is launched: more than 65535 features or more
+ * than 12 levels in a keyframe; after the chain and before anything is written: log_capacity, candidates_capacity or
+ * obs_capacity too small (every output is left untouched, the handle stays usable).
+ * Launches: 2 (staging, state) + 3 per Fuse call + 2 (candidate gather) + 1 (final state). */
+int orbx_search_in_neighbors(orbx_matcher *m, const orbx_fuse_slice *slice, int current, const int32_t *targets, int num_targets,
+                             const orbx_fuse_result *result);
+/* The apply stage alone for keyframe slot `kf` (searchable) on search results the caller supplies: list[n] (point id or
+ * -1), active[n], best_idx[n], best_dist[n] as prepare and search would have left them. */
+int orbx_fuse_apply(orbx_matcher *m, const orbx_fuse_slice *slice, int kf, const int32_t *list, const uint8_t *active,
+                    const int32_t *best_idx, const int32_t *best_dist, int n, const orbx_fuse_result *result);
+/* device time of the last chain, its kernel launches, and the time inside the apply kernels (0 unless profile_kernels) */
+int orbx_search_in_neighbors_last_timing(orbx_matcher *m, float *device_ms, int *launches, float *apply_ms);
+
+/* ----------------------------------------------------------------------------------
  * Monocular initialisation: Initializer::Initialize (reference src/Initializer.cc:68-230) and
  * everything below it - FindHomography / FindFundamental over the caller's RANSAC sets, the
  * choice between the two models, DecomposeE / ReconstructH's eight motions, CheckRT of all

@@ -561,6 +561,115 @@ class TriangulationParams(ctypes.Structure):
                 ("scale_factors", ctypes.c_void_p), ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int), ("check_orientation", ctypes.c_int)]
 
 
+class FuseKeyFrame(ctypes.Structure):
+    _fields_ = [("slot", ctypes.c_int), ("num_features", ctypes.c_int), ("keys_un", ctypes.c_void_p), ("descriptors", ctypes.c_void_p), ("u_right", ctypes.c_void_p),
+                ("kf_point", ctypes.c_void_p), ("tcw", ctypes.c_float * 12), ("ow", ctypes.c_float * 3), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
+                ("cy", ctypes.c_float), ("mbf", ctypes.c_float), ("grid_min_x", ctypes.c_float), ("grid_min_y", ctypes.c_float), ("grid_width_inv", ctypes.c_float),
+                ("grid_height_inv", ctypes.c_float), ("min_x", ctypes.c_int), ("max_x", ctypes.c_int), ("min_y", ctypes.c_int), ("max_y", ctypes.c_int),
+                ("scale_factors", ctypes.c_void_p), ("inv_level_sigma2", ctypes.c_void_p), ("log_scale_factor", ctypes.c_float), ("nlevels", ctypes.c_int)]
+
+
+class FuseSlice(ctypes.Structure):
+    _fields_ = [("num_keyframes", ctypes.c_int), ("kf_rank", ctypes.c_void_p), ("kf_bad", ctypes.c_void_p), ("num_searchable", ctypes.c_int), ("searchable", ctypes.c_void_p),
+                ("num_points", ctypes.c_int), ("num_obs", ctypes.c_int), ("pos", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("min_distance", ctypes.c_void_p),
+                ("max_distance", ctypes.c_void_p), ("raw_max_distance", ctypes.c_void_p), ("descriptors", ctypes.c_void_p), ("point_bad", ctypes.c_void_p),
+                ("visible", ctypes.c_void_p), ("found", ctypes.c_void_p), ("obs_offset", ctypes.c_void_p), ("obs_kf", ctypes.c_void_p), ("obs_idx", ctypes.c_void_p),
+                ("obs_stereo", ctypes.c_void_p), ("obs_descriptors", ctypes.c_void_p), ("th", ctypes.c_float), ("profile_kernels", ctypes.c_int)]
+
+
+class FuseResult(ctypes.Structure):
+    _fields_ = [("log", ctypes.c_void_p), ("log_capacity", ctypes.c_int), ("log_count", ctypes.c_void_p), ("nfused", ctypes.c_void_p), ("candidates", ctypes.c_void_p),
+                ("candidates_capacity", ctypes.c_int), ("candidates_count", ctypes.c_void_p), ("kf_point", ctypes.c_void_p), ("point_bad", ctypes.c_void_p),
+                ("replaced", ctypes.c_void_p), ("point_obs", ctypes.c_void_p), ("visible", ctypes.c_void_p), ("found", ctypes.c_void_p), ("descriptors", ctypes.c_void_p),
+                ("obs_offset", ctypes.c_void_p), ("obs_kf", ctypes.c_void_p), ("obs_idx", ctypes.c_void_p), ("obs_stereo", ctypes.c_void_p), ("obs_capacity", ctypes.c_int),
+                ("full_stride", ctypes.c_int), ("active", ctypes.c_void_p), ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("ur", ctypes.c_void_p), ("level", ctypes.c_void_p),
+                ("radius", ctypes.c_void_p), ("best_idx", ctypes.c_void_p), ("best_dist", ctypes.c_void_p)]
+
+
+FUSE_DECISION_DTYPE = np.dtype([("call", "<i4"), ("position", "<i4"), ("point", "<i4"), ("feature", "<i4"), ("kind", "<i4"), ("other", "<i4")])
+FUSE_ADDED, FUSE_REPLACED_BY_HOLDER, FUSE_REPLACED_HOLDER, FUSE_HOLDER_BAD = 0, 1, 2, 3      # ORBX_FUSE_*
+
+_FUSE_POINT_ARRAYS = (("pos", np.float32, 3), ("normal", np.float32, 3), ("min_dist", np.float32, 1), ("max_dist", np.float32, 1), ("raw_max_dist", np.float32, 1),
+                      ("desc", np.uint8, 32), ("bad", np.uint8, 1), ("visible", np.int32, 1), ("found", np.int32, 1))
+_FUSE_OBS_ARRAYS = (("obs_kf", np.int32, 1), ("obs_idx", np.int32, 1), ("obs_stereo", np.uint8, 1), ("obs_desc", np.uint8, 32))
+
+
+def fuse_slice(searchable, points, other_obs=(), num_keyframes=None, ranks=None, kf_bad=None, th=3.0):
+    """The arrays of orbx_fuse_slice.  searchable: one dict per searchable keyframe (slot, kps (mvKeysUn), desc, u_right, kf_point (mvpMapPoints as point ids
+    or -1), Tcw (3x4 or 4x4), ow, cam = (fx, fy, cx, cy, mbf), bounds = (min_x, min_y, max_x, max_y) of the Frame, scale_factors, inv_level_sigma2,
+    log_scale_factor); points: dict(pos, normal, min_dist, max_dist (the getters' values), raw_max_dist, desc, bad, visible, found).  The observations of the
+    searchable keyframes follow from their kf_point; other_obs = (point, keyframe slot, feature, stereo, descriptor[32]) tuples of the keyframes that are not
+    searchable.  Every point's observations are put in ascending rank.  ranks default to the slot numbers, kf_bad to 0."""
+    NK = int(num_keyframes) if num_keyframes is not None else 1 + max([int(k["slot"]) for k in searchable] + [int(o[1]) for o in other_obs])
+    rk = np.arange(NK, dtype=np.int32) if ranks is None else np.ascontiguousarray(ranks, np.int32)
+    pts = {k: np.ascontiguousarray(points[k], dt).reshape((-1, w) if w > 1 else (-1,)) for k, dt, w in _FUSE_POINT_ARRAYS}
+    P = len(pts["bad"])
+    per = [[] for _ in range(P)]
+    for k in searchable:
+        ur, d = np.asarray(k["u_right"], np.float32), np.asarray(k["desc"], np.uint8)
+        for f, p in enumerate(np.asarray(k["kf_point"], np.int32)):
+            if p >= 0:
+                per[int(p)].append((int(rk[int(k["slot"])]), int(k["slot"]), f, 1 if ur[f] >= 0 else 0, d[f]))
+    for p, kf, f, st, d in other_obs:
+        per[int(p)].append((int(rk[int(kf)]), int(kf), int(f), 1 if st else 0, np.asarray(d, np.uint8)))
+    for o in per:
+        o.sort(key=lambda t: t[0])
+    flat = [t for o in per for t in o]
+    off = np.zeros(P + 1, np.int32)
+    off[1:] = np.cumsum([len(o) for o in per])
+    out = dict(pts, kf_rank=rk, kf_bad=np.zeros(NK, np.uint8) if kf_bad is None else np.ascontiguousarray(kf_bad, np.uint8), searchable=list(searchable), obs_offset=off,
+               obs_kf=np.array([t[1] for t in flat], np.int32).reshape(-1), obs_idx=np.array([t[2] for t in flat], np.int32).reshape(-1),
+               obs_stereo=np.array([t[3] for t in flat], np.uint8).reshape(-1), obs_desc=np.array([t[4] for t in flat], np.uint8).reshape(-1, 32), th=float(th))
+    return out
+
+
+def fuse_marshal(map_slice, keep, profile_kernels=False):
+    """orbx_fuse_slice of a dict (fuse_slice's keys); what the struct points to is appended to `keep`, which must outlive the call"""
+    a = {k: np.ascontiguousarray(map_slice[k], dt).reshape(-1) for k, dt in (("kf_rank", np.int32), ("kf_bad", np.uint8), ("obs_offset", np.int32))}
+    for k, dt, _ in _FUSE_POINT_ARRAYS + _FUSE_OBS_ARRAYS:
+        a[k] = np.ascontiguousarray(map_slice[k], dt).reshape(-1)
+    NK, P, T0 = len(a["kf_rank"]), len(a["bad"]), len(a["obs_kf"])
+    if len(a["kf_bad"]) != NK or len(a["obs_offset"]) != P + 1 or any(len(a[k]) != P * w for k, _, w in _FUSE_POINT_ARRAYS) or any(len(a[k]) != T0 * w for k, _, w in _FUSE_OBS_ARRAYS):
+        raise ValueError("fuse slice: array sizes do not agree")
+    S = len(map_slice["searchable"])
+    tab = (FuseKeyFrame * max(S, 1))()
+    for i, k in enumerate(map_slice["searchable"]):
+        kp, d = np.ascontiguousarray(k["kps"], KEYPOINT_DTYPE), np.ascontiguousarray(k["desc"], np.uint8).reshape(-1)
+        ur, kfp = np.ascontiguousarray(k["u_right"], np.float32).reshape(-1), np.ascontiguousarray(k["kf_point"], np.int32).reshape(-1)
+        sf, s2 = np.ascontiguousarray(k["scale_factors"], np.float32).reshape(-1), np.ascontiguousarray(k["inv_level_sigma2"], np.float32).reshape(-1)
+        n = len(kp)
+        if len(d) != 32 * n or len(ur) != n or len(kfp) != n or len(s2) != len(sf):
+            raise ValueError("fuse slice: searchable keyframe %d: array sizes do not agree" % i)
+        keep.append((kp, d, ur, kfp, sf, s2))
+        T = np.asarray(k["Tcw"], np.float32).reshape(-1, 4)[:3].reshape(12)
+        minx, miny, maxx, maxy = (np.float32(b) for b in k["bounds"])
+        fx, fy, cx, cy, mbf = (float(np.float32(c)) for c in k["cam"])
+        tab[i] = FuseKeyFrame(int(k["slot"]), n, kp.ctypes.data, d.ctypes.data, ur.ctypes.data, kfp.ctypes.data, (ctypes.c_float * 12)(*T.tolist()),
+                              (ctypes.c_float * 3)(*np.asarray(k["ow"], np.float32).reshape(3).tolist()), fx, fy, cx, cy, mbf, float(minx), float(miny),
+                              float(np.float32(64) / (maxx - minx)), float(np.float32(48) / (maxy - miny)), int(minx), int(maxx), int(miny), int(maxy), sf.ctypes.data, s2.ctypes.data,
+                              float(np.float32(k["log_scale_factor"])), len(sf))
+    keep.append((a, tab))
+    p = {k: v.ctypes.data for k, v in a.items()}
+    return FuseSlice(NK, p["kf_rank"], p["kf_bad"], S, ctypes.addressof(tab), P, T0, p["pos"], p["normal"], p["min_dist"], p["max_dist"], p["raw_max_dist"], p["desc"], p["bad"],
+                     p["visible"], p["found"], p["obs_offset"], p["obs_kf"], p["obs_idx"], p["obs_stereo"], p["obs_desc"], float(map_slice.get("th", 3.0)),
+                     1 if profile_kernels else 0), a
+
+
+def fuse_next_slice(map_slice, result):
+    """The slice as a SearchInNeighbors / FuseApply call left it (its result dict): what the next call, orbx_mappoint_refresh or orbx_covis_update_connections
+    starts from.  An observation keeps the descriptor of its feature."""
+    sidx = {int(k["slot"]): i for i, k in enumerate(map_slice["searchable"])}
+    old = {(int(kf), int(f)): d for kf, f, d in zip(np.asarray(map_slice["obs_kf"]).reshape(-1), np.asarray(map_slice["obs_idx"]).reshape(-1),
+                                                     np.asarray(map_slice["obs_desc"], np.uint8).reshape(-1, 32))}
+    desc = [np.asarray(map_slice["searchable"][sidx[int(kf)]]["desc"], np.uint8).reshape(-1, 32)[int(f)] if int(kf) in sidx else old[(int(kf), int(f))]
+            for kf, f in zip(result["obs_kf"], result["obs_idx"])]
+    out = dict(map_slice, bad=result["point_bad"].copy(), visible=result["visible"].copy(), found=result["found"].copy(), desc=result["desc"].copy(),
+               obs_offset=result["obs_offset"].copy(), obs_kf=result["obs_kf"].copy(), obs_idx=result["obs_idx"].copy(), obs_stereo=result["obs_stereo"].copy(),
+               obs_desc=np.array(desc, np.uint8).reshape(-1, 32))
+    out["searchable"] = [dict(k, kf_point=result["kf_point"][i].copy()) for i, k in enumerate(map_slice["searchable"])]
+    return out
+
+
 class ORBmatcher(_Handle):
     """Mirror of the Hamming paths of ORB_SLAM2::ORBmatcher (reference include/ORBmatcher.h:57-215)."""
     _destroy = "orbx_matcher_destroy"
@@ -709,6 +818,110 @@ class ORBmatcher(_Handle):
         """(device ms of the last chain, kernel launches, ms inside k_triangulate - 0 unless profile_kernels)"""
         self._L.orbx_new_points_last_timing.argtypes = [ctypes.c_void_p] * 4
         return self._timing("orbx_new_points_last_timing", ctypes.c_float, ctypes.c_int, ctypes.c_float)
+
+    def _fuse_results(self, S, calls, lmax, full, log_capacity, candidates_capacity, obs_capacity):
+        """the result arrays of a SearchInNeighbors / FuseApply call at their worst-case sizes (or the given capacities) -> (dict, FuseResult, counters)"""
+        sk = [S.searchable_n[i] for i in range(S.num_searchable)]
+        empty = S.empty_features
+        P, i4, u1, f4 = S.num_points, np.int32, np.uint8, np.float32
+        lc = int(S.log_worst if log_capacity is None else log_capacity)
+        cc = int(S.cand_worst if candidates_capacity is None else candidates_capacity)
+        oc = int(S.num_obs + empty if obs_capacity is None else obs_capacity)
+        o = dict(log=np.zeros(max(lc, 1), FUSE_DECISION_DTYPE), nfused=np.zeros(max(calls, 1), i4), candidates=np.zeros(max(cc, 1), i4), kf_point=np.zeros(max(sum(sk), 1), i4),
+                 point_bad=np.zeros(max(P, 1), u1), replaced=np.zeros(max(P, 1), i4), point_obs=np.zeros(max(P, 1), i4), visible=np.zeros(max(P, 1), i4), found=np.zeros(max(P, 1), i4),
+                 desc=np.zeros((max(P, 1), 32), u1), obs_offset=np.zeros(P + 1, i4), obs_kf=np.zeros(max(oc, 1), i4), obs_idx=np.zeros(max(oc, 1), i4), obs_stereo=np.zeros(max(oc, 1), u1))
+        nlog, ncand = ctypes.c_int32(), ctypes.c_int32()
+        fl = {}
+        if full:
+            fl = dict(active=np.zeros((calls, lmax), u1), u=np.zeros((calls, lmax), f4), v=np.zeros((calls, lmax), f4), ur=np.zeros((calls, lmax), f4), level=np.zeros((calls, lmax), i4),
+                      radius=np.zeros((calls, lmax), f4), best_idx=np.zeros((calls, lmax), i4), best_dist=np.zeros((calls, lmax), i4))
+        R = FuseResult(o["log"].ctypes.data, lc, ctypes.addressof(nlog), o["nfused"].ctypes.data, o["candidates"].ctypes.data, cc, ctypes.addressof(ncand), o["kf_point"].ctypes.data,
+                       o["point_bad"].ctypes.data, o["replaced"].ctypes.data, o["point_obs"].ctypes.data, o["visible"].ctypes.data, o["found"].ctypes.data, o["desc"].ctypes.data,
+                       o["obs_offset"].ctypes.data, o["obs_kf"].ctypes.data, o["obs_idx"].ctypes.data, o["obs_stereo"].ctypes.data, oc, lmax,
+                       *[fl[k].ctypes.data if full else None for k in ("active", "u", "v", "ur", "level", "radius", "best_idx", "best_dist")])
+        o.update(fl)
+        return o, R, (nlog, ncand, sk)
+
+    @staticmethod
+    def _fuse_finish(o, S, calls, cnt, full, list_lengths):
+        nlog, ncand, sk = cnt
+        P, nobs = S.num_points, int(o["obs_offset"][S.num_points])
+        out = dict(log=o["log"][:nlog.value].copy(), nfused=o["nfused"][:calls].copy(), candidates=o["candidates"][:ncand.value].copy(),
+                   kf_point=[o["kf_point"][sum(sk[:i]):sum(sk[:i + 1])].copy() for i in range(len(sk))], obs_offset=o["obs_offset"].copy(),
+                   obs_kf=o["obs_kf"][:nobs].copy(), obs_idx=o["obs_idx"][:nobs].copy(), obs_stereo=o["obs_stereo"][:nobs].copy())
+        for k in ("point_bad", "replaced", "point_obs", "visible", "found", "desc"):
+            out[k] = o[k][:P].copy()
+        if full:
+            lens = list_lengths + [ncand.value]
+            for k in ("active", "u", "v", "ur", "level", "radius", "best_idx", "best_dist"):
+                out[k] = [o[k][c, :lens[c]].copy() for c in range(calls)]
+        return out
+
+    @staticmethod
+    def _fuse_shape(S, a, map_slice, n_cur, targets):
+        """sizes the wrappers allocate by: the features of the searchable keyframes, their empty features, the worst-case log and candidate list"""
+        sn = [len(np.asarray(k["kf_point"]).reshape(-1)) for k in map_slice["searchable"]]
+        by_slot = {int(k["slot"]): n for k, n in zip(map_slice["searchable"], sn)}
+        S.searchable_n = sn
+        S.empty_features = int(sum((np.asarray(k["kf_point"]).reshape(-1) < 0).sum() for k in map_slice["searchable"]))
+        tl = [] if targets is None else [int(t) for t in targets]
+        S.cand_worst = min(S.num_points, sum(by_slot.get(t, 0) for t in tl))
+        S.log_worst = len(tl) * n_cur + S.cand_worst if targets is not None else n_cur
+
+    def SearchInNeighbors(self, map_slice, current, targets, full=False, profile_kernels=False, log_capacity=None, candidates_capacity=None, obs_capacity=None):
+        """Steps 2 and 3 of LocalMapping::SearchInNeighbors (reference src/LocalMapping.cc:666-713) as one call: ORBmatcher::Fuse of every target keyframe on the
+        current keyframe's points, in order, then of the current keyframe on the points the targets hold then.  map_slice: fuse_slice(); current, targets:
+        keyframe slots.  Returns dict(log (FUSE_DECISION_DTYPE, execution order), nfused (T+1), candidates, kf_point (one array per searchable keyframe),
+        point_bad, replaced, point_obs, visible, found, desc, obs_offset, obs_kf, obs_idx, obs_stereo[, per call: active, u, v, ur, level, radius, best_idx,
+        best_dist]).  The capacities default to the worst case."""
+        return self.search_in_neighbors_prepare(map_slice, current, targets, full, profile_kernels, log_capacity, candidates_capacity, obs_capacity)()
+
+    def search_in_neighbors_prepare(self, map_slice, current, targets, full=False, profile_kernels=False, log_capacity=None, candidates_capacity=None, obs_capacity=None):
+        """SearchInNeighbors in two steps: the arrays marshalled once, and a function that makes the C call on them and returns the result dict; its attribute `raw`
+        makes the C call alone and returns the status code (what tools/latency_search_in_neighbors.py times)."""
+        L = self._L
+        L.orbx_search_in_neighbors.argtypes = [ctypes.c_void_p, ctypes.POINTER(FuseSlice), ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FuseResult)]
+        keep = []
+        S, a = fuse_marshal(map_slice, keep, profile_kernels)
+        tg = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        T = len(tg)
+        n_cur = max([len(np.asarray(k["kf_point"]).reshape(-1)) for k in map_slice["searchable"] if int(k["slot"]) == int(current)] + [0])
+        self._fuse_shape(S, a, map_slice, n_cur, tg)
+        lmax = max(n_cur, S.cand_worst, 1)
+        o, R, cnt = self._fuse_results(S, T + 1, lmax, full, log_capacity, candidates_capacity, obs_capacity)
+        keep += [tg, o, R, cnt]
+
+        def raw():
+            return L.orbx_search_in_neighbors(self._h, ctypes.byref(S), int(current), tg.ctypes.data, T, ctypes.byref(R))
+
+        def call():
+            _check(raw())
+            return self._fuse_finish(o, S, T + 1, cnt, full, [n_cur] * T)
+        call.keep, call.raw = keep, raw
+        return call
+
+    def FuseApply(self, map_slice, kf, points, active, best_idx, best_dist, log_capacity=None, obs_capacity=None):
+        """The apply stage of one ORBmatcher::Fuse call (reference src/ORBmatcher.cc:1150-1171) for keyframe slot kf on search results the caller supplies:
+        points (the list, -1 = NULL), active, best_idx, best_dist per entry.  Returns SearchInNeighbors' dict with one call."""
+        L = self._L
+        L.orbx_fuse_apply.argtypes = [ctypes.c_void_p, ctypes.POINTER(FuseSlice), ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.POINTER(FuseResult)]
+        keep = []
+        S, a = fuse_marshal(map_slice, keep)
+        lst, act = np.ascontiguousarray(points, np.int32).reshape(-1), np.ascontiguousarray(active, np.uint8).reshape(-1)
+        bi, bd = np.ascontiguousarray(best_idx, np.int32).reshape(-1), np.ascontiguousarray(best_dist, np.int32).reshape(-1)
+        n = len(lst)
+        if len(act) != n or len(bi) != n or len(bd) != n:
+            raise ValueError("FuseApply: the list arrays differ in length")
+        self._fuse_shape(S, a, map_slice, n, None)
+        S.cand_worst, S.log_worst = 0, n
+        o, R, cnt = self._fuse_results(S, 1, max(n, 1), False, log_capacity, 0, obs_capacity)
+        _check(L.orbx_fuse_apply(self._h, ctypes.byref(S), int(kf), lst.ctypes.data, act.ctypes.data, bi.ctypes.data, bd.ctypes.data, n, ctypes.byref(R)))
+        return self._fuse_finish(o, S, 1, cnt, False, [n])
+
+    def search_in_neighbors_last_timing(self):
+        """(device ms of the last chain, kernel launches, ms inside the apply kernels - 0 unless profile_kernels)"""
+        self._L.orbx_search_in_neighbors_last_timing.argtypes = [ctypes.c_void_p] * 4
+        return self._timing("orbx_search_in_neighbors_last_timing", ctypes.c_float, ctypes.c_int, ctypes.c_float)
 
     def FuseSearch(self, kf, points, chi2_gate=True):
         """Steps 2-3 of ORBmatcher::Fuse (reference src/ORBmatcher.cc:1093-1146 / 1258-1276): per map point the KeyFrame

@@ -58,6 +58,11 @@ __device__ __forceinline__ void three_maxima_wave(const int *hist, int lane, int
 struct ProjFrameDev { const orbx_keypoint *kp; const uint8_t *desc; const float *uRight; const uint8_t *occupied; const int32_t *counts; int cap;
                       float minX, minY, gwInv, ghInv; };
 
+// ORBmatcher::Fuse's search (k_fuse_best, orbx_match_proj.hip): the prepared points of one list per keyframe
+struct FusePointsDev { const float *u, *v, *ur; const int32_t *level; const float *radius; const uint8_t *active, *desc; const int32_t *counts; int cap;
+                       float kfMinX, kfMinY; };
+struct FuseLevels { float invSigma2[ORBX_MAX_LEVELS]; };
+
 struct orbx_matcher : OrbxHandle {
     int maxFeatures = 0, maxPairs = 0;
     hipEvent_t evDep = nullptr, evDone[2] = {nullptr, nullptr};
@@ -113,6 +118,13 @@ struct orbx_matcher : OrbxHandle {
     OrbxCallTimer npTimer;            // (its events are made by the first call)
     std::vector<hipEvent_t> npTriEv;  // profile_kernels: one pair per neighbour
     int npTriTimed = 0;
+    // SearchInNeighbors (orbx_fuse_chain.hip): the mutable map state, the per-call prepare / search arrays and the rank tables
+    OrbxOwnedBuf<uint8_t> fcWork;
+    OrbxWorkPlan fcPlan;
+    OrbxCallTimer fcTimer;            // (its events are made by the first call)
+    std::vector<hipEvent_t> fcApplyEv;  // profile_kernels: one pair per Fuse call
+    int fcApplyTimed = 0;
+    std::vector<int32_t> fcOrder, fcPos, fcSIndex;      // slots in ascending rank, slot -> position, slot -> searchable index
     ~orbx_matcher()
     {
         hipEvent_t *const one[] = {&evDep, &evDep2, &evPyr[0], &evPyr[1], &evDone[0], &evDone[1]};
@@ -120,6 +132,7 @@ struct orbx_matcher : OrbxHandle {
         for (int r = 0; r < MATCH_PROF_RING; r++)
             for (hipEvent_t e : {ev0[r], ev1[r], evMid[r]}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : npTriEv) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : fcApplyEv) if (e) (void)hipEventDestroy(e);
         if (sfHost) (void)hipHostFree(sfHost);
     }
 };
@@ -196,6 +209,8 @@ int check_producer_status(orbx_matcher *m);
 FeatDev to_dev(const orbx_feature_set *s);
 /* stage one frame of host features per side (nsides = 1 or 2) into the matcher's staging buffer; d[side] receives the device view */
 int stage_host(orbx_matcher *m, const orbx_feature_set *const *h, orbx_feature_set *const *d, int nsides);
+/* k_fuse_best (orbx_match_proj.hip) for one keyframe with chi2_gate = 1: P.cap slots, the list's length read on the device from P.counts */
+void launch_fuse_best(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int32_t *bestIdx, int32_t *bestDist);
 }  // namespace orbx_match
 
 #endif

@@ -583,9 +583,7 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_last_greedy(ProjFr
 // loop only couples them through Replace / AddObservation, which stay on the host in the shim).
 // One wave per map point, lanes over the KeyFrame's features.
 // ---------------------------------------------------------------------------------------------
-struct FusePointsDev { const float *u, *v, *ur; const int32_t *level; const float *radius; const uint8_t *active, *desc; const int32_t *counts; int cap;
-                       float kfMinX, kfMinY; };
-struct FuseLevels { float invSigma2[ORBX_MAX_LEVELS]; };
+// (FusePointsDev and FuseLevels live in orbx_match_internal.h: the chain of orbx_fuse_chain.hip launches this kernel too)
 
 __global__ __launch_bounds__(256) void k_fuse_best(ProjFrameDev F, FusePointsDev P, FuseLevels LV, int chi2Gate, int32_t *__restrict__ bestIdx,
                                                    int32_t *__restrict__ bestDist, int stride)
@@ -636,6 +634,12 @@ __global__ __launch_bounds__(256) void k_fuse_best(ProjFrameDev F, FusePointsDev
         bestIdx[o] = best == KEY64_EMPTY ? -1 : (int)(best & 0xffff);
         bestDist[o] = best == KEY64_EMPTY ? 256 : (int)(best >> 32);
     }
+}
+
+// one (keyframe, list) problem with chi2_gate = 1 on `st`: results at bestIdx[i] / bestDist[i]; the list's length is read on the device (P.counts)
+void orbx_match::launch_fuse_best(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int32_t *bestIdx, int32_t *bestDist)
+{
+    hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)((P.cap + 3) / 4), 1u), dim3(256), 0, st, F, P, LV, 1, bestIdx, bestDist, P.cap);
 }
 
 static int fuse_launch(orbx_matcher *m, const ProjFrameDev &F, const FusePointsDev &P, int nframes, const float *inv_level_sigma2, int nlevels, int chi2_gate)
