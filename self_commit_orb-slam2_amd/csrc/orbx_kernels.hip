@@ -12,6 +12,7 @@
 // the un-fused scalar reference.
 #include <algorithm>
 #include "orbx_internal.h"
+#include "orbx_trig.h"
 
 namespace {
 
@@ -956,67 +957,9 @@ __global__ __launch_bounds__(256) void k_octree(const OrbxGeom *__restrict__ g, 
     }
 }
 
-// sin/cos of the keypoint angle: glibc's sinf/cosf algorithm in double, restated so the device
-// rounds like the libm the reference calls (oracle/prims.h op_sincosf, tests/test_sincos.py).
-__device__ __forceinline__ float sinf_poly_d(double x, double x2, int n, bool neg)
-{
-    // coefficients of glibc 2.35 __sincosf_table[0]; table[1] is its negation (neg)
-    const double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10, c4 = 0x1.99343027bf8c3p-16;
-    const double s1 = -0x1.555545995a603p-3, s2 = 0x1.1107605230bc4p-7, s3 = -0x1.994eb3774cf24p-13;
-    if ((n & 1) == 0) {
-        double x3 = x * x2, t1 = s2 + x2 * s3, x7 = x3 * x2, s = x + x3 * s1;
-        return (float)(s + x7 * t1);
-    } else {
-        double k0 = neg ? -c0 : c0, k1 = neg ? -c1 : c1, k2 = neg ? -c2 : c2, k3 = neg ? -c3 : c3, k4 = neg ? -c4 : c4;
-        double x4 = x2 * x2, u2 = k3 + x2 * k4, u1 = k0 + x2 * k1, x6 = x4 * x2, c = u1 + x4 * k2;
-        return (float)(c + x6 * u2);
-    }
-}
-
-__device__ __forceinline__ void sincosf_glibc(float y, float &sn, float &cs)
-{
-    double x = y;
-    const uint32_t top = (__float_as_uint(y) >> 20) & 0x7ff;
-    if (top < ((0x3f490fdbu >> 20) & 0x7ff)) {   // |y| < pi/4 (abstop12 compare)
-        double x2 = x * x;
-        if (top < ((0x39800000u >> 20) & 0x7ff)) { sn = y; cs = 1.0f; return; }   // |y| < 2^-12
-        sn = sinf_poly_d(x, x2, 0, false);
-        cs = sinf_poly_d(x, x2, 1, false);
-        return;
-    }
-    double r = x * 0x1.45F306DC9C883p+23;
-    int n = ((int)r + 0x800000) >> 24;
-    x = x - n * 0x1.921FB54442D18p0;
-    const double sgn = ((n & 3) == 1 || (n & 3) == 2) ? -1.0 : 1.0;
-    const bool neg = (n & 2) != 0;
-    sn = sinf_poly_d(x * sgn, x * x, n, neg);
-    cs = sinf_poly_d(x * sgn, x * x, n ^ 1, neg);
-}
-
-// ------------------------------------------------------------------------------------
-// Orientation: IC_Angle (src/ORBextractor.cc:108-161) = integer moments over the
-// 749-pixel disc of radius 15 on the UNBLURRED level, then cv::fastAtan2.  Half a wave per
-// keypoint, lanes own the disc rows; integer sums are exact in any order.
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ float fast_atan2_deg(float y, float x)
-{
-    const float scale = (float)(180.0 / 3.14159265358979323846);
-    const float p1 = 0.9997878412794807f * scale, p3 = -0.3258083974640975f * scale, p5 = 0.1555786518463281f * scale,
-                p7 = -0.04432655554792128f * scale;
-    float ax = fabsf(x), ay = fabsf(y), a, c, c2;
-    if (ax >= ay) {
-        c = ay / (ax + 2.220446049250313e-16f);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = ax / (ay + 2.220446049250313e-16f);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
-    if (x < 0) a = 180.f - a;
-    if (y < 0) a = 360.f - a;
-    return a;
-}
+// Orientation: IC_Angle (src/ORBextractor.cc:108-161) = integer moments over the 749-pixel disc of radius 15 on the UNBLURRED level (k_orient_describe:
+// half a wave per keypoint, lanes own the disc rows; integer sums are exact in any order), then cv::fastAtan2 and the libm-exact sine / cosine of the
+// angle: fast_atan2_deg and sincosf_glibc of csrc/orbx_trig.h, branch-free, compiled for the CPU as well by tests/test_orient_trig_host.py.
 
 // ------------------------------------------------------------------------------------
 // 7x7 Gaussian, sigma 2, BORDER_REFLECT_101, u8 fixed point (cv::GaussianBlur on the
@@ -1454,16 +1397,26 @@ __global__ __launch_bounds__(OB_THREADS) void k_octree_blur(const OrbxGeom *__re
 
 // ------------------------------------------------------------------------------------
 // Orientation + descriptor in one pass over the keypoints (IC_Angle, src/ORBextractor.cc:108-161, then
-// computeOrbDescriptor, :173-227, and the final KeyPoint, :1175-1190 / :1651-1660).  One wave per
-// keypoint, four per workgroup.  Everything a keypoint needs from HBM is requested up front with
-// row-wise dword loads whose addresses depend on the keypoint alone:
-//   the 31 x 31 disc of the UNBLURRED level   lane = (disc row, half row): 16 bytes each, integer moments in registers;
+// computeOrbDescriptor, :173-227, and the final KeyPoint, :1175-1190 / :1651-1660).  TWO keypoints per wave - half-wave
+// h = lane >> 5 owns slot 2 * wave + h - and eight per workgroup of four waves.  Everything a keypoint needs from HBM is
+// requested up front with row-wise loads whose addresses depend on the keypoint alone:
+//   the 31 x 31 disc of the UNBLURRED level   lane of the half = disc row: 2 x 16 bytes, integer moments in registers, summed over the half by DPP;
 //   the 37 x 37 patch of the BLURRED level    (rotated test points stay within 18.39 px: |coordinate| <= 18) as
-//                                              37 rows x 10 aligned dwords -> LDS.
-// The steered 512 samples are then LDS byte reads: the former kernel issued them as 8 scattered byte gathers per lane
-// AFTER the angle was known (three dependent memory levels, up to 64 cache lines per instruction); now one memory
-// round trip covers both stages and a load instruction touches ~7 lines.  fastAtan2 and the libm-exact sin / cos run
-// once per workgroup on four lanes (one per keypoint) between two barriers instead of on all 64 lanes of every wave.
+//                                              37 rows x 5 aligned 8-byte units -> LDS, 30 lanes of the half x 7 rounds (six rows apart).
+// The steered 512 samples are then LDS byte reads, 8 rounds of 32 test pairs per keypoint; a ballot's two words are the two keypoints' bits.
+// fastAtan2 and the libm-exact sin / cos (orbx_trig.h, branch-free) run once per workgroup on eight lanes (one per keypoint) between two barriers.
+// What a wave does per KEYPOINT only (level search, counts, output index) is scalar work for both halves and one select per lane; a slot past its
+// level's count, or past the frame's last slot, leaves its half idle and the other half untouched.
+// Measured (profiles/orient_describe_ab.json; parent = one keypoint per wave, four per workgroup, branching trig on <= 4 of 64 lanes):
+//   this form                          headline 320.3k against 315.8k frames/s (median of five alternating runs, ranges apart), outputs identical;
+//   the parent kernel + branch-free trig alone     316.3k: inside the parent's range, not kept on its own;
+//   this form with EIGHT waves (16 keypoints) per workgroup     300.2k, 5 % BELOW the parent: twice as many waves stand at each of the three barriers;
+// vector instructions per batch 48.4 M against 67.9 M (179 against 251 per slot), alone 0.186 against 0.198 ms per batch; extract-only +2.0 %, the
+// stereo workload not separated from the parent by three runs (median -1.0 %).
+// Earlier, on the one-keypoint-per-wave kernel, measured and not kept: a workgroup taking TWO groups of four slots in a row (the prologue paid once per
+// eight keypoints: 63.2 M instead of 67.9 M vector instructions, but 0.230 instead of 0.207 ms alone and 271k instead of 282k frames/s - the kernel
+// lives on the number of keypoints that have their pixel loads in flight; here that number per wave slot doubles instead of halving); requesting the
+// keypoint record and the pixels BEFORE the counts are known (clamped coordinates for the ~7 % unused slots: one dependent level less, 7 % slower).
 // ------------------------------------------------------------------------------------
 // per-level constants of the geometry as a kernel ARGUMENT: the level lookup and the addresses come from a few wide scalar loads of the
 // kernarg segment instead of a chain of dependent loads through OrbxGeom (the prologue is most of a wave's latency here)
@@ -1481,34 +1434,43 @@ struct OdLevels {
 // the blurred-patch loads 0.114, without the disc load 0.122.  Its L2 misses (TCC_EA0_RDREQ 4.14 M x 128 B = 530 MB per 256 frames) are the two
 // pyramids fetched ONCE (2 x 243 MB: the patches of ~1000 keypoints cover every 128-byte line of a frame), at the ~2.5 TB/s that scattered 128-byte
 // lines reach here (TCC hit rate 81 %, L1 63 %); the byte-granular "algorithmic" 331 MB of SURVEY 8d is not reachable by any visiting order.
-#define OD_WPB 4
+#define OD_WPB 4                 /* waves of a workgroup */
+#define OD_KPB (2 * OD_WPB)      /* its keypoints: one per half-wave */
 #define OD_R 18
 #define OD_DW 10
 #define OD_ROWS (2 * OD_R + 1)
 #define OD_PATCH_DW (OD_ROWS * OD_DW)
 
-__global__ __launch_bounds__(64 * OD_WPB) void k_orient_describe(const OdLevels A, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
-                                                                 const uint8_t *__restrict__ pyr, const uint8_t *__restrict__ blur, OrbxLevelKp *__restrict__ lvlKp,
-                                                                 const int *__restrict__ lvlCnt, const int *__restrict__ outBase, orbx_keypoint *__restrict__ outKp,
-                                                                 uint8_t *__restrict__ outDesc, int *__restrict__ outCnt, const int *__restrict__ status,
-                                                                 int *__restrict__ outStatus)
+// One step of a slot's level search on the scalar unit: slot >= base ? (level + 1, base) : (level, kept).  Written as compare / select / add-with-carry by
+// hand: from the C++ form the compiler builds the level as a chain of VECTOR add-with-carry and select instructions (22 per slot) although every operand is
+// uniform.
+__device__ __forceinline__ void od_level_step(int &l, int &kb, int slot, int b)
 {
-    __shared__ uint32_t sPatch[OD_WPB][OD_PATCH_DW + 2];
+    asm("s_cmp_ge_i32 %2, %3\n\ts_cselect_b32 %1, %3, %1\n\ts_addc_u32 %0, %0, 0" : "+s"(l), "+s"(kb) : "s"(slot), "s"(b) : "scc");
+}
+
+__global__ __launch_bounds__(64 * OD_WPB) void k_orient_describe(const OdLevels A, const uint8_t *__restrict__ img0, int img0Stride, size_t img0FramePitch,
+                                                                const uint8_t *__restrict__ pyr, const uint8_t *__restrict__ blur, OrbxLevelKp *__restrict__ lvlKp,
+                                                                const int *__restrict__ lvlCnt, const int *__restrict__ outBase, orbx_keypoint *__restrict__ outKp,
+                                                                uint8_t *__restrict__ outDesc, int *__restrict__ outCnt, const int *__restrict__ status,
+                                                                int *__restrict__ outStatus)
+{
+    constexpr int K = OD_KPB;
+    constexpr int NIT = OD_ROWS * (OD_DW / 2);      // 185 eight-byte units of a patch
+    __shared__ uint32_t sPatch[K][OD_PATCH_DW + 2];
     __shared__ __attribute__((aligned(16))) float sPat[256][4];                  // test pair t as floats: x0, x1, y0, y1
-    __shared__ __attribute__((aligned(16))) uint32_t sDisc[64][4];               // byte masks of the disc: lane (row, half) x 4 dwords
-    __shared__ int sMom[OD_WPB][3];
+    __shared__ __attribute__((aligned(16))) uint32_t sDisc[32][8];               // byte masks of the disc: row r x the 8 dwords of its 32-byte segment
+    __shared__ int sMom[K][3];
     __shared__ int sBase[ORBX_MAX_LEVELS];
-    __shared__ float sTrig[OD_WPB][3];
+    __shared__ float sTrig[K][3];
     XCD_REMAP_XY(bx, f);
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));     // uniform: the keypoint bookkeeping below is scalar work
-    if (threadIdx.x < 256) {     // once per workgroup: both constant tables into LDS
+    const int lane = threadIdx.x & 63, hl = lane & 31, h = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));     // uniform: the keypoint bookkeeping below is scalar work, for both halves
+    if (threadIdx.x < 256) {     // once per workgroup: both constant tables into LDS (c_od.disc[2 r + half][4] is sDisc[r][8] as it lies)
         *(float4 *)sPat[threadIdx.x] = *(const float4 *)c_od.pat[threadIdx.x];
         ((uint32_t *)sDisc)[threadIdx.x] = ((const uint32_t *)c_od.disc)[threadIdx.x];
     }
     const int *cnts = lvlCnt + f * A.nlevels;
-    // where each level's keypoints start in the frame's output list (level 0 .. n-1 in order, src/ORBextractor.cc:1577-1668): once per workgroup,
-    // lane = level, into LDS (k_blur's first workgroup used to leave it in global memory; the blur no longer has to run behind the quadtree for it)
     if (!outBase && threadIdx.x < (unsigned)A.nlevels) {      // (batches: k_blur's first workgroup left the prefix in outBase)
         int run = 0;
         for (int i = 0; i < (int)threadIdx.x; i++) run += cnts[i];
@@ -1518,74 +1480,79 @@ __global__ __launch_bounds__(64 * OD_WPB) void k_orient_describe(const OdLevels 
         int tot = 0;
         for (int i = 0; i < A.nlevels; i++) tot += cnts[i];
         outCnt[f] = tot;
-        // the capacity words travel with the results: the running batch's words are cleared by the NEXT batch, a consumer of this
-        // result buffer reads the snapshot (which the producer only overwrites behind the consumer's event, like the results)
         outStatus[f] = status[f];
         if (f == 0) outStatus[gridDim.y] = status[gridDim.y];
     }
-    // (Measured and not kept: a workgroup taking TWO groups of four slots in a row, the table copies and the prologue paid once per eight keypoints: 63.2 M
-    // instead of 67.9 M vector instructions, but 0.230 instead of 0.207 ms alone and 271k instead of 282k frames/s - the kernel lives on the number of
-    // workgroups that have their pixel loads in flight.)
-    const int slot = bx * OD_WPB + wv;
-    // Is the slot in use?  (Measured: requesting the keypoint record and the pixels BEFORE the counts are known - clamped coordinates for
-    // the ~7 % unused slots - shortens the dependent chain by one level but is 7 % slower: 0.242 vs 0.226 ms per 256 frames.)
-    bool inRange = slot < A.kpPerFrame;
-    int l = 0, kb = 0;
+    // the wave's two slots: level, index in the level and "in use" of both as scalars, one select each per lane
+    const int slot0 = bx * K + 2 * wv, slot1 = slot0 + 1;
+    int l0 = 0, kb0 = 0, l1 = 0, kb1 = 0;
 #pragma unroll
     for (int i = 1; i < ORBX_MAX_LEVELS; i++) {      // (entries past the last level hold INT_MAX)
-        const bool ge = slot >= A.kpBase[i];
-        l += ge ? 1 : 0; kb = ge ? A.kpBase[i] : kb;
+        const int b = A.kpBase[i];
+        od_level_step(l0, kb0, slot0, b);
+        od_level_step(l1, kb1, slot1, b);
     }
-    const int idx = slot - kb;
-    inRange = inRange && idx < cnts[l];
-    const bool live = inRange;
-    const uint2 kraw = *(const uint2 *)&lvlKp[(size_t)f * A.kpPerFrame + (inRange ? slot : 0)];     // x | y << 16, score | pad: the first 8 bytes of OrbxLevelKp
+    const int idx0 = slot0 - kb0, idx1 = slot1 - kb1;
+    const bool in0 = slot0 < A.kpPerFrame && idx0 < cnts[l0], in1 = slot1 < A.kpPerFrame && idx1 < cnts[l1];
+    const bool live = h ? in1 : in0;
+    const int kk = 2 * wv + h;      // the half-wave's keypoint of the workgroup
+    const uint2 kraw = *(const uint2 *)&lvlKp[(size_t)f * A.kpPerFrame + (live ? slot0 + h : 0)];     // x | y << 16, score | pad: the first 8 bytes of OrbxLevelKp
     const int kx = (int)(kraw.x & 0xffffu), ky = (int)(kraw.x >> 16);
     const int ksc = (int)(kraw.y & 0xffu);
     const int xa = (kx - OD_R) & ~3;
     int m10 = 0, m01 = 0;
-    uint2 pw[3] = {make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};
-    uint4 wd = make_uint4(0u, 0u, 0u, 0u);
-    const int r = lane >> 1, hf = lane & 1;      // disc row r, bytes x - 15 + 16 * half .. + 15 (19 <= x < w - 19: inside the level)
-    if (inRange) {
-        const int bp = A.pitch[l], up = l ? bp : img0Stride;
-        const uint8_t *unb = l ? pyr + (size_t)f * A.pyrBytes + A.off[l] : img0 + (size_t)f * img0FramePitch;
-        const uint8_t *bl = blur + (size_t)f * A.pyrBytes + A.off[l];
-        if (r < 31) __builtin_memcpy(&wd, unb + (size_t)(ky + r - 15) * up + (kx - 15 + 16 * hf), 16);     // ONE 16-byte load per lane
-        // patch: 37 rows x 5 aligned 8-byte units
+    // patch: 37 rows x 5 aligned 8-byte units = 185 items; lane (< 30) of the half takes items lane, lane + 30, ...: the same column in every round and six
+    // rows on, so a round's address is the last one plus six pitches and its place in LDS a constant further (a seventh round for the last five items)
+    const int pr0 = (hl * 205) >> 10, pc = hl - (OD_DW / 2) * pr0;      // hl / 5, hl % 5
+    uint2 pw[7];
 #pragma unroll
-        for (int t = 0; t < 3; t++) {
-            const int item = lane + 64 * t;
-            if (item < OD_ROWS * (OD_DW / 2)) {
-                const int pr = (item * 205) >> 10, pc = item - (OD_DW / 2) * pr;      // item / 5
-                __builtin_memcpy(&pw[t], bl + (size_t)(ky - OD_R + pr) * bp + xa + 8 * pc, 8);
-            }
+    for (int t = 0; t < 7; t++) pw[t] = make_uint2(0u, 0u);
+    uint4 wl = make_uint4(0u, 0u, 0u, 0u), wr = wl;
+    if (live) {
+        const int bp0 = A.pitch[l0], bp1 = A.pitch[l1];
+        const int bp = h ? bp1 : bp0, up = h ? (l1 ? bp1 : img0Stride) : (l0 ? bp0 : img0Stride);
+        const uint8_t *unb0 = l0 ? pyr + (size_t)f * A.pyrBytes + A.off[l0] : img0 + (size_t)f * img0FramePitch;
+        const uint8_t *unb1 = l1 ? pyr + (size_t)f * A.pyrBytes + A.off[l1] : img0 + (size_t)f * img0FramePitch;
+        const uint8_t *unb = h ? unb1 : unb0;
+        const uint8_t *bl = blur + (size_t)f * A.pyrBytes;      // uniform: the lane's part of the address is a 32-bit offset
+        // disc: lane = row, bytes x - 15 .. x + 16 as two 16-byte loads (19 <= x < w - 19: inside the level)
+        if (hl < 31) {
+            const uint8_t *p = unb + (size_t)(ky + hl - 15) * up + (kx - 15);
+            __builtin_memcpy(&wl, p, 16);
+            __builtin_memcpy(&wr, p + 16, 16);
+        }
+        if (hl < 30) {
+            const uint32_t po = (uint32_t)((h ? A.off[l1] : A.off[l0]) + (ky - OD_R + pr0) * bp + xa + 8 * pc), ps = (uint32_t)(6 * bp);
+#pragma unroll
+            for (int t = 0; t < 7; t++)
+                if (t < 6 || hl < NIT - 180) __builtin_memcpy(&pw[t], bl + (po + t * ps), 8);
         }
     }
     __syncthreads();           // the tables are in LDS (the pixel loads are in flight meanwhile)
-    if (inRange && r < 31) {
-        // integer moments of the row segment: sum I and sum (u + 15) I as v_dot4_u32_u8 over the masked bytes, u + 15 = c (left half) / c + 16 (right half)
-        const uint4 mk = *(const uint4 *)sDisc[lane];
-        const uint32_t wb = hf ? 0x10101010u : 0u;
+    if (live && hl < 31) {
+        // integer moments of the row: sum I and sum (u + 15) I as v_dot4_u32_u8 over the masked bytes, u + 15 = byte index 0 .. 31
+        const uint4 ml = *(const uint4 *)&sDisc[hl][0], mr = *(const uint4 *)&sDisc[hl][4];
         uint32_t s1 = 0u, sw = 0u;
-        s1 = __builtin_amdgcn_udot4(wd.x & mk.x, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wd.x & mk.x, 0x03020100u + wb, sw, false);
-        s1 = __builtin_amdgcn_udot4(wd.y & mk.y, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wd.y & mk.y, 0x07060504u + wb, sw, false);
-        s1 = __builtin_amdgcn_udot4(wd.z & mk.z, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wd.z & mk.z, 0x0b0a0908u + wb, sw, false);
-        s1 = __builtin_amdgcn_udot4(wd.w & mk.w, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wd.w & mk.w, 0x0f0e0d0cu + wb, sw, false);
+        s1 = __builtin_amdgcn_udot4(wl.x & ml.x, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wl.x & ml.x, 0x03020100u, sw, false);
+        s1 = __builtin_amdgcn_udot4(wl.y & ml.y, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wl.y & ml.y, 0x07060504u, sw, false);
+        s1 = __builtin_amdgcn_udot4(wl.z & ml.z, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wl.z & ml.z, 0x0b0a0908u, sw, false);
+        s1 = __builtin_amdgcn_udot4(wl.w & ml.w, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wl.w & ml.w, 0x0f0e0d0cu, sw, false);
+        s1 = __builtin_amdgcn_udot4(wr.x & mr.x, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wr.x & mr.x, 0x13121110u, sw, false);
+        s1 = __builtin_amdgcn_udot4(wr.y & mr.y, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wr.y & mr.y, 0x17161514u, sw, false);
+        s1 = __builtin_amdgcn_udot4(wr.z & mr.z, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wr.z & mr.z, 0x1b1a1918u, sw, false);
+        s1 = __builtin_amdgcn_udot4(wr.w & mr.w, 0x01010101u, s1, false); sw = __builtin_amdgcn_udot4(wr.w & mr.w, 0x1f1e1d1cu, sw, false);
         m10 = (int)sw - 15 * (int)s1;
-        m01 = (r - 15) * (int)s1;
+        m01 = (hl - 15) * (int)s1;
     }
-    m10 = wave_sum_dpp(m10); m01 = wave_sum_dpp(m01);        // totals as wave-uniform scalars
-    if (lane == 0) { sMom[wv][0] = m01; sMom[wv][1] = m10; sMom[wv][2] = live ? slot : -1; }
+    m10 = halfwave_sum_dpp(m10); m01 = halfwave_sum_dpp(m01);        // each half's totals in its last lane (which owns no disc row)
+    if (hl == 31) { sMom[kk][0] = m01; sMom[kk][1] = m10; sMom[kk][2] = live ? slot0 + h : -1; }
     if (live) {
 #pragma unroll
-        for (int t = 0; t < 3; t++) {
-            const int item = lane + 64 * t;
-            if (item < OD_ROWS * (OD_DW / 2)) *(uint2 *)&sPatch[wv][2 * item] = pw[t];
-        }
+        for (int t = 0; t < 7; t++)
+            if (hl < 30 && (t < 6 || hl < NIT - 180)) *(uint2 *)&sPatch[kk][2 * (hl + 30 * t)] = pw[t];
     }
     __syncthreads();
-    if (threadIdx.x < OD_WPB && sMom[threadIdx.x][2] >= 0) {
+    if (threadIdx.x < K && sMom[threadIdx.x][2] >= 0) {      // one lane per keypoint of the workgroup; branch-free, so K lanes cost what one costs
         const float ang = fast_atan2_deg((float)sMom[threadIdx.x][0], (float)sMom[threadIdx.x][1]);
         const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
         float sn, cs;
@@ -1595,36 +1562,38 @@ __global__ __launch_bounds__(64 * OD_WPB) void k_orient_describe(const OdLevels 
         o->angle = ang; o->ca = cs; o->sb = sn;        // (read back by the stage taps and by nothing else)
     }
     __syncthreads();
-    if (!live) return;
-    const float a = sTrig[wv][0], b = sTrig[wv][1];
-    const uint8_t *pb = (const uint8_t *)sPatch[wv] + OD_R * (4 * OD_DW) + (kx - xa);     // the keypoint's own pixel
-    unsigned long long bits[4];
+    if (!live) return;      // (an idle half leaves; the other half's ballots then hold zeros in its bits)
+    const float a = sTrig[kk][0], b = sTrig[kk][1];
+    const uint8_t *pb = (const uint8_t *)sPatch[kk] + OD_R * (4 * OD_DW) + (kx - xa);     // the keypoint's own pixel
+    uint32_t dw[8];
     typedef float f2_t __attribute__((ext_vector_type(2)));
 #pragma unroll
-    for (int rd = 0; rd < 4; rd++) {
-        // both points of test pair 64 rd + lane at once (v_pk_mul_f32 / v_pk_add_f32: every product and sum is rounded on its own, exactly
+    for (int rd = 0; rd < 8; rd++) {
+        // both points of test pair 32 rd + lane-of-half at once (v_pk_mul_f32 / v_pk_add_f32: every product and sum is rounded on its own, exactly
         // like the scalar expressions of src/ORBextractor.cc:192-193 compiled without contraction)
-        const float4 pt = *(const float4 *)sPat[64 * rd + lane];
+        const float4 pt = *(const float4 *)sPat[32 * rd + hl];
         const f2_t xs = {pt.x, pt.y}, ys = {pt.z, pt.w};
         const f2_t rr = xs * b + ys * a, cc = xs * a - ys * b;
         // cvRound of both coordinates, then row * 40 + column: small integers, exact in float
         const int o0 = (int)__builtin_fmaf(__builtin_rintf(rr.x), (float)(4 * OD_DW), __builtin_rintf(cc.x));
         const int o1 = (int)__builtin_fmaf(__builtin_rintf(rr.y), (float)(4 * OD_DW), __builtin_rintf(cc.y));
         const int t0 = pb[o0], t1 = pb[o1];
-        bits[rd] = __ballot(t0 < t1);
+        const unsigned long long bits = __ballot(t0 < t1);      // low word: the first half's keypoint, high word: the second's
+        dw[rd] = h ? (uint32_t)(bits >> 32) : (uint32_t)bits;
     }
-    const int outIdx = (outBase ? outBase[f * A.nlevels + l] : sBase[l]) + idx;      // (< outCap: the output capacity is the sum of the levels' capacities)
-    if (outIdx >= A.outCap) return;
-    unsigned long long *d64 = (unsigned long long *)(outDesc + ((size_t)f * A.outCap + outIdx) * 32);
-    if (lane < 4) d64[lane] = lane == 0 ? bits[0] : lane == 1 ? bits[1] : lane == 2 ? bits[2] : bits[3];
-    if (lane == 0) {
-        orbx_keypoint o;
-        const float sc = A.scale[l];
-        o.x = l ? (float)kx * sc : (float)kx;
-        o.y = l ? (float)ky * sc : (float)ky;
-        o.size = (float)A.patch[l]; o.angle = sTrig[wv][2]; o.response = (float)ksc; o.octave = l; o.class_id = -1;
-        outKp[(size_t)f * A.outCap + outIdx] = o;
-    }
+    const int ob0 = outBase ? outBase[f * A.nlevels + l0] : sBase[l0], ob1 = outBase ? outBase[f * A.nlevels + l1] : sBase[l1];
+    const int outIdx = h ? ob1 + idx1 : ob0 + idx0;      // (< outCap: the output capacity is the sum of the levels' capacities)
+    if (outIdx >= A.outCap || hl != 0) return;
+    uint4 *d128 = (uint4 *)(outDesc + ((size_t)f * A.outCap + outIdx) * 32);
+    d128[0] = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    d128[1] = make_uint4(dw[4], dw[5], dw[6], dw[7]);
+    const int l = h ? l1 : l0;
+    orbx_keypoint o;
+    const float sc = h ? A.scale[l1] : A.scale[l0];
+    o.x = l ? (float)kx * sc : (float)kx;
+    o.y = l ? (float)ky * sc : (float)ky;
+    o.size = (float)(h ? A.patch[l1] : A.patch[l0]); o.angle = sTrig[kk][2]; o.response = (float)ksc; o.octave = l; o.class_id = -1;
+    outKp[(size_t)f * A.outCap + outIdx] = o;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1964,7 +1933,7 @@ int orbx_launch_pyr_band_fast(const OrbxLaunch &L, int l)
 
 int orbx_launch_orient_describe(const OrbxLaunch &L)
 {
-    dim3 grid((unsigned)((L.geom->kpPerFrame + OD_WPB - 1) / OD_WPB), (unsigned)L.batch);
+    dim3 grid((unsigned)((L.geom->kpPerFrame + OD_KPB - 1) / OD_KPB), (unsigned)L.batch);
     const OrbxGeom &g = *L.geom;
     OdLevels A;
     memset(&A, 0, sizeof(A));

@@ -83,6 +83,18 @@ __device__ __forceinline__ int wave_sum_dpp(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// integer sums over the two halves of the wave (lanes 0 - 31, lanes 32 - 63) at once: the reduction above stopped before its last step; the totals
+// land in lanes 31 and 63 (every other lane holds a partial sum)
+__device__ __forceinline__ int halfwave_sum_dpp(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4e, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);     // row_half_mirror
+    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);     // row_mirror: every lane holds its row's sum
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);     // row_bcast:15 into rows 1 and 3
+    return v;
+}
+
 // ---- minimum / maximum of 32- and 64-bit keys, in every lane ------------------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ T wave_min(T v)
 {
