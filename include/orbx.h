@@ -578,6 +578,52 @@ int orbx_vocabulary_create(int device, int k, int L, int num_nodes, const int32_
                            const uint8_t *descriptors, const double *weights, orbx_vocabulary **out);
 void orbx_vocabulary_destroy(orbx_vocabulary *v);
 int orbx_vocabulary_words(const orbx_vocabulary *v);
+
+/* ORBVocabulary::loadFromTextFile on the device (TemplatedVocabulary.h:1338-1420, what System::System runs before its first frame): the text
+ * "k L scoring weighting" + one line "parent isLeaf d0 .. d31 weight" per node, node id = line number (:1385), to the SAME device tree
+ * orbx_vocabulary_create builds from the same arrays - children in ascending node id for any line order with parent < id, word ids counting the
+ * leaves in node-id order (:1408-1415).  The device indexes the lines, parses one line per lane and builds the child lists; the file form reads
+ * the file in slices into pinned memory and uploads a slice while the next is read.  One host wait; a second one when the device flagged lines.
+ *
+ * Tokens are separated by what istream >> skips inside a line (space, tab, CR, VT, FF; CRLF files work); tokens behind the weight are ignored, as
+ * in the reference.  The weight [+-]?(digits[.digits*]|.digits)([eE][+-]?digits)? becomes the correctly rounded double of the token, bit for
+ * bit what istream >> double (glibc strtod) gives the reference (:1406): on the device by the Eisel-Lemire algorithm for up to 19 significant
+ * digits, and every token whose rounding that algorithm cannot prove - more digits, a subnormal or overflowing value, a tie - flags its line for
+ * the host statement (strtol / strtod, the body of orbx_voc_text_parse_host), as does a line of more than 1023 bytes.
+ *
+ * Stated differences (parity unpinned):
+ *   - the reference loops on !f.eof() (:1378): a file that ends in '\n' - every file its own saveToTextFile writes - gives it one more node
+ *     with parent 0 and an uninitialised descriptor.  Here the empty last line is dropped and final_newline = 1 says so;
+ *   - malformed lines, which the reference stores as 0 or stale values: too few tokens, a non-numeric token, a descriptor value outside 0..255,
+ *     a parent that is not a smaller node id (m_nodes[pid] out of bounds at :1392), an empty line in the middle, a child under a leaf, an
+ *     inner node without children, inf / nan / hex-float weights.  Here: ORBX_ERR_ARG, the 1-based line in orbx_last_error and in error_line,
+ *     *out NULL.  The header is held to the reference's range check (:1359) and to orbx_vocabulary_create's k >= 1 and two nodes.
+ * Text of 2^31 bytes or more: ORBX_ERR_CAPACITY. */
+typedef struct orbx_voc_text_info {
+    int32_t k, L, scoring, weighting;      /* the header line */
+    int32_t num_nodes, num_words;
+    int32_t final_newline;                 /* the text ended in '\n': the empty last line was dropped */
+    int32_t host_lines;                    /* lines the device flagged and the host statement re-parsed */
+    int32_t error_line;                    /* 1-based line of the first format error, 0 = none */
+    int32_t launches, waits;
+    int64_t bytes;
+    float read_ms, upload_ms, kernel_ms, host_ms, total_ms;
+} orbx_voc_text_info;
+int orbx_vocabulary_load_text(int device, const char *path, orbx_vocabulary **out, orbx_voc_text_info *info);
+int orbx_vocabulary_load_text_buffer(int device, const void *text, size_t size, orbx_vocabulary **out, orbx_voc_text_info *info);
+/* The tree of ANY orbx_vocabulary (loaded, created, trained) back as orbx_vocabulary_create's flat arrays; any pointer may be NULL.  The root's
+ * descriptor (unused by create) comes back as zeros. */
+int orbx_vocabulary_tree(orbx_vocabulary *v, int32_t *k, int32_t *L, int32_t *num_nodes, int32_t *parent, uint8_t *is_leaf,
+                         uint8_t *descriptors, double *weights);
+/* The literal host statement of the parse - split at '\n', tokens, strtol / strtod, then orbx_vocabulary_create's three checks: no device, no
+ * handle.  Format errors are reported before structure errors, each kind at its first line.  With all four arrays NULL it only sizes
+ * (info->num_nodes); ORBX_ERR_CAPACITY when capacity_nodes is too small. */
+int orbx_voc_text_parse_host(const void *text, size_t size, orbx_voc_text_info *info, int32_t capacity_nodes, int32_t *parent,
+                             uint8_t *is_leaf, uint8_t *descriptors, double *weights);
+/* The device's accept rule for one weight token, run on the host (the same code): 1 and *value when the device proves the token's double itself,
+ * 0 when it flags the line. */
+int orbx_voc_text_weight_rule(const char *token, size_t size, double *value);
+
 /* transform() of every feature of the extractor's LAST batch, on the extractor's stream (ordered
  * behind the extraction and ahead of any consumer that orders itself behind the extractor).
  * Results stay on the device, laid out like the extractor's results (feature i of frame f at

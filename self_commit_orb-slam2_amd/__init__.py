@@ -12,6 +12,7 @@ There is no CPU fallback: constructing an extractor without a HIP device raises.
 """
 import ctypes
 import importlib.util
+import os
 from pathlib import Path
 
 import numpy as np
@@ -1224,6 +1225,37 @@ class Vocabulary(_Handle):
         wt = np.ascontiguousarray(voc["weight"], np.float64)
         _check(L.orbx_vocabulary_create(device, int(voc["k"]), int(voc["L"]), len(par), _ptr(par), _ptr(leaf), _ptr(desc), _ptr(wt), ctypes.byref(self._h)))
 
+    @classmethod
+    def from_text(cls, path_or_bytes, device=0):
+        """ORBVocabulary::loadFromTextFile on the device (orbx_vocabulary_load_text / _load_text_buffer): a path, or the text itself as bytes.
+        .text_info: the header, the node and word counts, final_newline, host_lines, launches, waits and the times of the load."""
+        v = cls.__new__(cls)
+        v._L = load_library()
+        cls._bind(v._L)
+        _bind_voc_text(v._L)
+        v._h = ctypes.c_void_p()
+        info = VocTextInfo()
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            data = bytes(path_or_bytes)
+            rc = v._L.orbx_vocabulary_load_text_buffer(device, data, len(data), ctypes.byref(v._h), ctypes.byref(info))
+        else:
+            rc = v._L.orbx_vocabulary_load_text(device, os.fsencode(path_or_bytes), ctypes.byref(v._h), ctypes.byref(info))
+        v.text_info = info.as_dict()
+        if rc != ORBX_OK:
+            e = OrbxError(rc, v._L.orbx_last_error().decode("utf-8", "replace"))
+            e.text_info = v.text_info
+            raise e
+        return v
+
+    def tree(self):
+        """the tree of this vocabulary - loaded, created or trained - as voc_synth's dict (orbx_vocabulary_tree)"""
+        _bind_voc_text(self._L)
+        k, L, n = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(self._L.orbx_vocabulary_tree(self._h, ctypes.byref(k), ctypes.byref(L), ctypes.byref(n), None, None, None, None))
+        par, leaf, desc, wt = np.zeros(n.value, np.int32), np.zeros(n.value, np.uint8), np.zeros((n.value, 32), np.uint8), np.zeros(n.value, np.float64)
+        _check(self._L.orbx_vocabulary_tree(self._h, None, None, None, _ptr(par), _ptr(leaf), _ptr(desc), _ptr(wt)))
+        return dict(k=k.value, L=L.value, parent=par, is_leaf=leaf, desc=desc, weight=wt, num_nodes=n.value)
+
     def close(self):
         if getattr(self, "_job", None) is not None and self._job.value:      # (a job only reads the vocabulary and must go first)
             self._L.orbx_bow_job_destroy(self._job)
@@ -1289,6 +1321,50 @@ class Vocabulary(_Handle):
         w, nd, wt = np.zeros((batch, cap), np.int32), np.zeros((batch, cap), np.int32), np.zeros((batch, cap), np.float64)
         _check(self._L.orbx_bow_download(self._h, extractor._h, batch, _ptr(w), _ptr(nd), _ptr(wt)))
         return w, nd, wt
+
+
+class VocTextInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("k", "L", "scoring", "weighting", "num_nodes", "num_words", "final_newline", "host_lines", "error_line", "launches", "waits")] + \
+               [("bytes", ctypes.c_int64)] + [(n, ctypes.c_float) for n in ("read_ms", "upload_ms", "kernel_ms", "host_ms", "total_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _bind_voc_text(L):
+    vp, ci, ip = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(VocTextInfo)
+    L.orbx_vocabulary_load_text.argtypes = [ci, ctypes.c_char_p, ctypes.POINTER(vp), ip]
+    L.orbx_vocabulary_load_text_buffer.argtypes = [ci, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp), ip]
+    L.orbx_vocabulary_tree.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [vp] * 4
+    L.orbx_voc_text_parse_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ip, ctypes.c_int32, vp, vp, vp, vp]
+    L.orbx_voc_text_weight_rule.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double)]
+
+
+def voc_text_parse_host(data):
+    """orbx_voc_text_parse_host: the literal host statement of the text parse (no device) -> voc_synth's dict plus the header fields, num_words,
+    final_newline and error_line.  A format error raises OrbxError with .text_info."""
+    L = load_library()
+    _bind_voc_text(L)
+    data = bytes(data)
+    info = VocTextInfo()
+    rc = L.orbx_voc_text_parse_host(data, len(data), ctypes.byref(info), 0, None, None, None, None)
+    if rc == ORBX_OK:
+        n = info.num_nodes
+        par, leaf, desc, wt = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.float64)
+        rc = L.orbx_voc_text_parse_host(data, len(data), ctypes.byref(info), n, _ptr(par), _ptr(leaf), _ptr(desc), _ptr(wt))
+    if rc != ORBX_OK:
+        e = OrbxError(rc, L.orbx_last_error().decode("utf-8", "replace"))
+        e.text_info = info.as_dict()
+        raise e
+    return dict(info.as_dict(), parent=par, is_leaf=leaf, desc=desc, weight=wt)
+
+
+def voc_text_weight_rule(token):
+    """the device's accept rule for one weight token, run on the host: the double it proves, or None where it flags the line"""
+    L = load_library()
+    _bind_voc_text(L)
+    t, v = bytes(token), ctypes.c_double()
+    return v.value if L.orbx_voc_text_weight_rule(t, len(t), ctypes.byref(v)) else None
 
 
 VOC_MAX_K, VOC_MAX_L = 32, 10      # ORBX_VOC_MAX_K, ORBX_VOC_MAX_L

@@ -16,11 +16,9 @@
 
 #include <vector>
 
-#include "orbx_handle.h"
+#include "orbx_voc.h"
 
 namespace {
-
-struct VocNode { int32_t childStart, childCount, word, pad; };   // word >= 0: leaf
 
 __device__ __forceinline__ void bow_descend(const VocNode *__restrict__ nodes, const int32_t *__restrict__ childList, const uint4 *__restrict__ childDesc,
                                             const double *__restrict__ nodeWeight, int nidLevel, const uint8_t *__restrict__ desc, int cap, int32_t *__restrict__ word,
@@ -107,21 +105,6 @@ __global__ __launch_bounds__(256) void k_bow_ranks(const int32_t *__restrict__ w
 }
 
 }  // namespace
-
-struct orbx_vocabulary : OrbxHandle {      // (the stream: host-array form only; the device form runs on the extractor's stream)
-    int k = 0, L = 0, numNodes = 0, numWords = 0;
-    OrbxOwnedBuf<VocNode> nodes;
-    OrbxOwnedBuf<int32_t> childList;
-    OrbxOwnedBuf<uint4> childDesc;
-    OrbxOwnedBuf<double> nodeWeight;
-    // results, double buffered in lockstep with the extractor's result buffers
-    OrbxOwnedBuf<int32_t> word[2], node[2];
-    OrbxOwnedBuf<double> weight[2];
-    int cur = 0, lastBatch = 0, lastCap = 0;
-    OrbxCallBox box;   // host-array form: descriptors in, word / node / weight out through mapped pinned memory
-    OrbxOwnedBuf<int32_t> hostWord, hostNode;   // host-array _sorted form: the device copy k_bow_ranks reads - its own, never the device form's word[] / node[] (a
-                                              // host call between two device calls must leave the last batch's results, and the pointers handed out, alone)
-};
 
 extern "C" int orbx_vocabulary_create(int device, int k, int L, int num_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *descriptors,
                                       const double *weights, orbx_vocabulary **out)

@@ -1,5 +1,6 @@
 // shim/ORBVocabulary_hip.cc -- TemplatedVocabulary::create(training_features, k, L, weighting, scoring)
-// (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:604-616 over :557-587) through orbx_voc_train.
+// (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:604-616 over :557-587) through orbx_voc_train, and TemplatedVocabulary::loadFromTextFile
+// (:1338-1420) through orbx_vocabulary_load_text.
 //
 // Compiled against the REFERENCE's own headers, like the other shim files.  A file of its own: the drop-in library of oracle/Makefile does not
 // link it; it is compile-checked only.
@@ -11,6 +12,7 @@
 // shim_error.h) the vocabulary is left empty.
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "ORBVocabulary.h"
@@ -88,5 +90,58 @@ void ORBVocabulary_hip::create(const std::vector<std::vector<DBoW2::FORB::TDescr
         m_nodes[(size_t)id].word_id = (DBoW2::WordId)m_words.size();
         m_words.push_back(&m_nodes[(size_t)id]);
     }
+}
+
+ORBVocabulary_hip::~ORBVocabulary_hip()
+{
+    if (mpDevice) orbx_vocabulary_destroy(mpDevice);
+}
+
+// :1338-1420 with the parse and the tree on the device.  What stays on the host: m_nodes / m_words from the flat arrays (1.1 M cv::Mat at the
+// shape of ORBvoc.txt).  The reference's extra node behind a final newline is not made (include/orbx.h); a malformed file, which the reference
+// reads into zeros and stale values, is refused: false, vocabulary empty, counted and printed by orbx_shim::Fail.
+bool ORBVocabulary_hip::loadFromTextFile(const std::string &filename)
+{
+    m_words.clear();
+    m_nodes.clear();
+    if (mpDevice) { orbx_vocabulary_destroy(mpDevice); mpDevice = 0; }
+
+    orbx_voc_text_info info;
+    orbx_vocabulary *voc = 0;
+    if (orbx_vocabulary_load_text(orbx_shim::Device(), filename.c_str(), &voc, &info) != ORBX_OK) { orbx_shim::Fail("ORBVocabulary::loadFromTextFile"); return false; }
+    const size_t n = (size_t)info.num_nodes;
+    std::vector<int32_t> parent(n);
+    std::vector<uint8_t> leaf(n), desc(n * 32);
+    std::vector<double> weights(n);
+    if (orbx_vocabulary_tree(voc, 0, 0, 0, parent.data(), leaf.data(), desc.data(), weights.data()) != ORBX_OK) {
+        orbx_shim::Fail("ORBVocabulary::loadFromTextFile");
+        orbx_vocabulary_destroy(voc);
+        return false;
+    }
+    m_k = info.k;
+    m_L = info.L;
+    m_scoring = (DBoW2::ScoringType)info.scoring;
+    m_weighting = (DBoW2::WeightingType)info.weighting;
+    createScoringObject();
+
+    m_nodes.resize(n);
+    m_nodes[0].id = 0;
+    m_words.reserve((size_t)info.num_words);
+    for (size_t id = 1; id < n; id++) {      // in id order, as the lines come: children in ascending id (:1392), words in node-id order (:1408-1415)
+        Node &nd = m_nodes[id];
+        nd.id = (DBoW2::NodeId)id;
+        nd.parent = (DBoW2::NodeId)parent[id];
+        m_nodes[(size_t)parent[id]].children.push_back((DBoW2::NodeId)id);
+        nd.descriptor = cv::Mat(1, 32, CV_8U);
+        memcpy(nd.descriptor.ptr<unsigned char>(), &desc[id * 32], 32);
+        nd.weight = weights[id];
+        if (leaf[id]) {
+            nd.word_id = (DBoW2::WordId)m_words.size();
+            m_words.push_back(&nd);
+        } else
+            nd.children.reserve((size_t)m_k);
+    }
+    mpDevice = voc;
+    return true;
 }
 }  // namespace ORB_SLAM2
