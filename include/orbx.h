@@ -472,6 +472,87 @@ int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projection_frame 
                                    const orbx_projection_last *last_host, const float *scale_factors, int nlevels,
                                    float th, int b_mono, int check_orientation, int32_t *assigned, int32_t *nmatches);
 
+/* ------------------------------------------------------------------------------------
+ * A tracked frame on the device: the two functions of the tracking thread that run on EVERY frame, each as one
+ * launch chain with ONE host wait (inputs staged once through mapped pinned memory, results written by the chain's last
+ * kernel into mapped pinned memory, a sequence word polled).  Both live on the matcher handle; host memory throughout.
+ *
+ * Limits of both: at most ORBX_TRACK_MAX_CORRESPONDENCES possible correspondences (the pose kernel keeps a frame's edges
+ * in the registers of one workgroup) - for the motion model min(N, valid last-frame points), for the local map
+ * min(N, held features + local points); N <= the matcher's max_features; the replays' LDS tiles (5 / 6 bytes per
+ * feature: N <= 32000 / 27000).  ORBX_ERR_CAPACITY beyond, ORBX_ERR_ARG for NULL arguments or nlevels out of range;
+ * neither launches anything.
+ *
+ * orbx_track_with_motion_model == Tracking::TrackWithMotionModel, src/Tracking.cc:1370-1421 (UpdateLastFrame, the
+ * velocity product - last->tcw_current = mVelocity * mLastFrame.mTcw - and the final mbOnlyTracking decision stay the
+ * caller's):
+ *   SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1382); if it returns < 20, again with 2 * th from cleared
+ *   matches (:1386-1390; enqueued unconditionally, its workgroups read the first pass' count on the device and leave
+ *   unless it is < 20); if still < 20 the function fails (:1393): ran_pose = 0, pose = tcw_current unchanged, matches as
+ *   the search left them, nmatches = nmatches_search, nmatches_map = 0.  Otherwise a gather kernel builds the pose
+ *   problem on the device from the pass that counts (features i in ascending order with a match >= 0: the last-frame
+ *   point's world_pos, keypoints_un[i].pt, u_right[i], inv_level_sigma2[keypoints_un[i].octave]), PoseOptimization
+ *   (:1398) runs from tcw_current with camera fx, fy, cx, cy, mbf, and a discard kernel does :1403-1421.
+ * Results (N = frame->counts[0] entries; any pointer may be NULL):
+ *   matches[i]        last-frame feature whose MapPoint CurrentFrame.mvpMapPoints[i] holds on return, or -1
+ *   search_matches[i] as orbx_search_by_projection_last reports the pass that counted (-2 = assigned, then pruned)
+ *   discarded[i]      1 where :1409-1415 fired (the caller sets mbTrackInView = false, mnLastFrameSeen on that point)
+ *   pose[16]          mTcw after PoseOptimization
+ *   counts            nmatches_search (the search's return value), wide (1 = the 2 * th pass counted),
+ *                     n_correspondences, pose_inliers (PoseOptimization's return value), nmatches (after the decrements
+ *                     of :1415), nmatches_map (:1417-1419), ran_pose
+ *   stats[8]          as orbx_pose_optimization
+ * Contract: every field equals, bit for bit, orbx_search_by_projection_last (once or twice) followed by
+ * orbx_pose_optimization on the problem a host loop builds from its result; against the CPU restatement the pose is
+ * held to 1e-5 and everything else is equal (orbx_pose_optimization's own contract). */
+#define ORBX_TRACK_MAX_CORRESPONDENCES 8192
+typedef struct orbx_track_motion_result {
+    int32_t *matches, *search_matches;
+    uint8_t *discarded;
+    float *pose;
+    int32_t nmatches_search, wide, n_correspondences, pose_inliers, nmatches, nmatches_map, ran_pose;
+    double stats[8];
+} orbx_track_motion_result;
+int orbx_track_with_motion_model(orbx_matcher *m, const orbx_projection_frame *frame_host, const orbx_projection_last *last_host,
+                                 const float *scale_factors, int nlevels, const float *inv_level_sigma2, float th, int b_mono,
+                                 int check_orientation, orbx_track_motion_result *result);
+
+/* orbx_track_local_map == Tracking::TrackLocalMap, src/Tracking.cc:1454-1489 (UpdateLocalMap and the bookkeeping loop
+ * of SearchLocalPoints over the points the frame already holds, :1770-1788, stay the caller's):
+ *   orbx_search_local_points' chain (Frame::isInFrustum + SearchByProjection(F, vpMapPoints, th)), a gather kernel - the
+ *   edges are the features in ascending order that are held (held[i] = 1: mvpMapPoints[i] != NULL on entry) or newly
+ *   assigned; world position from the local point if assigned, else held_world_pos[i] -, PoseOptimization (:1459) from
+ *   pose->tcw, and a statistics kernel for :1464-1489.
+ * Inputs as orbx_search_local_points plus held[N], held_world_pos[N*3], inv_level_sigma2[nlevels], sensor_stereo
+ * (mSensor == System::STEREO).  frame->occupied[i] = 1 where the held point has Observations() > 0 (NULL = none).
+ * Results (any pointer may be NULL): assigned / nmatches / in_view / proj_x .. view_cos as orbx_search_local_points;
+ *   pose[16]; outlier[N] = mvbOutlier of the features with an edge (0 elsewhere: the function does not touch those);
+ *   found[N] = 1: IncreaseFound() is due (:1469-1471); cleared[N] = 1: outlier under sensor_stereo, mvpMapPoints[i]
+ *   becomes NULL (:1485-1486); pose_inliers; inliers_map = non-outliers with Observations() > 0 (occupied for a held
+ *   feature, the point's has_observations for a new one): mnMatchesInliers unless mbOnlyTracking; inliers_all =
+ *   mnMatchesInliers under mbOnlyTracking; n_correspondences; stats[8].
+ * Contract: as above, against orbx_search_local_points followed by orbx_pose_optimization. */
+typedef struct orbx_track_local_result {
+    int32_t *assigned;
+    uint8_t *in_view;
+    float *proj_x, *proj_y, *proj_xr;
+    int32_t *scale_level;
+    float *view_cos;
+    float *pose;
+    uint8_t *outlier, *found, *cleared;
+    int32_t nmatches, n_correspondences, pose_inliers, inliers_map, inliers_all;
+    double stats[8];
+} orbx_track_local_result;
+int orbx_track_local_map(orbx_matcher *m, const orbx_projection_frame *frame_host, const orbx_frustum_frame *pose_host,
+                         const orbx_local_points *points_host, const float *scale_factors, int nlevels, float viewing_cos_limit,
+                         float th, float nn_ratio, const uint8_t *held, const float *held_world_pos, const float *inv_level_sigma2,
+                         int sensor_stereo, orbx_track_local_result *result);
+/* profile_kernels (developer tap of tools/latency_track_chain.py): on != 0 records an event between the launches of the next
+ * chain calls; orbx_track_last_kernel_times returns the device milliseconds between them (at most `capacity`, *count of them;
+ * motion model: stage, pass 1, pass 2, gather, pose, discard; local map: stage, search, gather, pose, statistics). */
+int orbx_track_set_profiling(orbx_matcher *m, int on);
+int orbx_track_last_kernel_times(orbx_matcher *m, float *ms, int capacity, int *count);
+
 /* ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1020-1177; LocalMapping::SearchInNeighbors)
  * and ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1179-1312; LoopClosing): the search of
  * steps 2-3 for every map point - KeyFrame::GetFeaturesInArea(u, v, radius), the level gate, for the

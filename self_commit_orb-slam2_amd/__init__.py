@@ -411,6 +411,17 @@ class BowParams(ctypes.Structure):
     _fields_ = [("nn_ratio", ctypes.c_float), ("check_orientation", ctypes.c_int), ("mode", ctypes.c_int)]
 
 
+class TrackMotionResult(ctypes.Structure):      # orbx_track_motion_result
+    _fields_ = [("matches", ctypes.c_void_p), ("search_matches", ctypes.c_void_p), ("discarded", ctypes.c_void_p), ("pose", ctypes.c_void_p)] + \
+               [(k, ctypes.c_int32) for k in ("nmatches_search", "wide", "n_correspondences", "pose_inliers", "nmatches", "nmatches_map", "ran_pose")] + \
+               [("stats", ctypes.c_double * 8)]
+
+
+class TrackLocalResult(ctypes.Structure):       # orbx_track_local_result
+    _fields_ = [(k, ctypes.c_void_p) for k in ("assigned", "in_view", "proj_x", "proj_y", "proj_xr", "scale_level", "view_cos", "pose", "outlier", "found", "cleared")] + \
+               [(k, ctypes.c_int32) for k in ("nmatches", "n_correspondences", "pose_inliers", "inliers_map", "inliers_all")] + [("stats", ctypes.c_double * 8)]
+
+
 def _bind_matcher(L):
     if getattr(L, "_matcher_bound", False):
         return
@@ -1118,6 +1129,133 @@ class ORBmatcher(_Handle):
         _check(self._L.orbx_search_by_projection_last(self._h, ctypes.byref(F), ctypes.byref(Ls), _ptr(sf), len(sf), ctypes.c_float(th), 1 if mono else 0,
                                                       1 if self.checkOri else 0, _ptr(out), ctypes.byref(nm)))
         return nm.value, out[:n]
+
+    def _frame_arrays(self, frame):
+        """The frame side of the projection searches as (ProjectionFrame, keep-alive list, n, scale factors, (minx, maxx, miny, maxy))."""
+        k = np.ascontiguousarray(frame["kps"], KEYPOINT_DTYPE)
+        n = len(k)
+        d = np.ascontiguousarray(frame["desc"], np.uint8)
+        ur = np.ascontiguousarray(frame["u_right"], np.float32)
+        occ = None if frame.get("occupied") is None else np.ascontiguousarray(frame["occupied"], np.uint8)
+        sf = np.ascontiguousarray(frame["scale_factors"], np.float32)
+        minx, miny = np.float32(frame.get("min_x", 0.0)), np.float32(frame.get("min_y", 0.0))
+        maxx, maxy = np.float32(frame.get("max_x", frame["width"])), np.float32(frame.get("max_y", frame["height"]))
+        gw, gh = np.float32(64) / (maxx - minx), np.float32(48) / (maxy - miny)
+        cn = np.array([n], np.int32)
+        F = ProjectionFrame(_ptr(k).value, _ptr(d).value, _ptr(ur).value, None if occ is None else _ptr(occ).value, _ptr(cn).value, max(n, 1), 1, float(minx), float(miny),
+                            float(gw), float(gh))
+        return F, [k, d, ur, occ, cn], n, sf, (float(minx), float(maxx), float(miny), float(maxy))
+
+    def TrackWithMotionModel(self, frame, last, th, mono, inv_level_sigma2):
+        return self.track_motion_prepare(frame, last, th, mono, inv_level_sigma2)()
+
+    def track_motion_prepare(self, frame, last, th, mono, inv_level_sigma2):
+        """Tracking::TrackWithMotionModel (reference src/Tracking.cc:1370-1421) as one device chain with one host wait (orbx_track_with_motion_model):
+        SearchByProjection(Current, Last, th), again with 2 * th if it found < 20, PoseOptimization from frame["Tcw"] (= mVelocity * mLastFrame.mTcw),
+        the discard loop.  frame / last as in SearchByProjectionLast (occupied may be None); inv_level_sigma2 = mvInvLevelSigma2.
+        Returns a prepared call: call() -> dict(matches, search_matches, discarded, pose, nmatches_search, wide, n_correspondences, pose_inliers, nmatches,
+        nmatches_map, ran_pose, stats); call.raw() is the C call alone on the marshalled arrays (tools/latency_track_chain.py), call.result() the dict."""
+        F, keep, n, sf, (minx, maxx, miny, maxy) = self._frame_arrays(frame)
+        lk = np.ascontiguousarray(last["kps"], KEYPOINT_DTYPE)
+        nl = len(lk)
+        cl = np.array([nl], np.int32)
+        valid = np.ascontiguousarray(last["valid"], np.uint8)
+        pos = np.ascontiguousarray(last["pos"], np.float32)
+        ld = np.ascontiguousarray(last["desc"], np.uint8)
+        obs = None if last.get("has_obs") is None else np.ascontiguousarray(last["has_obs"], np.uint8)
+        octv = np.ascontiguousarray(lk["octave"], np.int32)
+        ang = np.ascontiguousarray(lk["angle"], np.float32)
+        tc, tl = np.ascontiguousarray(frame["Tcw"], np.float32), np.ascontiguousarray(last["Tcw"], np.float32)
+        fx, fy, cx, cy, bf = [np.float32(v) for v in frame["cam"]]
+        is2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        if len(is2) != len(sf):
+            raise ValueError("inv_level_sigma2 and scale_factors must have one entry per level")
+        Ls = ProjectionLast(_ptr(valid).value, _ptr(pos).value, _ptr(ld).value, None if obs is None else _ptr(obs).value, _ptr(octv).value, _ptr(ang).value,
+                            _ptr(cl).value, max(nl, 1), _ptr(tc).value, _ptr(tl).value, float(fx), float(fy), float(cx), float(cy), float(bf), float(bf / fx), maxx, maxy)
+        m1 = max(n, 1)
+        mt, sm, dc, po = np.full(m1, -1, np.int32), np.full(m1, -1, np.int32), np.zeros(m1, np.uint8), np.zeros(16, np.float32)
+        R = TrackMotionResult(_ptr(mt).value, _ptr(sm).value, _ptr(dc).value, _ptr(po).value)
+        self._L.orbx_track_with_motion_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(ProjectionFrame), ctypes.POINTER(ProjectionLast), ctypes.c_void_p, ctypes.c_int,
+                                                         ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.POINTER(TrackMotionResult)]
+        fn, h, psf, pis, cth, cm, co = self._L.orbx_track_with_motion_model, self._h, _ptr(sf), _ptr(is2), ctypes.c_float(th), 1 if mono else 0, 1 if self.checkOri else 0
+
+        def raw():
+            return fn(h, ctypes.byref(F), ctypes.byref(Ls), psf, len(sf), pis, cth, cm, co, ctypes.byref(R))
+
+        def result():
+            return dict(matches=mt[:n].copy(), search_matches=sm[:n].copy(), discarded=dc[:n].copy(), pose=po.reshape(4, 4).copy(), nmatches_search=R.nmatches_search,
+                        wide=R.wide, n_correspondences=R.n_correspondences, pose_inliers=R.pose_inliers, nmatches=R.nmatches, nmatches_map=R.nmatches_map,
+                        ran_pose=R.ran_pose, stats=np.array(R.stats[:], np.float64))
+
+        def call():
+            _check(raw())
+            return result()
+        call.raw, call.result, call.F, call.Ls, call.sf = raw, result, F, Ls, sf
+        call.keep = [keep, lk, cl, valid, pos, ld, obs, octv, ang, tc, tl, is2, mt, sm, dc, po, R]
+        return call
+
+    def TrackLocalMap(self, frame, Tcw, cam, log_scale_factor, points, th, held, held_pos, inv_level_sigma2, sensor_stereo, nnratio=None, viewing_cos_limit=0.5):
+        return self.track_local_prepare(frame, Tcw, cam, log_scale_factor, points, th, held, held_pos, inv_level_sigma2, sensor_stereo, nnratio, viewing_cos_limit)()
+
+    def track_local_prepare(self, frame, Tcw, cam, log_scale_factor, points, th, held, held_pos, inv_level_sigma2, sensor_stereo, nnratio=None, viewing_cos_limit=0.5):
+        """Tracking::TrackLocalMap (reference src/Tracking.cc:1454-1489) as one device chain with one host wait (orbx_track_local_map): SearchLocalPoints
+        (arguments as SearchLocalPoints), PoseOptimization from Tcw over the features that are held (held[n] = 1, position held_pos[n, 3]) or newly
+        assigned, the statistics loop.  frame["occupied"][i] = 1 where the held point has observations (may be None).
+        Returns a prepared call (as track_motion_prepare): call() -> dict(assigned, nmatches, frustum=dict(in_view, ..), pose, outlier, found, cleared,
+        n_correspondences, pose_inliers, inliers_map, inliers_all, stats)."""
+        F, keep, n, sf, (minx, maxx, miny, maxy) = self._frame_arrays(frame)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        thr = predict_scale_thresholds(log_scale_factor, len(sf))
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        pos, nrm, mx, mn = f32(points["pos"]), f32(points["normal"]), f32(points["max_distance"]), f32(points["min_distance"])
+        md = np.ascontiguousarray(points["desc"], np.uint8)
+        obs = None if points.get("has_obs") is None else np.ascontiguousarray(points["has_obs"], np.uint8)
+        m = len(mx)
+        hd, hp, is2 = np.ascontiguousarray(held, np.uint8), f32(held_pos), f32(inv_level_sigma2)
+        if len(hd) != n or hp.size != 3 * n or len(is2) != len(sf):
+            raise ValueError("held / held_pos need one entry per feature, inv_level_sigma2 one per level")
+        fr = FrustumFrame(T.ctypes.data, cam[0], cam[1], cam[2], cam[3], cam[4], minx, maxx, miny, maxy, thr.ctypes.data, len(sf), 1)
+        P = LocalPoints(pos.ctypes.data, nrm.ctypes.data, mx.ctypes.data, mn.ctypes.data, md.ctypes.data, None if obs is None else obs.ctypes.data, m)
+        n1, m1 = max(n, 1), max(m, 1)
+        z = lambda dt: np.zeros(m1, dt)
+        iv, px, py, pxr, lvl, vc = z(np.uint8), z(np.float32), z(np.float32), z(np.float32), z(np.int32), z(np.float32)
+        asg, po = np.full(n1, -1, np.int32), np.zeros(16, np.float32)
+        outl, fnd, clr = np.zeros(n1, np.uint8), np.zeros(n1, np.uint8), np.zeros(n1, np.uint8)
+        R = TrackLocalResult(_ptr(asg).value, _ptr(iv).value, _ptr(px).value, _ptr(py).value, _ptr(pxr).value, _ptr(lvl).value, _ptr(vc).value, _ptr(po).value,
+                             _ptr(outl).value, _ptr(fnd).value, _ptr(clr).value)
+        self._L.orbx_track_local_map.argtypes = [ctypes.c_void_p, ctypes.POINTER(ProjectionFrame), ctypes.POINTER(FrustumFrame), ctypes.POINTER(LocalPoints), ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.POINTER(TrackLocalResult)]
+        fn, h, psf, phd, php, pis = self._L.orbx_track_local_map, self._h, _ptr(sf), _ptr(hd), _ptr(hp), _ptr(is2)
+        cvc, cth, cnn, cst = ctypes.c_float(viewing_cos_limit), ctypes.c_float(th), ctypes.c_float(self.nnratio if nnratio is None else nnratio), 1 if sensor_stereo else 0
+
+        def raw():
+            return fn(h, ctypes.byref(F), ctypes.byref(fr), ctypes.byref(P), psf, len(sf), cvc, cth, cnn, phd, php, pis, cst, ctypes.byref(R))
+
+        def result():
+            c = lambda a, k: a[:k].copy()
+            return dict(assigned=c(asg, n), nmatches=R.nmatches, frustum=dict(in_view=c(iv, m), proj_x=c(px, m), proj_y=c(py, m), proj_xr=c(pxr, m), level=c(lvl, m), view_cos=c(vc, m)),
+                        pose=po.reshape(4, 4).copy(), outlier=c(outl, n), found=c(fnd, n), cleared=c(clr, n), n_correspondences=R.n_correspondences,
+                        pose_inliers=R.pose_inliers, inliers_map=R.inliers_map, inliers_all=R.inliers_all, stats=np.array(R.stats[:], np.float64))
+
+        def call():
+            _check(raw())
+            return result()
+        call.raw, call.result, call.F, call.fr, call.P, call.sf = raw, result, F, fr, P, sf
+        call.keep = [keep, T, thr, pos, nrm, mx, mn, md, obs, hd, hp, is2, iv, px, py, pxr, lvl, vc, asg, po, outl, fnd, clr, R]
+        return call
+
+    def track_kernel_times(self, on=None):
+        """profile_kernels tap of the two chains above: track_kernel_times(True / False) switches the events between their launches on or off;
+        track_kernel_times() returns the device milliseconds between the launches of the last profiled call."""
+        self._L.orbx_track_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self._L.orbx_track_last_kernel_times.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        if on is not None:
+            _check(self._L.orbx_track_set_profiling(self._h, 1 if on else 0))
+            return None
+        ms, cnt = np.zeros(8, np.float32), ctypes.c_int()
+        _check(self._L.orbx_track_last_kernel_times(self._h, _ptr(ms), 8, ctypes.byref(cnt)))
+        return ms[:cnt.value].copy()
 
     def StereoHamming(self, kpsL, descL, kpsR, descR, scale_factors, max_disparity=float("inf")):
         fl, kl = _host_set(kpsL, descL)

@@ -408,6 +408,23 @@ static inline int orbx_stage_to_arena(OrbxCallBox &box, Arena &arena, hipStream_
 }
 #endif
 
+/* k_pose_opt (orbx_lba.hip) for ONE frame as a link of another file's chain (orbx_track.hip; the build has no relocatable device code): every pointer
+ * is device memory, the number of correspondences is read there (counts[0], at most cap), the host only knows an upper bound maxCount.  *gate (device) = that
+ * number, or -1 = do not run: one launch per instantiation up to maxCount's is enqueued, each predicated on its range of *gate, so that the instantiation
+ * the count asks for runs and nothing else; -1 leaves every output untouched.  ORBX_ERR_CAPACITY for maxCount > 8192. */
+struct OrbxPoseOptArgs {
+    const float *pose0, *cam;      /* [16] mTcw, [5] fx fy cx cy mbf */
+    const float *Xw, *obs, *invS2; /* [cap*3], [cap*3], [cap]: orbx_pose_problem's arrays */
+    const int32_t *counts;         /* [1] */
+    int cap, maxCount;
+    float *poseOut;                /* [16] */
+    uint8_t *outlier;              /* [cap] */
+    int32_t *ret;                  /* [1] */
+    double *stats;                 /* [8] */
+    const int32_t *gate;           /* [1] */
+};
+int orbx_pose_opt_enqueue(hipStream_t st, const OrbxPoseOptArgs &a);
+
 /* Device view of the LAST batch of an extractor: results + the unblurred pyramid (what the
  * reference keeps in ORBextractor::mvImagePyramid, read by Frame::ComputeStereoMatches). */
 struct OrbxLastBatchView {

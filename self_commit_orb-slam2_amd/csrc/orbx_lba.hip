@@ -2107,6 +2107,10 @@ struct PoseOptDev {
     // - the count, then everything sized by it - at the head of a kernel the caller is waiting for)
     int one, count0;
     float cam0[5], pose00[16];
+    // a chain that decides on the device whether - and through which instantiation - the optimisation runs (orbx_track.hip): the workgroups leave at once
+    // unless gateMin <= *gate < gateBelow; NULL = run
+    const int32_t *gate;
+    int gateMin, gateBelow;
 };
 
 #define PO_NRED 28   /* 21 upper-triangle entries of H + 6 of b + chi2 */
@@ -2216,6 +2220,10 @@ __global__ __launch_bounds__(256) void k_pose_opt(PoseOptDev P, Huber hub)
     __shared__ double sLambda, sNi, sCur, sRho;
     __shared__ int sOk, sIterOk, sNBad;
     const int f = blockIdx.x, tid = threadIdx.x;
+    if (P.gate) {      // (uniform; a gated launch never publishes)
+        const int g = *P.gate;
+        if (g < P.gateMin || g >= P.gateBelow) return;
+    }
     const int n = min(P.one ? P.count0 : P.counts[f], P.cap);
     const size_t base = (size_t)f * P.cap;
     const float *Xw = P.Xw + base * 3, *obs = P.obs + base * 3, *invS2 = P.invS2 + base;
@@ -3216,6 +3224,51 @@ extern "C" void orbx_pose_optimizer_destroy(orbx_pose_optimizer *h) { orbx_destr
 static unsigned long long *g_poProf = nullptr;
 extern "C" void orbx_debug_pose_opt_profile(unsigned long long *dev32) { g_poProf = dev32; }
 
+// k_pose_opt for B frames on `st`: the instantiation (edges per thread) that holds maxCount correspondences.  D's pointers may be device or mapped host memory.
+static int pose_opt_launch(hipStream_t st, const PoseOptDev &D, int B, int maxCount)
+{
+    const float thMono = (float)sqrt(5.991), thStereo = (float)sqrt(7.815);   // deltaMono / deltaStereo are floats (:389-390)
+    Huber hub;
+    hub.dMono = thMono; hub.dStereo = thStereo;
+    hub.dsqrMono = (float)(hub.dMono * hub.dMono); hub.dsqrStereo = (float)(hub.dStereo * hub.dStereo);   // dsqr is a float member in this fork
+    if (maxCount > 256 * 32) { orbx_set_error("%d correspondences in a frame exceed the pose optimizer's limit %d", maxCount, 256 * 32); return ORBX_ERR_CAPACITY; }
+    // edges per thread = ceil(count / 256) up to 4 (a thread's dead slots cost what live ones do in the error pass), then 8 / 16 / 32
+    if (g_poProf && maxCount <= 256 * 2) hipLaunchKernelGGL((k_pose_opt<2, true>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (g_poProf && maxCount <= 256 * 3) hipLaunchKernelGGL((k_pose_opt<3, true>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (g_poProf && maxCount <= 256 * 4) hipLaunchKernelGGL((k_pose_opt<4, true>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (maxCount <= 256) hipLaunchKernelGGL((k_pose_opt<1, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (maxCount <= 256 * 2) hipLaunchKernelGGL((k_pose_opt<2, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (maxCount <= 256 * 3) hipLaunchKernelGGL((k_pose_opt<3, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (maxCount <= 256 * 4) hipLaunchKernelGGL((k_pose_opt<4, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (maxCount <= 256 * 8) hipLaunchKernelGGL((k_pose_opt<8, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else if (maxCount <= 256 * 16) hipLaunchKernelGGL((k_pose_opt<16, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
+    else hipLaunchKernelGGL((k_pose_opt<32, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);      // up to 8192 correspondences: 32 per thread, one wave per SIMD
+    ORBX_LAUNCH_CHECK();
+    return ORBX_OK;
+}
+
+// ... for the chains of other files (orbx_internal.h): everything in device memory, the count read there.  The host knows an upper bound only, and an
+// instantiation with more edges per thread than the count needs pays for its dead slots in every error pass (profiles/track_chain_latency.txt: eight per
+// thread instead of one to three costs 25 - 70 us of a 100 - 130 us kernel, more than the chain gains).  So every instantiation up to the bound's is
+// enqueued, each one predicated on the device on ITS range of counts: exactly one runs - the one orbx_pose_optimization picks for that count - and the
+// others leave at once (~4 us each).
+int orbx_pose_opt_enqueue(hipStream_t st, const OrbxPoseOptArgs &a)
+{
+    PoseOptDev D = {a.pose0, a.cam, a.Xw, a.obs, a.invS2, a.counts, a.cap, a.poseOut, a.outlier, a.ret, a.stats, nullptr, nullptr, 0ull, nullptr, 0, 0, {}, {}, a.gate, 0, 0};
+    if (a.maxCount > 256 * 32) return pose_opt_launch(st, D, 1, a.maxCount);      // (the capacity error)
+    static const int kEdges[] = {1, 2, 3, 4, 8, 16, 32};
+    int prev = -1;      // largest count of the instantiation in front
+    for (const int ne : kEdges) {
+        const int top = 256 * ne;
+        D.gateMin = prev + 1; D.gateBelow = top + 1;
+        const int rc = pose_opt_launch(st, D, 1, top);
+        if (rc != ORBX_OK) return rc;
+        if (top >= a.maxCount) break;
+        prev = top;
+    }
+    return ORBX_OK;
+}
+
 extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_problem *p, float *poses_out, uint8_t *outlier, int32_t *inliers, double *stats)
 {
     if (!h || !p || !p->poses || !p->cameras || !p->counts || !p->world_points || !p->observations || !p->inv_sigma2) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
@@ -3240,27 +3293,11 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
     if (rcs != ORBX_OK) return rcs;
     const uint8_t *o1 = sg.host(rOutlier);
     PoseOptDev D = {sg.dev(sPose), sg.dev(sCam), sg.dev(sXw), sg.dev(sObs), sg.dev(sInv), sg.dev(sCnt), cap, sg.dev(rPose), sg.dev(rOutlier), sg.dev(rInliers), sg.dev(rStats), bx.counter, bx.flagDev, bx.arm(), g_poProf,
-                    B == 1 ? 1 : 0, p->counts[0], {}, {}};
+                    B == 1 ? 1 : 0, p->counts[0], {}, {}, nullptr, 0, 0};
     if (B == 1) { memcpy(D.cam0, p->cameras, sizeof D.cam0); memcpy(D.pose00, p->poses, sizeof D.pose00); }
-    const float thMono = (float)sqrt(5.991), thStereo = (float)sqrt(7.815);   // deltaMono / deltaStereo are floats (:389-390)
-    Huber hub;
-    hub.dMono = thMono; hub.dStereo = thStereo;
-    hub.dsqrMono = (float)(hub.dMono * hub.dMono); hub.dsqrStereo = (float)(hub.dStereo * hub.dStereo);   // dsqr is a float member in this fork
     int maxCount = 0;
     for (int i = 0; i < B; i++) maxCount = std::max(maxCount, std::min((int)p->counts[i], cap));
-    if (maxCount > 256 * 32) { orbx_set_error("%d correspondences in a frame exceed the pose optimizer's limit %d", maxCount, 256 * 32); return ORBX_ERR_CAPACITY; }
-    // edges per thread = ceil(count / 256) up to 4 (a thread's dead slots cost what live ones do in the error pass), then 8 / 16 / 32
-    if (g_poProf && maxCount <= 256 * 2) hipLaunchKernelGGL((k_pose_opt<2, true>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (g_poProf && maxCount <= 256 * 3) hipLaunchKernelGGL((k_pose_opt<3, true>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (g_poProf && maxCount <= 256 * 4) hipLaunchKernelGGL((k_pose_opt<4, true>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (maxCount <= 256) hipLaunchKernelGGL((k_pose_opt<1, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (maxCount <= 256 * 2) hipLaunchKernelGGL((k_pose_opt<2, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (maxCount <= 256 * 3) hipLaunchKernelGGL((k_pose_opt<3, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (maxCount <= 256 * 4) hipLaunchKernelGGL((k_pose_opt<4, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (maxCount <= 256 * 8) hipLaunchKernelGGL((k_pose_opt<8, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else if (maxCount <= 256 * 16) hipLaunchKernelGGL((k_pose_opt<16, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);
-    else hipLaunchKernelGGL((k_pose_opt<32, false>), dim3((unsigned)B), dim3(256), 0, st, D, hub);      // up to 8192 correspondences: 32 per thread, one wave per SIMD
-    ORBX_LAUNCH_CHECK();
+    if ((rcs = pose_opt_launch(st, D, B, maxCount)) != ORBX_OK) return rcs;
     if ((rcs = bx.wait(st)) != ORBX_OK) return rcs;
     if (poses_out) memcpy(poses_out, sg.host(rPose), (size_t)B * 64);
     if (outlier)      // entries past a frame's count are not written by the kernel: they read 0

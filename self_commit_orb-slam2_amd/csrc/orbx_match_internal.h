@@ -63,6 +63,23 @@ struct FusePointsDev { const float *u, *v, *ur; const int32_t *level; const floa
                        float kfMinX, kfMinY; };
 struct FuseLevels { float invSigma2[ORBX_MAX_LEVELS]; };
 
+// The views of the two tracking searches (kernels in orbx_match_proj.hip; orbx_track.hip chains them through enqueue_proj_last / enqueue_local_points)
+// SearchByProjection(CurrentFrame, LastFrame, th, bMono): the last frame's side
+struct ProjLastDev { const uint8_t *valid; const float *pos; const uint8_t *desc, *hasObs; const int32_t *octave; const float *angle; const int32_t *counts;
+                     int cap; const float *tcwCur, *tcwLast; float fx, fy, cx, cy, mbf, mb, maxX, maxY; };
+// Frame::isInFrustum: the frame's side, the map points, and where k_frustum_topk leaves the mTrack* values for the caller (mapped host memory)
+struct FrustumDev {
+    const float *tcw;        // [16] per frame
+    float fx, fy, cx, cy, mbf, minX, maxX, minY, maxY, cosLimit;
+    int nlevels;
+    float ratioTh[ORBX_MAX_LEVELS];   // ratioTh[k] = largest ratio with PredictScale <= k, k = 0 .. nlevels-2
+};
+struct MapPointsDev { const float *pos, *normal, *maxDist, *minDist; const int32_t *counts; int cap; };
+struct FrustumHostOut { float *px, *py, *pxr, *vc; int32_t *lvl; uint8_t *inView; };
+// "skip unless": a launch that is enqueued unconditionally and decided on the device - its workgroups leave at once, writing nothing, unless
+// *word < below.  word == nullptr: run.
+struct ProjGate { const int32_t *word; int below; };
+
 struct orbx_matcher : OrbxHandle {
     int maxFeatures = 0, maxPairs = 0;
     hipEvent_t evDep = nullptr, evDone[2] = {nullptr, nullptr};
@@ -125,6 +142,12 @@ struct orbx_matcher : OrbxHandle {
     std::vector<hipEvent_t> fcApplyEv;  // profile_kernels: one pair per Fuse call
     int fcApplyTimed = 0;
     std::vector<int32_t> fcOrder, fcPos, fcSIndex;      // slots in ascending rank, slot -> position, slot -> searchable index
+    // TrackWithMotionModel / TrackLocalMap (orbx_track.hip): match arrays, the gathered pose problem and the optimisation's results, all device memory
+    OrbxOwnedBuf<uint8_t> trWork;
+    OrbxWorkPlan trPlan;
+    std::vector<hipEvent_t> trEv;     // profile_kernels: one event per boundary between the chain's launches
+    int trTimed = 0;
+    bool trProfile = false;
     ~orbx_matcher()
     {
         hipEvent_t *const one[] = {&evDep, &evDep2, &evPyr[0], &evPyr[1], &evDone[0], &evDone[1]};
@@ -133,6 +156,7 @@ struct orbx_matcher : OrbxHandle {
             for (hipEvent_t e : {ev0[r], ev1[r], evMid[r]}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : npTriEv) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : fcApplyEv) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : trEv) if (e) (void)hipEventDestroy(e);
         if (sfHost) (void)hipHostFree(sfHost);
     }
 };
@@ -211,6 +235,16 @@ FeatDev to_dev(const orbx_feature_set *s);
 int stage_host(orbx_matcher *m, const orbx_feature_set *const *h, orbx_feature_set *const *d, int nsides);
 /* k_fuse_best (orbx_match_proj.hip) for one keyframe with chi2_gate = 1: P.cap slots, the list's length read on the device from P.counts */
 void launch_fuse_best(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int32_t *bestIdx, int32_t *bestDist);
+/* k_proj_last_topk + k_proj_last_greedy for ONE frame (F.cap features, L.cap last-frame features; every pointer device memory) on `st`:
+ * matches[0..stride) and nmatches[0] as orbx_search_by_projection_last_device leaves them.  pubFlag != nullptr: the replay also writes
+ * pubAssigned[0..n] (mapped host memory) and raises the sequence word.  Both launches obey `gate`.  Grows the handle's candidate / replay buffers. */
+int enqueue_proj_last(orbx_matcher *m, hipStream_t st, const ProjFrameDev &F, const ProjLastDev &L, const float *scalesDev, float th, int bMono, int checkOri,
+                      int32_t *matches, int32_t *nmatches, int stride, int32_t *pubAssigned, unsigned long long *pubFlag, unsigned long long pubSeq, ProjGate gate);
+/* k_frustum_topk + k_proj_greedy for ONE frame (Tracking::SearchLocalPoints): the mTrack* values go to the handle's frustum arrays and to H, the
+ * matches as above.  hasObs may be nullptr (= all). */
+int enqueue_local_points(orbx_matcher *m, hipStream_t st, const FrustumDev &Fr, const MapPointsDev &Mp, const ProjFrameDev &F, const uint8_t *pointDesc,
+                         const uint8_t *hasObs, const float *scalesDev, float th, float nnRatio, const FrustumHostOut &H, int32_t *matches, int32_t *nmatches,
+                         int stride, int32_t *pubAssigned, unsigned long long *pubFlag, unsigned long long pubSeq);
 }  // namespace orbx_match
 
 #endif

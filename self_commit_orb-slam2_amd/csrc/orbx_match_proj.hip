@@ -352,8 +352,7 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_greedy(ProjFrameDe
 // searched in a window whose pyramid-level range depends on forward / backward motion, and given
 // to the free feature of minimum distance; rotation histogram pruning at the end.
 // ---------------------------------------------------------------------------------------------
-struct ProjLastDev { const uint8_t *valid; const float *pos; const uint8_t *desc, *hasObs; const int32_t *octave; const float *angle; const int32_t *counts;
-                     int cap; const float *tcwCur, *tcwLast; float fx, fy, cx, cy, mbf, mb, maxX, maxY; };
+// (ProjLastDev lives in orbx_match_internal.h: orbx_track.hip chains these kernels through orbx_match::enqueue_proj_last)
 
 __device__ __forceinline__ void proj_motion(const float *Rc, const float *Rl, float mb, int bMono, bool &bForward, bool &bBackward)
 {
@@ -410,9 +409,10 @@ __device__ __forceinline__ bool proj_last_query(const ProjFrameDev &F, const Pro
 }
 
 __global__ __launch_bounds__(256) void k_proj_last_topk(ProjFrameDev F, ProjLastDev L, const float *__restrict__ scaleFactors, float th, int bMono,
-                                                        unsigned long long *__restrict__ topk)
+                                                        unsigned long long *__restrict__ topk, ProjGate gate)
 {
     __shared__ uint32_t sQueue[4][PT_QUEUE];
+    if (gate.word && !(*gate.word < gate.below)) return;      // (uniform)
     const int f = blockIdx.y, lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int n = min(F.counts[f], F.cap), nl = min(L.counts[f], L.cap);
     if (i >= nl) return;
@@ -432,11 +432,12 @@ __global__ __launch_bounds__(PROJ_GREEDY_THREADS) void k_proj_last_greedy(ProjFr
                                                                           int checkOri, const unsigned long long *__restrict__ topk, int32_t *__restrict__ assigned,
                                                                           int32_t *__restrict__ nmatches, int stride, uint32_t *__restrict__ decBuf,
                                                                           uint32_t *__restrict__ queueBuf, int32_t *__restrict__ pubAssigned, unsigned long long *pubFlag,
-                                                                          unsigned long long pubSeq)
+                                                                          unsigned long long pubSeq, ProjGate gate)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int hist[HISTO_LENGTH];
     __shared__ int sTotal, sRemoved, sChangedP[2], sQueued;
+    if (gate.word && !(*gate.word < gate.below)) return;      // (uniform; a gated launch never publishes)
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = min(F.counts[f], F.cap), nl = min(L.counts[f], L.cap);
     uint32_t *owner = (uint32_t *)smem;                     // [cap] lowest observation-carrying point choosing the feature; later: its final holder
@@ -1329,6 +1330,25 @@ extern "C" int orbx_search_by_projection(orbx_matcher *m, const orbx_projection_
     return ORBX_OK;
 }
 
+// one frame's two launches on a stream of the caller's choice (orbx_match_internal.h): the host-array entry point below and the tracking chains of orbx_track.hip
+int orbx_match::enqueue_proj_last(orbx_matcher *m, hipStream_t st, const ProjFrameDev &F, const ProjLastDev &L, const float *scalesDev, float th, int bMono, int checkOri,
+                                  int32_t *matches, int32_t *nmatches, int stride, int32_t *pubAssigned, unsigned long long *pubFlag, unsigned long long pubSeq,
+                                  ProjGate gate)
+{
+    const size_t NL = (size_t)L.cap;
+    int rc;
+    if ((rc = m->topk64.ensure(NL * TOPK)) != ORBX_OK || (rc = m->projDec.ensure(NL)) != ORBX_OK || (rc = m->projQueue.ensure(NL)) != ORBX_OK) return rc;
+    hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((L.cap + 3) / 4), 1u), dim3(256), 0, st, F, L, scalesDev, th, bMono, m->topk64.p, gate);
+    ORBX_LAUNCH_CHECK();
+    const size_t lds = (size_t)F.cap * 5 + 16;
+    if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
+    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_last_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_proj_last_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, L, scalesDev, th, bMono, checkOri, m->topk64.p, matches, nmatches, stride,
+                       m->projDec.p, m->projQueue.p, pubAssigned, pubFlag, pubSeq, gate);
+    ORBX_LAUNCH_CHECK();
+    return ORBX_OK;
+}
+
 static int proj_last_launch(orbx_matcher *m, const ProjFrameDev &F, const ProjLastDev &L, int nframes, const float *scale_factors, int nlevels, float th,
                             int b_mono, int check_ori)
 {
@@ -1342,14 +1362,15 @@ static int proj_last_launch(orbx_matcher *m, const ProjFrameDev &F, const ProjLa
     const int slot = m->profCount % MATCH_PROF_RING;
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     m->midValid[slot] = false;
-    hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((L.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, L, m->scales.p, th, b_mono, m->topk64.p);
+    hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((L.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, L, m->scales.p, th, b_mono, m->topk64.p,
+                       ProjGate{nullptr, 0});
     ORBX_LAUNCH_CHECK();
     const size_t lds = (size_t)F.cap * 5 + 16;
     if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
     if ((rc = m->projDec.ensure((size_t)nframes * L.cap)) != ORBX_OK || (rc = m->projQueue.ensure((size_t)nframes * L.cap)) != ORBX_OK) return rc;
     if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_last_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_proj_last_greedy, dim3((unsigned)nframes), dim3(PROJ_GREEDY_THREADS), lds, m->stream, F, L, m->scales.p, th, b_mono, check_ori, m->topk64.p,
-                       m->matches.p, m->nmatches.p, stride, m->projDec.p, m->projQueue.p, (int32_t *)nullptr, (unsigned long long *)nullptr, 0ull);
+                       m->matches.p, m->nmatches.p, stride, m->projDec.p, m->projQueue.p, (int32_t *)nullptr, (unsigned long long *)nullptr, 0ull, ProjGate{nullptr, 0});
     ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
@@ -1418,17 +1439,10 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
                       fr->grid_height_inv};
     ProjLastDev L = {sVal.in(ar), sPos.in(ar), sLd.in(ar), ls->has_observations ? sObs.in(ar) : nullptr, sOct.in(ar), sAng.in(ar), dCnt + 1, nl,
                      sTc.in(ar), sTl.in(ar), ls->fx, ls->fy, ls->cx, ls->cy, ls->mbf, ls->mb, ls->max_x, ls->max_y};
-    if ((rc = m->topk64.ensure(NL * TOPK)) != ORBX_OK || (rc = m->projDec.ensure(NL)) != ORBX_OK || (rc = m->projQueue.ensure(NL)) != ORBX_OK) return rc;
-    hipLaunchKernelGGL(k_proj_last_topk, dim3((unsigned)((nl + 3) / 4), 1u), dim3(256), 0, st, F, L, dScales, th, b_mono, m->topk64.p);
-    ORBX_LAUNCH_CHECK();
-    const size_t lds = (size_t)n * 5 + 16;
-    if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
-    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_last_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
-    hipLaunchKernelGGL(k_proj_last_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, L, dScales, th, b_mono, check_orientation, m->topk64.p, m->matches.p, m->nmatches.p, stride,
-                       m->projDec.p, m->projQueue.p, sg.dev(rAs), bx.flagDev, seq);
-    ORBX_LAUNCH_CHECK();
+    if ((rc = orbx_match::enqueue_proj_last(m, st, F, L, dScales, th, b_mono, check_orientation, m->matches.p, m->nmatches.p, stride, sg.dev(rAs), bx.flagDev, seq,
+                                            ProjGate{nullptr, 0})) != ORBX_OK) return rc;
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     const int32_t *as = sg.host(rAs);
@@ -1448,13 +1462,7 @@ extern "C" int orbx_search_by_projection_last(orbx_matcher *m, const orbx_projec
 // with the same libm log the reference calls, the largest float ratio that still maps to each level
 // (orbx_predict_scale_thresholds; exact as long as that log is monotonic), the device compares.
 // ---------------------------------------------------------------------------------------------
-struct FrustumDev {
-    const float *tcw;        // [16] per frame
-    float fx, fy, cx, cy, mbf, minX, maxX, minY, maxY, cosLimit;
-    int nlevels;
-    float ratioTh[ORBX_MAX_LEVELS];   // ratioTh[k] = largest ratio with PredictScale <= k, k = 0 .. nlevels-2
-};
-struct MapPointsDev { const float *pos, *normal, *maxDist, *minDist; const int32_t *counts; int cap; };
+// (FrustumDev, MapPointsDev and FrustumHostOut live in orbx_match_internal.h: orbx_track.hip chains k_frustum_topk through orbx_match::enqueue_local_points)
 
 // Frame::isInFrustum for one point from its values: false = not in view (:615); true: the mTrack* values (:721-731)
 __device__ __forceinline__ bool frustum_eval(const FrustumDev &Fr, const float *T, const float P[3], const float Pn[3], float maxD, float minD, float &u, float &v, float &ur,
@@ -1522,7 +1530,6 @@ __global__ __launch_bounds__(256) void k_is_in_frustum(FrustumDev Fr, MapPointsD
 // wave per map point: every lane evaluates the point's frustum test (the same few dozen operations in all lanes; the point's position / normal /
 // distances are read from MAPPED host memory, once per wave), lane 0 stores the mTrack* values for the replay's rescans (device) and for the caller
 // (mapped host), then the wave scans the frame's features for the point's TOPK keys as k_proj_topk does.
-struct FrustumHostOut { float *px, *py, *pxr, *vc; int32_t *lvl; uint8_t *inView; };
 __global__ __launch_bounds__(256) void k_frustum_topk(FrustumDev Fr, MapPointsDev M, ProjFrameDev F, const uint8_t *__restrict__ pdesc, const float *__restrict__ scaleFactors, float th,
                                                       float *__restrict__ dPx, float *__restrict__ dPy, float *__restrict__ dPxr, int32_t *__restrict__ dLvl, float *__restrict__ dVc,
                                                       uint8_t *__restrict__ dIn, FrustumHostOut H, unsigned long long *__restrict__ topk)
@@ -1674,6 +1681,33 @@ extern "C" int orbx_is_in_frustum(orbx_matcher *m, const orbx_frustum_frame *fra
 }
 
 
+// one frame's two launches of Tracking::SearchLocalPoints on a stream of the caller's choice (orbx_match_internal.h): the entry point below and
+// orbx_track.hip's TrackLocalMap chain
+int orbx_match::enqueue_local_points(orbx_matcher *m, hipStream_t st, const FrustumDev &Fr, const MapPointsDev &Mp, const ProjFrameDev &F, const uint8_t *pointDesc,
+                                     const uint8_t *hasObs, const float *scalesDev, float th, float nnRatio, const FrustumHostOut &H, int32_t *matches, int32_t *nmatches,
+                                     int stride, int32_t *pubAssigned, unsigned long long *pubFlag, unsigned long long pubSeq)
+{
+    const int n = F.cap, mm = Mp.cap;
+    const size_t M = (size_t)mm;
+    int rc;
+    if ((rc = m->frProj.ensure(4 * M)) || (rc = m->frLevel.ensure(M)) || (rc = m->frInView.ensure(M)) || (rc = m->topk64.ensure(M * TOPK)) || (rc = m->projDec.ensure(M)) ||
+        (rc = m->projQueue.ensure(M))) return rc;
+    hipLaunchKernelGGL(k_frustum_topk, dim3((unsigned)((mm + 3) / 4)), dim3(256), 0, st, Fr, Mp, F, pointDesc, scalesDev, th, m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p,
+                       m->frProj.p + 3 * M, m->frInView.p, H, m->topk64.p);
+    ORBX_LAUNCH_CHECK();
+    m->frCount = M;
+    ProjPointsDev P = {m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p, m->frProj.p + 3 * M, m->frInView.p, hasObs, pointDesc, Mp.counts, mm};
+    size_t lds = (size_t)n * 6 + 16;
+    if (lds > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile of the projection replay", n); return ORBX_ERR_CAPACITY; }
+    int decLds = 0;      // dec[mm] + the observation flags behind the feature tile, when they fit (k_proj_greedy)
+    if (((lds + 15) & ~(size_t)15) + M * 5 <= 150 * 1024) { decLds = (int)((lds + 15) & ~(size_t)15); lds = (size_t)decLds + M * 5; }
+    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_proj_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, P, scalesDev, th, nnRatio, m->topk64.p, matches, nmatches, stride, m->projDec.p,
+                       m->projQueue.p, pubAssigned, pubFlag, pubSeq, decLds);
+    ORBX_LAUNCH_CHECK();
+    return ORBX_OK;
+}
+
 // Tracking::SearchLocalPoints as one device chain (include/orbx.h): the frustum kernel's outputs are the projection search's inputs.
 extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_frame *fr, const orbx_frustum_frame *pose, const orbx_local_points *pt,
                                         const float *scale_factors, int nlevels, float viewing_cos_limit, float th, float nn_ratio, int32_t *assigned,
@@ -1730,8 +1764,6 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
     if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
     const uint8_t *zDesc = sPd.in(ar);
-    if ((rc = m->frProj.ensure(4 * M)) || (rc = m->frLevel.ensure(M)) || (rc = m->frInView.ensure(M)) || (rc = m->topk64.ensure(M * TOPK)) || (rc = m->projDec.ensure(M)) ||
-        (rc = m->projQueue.ensure(M))) return rc;
     const int32_t *dCnt = sCnt.in(ar);
     FrustumDev Fr;
     Fr.tcw = sTcw.in(ar); Fr.fx = pose->fx; Fr.fy = pose->fy; Fr.cx = pose->cx; Fr.cy = pose->cy; Fr.mbf = pose->mbf;
@@ -1742,21 +1774,10 @@ extern "C" int orbx_search_local_points(orbx_matcher *m, const orbx_projection_f
                       fr->grid_height_inv};
     const float *dScales = sSc.in(ar);
     FrustumHostOut Ho = {sg.dev(rPx), sg.dev(rPy), sg.dev(rPxr), sg.dev(rVc), sg.dev(rLvl), sg.dev(rIn)};
-    hipLaunchKernelGGL(k_frustum_topk, dim3((unsigned)((mm + 3) / 4)), dim3(256), 0, st, Fr, Mp, F, zDesc, dScales, th, m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p,
-                       m->frProj.p + 3 * M, m->frInView.p, Ho, m->topk64.p);
-    ORBX_LAUNCH_CHECK();
-    m->frCount = M;
-    ProjPointsDev P = {m->frProj.p, m->frProj.p + M, m->frProj.p + 2 * M, m->frLevel.p, m->frProj.p + 3 * M, m->frInView.p, pt->has_observations ? sObs.in(ar) : nullptr, zDesc, dCnt + 1, mm};
-    size_t lds = (size_t)n * 6 + 16;
-    if (lds > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile of the projection replay", n); return ORBX_ERR_CAPACITY; }
-    int decLds = 0;      // dec[mm] + the observation flags behind the feature tile, when they fit (k_proj_greedy)
-    if (((lds + 15) & ~(size_t)15) + M * 5 <= 150 * 1024) { decLds = (int)((lds + 15) & ~(size_t)15); lds = (size_t)decLds + M * 5; }
-    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_proj_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
-    hipLaunchKernelGGL(k_proj_greedy, dim3(1), dim3(PROJ_GREEDY_THREADS), lds, st, F, P, dScales, th, nn_ratio, m->topk64.p, m->matches.p, m->nmatches.p, stride, m->projDec.p,
-                       m->projQueue.p, sg.dev(rAs), bx.flagDev, seq, decLds);
-    ORBX_LAUNCH_CHECK();
+    if ((rc = orbx_match::enqueue_local_points(m, st, Fr, Mp, F, zDesc, pt->has_observations ? sObs.in(ar) : nullptr, dScales, th, nn_ratio, Ho, m->matches.p, m->nmatches.p, stride,
+                                               sg.dev(rAs), bx.flagDev, seq)) != ORBX_OK) return rc;
     m->lastPairs = 1; m->lastStride = stride;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     memcpy(in_view, sg.host(rIn), M);
