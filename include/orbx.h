@@ -268,7 +268,16 @@ void orbx_matcher_destroy(orbx_matcher *m);
 /* SearchByBoW for `npairs` independent (A frame, B frame) pairs; A plays the KeyFrame.
  * a/b hold DEVICE pointers; pairs_a/pairs_b are host arrays of frame indices.  Asynchronous
  * on the matcher's stream (which first waits for `after_stream_of`, an extractor whose
- * outputs are being consumed; may be NULL).  Results stay on the device:
+ * outputs are being consumed; may be NULL).
+ * Chaining contract (every call that takes `after_stream_of`, and orbx_compute_stereo_matches_device
+ * for its two extractors): the extractor double-buffers its results, so the batch extracted NEXT
+ * leaves what this call reads alone and the one after that waits for this call before it
+ * overwrites the buffer; a/b must be the pointers orbx_batch_results_device returned AFTER the
+ * batch being consumed (they alternate from batch to batch).  Any number of matcher handles may
+ * be chained behind the same batch, in any order: the extractor waits for every one of them, not
+ * only for the last.  A call that is not chained (NULL) is ordered by the caller
+ * (orbx_extractor_sync before it, orbx_matcher_sync before the extractor's next batch but one).
+ * Results stay on the device:
  *   matches[p*stride + slot] = index of the matched feature in the other set or -1,
  *   dists[p*stride + slot]   = Hamming distance of that match,
  *   nmatches[p]              = return value of SearchByBoW.

@@ -103,7 +103,7 @@ struct orbx_extractor {
     DevBuf<OrbxFcCell> fcDev;
     DevBuf<int> cellCount, lvlCnt, lvlBase, status;
     // results are double buffered: a consumer (matcher) may still read batch i while batch i+1 is
-    // extracted; consumerEv[b] = event after which buffer b may be overwritten again
+    // extracted; consumers[b] = the events after which buffer b may be overwritten again
     // counts | capacity words | keypoints | descriptors of a buffer live in ONE allocation, so that a whole-batch read-back is one copy
     DevBuf<uint8_t> outArena[2];
     int *outCntP[2] = {nullptr, nullptr};
@@ -111,8 +111,39 @@ struct orbx_extractor {
     orbx_keypoint *outKpP[2] = {nullptr, nullptr};
     uint8_t *outDescP[2] = {nullptr, nullptr};
     size_t arenaKpOff = 0, arenaDescOff = 0, arenaBytes = 0;
-    hipEvent_t consumerEv[2] = {nullptr, nullptr};
-    hipEvent_t pyrConsumerEv = nullptr;   // a consumer still reads the (single buffered) pyramid of the last batch
+    // Events of the consumers on OTHER streams that still read a buffer of this handle; the launch that overwrites the buffer waits for every one
+    // of them.  One entry per consumer stream: a stream runs in order, so a later event of the same stream implies its earlier one and replaces
+    // it.  With one consumer per buffer - the benchmark's schedule and every chained call of one matcher - this is one event stored and one
+    // hipStreamWaitEvent in front of the overwriting launch, runtime call for runtime call what a single event slot did.
+    struct ConsumerEvents {
+        enum { CAP = 4 };
+        hipEvent_t ev[CAP] = {};
+        hipStream_t from[CAP] = {};
+        int n = 0;
+        // `waiter` = this handle's stream.  A fifth consumer stream: the handle's stream waits for the oldest entry at once (early, never late)
+        int add(hipStream_t waiter, hipStream_t consumer, hipEvent_t e)
+        {
+            for (int i = 0; i < n; i++)
+                if (from[i] == consumer) { ev[i] = e; return ORBX_OK; }
+            if (n == CAP) {
+                ORBX_HIP_CHECK(hipStreamWaitEvent(waiter, ev[0], 0));
+                for (int i = 1; i < n; i++) { ev[i - 1] = ev[i]; from[i - 1] = from[i]; }
+                n--;
+            }
+            ev[n] = e; from[n] = consumer; n++;
+            return ORBX_OK;
+        }
+        int wait_all(hipStream_t waiter)
+        {
+            const int m = n;
+            n = 0;
+            for (int i = 0; i < m; i++) ORBX_HIP_CHECK(hipStreamWaitEvent(waiter, ev[i], 0));
+            return ORBX_OK;
+        }
+        void host_wait_all() { for (int i = 0; i < n; i++) (void)hipEventSynchronize(ev[i]); n = 0; }
+    };
+    ConsumerEvents consumers[2];          // per result buffer
+    ConsumerEvents pyrConsumers;          // consumers that still read the (single buffered) pyramid of the last batch
     int cur = 0;
     DevBuf<uint32_t> cellSlots, ptBuf, labBuf;
     DevBuf<OrbxLevelKp> lvlKp;
@@ -548,7 +579,7 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
     fill_launch(h, L, img0Dev, batch, stride, framePitch, cb);
     const bool prof = h->profiling;
     hipEvent_t *ev = h->ev[h->profCount % ORBX_PROF_RING];
-    if (h->pyrConsumerEv) { ORBX_HIP_CHECK(hipStreamWaitEvent(h->stream, h->pyrConsumerEv, 0)); h->pyrConsumerEv = nullptr; }
+    if ((rc = h->pyrConsumers.wait_all(h->stream)) != ORBX_OK) return rc;
     ORBX_HIP_CHECK(hipMemsetAsync(h->status.p, 0, (size_t)(batch + 1) * sizeof(int), h->stream));
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[0], h->stream));
     static const bool batchTiles = getenv("ORBX_BATCH_PYR_TILES") && getenv("ORBX_BATCH_PYR_TILES")[0] == '1';
@@ -594,7 +625,7 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_ORIENT + 1], h->stream));      // (orientation is part of the descriptor kernel: this span is empty)
     if (!L.pyrBand && (rc = orbx_launch_blur(L)) != ORBX_OK) return rc;
     if (prof) ORBX_HIP_CHECK(hipEventRecord(ev[ST_BLUR + 1], h->stream));      // (k_pyr_band: empty, the blur is part of the pyramid span)
-    if (h->consumerEv[cb]) { ORBX_HIP_CHECK(hipStreamWaitEvent(h->stream, h->consumerEv[cb], 0)); h->consumerEv[cb] = nullptr; }
+    if ((rc = h->consumers[cb].wait_all(h->stream)) != ORBX_OK) return rc;
     if ((rc = orbx_launch_orient_describe(L)) != ORBX_OK) return rc;
     if (prof) { ORBX_HIP_CHECK(hipEventRecord(ev[ST_DESC + 1], h->stream)); h->profCount++; }
     h->lastBatch = batch; h->lastImg0 = img0Dev; h->lastStride = stride; h->lastFramePitch = framePitch;
@@ -737,8 +768,8 @@ bool orbx_extractor_host_complete_internal(orbx_extractor *h, int *status)
 }
 int orbx_extractor_host_count_internal(orbx_extractor *h) { return h && h->hostOut ? ((const int *)h->hostOut)[0] : 0; }
 const orbx_keypoint *orbx_extractor_host_keypoints_internal(orbx_extractor *h) { return h && h->hostOut ? (const orbx_keypoint *)(h->hostOut + h->arenaKpOff) : nullptr; }
-void orbx_extractor_set_consumer_event_internal(orbx_extractor *h, hipEvent_t ev) { if (h) h->consumerEv[h->cur] = ev; }
-void orbx_extractor_set_pyramid_consumer_event_internal(orbx_extractor *h, hipEvent_t ev) { if (h) h->pyrConsumerEv = ev; }
+int orbx_extractor_add_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev) { return h ? h->consumers[h->cur].add(h->stream, consumer, ev) : ORBX_OK; }
+int orbx_extractor_add_pyramid_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev) { return h ? h->pyrConsumers.add(h->stream, consumer, ev) : ORBX_OK; }
 int orbx_extractor_last_batch_view_internal(orbx_extractor *h, OrbxLastBatchView *v)
 {
     if (!h || !v) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
@@ -1605,8 +1636,8 @@ static int extract_single_combined(orbx_extractor *h, const uint8_t *image, int 
     const int cb = h->cur;
     // consumers of this handle's buffers on other streams (a matcher chained behind the previous frames): the engine's stream knows nothing of
     // them, the host waits (they finished long ago in a synchronous caller)
-    if (h->pyrConsumerEv) { (void)hipEventSynchronize(h->pyrConsumerEv); h->pyrConsumerEv = nullptr; }
-    if (h->consumerEv[cb]) { (void)hipEventSynchronize(h->consumerEv[cb]); h->consumerEv[cb] = nullptr; }
+    h->pyrConsumers.host_wait_all();
+    h->consumers[cb].host_wait_all();
 
     std::unique_lock<std::mutex> lk(C->mu);
     while (C->open && C->open->n >= C->maxB) { lk.unlock(); cpu_relax(); lk.lock(); }      // a full batch waiting for an engine: the next one
@@ -1707,8 +1738,7 @@ static int extract_single_host_impl(orbx_extractor *h, const uint8_t *image, int
         if ((rc = stage_rows(h, image, W, H, stride, dstStride, fp)) != ORBX_OK) return rc;
         h->cur ^= 1;
         const int cb = h->cur;
-        if (h->pyrConsumerEv) { ORBX_HIP_CHECK(hipStreamWaitEvent(h->stream, h->pyrConsumerEv, 0)); h->pyrConsumerEv = nullptr; }
-        if (h->consumerEv[cb]) { ORBX_HIP_CHECK(hipStreamWaitEvent(h->stream, h->consumerEv[cb], 0)); h->consumerEv[cb] = nullptr; }
+        if ((rc = h->pyrConsumers.wait_all(h->stream)) != ORBX_OK || (rc = h->consumers[cb].wait_all(h->stream)) != ORBX_OK) return rc;
         ORBX_HIP_CHECK(hipGraphLaunch(h->sgExec[cb], h->stream));
         h->lastCombined = false;
         h->lastBatch = 1; h->lastImg0 = h->staging.p; h->lastStride = dstStride; h->lastFramePitch = fp;
@@ -1964,7 +1994,8 @@ extern "C" int orbx_extract_batch_begin(orbx_extractor *h, const uint8_t *const 
         (void)hipStreamSynchronize(h->downStream);
         return drain(ORBX_ERR_HIP);
     }
-    h->consumerEv[cb] = S.evDown;      // the batch after the next one overwrites this result buffer: only behind the read-back
+    // the batch after the next one overwrites this result buffer: only behind the read-back (beside a matcher chained behind this batch, not instead of it)
+    if ((rc = h->consumers[cb].add(h->stream, h->downStream, S.evDown)) != ORBX_OK) return drain(rc);
     S.batch = batch; S.cap = cap;
     h->pipeCount++;
     const auto tB2 = std::chrono::steady_clock::now();

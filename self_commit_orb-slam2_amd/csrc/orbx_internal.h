@@ -200,9 +200,10 @@ hipStream_t orbx_extractor_stream_internal(orbx_extractor *h);
 bool orbx_extractor_host_complete_internal(orbx_extractor *h, int *status);
 int orbx_extractor_host_count_internal(orbx_extractor *h);      // keypoints of frame 0 of a host-complete call (its pinned result arena)
 const orbx_keypoint *orbx_extractor_host_keypoints_internal(orbx_extractor *h);      // ... and the keypoints themselves, same arena
-/* `ev` (recorded by a consumer on its own stream) guards the result buffer of the LAST batch: the
- * extractor waits for it before that buffer is overwritten two batches later */
-void orbx_extractor_set_consumer_event_internal(orbx_extractor *h, hipEvent_t ev);
+/* `ev` (recorded by a consumer on its own stream `consumer`) guards the result buffer of the LAST batch: the
+ * extractor waits for it before that buffer is overwritten two batches later.  Every consumer stream of a
+ * buffer is waited for; a later event of the same stream replaces that stream's earlier one */
+int orbx_extractor_add_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev);
 /* device word holding the OR of the capacity bits of the producer's last batch (nullptr before the first batch) */
 const int *orbx_extractor_status_word_internal(orbx_extractor *h);
 
@@ -442,8 +443,8 @@ struct OrbxLastBatchView {
     const float *scale, *invScale; /* host tables, nlevels entries */
 };
 int orbx_extractor_last_batch_view_internal(orbx_extractor *h, OrbxLastBatchView *v);
-/* `ev` guards the PYRAMID of the last batch (single buffered): the next batch waits for it before
- * its first kernel */
-void orbx_extractor_set_pyramid_consumer_event_internal(orbx_extractor *h, hipEvent_t ev);
+/* `ev` guards the PYRAMID of the last batch (single buffered): the next batch waits for it - and for the
+ * event of every other consumer stream - before its first kernel */
+int orbx_extractor_add_pyramid_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev);
 
 #endif

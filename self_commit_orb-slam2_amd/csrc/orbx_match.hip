@@ -1297,8 +1297,7 @@ int chain_back(orbx_matcher *m, orbx_extractor *after)
     hipEvent_t ev = m->evDone[m->doneSlot];
     m->doneSlot ^= 1;
     ORBX_HIP_CHECK(hipEventRecord(ev, m->stream));
-    orbx_extractor_set_consumer_event_internal(after, ev);
-    return ORBX_OK;
+    return orbx_extractor_add_consumer_event_internal(after, m->stream, ev);
 }
 
 FeatDev to_dev(const orbx_feature_set *s)
@@ -1428,8 +1427,8 @@ extern "C" int orbx_compute_stereo_matches_device(orbx_matcher *m, orbx_extracto
     m->lastPairs = npairs; m->lastStride = stride; m->lastStereoPairs = npairs;
     // the pyramids are single buffered: the extractors' next batch waits for these kernels
     ORBX_HIP_CHECK(hipEventRecord(m->evPyr[0], m->stream));
-    orbx_extractor_set_pyramid_consumer_event_internal(left, m->evPyr[0]);
-    if (right != left) orbx_extractor_set_pyramid_consumer_event_internal(right, m->evPyr[0]);
+    if ((rc = orbx_extractor_add_pyramid_consumer_event_internal(left, m->stream, m->evPyr[0])) != ORBX_OK) return rc;
+    if (right != left && (rc = orbx_extractor_add_pyramid_consumer_event_internal(right, m->stream, m->evPyr[0])) != ORBX_OK) return rc;
     rc = chain_back(m, left);
     if (rc == ORBX_OK && right != left) rc = chain_back(m, right);
     return rc;
