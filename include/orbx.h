@@ -562,6 +562,108 @@ int orbx_track_local_map(orbx_matcher *m, const orbx_projection_frame *frame_hos
 int orbx_track_set_profiling(orbx_matcher *m, int on);
 int orbx_track_last_kernel_times(orbx_matcher *m, float *ms, int capacity, int *count);
 
+/* ------------------------------------------------------------------------------------
+ * The refine loop of Tracking::Relocalization (src/Tracking.cc:2135-2223) for every pose that PnPsolver::iterate
+ * returns, for ALL hypotheses of ALL candidates as one launch chain with ONE host wait.  Lives on the matcher handle;
+ * host memory throughout; the handle keeps no state between calls.
+ *
+ * Per distinct hypothesis h = (candidate, Tcw, inlier mask), all H in parallel (one workgroup each):
+ *   seed     mvpMapPoints[j] = bow_match[j] where inliers[j], else -1; sFound = those slots (:2137-2152)
+ *   pose 1   PoseOptimization from Tcw over the features with a point, ascending (:2156) -> ngood[0]
+ *            exit 0: ngood[0] < 10 (the outliers stay, :2159); then the outliers leave (:2162-2164)
+ *            exit 1: ngood[0] >= 50, success
+ *   search 1 SearchByProjection(CurrentFrame, pKF, sFound, 10, 100) (:2171; the whole of src/ORBmatcher.cc:1731-1863: Ow,
+ *            projection, image bounds, dist3D in [0.8 min_distance, 1.2 max_distance], PredictScale, radius, levels
+ *            [l-1, l+1], the greedy search in slot order with the features that hold a point blocked, the rotation
+ *            histogram under check_orientation) -> nadditional[0]
+ *            exit 2: nadditional[0] + ngood[0] < 50 (the additional matches stay)
+ *   pose 2   (:2182) -> ngood[1]; its outliers are NOT dropped (the reference's quirk)
+ *            exit 3: ngood[1] >= 50, success;  exit 4: ngood[1] <= 30
+ *   search 2 sFound rebuilt from every feature that holds a point (:2191-2194); th 3, ORBdist 64 -> nadditional[1]
+ *            exit 5: ngood[1] + nadditional[1] < 50
+ *   pose 3   (:2205-2209) -> ngood[2], the outliers leave;  exit 6: ngood[2] >= 50, success;  exit 7: failure
+ * Every stage is enqueued unconditionally; the workgroups of a hypothesis that has taken its exit leave at once.
+ * A last kernel walks sequence[S] - indices into the H hypotheses in the order in which the reference's round-robin
+ * loop (:2105-2226) would process the returned poses; one record may appear several times, its tail is computed once -
+ * and reports winner = the first entry whose hypothesis succeeded, or -1.
+ *
+ * The identity of a map point is its keyframe slot: the same MapPoint in two slots of one keyframe would be two
+ * points to sFound.  mvbOutlier starts as all zero for every hypothesis (the reference carries the flags of the
+ * hypothesis before into features that hold no point; nothing reads them there).
+ *
+ * Results, per hypothesis (arrays of H entries; any pointer may be NULL): stage (the exit, 0..7), success, ngood[3],
+ * nadditional[2], n_correspondences[3] (edges of each pose call; 0 = did not run), pose[16] (mTcw as the hypothesis
+ * leaves it), stats[3][8] (as orbx_pose_optimization, per pose call; zeros = did not run).  For the winner - or, when
+ * nothing won, for the LAST entry of sequence (what the reference leaves in mCurrentFrame): map_point[N] (keyframe
+ * slot held by each feature or -1), outlier[N] (mvbOutlier), hypothesis, candidate.
+ *
+ * ORBX_ERR_ARG: NULL arguments, nlevels outside 1..12, an empty frame / candidate list / hypothesis list / sequence,
+ * a bow_match outside -1..npoints-1, a hypothesis' candidate or a sequence entry out of range; in form (b) a PnP handle without
+ * a solve or on another device, a candidate or record outside that solve, a keypoint_count that is not the solve's n, a
+ * keypoint_index outside 0..N-1 or one feature named twice.  ORBX_ERR_CAPACITY: more than
+ * ORBX_TRACK_MAX_CORRESPONDENCES possible correspondences (min(N, seeds + valid slots) of a hypothesis), N or npoints
+ * beyond the matcher's max_features or 65535 or the replay's LDS tile (4 N + 6 npoints + 16 <= 160 KB), H beyond
+ * ORBX_RELOC_MAX_HYPOTHESES, S beyond ORBX_RELOC_MAX_SEQUENCE.  Neither launches anything.
+ *
+ * Contract: every field equals, bit for bit, the composition per hypothesis of orbx_pose_optimization (one frame),
+ * the projection restated on the host, orbx_area_search_greedy and the histogram / control flow on the host. */
+#define ORBX_RELOC_MAX_HYPOTHESES 64
+#define ORBX_RELOC_MAX_SEQUENCE 4096
+typedef struct orbx_reloc_frame {
+    orbx_projection_frame frame;      /* keypoints_un, descriptors, u_right, counts, grid statics (occupied is not read) */
+    float fx, fy, cx, cy, mbf;
+    float max_x, max_y;               /* Frame::mnMaxX, mnMaxY */
+    const float *scale_factors;       /* mvScaleFactors [nlevels] */
+    const float *ratio_thresholds;    /* [nlevels-1] from orbx_predict_scale_thresholds */
+    const float *inv_level_sigma2;    /* mvInvLevelSigma2 [nlevels] */
+    int nlevels;
+    int check_orientation;
+} orbx_reloc_frame;
+typedef struct orbx_reloc_candidate {  /* pKF->GetMapPointMatches() as arrays over its npoints slots */
+    int npoints;
+    const uint8_t *valid;             /* pMP && !pMP->isBad() */
+    const float *world_pos;           /* [3] */
+    const float *max_distance;        /* mfMaxDistance (GetMaxDistanceInvariance() / 1.2f) */
+    const float *min_distance;        /* mfMinDistance */
+    const uint8_t *descriptors;       /* [32] */
+    const float *kf_angle;            /* pKF->mvKeysUn[i].angle */
+    const int32_t *bow_match;         /* [N] keyframe slot that vvpMapPointMatches[c][j] holds for frame feature j, or -1 */
+} orbx_reloc_candidate;
+typedef struct orbx_reloc_hypotheses {
+    int count;                        /* H distinct hypotheses */
+    const int32_t *candidate;         /* [H] */
+    const float *tcw;                 /* form (a): [H*12] rows of [R | t] */
+    const uint8_t *inliers;           /* form (a): [H*N] over the frame's features */
+    const int32_t *sequence;          /* [S] indices into the H hypotheses */
+    int sequence_length;
+    /* form (b), pnp != NULL (tcw and inliers are then not read): hypothesis h is record record[h] of candidate candidate[h] of the LAST orbx_pnp_solve
+     * of `pnp` (same device, same candidate order as `cands`).  Its pose is the record's mRefinedRi / mRefinedti narrowed to float (refined_tcw), its
+     * mask the record's mvbRefinedInliers, both read where the PnP chain left them in device memory: no mask crosses to the host.
+     * keypoint_index[c][i] (mvKeyPointIndices: compacted match i of candidate c -> frame feature), keypoint_count[c] entries = that solve's n. */
+    struct orbx_pnp_solver *pnp;
+    const int32_t *record;            /* [H] */
+    const int32_t *const *keypoint_index;   /* [ncands] (entries of candidates no hypothesis names may be NULL) */
+    const int32_t *keypoint_count;    /* [ncands] */
+} orbx_reloc_hypotheses;
+typedef struct orbx_reloc_result {
+    int32_t *stage, *success, *ngood, *nadditional, *n_correspondences;   /* [H], [H], [H*3], [H*2], [H*3] */
+    float *pose;                      /* [H*16] */
+    double *stats;                    /* [H*24] */
+    int32_t *map_point;               /* [N] */
+    uint8_t *outlier;                 /* [N] */
+    int32_t winner, hypothesis, candidate;
+} orbx_reloc_result;
+int orbx_relocalize_refine(orbx_matcher *m, const orbx_reloc_frame *frame, const orbx_reloc_candidate *cands, int ncands,
+                           const orbx_reloc_hypotheses *hyp, orbx_reloc_result *result);
+/* The chain's projection stage on explicit inputs (src/ORBmatcher.cc:1735-1790), from the chain's own kernel: per slot of
+ * `candidate` (bow_match, descriptors and kf_angle are not read) u, v, radius, min_level, max_level of the query and
+ * active = the slot reaches the search (valid, not in found[npoints] - NULL = none -, inside the image and the distance
+ * range; the other values are 0 where it does not).  tcw: [12].  Only the scale tables, intrinsics and bounds of `frame`
+ * are read. */
+int orbx_reloc_project(orbx_matcher *m, const orbx_reloc_frame *frame, const orbx_reloc_candidate *candidate, const float *tcw,
+                       const uint8_t *found, float th, float *u, float *v, float *radius, int32_t *min_level, int32_t *max_level,
+                       uint8_t *active);
+
 /* ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1020-1177; LocalMapping::SearchInNeighbors)
  * and ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1179-1312; LoopClosing): the search of
  * steps 2-3 for every map point - KeyFrame::GetFeaturesInArea(u, v, radius), the level gate, for the

@@ -682,6 +682,118 @@ def fuse_next_slice(map_slice, result):
     return out
 
 
+class RelocFrame(ctypes.Structure):            # orbx_reloc_frame
+    _fields_ = [("frame", ProjectionFrame)] + [(k, ctypes.c_float) for k in ("fx", "fy", "cx", "cy", "mbf", "max_x", "max_y")] + \
+               [("scale_factors", ctypes.c_void_p), ("ratio_thresholds", ctypes.c_void_p), ("inv_level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int),
+                ("check_orientation", ctypes.c_int)]
+
+
+class RelocCandidate(ctypes.Structure):        # orbx_reloc_candidate
+    _fields_ = [("npoints", ctypes.c_int)] + [(k, ctypes.c_void_p) for k in ("valid", "world_pos", "max_distance", "min_distance", "descriptors", "kf_angle", "bow_match")]
+
+
+class RelocHypotheses(ctypes.Structure):       # orbx_reloc_hypotheses
+    _fields_ = [("count", ctypes.c_int), ("candidate", ctypes.c_void_p), ("tcw", ctypes.c_void_p), ("inliers", ctypes.c_void_p), ("sequence", ctypes.c_void_p),
+                ("sequence_length", ctypes.c_int), ("pnp", ctypes.c_void_p), ("record", ctypes.c_void_p), ("keypoint_index", ctypes.c_void_p),
+                ("keypoint_count", ctypes.c_void_p)]
+
+
+class RelocResult(ctypes.Structure):           # orbx_reloc_result
+    _fields_ = [(k, ctypes.c_void_p) for k in ("stage", "success", "ngood", "nadditional", "n_correspondences", "pose", "stats", "map_point", "outlier")] + \
+               [(k, ctypes.c_int32) for k in ("winner", "hypothesis", "candidate")]
+
+
+RELOC_MAX_HYPOTHESES = 64      # ORBX_RELOC_MAX_HYPOTHESES
+RELOC_MAX_SEQUENCE = 4096      # ORBX_RELOC_MAX_SEQUENCE
+
+
+def reloc_sequence(pnp_results, max_its=None, n_iterations=5, max_hypotheses=RELOC_MAX_HYPOTHESES, max_sequence=RELOC_MAX_SEQUENCE):
+    """The order in which Tracking::Relocalization's loop (reference src/Tracking.cc:2105-2226) receives poses from its PnP solvers: round-robin over the
+    undiscarded candidates, iterate(5) on each (src/PnPsolver.cc:247-330, replayed from what the device solved: count / record_of / record_iteration /
+    refined_count per candidate, with n, min_inliers and the solver's iteration limit), a candidate discarded when iterate reports bNoMore.
+    pnp_results: per candidate an object or dict with n, min_inliers, count[its], record_of[its], refined_count[records] and mRansacMaxIts (or max_its here).
+    Returns dict(hypotheses = the distinct (candidate, record, final) in order of first appearance - final = 0: the refined pose and mask of the record
+    (:292-309), 1: the record's own pose and mask returned with bNoMore when the iterations run out (:318-327) -, sequence = indices into them, truncated =
+    the hypothesis or sequence limit cut the order short, exhausted = a candidate ran past the iterations that were solved (the caller solves more and
+    asks again).  Where the reference's loop would stop is not known here: the device's `winner` tells."""
+    def get(r, k, d=None):
+        return r.get(k, d) if isinstance(r, dict) else getattr(r, k, d)
+    K = len(pnp_results)
+    st = []
+    for r in pnp_results:
+        mx = get(r, "mRansacMaxIts", max_its)
+        if mx is None:
+            raise ValueError("no iteration limit: pass max_its")
+        st.append(dict(n=int(get(r, "n")), min_inliers=int(get(r, "min_inliers")), count=np.asarray(get(r, "count")), record_of=np.asarray(get(r, "record_of")),
+                       refined_count=np.asarray(get(r, "refined_count")), max_its=int(mx), it=0))
+    discarded = [False] * K
+    ncand = K
+    hyps, index, seq = [], {}, []
+    truncated = exhausted = False
+    while ncand > 0 and not truncated and not exhausted:
+        for i in range(K):
+            if discarded[i]:
+                continue
+            c = st[i]
+            ret, no_more = None, False
+            if c["n"] < c["min_inliers"]:                                      # :251-255
+                no_more = True
+            else:
+                cur = 0
+                while c["it"] < c["max_its"] or cur < n_iterations:            # :266
+                    if c["it"] >= len(c["count"]):
+                        exhausted = True
+                        break
+                    cur += 1
+                    it = c["it"]
+                    c["it"] += 1
+                    if c["count"][it] >= c["min_inliers"]:                     # :283-309
+                        rec = int(c["record_of"][it])
+                        if c["refined_count"][rec] > c["min_inliers"]:
+                            ret = (i, rec, 0)
+                            break
+                if exhausted:
+                    break
+                if ret is None and c["it"] >= c["max_its"]:                    # :318-327
+                    no_more = True
+                    rec = int(c["record_of"][c["it"] - 1])
+                    if rec >= 0:
+                        ret = (i, rec, 1)
+            if no_more:                                                        # src/Tracking.cc:2128-2132
+                discarded[i] = True
+                ncand -= 1
+            if ret is not None:
+                if ret not in index:
+                    if len(hyps) >= max_hypotheses:
+                        truncated = True
+                        break
+                    index[ret] = len(hyps)
+                    hyps.append(ret)
+                if len(seq) >= max_sequence:
+                    truncated = True
+                    break
+                seq.append(index[ret])
+    return dict(hypotheses=hyps, sequence=np.asarray(seq, np.int32), truncated=truncated, exhausted=exhausted)
+
+
+def reloc_hypotheses(pnp_candidates, triples):
+    """The hypotheses of ORBmatcher.RelocalizeRefine from solved PnPCandidate objects: for every (candidate, record, final) of reloc_sequence what
+    PnPCandidate.iterate returns for it - the record's refined pose and mask (final = 0) or its own pose and mask (final = 1) - with the mask over the
+    frame's features (through mvKeyPointIndices)."""
+    out = []
+    for c, rec, final in triples:
+        r = pnp_candidates[c]
+        vb = np.zeros(r.mN, np.uint8)
+        if final:
+            vb[r.indices[np.asarray(r.record_masks[rec], bool)]] = 1
+            T = r.Tcw(int(r.record_iteration[rec]))
+        else:
+            vb[r.indices[np.asarray(r.refined_masks[rec], bool)]] = 1
+            T = r._tcw(r.refined_tcw[rec])
+        out.append(dict(candidate=int(c), Tcw=T, inliers=vb))
+    return out
+
+
 class ORBmatcher(_Handle):
     """Mirror of the Hamming paths of ORB_SLAM2::ORBmatcher (reference include/ORBmatcher.h:57-215)."""
     _destroy = "orbx_matcher_destroy"
@@ -1329,6 +1441,121 @@ class ORBmatcher(_Handle):
     def last_kernel_timing(self):
         """(distance kernels ms, greedy replay ms) of the SearchByBoW calls averaged by the last last_timing()."""
         return self._timing("orbx_matcher_last_kernel_timing", ctypes.c_float, ctypes.c_float)
+
+    def _reloc_frame(self, frame, inv_level_sigma2=None, features=True):
+        """orbx_reloc_frame from frame = dict(cam = (fx, fy, cx, cy, bf), scale_factors, log_scale_factor, width, height[, min_x ..][, kps, desc, u_right])."""
+        sf = np.ascontiguousarray(frame["scale_factors"], np.float32)
+        minx, miny = np.float32(frame.get("min_x", 0.0)), np.float32(frame.get("min_y", 0.0))
+        maxx, maxy = np.float32(frame.get("max_x", frame["width"])), np.float32(frame.get("max_y", frame["height"]))
+        gw, gh = np.float32(64) / (maxx - minx), np.float32(48) / (maxy - miny)
+        keep = [sf]
+        if features:
+            k = np.ascontiguousarray(frame["kps"], KEYPOINT_DTYPE)
+            n = len(k)
+            d, ur, cn = np.ascontiguousarray(frame["desc"], np.uint8), np.ascontiguousarray(frame["u_right"], np.float32), np.array([n], np.int32)
+            F = ProjectionFrame(_ptr(k).value, _ptr(d).value, _ptr(ur).value, None, _ptr(cn).value, max(n, 1), 1, float(minx), float(miny), float(gw), float(gh))
+            keep += [k, d, ur, cn]
+        else:
+            n = 0
+            F = ProjectionFrame(None, None, None, None, None, 1, 1, float(minx), float(miny), float(gw), float(gh))
+        rt = np.ascontiguousarray(np.concatenate([predict_scale_thresholds(frame["log_scale_factor"], len(sf)), np.zeros(1, np.float32)]), np.float32)
+        is2 = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
+        if is2 is not None and len(is2) != len(sf):
+            raise ValueError("inv_level_sigma2 and scale_factors must have one entry per level")
+        fx, fy, cx, cy, bf = [float(np.float32(v)) for v in frame["cam"]]
+        R = RelocFrame(F, fx, fy, cx, cy, bf, float(maxx), float(maxy), _ptr(sf).value, _ptr(rt).value, None if is2 is None else _ptr(is2).value, len(sf),
+                       1 if self.checkOri else 0)
+        keep += [rt, is2, F]
+        return R, keep, n
+
+    @staticmethod
+    def _reloc_candidate(c, n=None):
+        """orbx_reloc_candidate from dict(valid, pos, max_distance (mfMaxDistance), min_distance[, desc, kf_angle, bow_match])."""
+        valid = np.ascontiguousarray(c["valid"], np.uint8)
+        npts = len(valid)
+        pos = np.ascontiguousarray(np.asarray(c["pos"], np.float32).reshape(-1, 3))
+        mx, mn = np.ascontiguousarray(c["max_distance"], np.float32), np.ascontiguousarray(c["min_distance"], np.float32)
+        d = None if c.get("desc") is None else np.ascontiguousarray(c["desc"], np.uint8)
+        ang = None if c.get("kf_angle") is None else np.ascontiguousarray(c["kf_angle"], np.float32)
+        bow = None if c.get("bow_match") is None else np.ascontiguousarray(c["bow_match"], np.int32)
+        if bow is not None and n is not None and len(bow) != n:
+            raise ValueError("bow_match must have one entry per frame feature")
+        if len(pos) != npts or len(mx) != npts or len(mn) != npts or (d is not None and len(d) != npts) or (ang is not None and len(ang) != npts):
+            raise ValueError("the arrays of a candidate must have one entry per slot")
+        opt = lambda a: None if a is None else _ptr(a).value
+        return RelocCandidate(npts, _ptr(valid).value, _ptr(pos).value, _ptr(mx).value, _ptr(mn).value, opt(d), opt(ang), opt(bow)), [valid, pos, mx, mn, d, ang, bow]
+
+    def RelocProject(self, frame, cand, Tcw, found, th):
+        """The projection stage of the relocalisation chain on explicit inputs (orbx_reloc_project; reference src/ORBmatcher.cc:1735-1790): per keyframe slot the
+        query of SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist).  found: [npoints] flags or None.
+        Returns dict(u, v, radius, min_level, max_level, active)."""
+        R, keep, _ = self._reloc_frame(frame, features=False)
+        C, keepc = self._reloc_candidate(cand)
+        T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(-1)[:12])
+        fnd = None if found is None else np.ascontiguousarray(found, np.uint8)
+        m = max(C.npoints, 1)
+        u, v, r = np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        lo, hi, act = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        self._L.orbx_reloc_project.argtypes = [ctypes.c_void_p, ctypes.POINTER(RelocFrame), ctypes.POINTER(RelocCandidate), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float] + \
+                                              [ctypes.c_void_p] * 6
+        _check(self._L.orbx_reloc_project(self._h, ctypes.byref(R), ctypes.byref(C), _ptr(T), None if fnd is None else _ptr(fnd), ctypes.c_float(th), _ptr(u), _ptr(v), _ptr(r),
+                                          _ptr(lo), _ptr(hi), _ptr(act)))
+        k = C.npoints
+        return dict(u=u[:k], v=v[:k], radius=r[:k], min_level=lo[:k], max_level=hi[:k], active=act[:k])
+
+    def RelocalizeRefine(self, frame, cands, hyps, sequence, inv_level_sigma2, pnp=None, keypoint_index=None):
+        return self.reloc_prepare(frame, cands, hyps, sequence, inv_level_sigma2, pnp, keypoint_index)()
+
+    def reloc_prepare(self, frame, cands, hyps, sequence, inv_level_sigma2, pnp=None, keypoint_index=None):
+        """The refine loop of Tracking::Relocalization (reference src/Tracking.cc:2135-2223) for all hypotheses of all candidates as one device chain with one
+        host wait (orbx_relocalize_refine).  frame: dict(kps, desc, u_right, scale_factors, log_scale_factor, cam, width, height[, min_x ..]); cands: list of
+        dict(valid, pos, max_distance, min_distance, desc, kf_angle, bow_match[N]); hyps: list of dict(candidate, Tcw, inliers[N]); sequence: indices into hyps.
+        Returns a prepared call: call() -> dict(stage[H], success[H], ngood[H, 3], nadditional[H, 2], n_correspondences[H, 3], pose[H, 4, 4], stats[H, 3, 8],
+        map_point[N], outlier[N], winner, hypothesis, candidate); call.raw() is the C call alone on the marshalled arrays.
+        pnp = a PnPsolver whose last Solve was over these candidates, in this order: hyps is then a list of dict(candidate, record) and every hypothesis' pose and
+        mask are the record's refined ones, read where that solve left them on the device (no mask crosses to the host); keypoint_index[c] = mvKeyPointIndices of
+        candidate c (compacted match -> frame feature; None for a candidate no hypothesis names)."""
+        R, keep, n = self._reloc_frame(frame, inv_level_sigma2)
+        cs = [self._reloc_candidate(c, n) for c in cands]
+        CA = (RelocCandidate * max(len(cs), 1))(*[c[0] for c in cs])
+        H = len(hyps)
+        hc = np.ascontiguousarray([int(h["candidate"]) for h in hyps], np.int32)
+        sq = np.ascontiguousarray(sequence, np.int32)
+        if pnp is None:
+            ht = np.ascontiguousarray(np.stack([np.asarray(h["Tcw"], np.float32).reshape(-1)[:12] for h in hyps]) if H else np.zeros((0, 12), np.float32))
+            hm = np.ascontiguousarray(np.stack([np.asarray(h["inliers"], np.uint8) for h in hyps]) if H else np.zeros((0, n), np.uint8))
+            if H and hm.shape[1] != n:
+                raise ValueError("inliers must have one entry per frame feature")
+            HY = RelocHypotheses(H, _ptr(hc).value, _ptr(ht).value, _ptr(hm).value, _ptr(sq).value, len(sq), None, None, None, None)
+        else:
+            ht = np.ascontiguousarray([int(h["record"]) for h in hyps], np.int32)
+            ki = [None if k is None else np.ascontiguousarray(k, np.int32) for k in (keypoint_index if keypoint_index is not None else [None] * len(cs))]
+            if len(ki) != len(cs):
+                raise ValueError("keypoint_index must have one entry per candidate")
+            kp = (ctypes.c_void_p * max(len(ki), 1))(*[None if k is None else _ptr(k).value for k in ki])
+            hm = [ki, kp, np.ascontiguousarray([0 if k is None else len(k) for k in ki], np.int32), pnp]
+            HY = RelocHypotheses(H, _ptr(hc).value, None, None, _ptr(sq).value, len(sq), pnp._h, _ptr(ht).value, ctypes.cast(kp, ctypes.c_void_p), _ptr(hm[2]).value)
+        h1, n1 = max(H, 1), max(n, 1)
+        stage, succ, ng, na, nc = np.zeros(h1, np.int32), np.zeros(h1, np.int32), np.zeros((h1, 3), np.int32), np.zeros((h1, 2), np.int32), np.zeros((h1, 3), np.int32)
+        pose, stats, mp, outl = np.zeros((h1, 4, 4), np.float32), np.zeros((h1, 3, 8), np.float64), np.full(n1, -1, np.int32), np.zeros(n1, np.uint8)
+        RS = RelocResult(*[_ptr(a).value for a in (stage, succ, ng, na, nc, pose, stats, mp, outl)])
+        self._L.orbx_relocalize_refine.argtypes = [ctypes.c_void_p, ctypes.POINTER(RelocFrame), ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RelocHypotheses),
+                                                   ctypes.POINTER(RelocResult)]
+        fn, hnd, nca = self._L.orbx_relocalize_refine, self._h, len(cs)
+
+        def raw():
+            return fn(hnd, ctypes.byref(R), ctypes.cast(CA, ctypes.c_void_p), nca, ctypes.byref(HY), ctypes.byref(RS))
+
+        def result():
+            return dict(stage=stage[:H].copy(), success=succ[:H].copy(), ngood=ng[:H].copy(), nadditional=na[:H].copy(), n_correspondences=nc[:H].copy(), pose=pose[:H].copy(),
+                        stats=stats[:H].copy(), map_point=mp[:n].copy(), outlier=outl[:n].copy(), winner=RS.winner, hypothesis=RS.hypothesis, candidate=RS.candidate)
+
+        def call():
+            _check(raw())
+            return result()
+        call.raw, call.result = raw, result
+        call.keep = [keep, cs, CA, hc, ht, hm, sq, HY, stage, succ, ng, na, nc, pose, stats, mp, outl, RS, R]
+        return call
 
 
 # =====================================================================================

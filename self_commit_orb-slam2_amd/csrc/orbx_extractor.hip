@@ -115,22 +115,32 @@ struct orbx_extractor {
     // of them.  One entry per consumer stream: a stream runs in order, so a later event of the same stream implies its earlier one and replaces
     // it.  With one consumer per buffer - the benchmark's schedule and every chained call of one matcher - this is one event stored and one
     // hipStreamWaitEvent in front of the overwriting launch, runtime call for runtime call what a single event slot did.
+    // The events are this handle's OWN, recorded on the consumer's stream when the consumer reports: a consumer
+    // handle may be destroyed - and its events with it - long before the buffer it read is overwritten, and a wait for a destroyed event reads freed memory.
     struct ConsumerEvents {
         enum { CAP = 4 };
-        hipEvent_t ev[CAP] = {};
+        hipEvent_t ev[CAP] = {};          // created on first use, kept until the handle goes (release())
         hipStream_t from[CAP] = {};
         int n = 0;
         // `waiter` = this handle's stream.  A fifth consumer stream: the handle's stream waits for the oldest entry at once (early, never late)
-        int add(hipStream_t waiter, hipStream_t consumer, hipEvent_t e)
+        int add(hipStream_t waiter, hipStream_t consumer)
         {
+            int slot = -1;
             for (int i = 0; i < n; i++)
-                if (from[i] == consumer) { ev[i] = e; return ORBX_OK; }
-            if (n == CAP) {
-                ORBX_HIP_CHECK(hipStreamWaitEvent(waiter, ev[0], 0));
-                for (int i = 1; i < n; i++) { ev[i - 1] = ev[i]; from[i - 1] = from[i]; }
-                n--;
+                if (from[i] == consumer) slot = i;
+            if (slot < 0) {
+                if (n == CAP) {
+                    ORBX_HIP_CHECK(hipStreamWaitEvent(waiter, ev[0], 0));
+                    hipEvent_t first = ev[0];
+                    for (int i = 1; i < n; i++) { ev[i - 1] = ev[i]; from[i - 1] = from[i]; }
+                    ev[n - 1] = first;
+                    n--;
+                }
+                slot = n++;
             }
-            ev[n] = e; from[n] = consumer; n++;
+            if (!ev[slot]) ORBX_HIP_CHECK(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
+            ORBX_HIP_CHECK(hipEventRecord(ev[slot], consumer));
+            from[slot] = consumer;
             return ORBX_OK;
         }
         int wait_all(hipStream_t waiter)
@@ -141,6 +151,7 @@ struct orbx_extractor {
             return ORBX_OK;
         }
         void host_wait_all() { for (int i = 0; i < n; i++) (void)hipEventSynchronize(ev[i]); n = 0; }
+        void release() { for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; } n = 0; }
     };
     ConsumerEvents consumers[2];          // per result buffer
     ConsumerEvents pyrConsumers;          // consumers that still read the (single buffered) pyramid of the last batch
@@ -768,8 +779,8 @@ bool orbx_extractor_host_complete_internal(orbx_extractor *h, int *status)
 }
 int orbx_extractor_host_count_internal(orbx_extractor *h) { return h && h->hostOut ? ((const int *)h->hostOut)[0] : 0; }
 const orbx_keypoint *orbx_extractor_host_keypoints_internal(orbx_extractor *h) { return h && h->hostOut ? (const orbx_keypoint *)(h->hostOut + h->arenaKpOff) : nullptr; }
-int orbx_extractor_add_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev) { return h ? h->consumers[h->cur].add(h->stream, consumer, ev) : ORBX_OK; }
-int orbx_extractor_add_pyramid_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev) { return h ? h->pyrConsumers.add(h->stream, consumer, ev) : ORBX_OK; }
+int orbx_extractor_add_consumer_event_internal(orbx_extractor *h, hipStream_t consumer) { return h ? h->consumers[h->cur].add(h->stream, consumer) : ORBX_OK; }
+int orbx_extractor_add_pyramid_consumer_event_internal(orbx_extractor *h, hipStream_t consumer) { return h ? h->pyrConsumers.add(h->stream, consumer) : ORBX_OK; }
 int orbx_extractor_last_batch_view_internal(orbx_extractor *h, OrbxLastBatchView *v)
 {
     if (!h || !v) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
@@ -883,6 +894,7 @@ extern "C" void orbx_extractor_destroy(orbx_extractor *h)
     h->status.release(); h->cellSlots.release(); h->ptBuf.release(); h->labBuf.release(); h->lvlKp.release();
     for (int r = 0; r < ORBX_PROF_RING; r++)
         for (int i = 0; i <= ST_COUNT; i++) if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
+    h->consumers[0].release(); h->consumers[1].release(); h->pyrConsumers.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1995,7 +2007,7 @@ extern "C" int orbx_extract_batch_begin(orbx_extractor *h, const uint8_t *const 
         return drain(ORBX_ERR_HIP);
     }
     // the batch after the next one overwrites this result buffer: only behind the read-back (beside a matcher chained behind this batch, not instead of it)
-    if ((rc = h->consumers[cb].add(h->stream, h->downStream, S.evDown)) != ORBX_OK) return drain(rc);
+    if ((rc = h->consumers[cb].add(h->stream, h->downStream)) != ORBX_OK) return drain(rc);
     S.batch = batch; S.cap = cap;
     h->pipeCount++;
     const auto tB2 = std::chrono::steady_clock::now();

@@ -200,10 +200,10 @@ hipStream_t orbx_extractor_stream_internal(orbx_extractor *h);
 bool orbx_extractor_host_complete_internal(orbx_extractor *h, int *status);
 int orbx_extractor_host_count_internal(orbx_extractor *h);      // keypoints of frame 0 of a host-complete call (its pinned result arena)
 const orbx_keypoint *orbx_extractor_host_keypoints_internal(orbx_extractor *h);      // ... and the keypoints themselves, same arena
-/* `ev` (recorded by a consumer on its own stream `consumer`) guards the result buffer of the LAST batch: the
- * extractor waits for it before that buffer is overwritten two batches later.  Every consumer stream of a
- * buffer is waited for; a later event of the same stream replaces that stream's earlier one */
-int orbx_extractor_add_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev);
+/* A consumer reports that the work it has enqueued on its stream `consumer` so far reads the result buffer of the LAST batch: the extractor
+ * records an event of its OWN there (a consumer handle may be destroyed long before the wait) and waits for it before that buffer is overwritten
+ * two batches later.  Every consumer stream of a buffer is waited for; a later report of the same stream replaces that stream's earlier one */
+int orbx_extractor_add_consumer_event_internal(orbx_extractor *h, hipStream_t consumer);
 /* device word holding the OR of the capacity bits of the producer's last batch (nullptr before the first batch) */
 const int *orbx_extractor_status_word_internal(orbx_extractor *h);
 
@@ -425,6 +425,17 @@ struct OrbxPoseOptArgs {
     const int32_t *gate;           /* [1] */
 };
 int orbx_pose_opt_enqueue(hipStream_t st, const OrbxPoseOptArgs &a);
+/* ... for B frames in ONE launch (orbx_reloc.hip): frame f's arrays at f * cap, pose0 / poseOut at 16 f, cam at 5 f, stats at 8 f, counts[f], and a gate word
+ * PER FRAME: gate[f] < 0 = frame f's workgroup leaves at once and writes nothing.  One instantiation, the one that holds maxCount (the host's bound over
+ * all frames), serves every frame. */
+int orbx_pose_opt_enqueue_batch(hipStream_t st, const OrbxPoseOptArgs &a, int B);
+
+/* Where the last orbx_pnp_solve of a PnP handle left ONE candidate's refined records in device memory (orbx_reloc.hip reads the hypotheses there, no
+ * mask crosses to the host): record r's mRefinedRi / mRefinedti at refR + 9 r / refT + 3 r (doubles; narrowed to float they are refined_tcw), its
+ * mvbRefinedInliers as bit i of refMask[r * words + (i >> 6)] over the candidate's n compacted matches; nrec records.
+ * ORBX_ERR_ARG: no solve yet, a handle on another device than `device`, a candidate outside the last solve. */
+struct OrbxPnpRows { const double *refR, *refT; const unsigned long long *refMask; int n, words, nrec; };
+int orbx_pnp_device_rows_internal(orbx_pnp_solver *h, int candidate, int device, OrbxPnpRows *out);
 
 /* Device view of the LAST batch of an extractor: results + the unblurred pyramid (what the
  * reference keeps in ORBextractor::mvImagePyramid, read by Frame::ComputeStereoMatches). */
@@ -443,8 +454,7 @@ struct OrbxLastBatchView {
     const float *scale, *invScale; /* host tables, nlevels entries */
 };
 int orbx_extractor_last_batch_view_internal(orbx_extractor *h, OrbxLastBatchView *v);
-/* `ev` guards the PYRAMID of the last batch (single buffered): the next batch waits for it - and for the
- * event of every other consumer stream - before its first kernel */
-int orbx_extractor_add_pyramid_consumer_event_internal(orbx_extractor *h, hipStream_t consumer, hipEvent_t ev);
+/* ... for the PYRAMID of the last batch (single buffered): the next batch waits for every consumer stream that reported, before its first kernel */
+int orbx_extractor_add_pyramid_consumer_event_internal(orbx_extractor *h, hipStream_t consumer);
 
 #endif

@@ -2111,6 +2111,7 @@ struct PoseOptDev {
     // unless gateMin <= *gate < gateBelow; NULL = run
     const int32_t *gate;
     int gateMin, gateBelow;
+    int gateStride;          // 0: one word for the launch; 1: a word per frame (orbx_pose_opt_enqueue_batch)
 };
 
 #define PO_NRED 28   /* 21 upper-triangle entries of H + 6 of b + chi2 */
@@ -2221,7 +2222,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(PoseOptDev P, Huber hub)
     __shared__ int sOk, sIterOk, sNBad;
     const int f = blockIdx.x, tid = threadIdx.x;
     if (P.gate) {      // (uniform; a gated launch never publishes)
-        const int g = *P.gate;
+        const int g = P.gate[(size_t)f * P.gateStride];
         if (g < P.gateMin || g >= P.gateBelow) return;
     }
     const int n = min(P.one ? P.count0 : P.counts[f], P.cap);
@@ -3254,7 +3255,7 @@ static int pose_opt_launch(hipStream_t st, const PoseOptDev &D, int B, int maxCo
 // others leave at once (~4 us each).
 int orbx_pose_opt_enqueue(hipStream_t st, const OrbxPoseOptArgs &a)
 {
-    PoseOptDev D = {a.pose0, a.cam, a.Xw, a.obs, a.invS2, a.counts, a.cap, a.poseOut, a.outlier, a.ret, a.stats, nullptr, nullptr, 0ull, nullptr, 0, 0, {}, {}, a.gate, 0, 0};
+    PoseOptDev D = {a.pose0, a.cam, a.Xw, a.obs, a.invS2, a.counts, a.cap, a.poseOut, a.outlier, a.ret, a.stats, nullptr, nullptr, 0ull, nullptr, 0, 0, {}, {}, a.gate, 0, 0, 0};
     if (a.maxCount > 256 * 32) return pose_opt_launch(st, D, 1, a.maxCount);      // (the capacity error)
     static const int kEdges[] = {1, 2, 3, 4, 8, 16, 32};
     int prev = -1;      // largest count of the instantiation in front
@@ -3267,6 +3268,15 @@ int orbx_pose_opt_enqueue(hipStream_t st, const OrbxPoseOptArgs &a)
         prev = top;
     }
     return ORBX_OK;
+}
+
+// ... and for B frames in ONE launch (orbx_reloc.hip): frame f's arrays at f * cap (pose0 / poseOut at 16 f, cam at 5 f), its count in counts[f], its
+// own word gate[f] (< 0: the frame's workgroup leaves at once and writes nothing).  One instantiation - the one that holds maxCount, the host's bound over
+// all frames - serves every frame: an instantiation with more edges per thread than a count needs computes the same bits.
+int orbx_pose_opt_enqueue_batch(hipStream_t st, const OrbxPoseOptArgs &a, int B)
+{
+    PoseOptDev D = {a.pose0, a.cam, a.Xw, a.obs, a.invS2, a.counts, a.cap, a.poseOut, a.outlier, a.ret, a.stats, nullptr, nullptr, 0ull, nullptr, 0, 0, {}, {}, a.gate, 0, 0x7fffffff, 1};
+    return pose_opt_launch(st, D, B, a.maxCount);
 }
 
 extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_problem *p, float *poses_out, uint8_t *outlier, int32_t *inliers, double *stats)
@@ -3293,7 +3303,7 @@ extern "C" int orbx_pose_optimization(orbx_pose_optimizer *h, const orbx_pose_pr
     if (rcs != ORBX_OK) return rcs;
     const uint8_t *o1 = sg.host(rOutlier);
     PoseOptDev D = {sg.dev(sPose), sg.dev(sCam), sg.dev(sXw), sg.dev(sObs), sg.dev(sInv), sg.dev(sCnt), cap, sg.dev(rPose), sg.dev(rOutlier), sg.dev(rInliers), sg.dev(rStats), bx.counter, bx.flagDev, bx.arm(), g_poProf,
-                    B == 1 ? 1 : 0, p->counts[0], {}, {}, nullptr, 0, 0};
+                    B == 1 ? 1 : 0, p->counts[0], {}, {}, nullptr, 0, 0, 0};
     if (B == 1) { memcpy(D.cam0, p->cameras, sizeof D.cam0); memcpy(D.pose00, p->poses, sizeof D.pose00); }
     int maxCount = 0;
     for (int i = 0; i < B; i++) maxCount = std::max(maxCount, std::min((int)p->counts[i], cap));

@@ -1212,7 +1212,7 @@ extern "C" int orbx_matcher_create(int device, int max_features, int max_pairs, 
     orbx_matcher *m = new orbx_matcher();
     m->maxFeatures = max_features; m->maxPairs = max_pairs;
     int rc = m->open(device);
-    hipEvent_t *const sync[] = {&m->evDep, &m->evDep2, &m->evPyr[0], &m->evPyr[1], &m->evDone[0], &m->evDone[1]};
+    hipEvent_t *const sync[] = {&m->evDep, &m->evDep2};
     for (hipEvent_t *e : sync) if (!rc) rc = orbx_event_create(e, hipEventDisableTiming);
     for (int r = 0; r < MATCH_PROF_RING; r++)
         for (hipEvent_t *e : {&m->ev0[r], &m->ev1[r], &m->evMid[r]}) if (!rc) rc = orbx_event_create(e);
@@ -1288,16 +1288,13 @@ int prep_pairs(orbx_matcher *m, const orbx_feature_set *a, const orbx_feature_se
 }
 
 // The producer double-buffers its results: the batch extracted next does not touch what this call
-// reads, the one after that does.  Hand the producer an event recorded behind the match kernels; it
-// waits for it right before overwriting this buffer again, so matching batch i overlaps with the
+// reads, the one after that does.  Tell the producer: it records an event of its own behind the match kernels
+// and waits for it right before overwriting this buffer again, so matching batch i overlaps with the
 // extraction of batch i+1 (the greedy replay occupies one wave per CU and is latency bound).
 int chain_back(orbx_matcher *m, orbx_extractor *after)
 {
     if (!after) return ORBX_OK;
-    hipEvent_t ev = m->evDone[m->doneSlot];
-    m->doneSlot ^= 1;
-    ORBX_HIP_CHECK(hipEventRecord(ev, m->stream));
-    return orbx_extractor_add_consumer_event_internal(after, m->stream, ev);
+    return orbx_extractor_add_consumer_event_internal(after, m->stream);
 }
 
 FeatDev to_dev(const orbx_feature_set *s)
@@ -1426,9 +1423,8 @@ extern "C" int orbx_compute_stereo_matches_device(orbx_matcher *m, orbx_extracto
     m->profCount++;
     m->lastPairs = npairs; m->lastStride = stride; m->lastStereoPairs = npairs;
     // the pyramids are single buffered: the extractors' next batch waits for these kernels
-    ORBX_HIP_CHECK(hipEventRecord(m->evPyr[0], m->stream));
-    if ((rc = orbx_extractor_add_pyramid_consumer_event_internal(left, m->stream, m->evPyr[0])) != ORBX_OK) return rc;
-    if (right != left && (rc = orbx_extractor_add_pyramid_consumer_event_internal(right, m->stream, m->evPyr[0])) != ORBX_OK) return rc;
+    if ((rc = orbx_extractor_add_pyramid_consumer_event_internal(left, m->stream)) != ORBX_OK) return rc;
+    if (right != left && (rc = orbx_extractor_add_pyramid_consumer_event_internal(right, m->stream)) != ORBX_OK) return rc;
     rc = chain_back(m, left);
     if (rc == ORBX_OK && right != left) rc = chain_back(m, right);
     return rc;

@@ -80,10 +80,17 @@ struct FrustumHostOut { float *px, *py, *pxr, *vc; int32_t *lvl; uint8_t *inView
 // *word < below.  word == nullptr: run.
 struct ProjGate { const int32_t *word; int below; };
 
+// The greedy area search as a link of a chain (orbx_reloc.hip): H problems that share ONE frame.  status[f] != 0: problem f's workgroups leave at once;
+// descBase[f]: first descriptor (32-byte units into the queries' descriptor array) of problem f's queries; blocked[f * F.cap + j]: feature j is taken
+// from the start in problem f.
+struct AreaChainDev { const int32_t *status, *descBase; const uint8_t *blocked; };
+// ... its queries: problem f's query i at f * cap + i (descriptors: see descBase), counts[f] queries
+struct AreaQueriesArgs { const float *u, *v, *radius; const int32_t *minLevel, *maxLevel; const uint8_t *active, *desc; const int32_t *counts; int cap;
+                         float winMinX, winMinY; };
+
 struct orbx_matcher : OrbxHandle {
     int maxFeatures = 0, maxPairs = 0;
-    hipEvent_t evDep = nullptr, evDone[2] = {nullptr, nullptr};
-    int doneSlot = 0;
+    hipEvent_t evDep = nullptr;
     hipEvent_t ev0[MATCH_PROF_RING] = {}, ev1[MATCH_PROF_RING] = {};   // one pair per *_device call (ring)
     hipEvent_t evMid[MATCH_PROF_RING] = {};                             // SearchByBoW: between the distance kernel and the greedy replay
     bool midValid[MATCH_PROF_RING] = {};
@@ -102,7 +109,7 @@ struct orbx_matcher : OrbxHandle {
     OrbxOwnedBuf<uint8_t> arena;   // ... their inputs on the device, copied there once by k_stage_copy (same offsets as in box.in)
     OrbxOwnedBuf<int32_t> sad;
     OrbxOwnedBuf<int32_t> stRowStart, stRowList;   // ComputeStereoMatches: vRowIndices of the right frames (k_stereo_rows)
-    hipEvent_t evDep2 = nullptr, evPyr[2] = {nullptr, nullptr};
+    hipEvent_t evDep2 = nullptr;
     int lastStereoPairs = 0;
     // orbx_stereo_frame (one stereo frame, host-synchronous): scale tables as last uploaded, a device zero for the pair arrays, pinned results
     float sfScales[128] = {};
@@ -148,9 +155,12 @@ struct orbx_matcher : OrbxHandle {
     std::vector<hipEvent_t> trEv;     // profile_kernels: one event per boundary between the chain's launches
     int trTimed = 0;
     bool trProfile = false;
+    // Relocalization's refine loop (orbx_reloc.hip): the per-hypothesis state, queries, pose problems and results of one call, all device memory
+    OrbxOwnedBuf<uint8_t> rlWork;
+    OrbxWorkPlan rlPlan;
     ~orbx_matcher()
     {
-        hipEvent_t *const one[] = {&evDep, &evDep2, &evPyr[0], &evPyr[1], &evDone[0], &evDone[1]};
+        hipEvent_t *const one[] = {&evDep, &evDep2};
         for (hipEvent_t *e : one) if (*e) (void)hipEventDestroy(*e);
         for (int r = 0; r < MATCH_PROF_RING; r++)
             for (hipEvent_t e : {ev0[r], ev1[r], evMid[r]}) if (e) (void)hipEventDestroy(e);
@@ -245,6 +255,10 @@ int enqueue_proj_last(orbx_matcher *m, hipStream_t st, const ProjFrameDev &F, co
 int enqueue_local_points(orbx_matcher *m, hipStream_t st, const FrustumDev &Fr, const MapPointsDev &Mp, const ProjFrameDev &F, const uint8_t *pointDesc,
                          const uint8_t *hasObs, const float *scalesDev, float th, float nnRatio, const FrustumHostOut &H, int32_t *matches, int32_t *nmatches,
                          int stride, int32_t *pubAssigned, unsigned long long *pubFlag, unsigned long long pubSeq);
+/* k_area_topk + k_area_greedy for the H problems of a chain on `st` (every pointer device memory): assigned / dists [f * A.cap + i] and nmatches[f] as
+ * orbx_area_search_greedy leaves them, untouched where status[f] != 0.  F.counts[0] features, shared by all problems.  Grows the handle's candidate buffer. */
+int enqueue_area_greedy(orbx_matcher *m, hipStream_t st, const ProjFrameDev &F, const AreaQueriesArgs &A, const AreaChainDev &C, int H, int maxDist,
+                        int32_t *assigned, int32_t *dists, int32_t *nmatches);
 }  // namespace orbx_match
 
 #endif

@@ -737,7 +737,8 @@ struct AreaQueriesDev { const float *u, *v, *radius; const int32_t *minLevel, *m
                         float winMinX, winMinY; };
 struct AreaQuery { float x, y, r; int minLevel, maxLevel, cx0, cx1, cy0, cy1; bool any; unsigned long long d[4]; };
 
-__device__ __forceinline__ AreaQuery area_query(const ProjFrameDev &F, const AreaQueriesDev &Q, size_t qi)
+// di: the query's descriptor (= qi, except in a chain whose queries share a candidate's descriptors, AreaChainDev)
+__device__ __forceinline__ AreaQuery area_query(const ProjFrameDev &F, const AreaQueriesDev &Q, size_t qi, size_t di)
 {
     AreaQuery q;
     q.x = Q.u[qi]; q.y = Q.v[qi]; q.r = Q.radius[qi];
@@ -746,7 +747,7 @@ __device__ __forceinline__ AreaQuery area_query(const ProjFrameDev &F, const Are
     const int y0 = max(0, (int)floorf((q.y - Q.winMinY - q.r) * F.ghInv)), y1 = min(GRID_ROWS - 1, (int)ceilf((q.y - Q.winMinY + q.r) * F.ghInv));
     q.any = !(x0 >= GRID_COLS || x1 < 0 || y0 >= GRID_ROWS || y1 < 0);
     q.cx0 = x0; q.cx1 = x1; q.cy0 = y0; q.cy1 = y1;
-    const unsigned long long *dp = (const unsigned long long *)(Q.desc + qi * 32);
+    const unsigned long long *dp = (const unsigned long long *)(Q.desc + di * 32);
     q.d[0] = dp[0]; q.d[1] = dp[1]; q.d[2] = dp[2]; q.d[3] = dp[3];
     return q;
 }
@@ -764,15 +765,20 @@ __device__ __forceinline__ unsigned long long area_key(const ProjFrameDev &F, si
     return ((unsigned long long)dist << 32) | ((unsigned long long)cx << 22) | ((unsigned long long)cy << 16) | (unsigned long long)idx;
 }
 
-__global__ __launch_bounds__(256) void k_area_topk(ProjFrameDev F, AreaQueriesDev Q, unsigned long long *__restrict__ topk)
+// CHAIN (orbx_reloc.hip, enqueue_area_greedy): the problems f of one launch share ONE frame (F's arrays and count are frame 0's; only the blocked flags
+// are per problem, C.blocked[f * F.cap + j]), problem f's queries take their descriptors from Q.desc + 32 * (C.descBase[f] + i), and its workgroups leave
+// at once, writing nothing, unless C.status[f] == 0.
+template <bool CHAIN>
+__global__ __launch_bounds__(256) void k_area_topk(ProjFrameDev F, AreaQueriesDev Q, unsigned long long *__restrict__ topk, AreaChainDev C)
 {
     const int f = blockIdx.y, lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int n = min(F.counts[f], F.cap), m = min(Q.counts[f], Q.cap);
+    if (CHAIN && C.status[f] != 0) return;
+    const int n = min(F.counts[CHAIN ? 0 : f], F.cap), m = min(Q.counts[f], Q.cap);
     if (i >= m) return;
-    const size_t qi = (size_t)f * Q.cap + i, fbase = (size_t)f * F.cap;
+    const size_t qi = (size_t)f * Q.cap + i, fbase = CHAIN ? 0 : (size_t)f * F.cap;
     unsigned long long *out = topk + qi * TOPK;
     if (Q.active && !Q.active[qi]) { if (lane < TOPK) out[lane] = KEY64_EMPTY; return; }
-    const AreaQuery q = area_query(F, Q, qi);
+    const AreaQuery q = area_query(F, Q, qi, CHAIN ? (size_t)C.descBase[f] + i : qi);
     unsigned long long kk[TOPK];
 #pragma unroll
     for (int t = 0; t < TOPK; t++) kk[t] = KEY64_EMPTY;
@@ -798,24 +804,28 @@ __global__ __launch_bounds__(256) void k_area_topk(ProjFrameDev F, AreaQueriesDe
     }
 }
 
+template <bool CHAIN>
 __global__ __launch_bounds__(256) void k_area_greedy(ProjFrameDev F, AreaQueriesDev Q, int maxDist, const unsigned long long *__restrict__ topk,
-                                                     int32_t *__restrict__ assigned, int32_t *__restrict__ dists, int32_t *__restrict__ nmatches, int stride)
+                                                     int32_t *__restrict__ assigned, int32_t *__restrict__ dists, int32_t *__restrict__ nmatches, int stride,
+                                                     AreaChainDev C)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int sChanged, sQueued, sTotal;
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int n = min(F.counts[f], F.cap), m = min(Q.counts[f], Q.cap);
+    if (CHAIN && C.status[f] != 0) return;
+    const int n = min(F.counts[CHAIN ? 0 : f], F.cap), m = min(Q.counts[f], Q.cap);
+    const uint8_t *occupied = CHAIN ? C.blocked + (size_t)f * F.cap : (F.occupied ? F.occupied + (size_t)f * F.cap : nullptr);
     // LDS: owner[F.cap] (0 = blocked from the start, else 1 + lowest accepted query taking the feature, ~0 = free) | dec[Q.cap] | queue (u16)
     uint32_t *owner = (uint32_t *)smem;
     uint32_t *dec = owner + F.cap;                        // KEY_EMPTY or dist << 16 | feature
     unsigned short *queue = (unsigned short *)(dec + Q.cap);
-    const size_t fbase = (size_t)f * F.cap, qbase = (size_t)f * Q.cap;
+    const size_t fbase = CHAIN ? 0 : (size_t)f * F.cap, qbase = (size_t)f * Q.cap;
     const unsigned long long *tk = topk + qbase * TOPK;
     int32_t *aout = assigned + (size_t)f * stride, *dout = dists + (size_t)f * stride;
     for (int i = tid; i < m; i += 256) dec[i] = KEY_EMPTY;
     if (tid == 0) sTotal = 0;
     for (;;) {
-        for (int j = tid; j < n; j += 256) owner[j] = (F.occupied && F.occupied[fbase + j]) ? 0u : 0xffffffffu;
+        for (int j = tid; j < n; j += 256) owner[j] = (occupied && occupied[j]) ? 0u : 0xffffffffu;
         if (tid == 0) { sChanged = 0; sQueued = 0; }
         __syncthreads();
         for (int r = tid; r < m; r += 256) {
@@ -847,7 +857,7 @@ __global__ __launch_bounds__(256) void k_area_greedy(ProjFrameDev F, AreaQueries
         const int nq = sQueued;
         for (int qq = wv; qq < nq; qq += 4) {   // exact rescan over the free features
             const int r = queue[qq];
-            const AreaQuery q = area_query(F, Q, qbase + r);
+            const AreaQuery q = area_query(F, Q, qbase + r, CHAIN ? (size_t)C.descBase[f] + r : qbase + r);
             unsigned long long best = KEY64_EMPTY;
             for (int idx = lane; idx < n; idx += 64) {
                 if (!(owner[idx] > (uint32_t)r)) continue;
@@ -890,17 +900,35 @@ static int area_launch(orbx_matcher *m, const ProjFrameDev &F, const AreaQueries
     const int slot = m->profCount % MATCH_PROF_RING;
     ORBX_HIP_CHECK(hipEventRecord(m->ev0[slot], m->stream));
     m->midValid[slot] = false;
-    hipLaunchKernelGGL(k_area_topk, dim3((unsigned)((Q.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, Q, m->topk64.p);
+    hipLaunchKernelGGL(k_area_topk<false>, dim3((unsigned)((Q.cap + 3) / 4), (unsigned)nframes), dim3(256), 0, m->stream, F, Q, m->topk64.p, AreaChainDev{});
     ORBX_LAUNCH_CHECK();
     const size_t lds = (size_t)F.cap * 4 + (size_t)Q.cap * 4 + (size_t)Q.cap * 2 + 16;
     if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
-    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_area_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_area_greedy, dim3((unsigned)nframes), dim3(256), lds, m->stream, F, Q, max_dist, m->topk64.p, m->matches.p, m->dists.p, m->nmatches.p,
-                       stride);
+    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_area_greedy<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_area_greedy<false>, dim3((unsigned)nframes), dim3(256), lds, m->stream, F, Q, max_dist, m->topk64.p, m->matches.p, m->dists.p, m->nmatches.p,
+                       stride, AreaChainDev{});
     ORBX_LAUNCH_CHECK();
     ORBX_HIP_CHECK(hipEventRecord(m->ev1[slot], m->stream));
     m->profCount++;
     m->lastPairs = nframes; m->lastStride = stride;
+    return ORBX_OK;
+}
+
+// k_area_topk + k_area_greedy for the H problems of a chain on `st` (orbx_match_internal.h)
+int orbx_match::enqueue_area_greedy(orbx_matcher *m, hipStream_t st, const ProjFrameDev &F, const AreaQueriesArgs &A, const AreaChainDev &C, int H, int maxDist,
+                                    int32_t *assigned, int32_t *dists, int32_t *nmatches)
+{
+    if (H < 1 || F.cap < 1 || F.cap > 65535 || A.cap < 1 || A.cap > 65535) { orbx_set_error("bad capacities (features %d, queries %d)", F.cap, A.cap); return ORBX_ERR_CAPACITY; }
+    const size_t lds = (size_t)F.cap * 4 + (size_t)A.cap * 4 + (size_t)A.cap * 2 + 16;
+    if (lds > 160 * 1024) { orbx_set_error("capacities too large for the LDS tile"); return ORBX_ERR_CAPACITY; }
+    int rc = m->topk64.ensure((size_t)H * A.cap * TOPK);
+    if (rc != ORBX_OK) return rc;
+    const AreaQueriesDev Q = {A.u, A.v, A.radius, A.minLevel, A.maxLevel, A.active, A.desc, A.counts, A.cap, A.winMinX, A.winMinY};
+    hipLaunchKernelGGL(k_area_topk<true>, dim3((unsigned)((Q.cap + 3) / 4), (unsigned)H), dim3(256), 0, st, F, Q, m->topk64.p, C);
+    ORBX_LAUNCH_CHECK();
+    if (lds > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_area_greedy<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_area_greedy<true>, dim3((unsigned)H), dim3(256), lds, st, F, Q, maxDist, m->topk64.p, assigned, dists, nmatches, A.cap, C);
+    ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }
 

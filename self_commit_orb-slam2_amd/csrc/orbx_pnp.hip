@@ -830,6 +830,7 @@ struct orbx_pnp_solver : OrbxHandle {
     OrbxOwnedBuf<unsigned long long> mask, cmMask;
     OrbxOwnedBuf<double> epOut, epFull, epAlphas;
     std::vector<PnpCand> last;            // the candidates of the last solve (orbx_pnp_inliers)
+    std::vector<int32_t> lastNrec;        // ... and how many records each of them has (orbx_pnp_device_rows_internal)
 };
 
 namespace {
@@ -1022,6 +1023,7 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
     h->last = cands; h->solved = true;
+    h->lastNrec.assign((size_t)nc, 0);
 
     bool diag = false;
     for (int c = 0; c < nc; c++) {
@@ -1035,6 +1037,7 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
         if (R.best_iteration) *R.best_iteration = head[1];
         if (R.no_more) *R.no_more = head[2];
         if (R.nrecords) *R.nrecords = head[3];
+        h->lastNrec[(size_t)c] = head[3];
         if (R.min_inliers) *R.min_inliers = head[4];
         if (R.count && it) memcpy(R.count, blk + B.count, it * 4);
         if (R.r && it) memcpy(R.r, blk + B.r, it * 72);
@@ -1058,6 +1061,20 @@ extern "C" int orbx_pnp_solve(orbx_pnp_solver *h, const orbx_pnp_problem *Ps, in
         for (int c = 0; c < nc; c++)
             if (Rs[c].max_error && cands[c].n) ORBX_HIP_CHECK(hipMemcpy(Rs[c].max_error, D.maxErr + cands[c].mb, (size_t)cands[c].n * 4, hipMemcpyDeviceToHost));
     }
+    return ORBX_OK;
+}
+
+// Where the last solve left a candidate's refined records in DEVICE memory (orbx_internal.h; orbx_reloc.hip reads them in place)
+int orbx_pnp_device_rows_internal(orbx_pnp_solver *h, int candidate, int device, OrbxPnpRows *out)
+{
+    if (!h || !out) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    if (!h->solved) { orbx_set_error("the PnP solver has no orbx_pnp_solve call to read from"); return ORBX_ERR_ARG; }
+    if (h->device != device) { orbx_set_error("the PnP solver lives on device %d, the caller on device %d", h->device, device); return ORBX_ERR_ARG; }
+    if (candidate < 0 || candidate >= (int)h->last.size()) { orbx_set_error("candidate %d outside the last solve (%d candidates)", candidate, (int)h->last.size()); return ORBX_ERR_ARG; }
+    const PnpCand &H = h->last[(size_t)candidate];
+    const PnpDev D = dev_view(h);
+    out->refR = D.refR + 9 * (size_t)H.ib; out->refT = D.refT + 3 * (size_t)H.ib; out->refMask = D.refMask + H.wb;
+    out->n = H.n; out->words = H.words; out->nrec = h->lastNrec[(size_t)candidate];
     return ORBX_OK;
 }
 
