@@ -556,9 +556,112 @@ int orbx_track_local_map(orbx_matcher *m, const orbx_projection_frame *frame_hos
                          const orbx_local_points *points_host, const float *scale_factors, int nlevels, float viewing_cos_limit,
                          float th, float nn_ratio, const uint8_t *held, const float *held_world_pos, const float *inv_level_sigma2,
                          int sensor_stereo, orbx_track_local_result *result);
-/* profile_kernels (developer tap of tools/latency_track_chain.py): on != 0 records an event between the launches of the next
- * chain calls; orbx_track_last_kernel_times returns the device milliseconds between them (at most `capacity`, *count of them;
- * motion model: stage, pass 1, pass 2, gather, pose, discard; local map: stage, search, gather, pose, statistics). */
+
+/* orbx_track_reference_keyframe == Tracking::TrackReferenceKeyFrame, src/Tracking.cc:1189-1238, the third way to a first
+ * pose (after initialisation, after a relocalisation, when the motion model fails).  ComputeBoW (:1185: the frame's
+ * `groups` are an input, as for orbx_search_by_bow) and the pose handed to SetPose (mLastFrame.mTcw, :1206) stay the
+ * caller's, as does the final nmatchesMap >= 10 (:1238).
+ *   SearchByBoW(mpReferenceKF, mCurrentFrame, vpMapPointMatches) (:1195; ORBmatcher(0.7, true): nn_ratio and
+ *   check_orientation are parameters) with the launches of orbx_search_by_bow's single-pair path; if it returns < 15 the
+ *   function fails (:1201): ran_pose = 0, pose = tcw unchanged, matches as the search left them, nmatches =
+ *   nmatches_search, nmatches_map = 0.  Otherwise a gather kernel builds the pose problem on the device (frame features i
+ *   in ascending order with a match: the keyframe's world_pos at the matched slot, keypoints_un[i].pt, u_right[i],
+ *   inv_level_sigma2[keypoints_un[i].octave]), PoseOptimization (:1209) runs from tcw with camera fx, fy, cx, cy, mbf, and
+ *   the discard kernel does :1215-1236 (the keyframe's has_observations in the place of the last frame's).
+ * keyframe->features: mvKeysUn, mDescriptors, groups = mFeatVec node ids, valid = the slot holds a non-bad MapPoint (NULL
+ *   = all); frame->features: mvKeys (the angle is read, src/ORBmatcher.cc:320), mDescriptors, groups (NULL on both sides =
+ *   brute force); its `valid` is not read.
+ * Results (N = frame->features->counts[0] entries; any pointer may be NULL): the fields of orbx_track_motion_result
+ *   without `wide`; matches / search_matches name KEYFRAME SLOTS (search_matches = what orbx_search_by_bow returns: a match
+ *   pruned by the rotation histogram is -1 there).  discarded[i] = 1: the caller sets mbTrackInView = false and
+ *   mnLastFrameSeen on that point (:1227-1228).
+ * Limits: ORBX_TRACK_MAX_CORRESPONDENCES possible correspondences (min(N, valid keyframe slots)); N <= 4000 (the frame
+ *   sits in the pair kernel's LDS, the bound orbx_search_by_bow tests before it takes its single-pair path) and both
+ *   counts <= max_features; the replay's tile 4 N + 8 nA <= 160 KB.  ORBX_ERR_CAPACITY beyond, ORBX_ERR_ARG for NULL
+ *   arguments or nlevels outside 1..64; neither stages or launches anything.  An empty frame or keyframe: the failure
+ *   result, no launch.
+ * Contract: every field equals, bit for bit, orbx_search_by_bow (mode 0) followed by orbx_pose_optimization on the
+ * problem a host loop builds from its result and the host's discard loop; against the CPU restatement the pose is held
+ * to 1e-5 and everything else is equal. */
+typedef struct orbx_reference_keyframe {   /* host memory */
+    const orbx_feature_set *features;
+    const float *world_pos;                /* [nA*3] MapPoint::GetWorldPos of the slot's point (read where a match lands)  */
+    const uint8_t *has_observations;       /* [nA] Observations() > 0 of the slot's point; NULL = all                      */
+} orbx_reference_keyframe;
+typedef struct orbx_reference_frame {      /* host memory */
+    const orbx_feature_set *features;
+    const orbx_keypoint *keypoints_un;     /* [N] mvKeysUn: pt and octave are read                                         */
+    const float *u_right;                  /* [N] mvuRight                                                                 */
+    const float *tcw;                      /* [16] the pose PoseOptimization starts from (mLastFrame.mTcw)                 */
+    float fx, fy, cx, cy, mbf;
+    const float *inv_level_sigma2;         /* mvInvLevelSigma2 [nlevels]                                                   */
+    int nlevels;
+} orbx_reference_frame;
+typedef struct orbx_track_reference_result {
+    int32_t *matches, *search_matches;
+    uint8_t *discarded;
+    float *pose;
+    int32_t nmatches_search, n_correspondences, pose_inliers, nmatches, nmatches_map, ran_pose;
+    double stats[8];
+} orbx_track_reference_result;
+int orbx_track_reference_keyframe(orbx_matcher *m, const orbx_reference_keyframe *keyframe_host, const orbx_reference_frame *frame_host,
+                                  float nn_ratio, int check_orientation, orbx_track_reference_result *result);
+
+/* orbx_reloc_match_candidates == the head of Tracking::Relocalization, src/Tracking.cc:2063-2095, without the
+ * `new PnPsolver` itself: SearchByBoW(pKF, mCurrentFrame, vvpMapPointMatches[k]) for ALL K candidate keyframes, the < 15
+ * decision (:2075) and the arrays the PnPsolver constructor collects (src/PnPsolver.cc:120-167), as one launch chain with
+ * ONE host wait.  It sits between orbx_kfdb_query and orbx_pnp_solve / orbx_relocalize_refine, which already take all
+ * candidates in one call.  The frame is staged ONCE.
+ *   A K-pair form of the single-pair distance kernel (candidate on the grid's y; a keyframe feature per wave, the frame
+ *   split over 64 lanes and held in LDS; every candidate's processing order in the same launch), the greedy replay with K
+ *   workgroups, and a gather kernel with one workgroup per candidate.  A bad keyframe (:2066) is staged with zero
+ *   features: its workgroups leave at once.
+ * frame: features as orbx_reference_frame (mvKeys, mDescriptors, groups), keypoints_un, level_sigma2 = mvLevelSigma2.
+ * keyframes[k]: features (valid = the slot holds a non-bad MapPoint; groups on every keyframe or on none), world_pos,
+ *   is_bad.
+ * Results (host arrays, row k at k * N, N = the frame's features; any pointer may be NULL):
+ *   matches[K][N]     keyframe slot or -1: the vvpMapPointMatches rows as the searches left them, also for a candidate
+ *                     that is discarded for < 15 matches (all -1 for a bad keyframe)
+ *   nmatches[K]       the searches' return values (0 for a bad keyframe)
+ *   discarded[K]      vbDiscarded: bad, or nmatches < 15
+ *   n[K]              kept matches of the PnP problem (= nmatches), 0 for a discarded candidate
+ *   key_index[K][N], p2d[K][N][2], sigma2[K][N], p3dw[K][N][3]: the first n[k] entries of row k are mvKeyPointIndices,
+ *                     mvP2D, mvSigma2 = level_sigma2[octave] and mvP3Dw in ascending feature order - the layout
+ *                     orbx_pnp_problem takes; the rest of a row, and the whole row of a discarded candidate, is not
+ *                     written.
+ * The host still draws the RANSAC sets from n[k] and calls orbx_pnp_solve with these host arrays.  Handing the arrays to
+ * the PnP handle in device memory is OUT OF SCOPE here: they cross to the host once and back.
+ * Limits, per candidate, as orbx_track_reference_keyframe (N <= 4000, counts <= max_features, the replay's tile for the
+ * largest candidate); K <= the handle's max_pairs.  ORBX_ERR_CAPACITY beyond; ORBX_ERR_ARG for NULL arguments, K < 1,
+ * nlevels outside 1..64 or groups on some keyframes only; neither stages or launches anything.  An empty frame, or no
+ * candidate with a feature: every candidate discarded, no launch.
+ * Contract: every matches row and nmatches equals orbx_search_by_bow(kf_k, frame) (mode 0) and the arrays equal the
+ * constructor's loop over that row, float bits included. */
+typedef struct orbx_reloc_match_frame {    /* host memory */
+    const orbx_feature_set *features;
+    const orbx_keypoint *keypoints_un;     /* [N] mvKeysUn                                                                 */
+    const float *level_sigma2;             /* mvLevelSigma2 [nlevels]                                                      */
+    int nlevels;
+} orbx_reloc_match_frame;
+typedef struct orbx_reloc_match_keyframe { /* host memory */
+    const orbx_feature_set *features;
+    const float *world_pos;                /* [nA*3]                                                                       */
+    int is_bad;                            /* pKF->isBad(): nothing else is read                                           */
+} orbx_reloc_match_keyframe;
+typedef struct orbx_reloc_match_result {
+    int32_t *matches, *key_index;
+    float *p2d, *sigma2, *p3dw;
+    int32_t *n, *nmatches;
+    uint8_t *discarded;
+} orbx_reloc_match_result;
+int orbx_reloc_match_candidates(orbx_matcher *m, const orbx_reloc_match_frame *frame_host, const orbx_reloc_match_keyframe *keyframes_host,
+                                int ncandidates, float nn_ratio, int check_orientation, const orbx_reloc_match_result *result);
+
+/* profile_kernels (developer tap of tools/latency_track_chain.py / latency_track_ref.py): on != 0 records an event between the
+ * launches of the next chain calls; orbx_track_last_kernel_times returns the device milliseconds between them (at most
+ * `capacity`, *count of them; motion model: stage, pass 1, pass 2, gather, pose, discard; local map: stage, search, gather,
+ * pose, statistics; reference keyframe: stage, search, gather, pose, discard; relocalisation candidates: stage, search,
+ * gather). */
 int orbx_track_set_profiling(orbx_matcher *m, int on);
 int orbx_track_last_kernel_times(orbx_matcher *m, float *ms, int capacity, int *count);
 

@@ -417,6 +417,33 @@ class TrackMotionResult(ctypes.Structure):      # orbx_track_motion_result
                [("stats", ctypes.c_double * 8)]
 
 
+class ReferenceKeyFrame(ctypes.Structure):      # orbx_reference_keyframe
+    _fields_ = [("features", ctypes.POINTER(FeatureSet)), ("world_pos", ctypes.c_void_p), ("has_observations", ctypes.c_void_p)]
+
+
+class ReferenceFrame(ctypes.Structure):         # orbx_reference_frame
+    _fields_ = [("features", ctypes.POINTER(FeatureSet)), ("keypoints_un", ctypes.c_void_p), ("u_right", ctypes.c_void_p), ("tcw", ctypes.c_void_p)] + \
+               [(k, ctypes.c_float) for k in ("fx", "fy", "cx", "cy", "mbf")] + [("inv_level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
+
+
+class TrackReferenceResult(ctypes.Structure):   # orbx_track_reference_result
+    _fields_ = [("matches", ctypes.c_void_p), ("search_matches", ctypes.c_void_p), ("discarded", ctypes.c_void_p), ("pose", ctypes.c_void_p)] + \
+               [(k, ctypes.c_int32) for k in ("nmatches_search", "n_correspondences", "pose_inliers", "nmatches", "nmatches_map", "ran_pose")] + \
+               [("stats", ctypes.c_double * 8)]
+
+
+class RelocMatchFrame(ctypes.Structure):        # orbx_reloc_match_frame
+    _fields_ = [("features", ctypes.POINTER(FeatureSet)), ("keypoints_un", ctypes.c_void_p), ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
+
+
+class RelocMatchKeyFrame(ctypes.Structure):     # orbx_reloc_match_keyframe
+    _fields_ = [("features", ctypes.POINTER(FeatureSet)), ("world_pos", ctypes.c_void_p), ("is_bad", ctypes.c_int)]
+
+
+class RelocMatchResult(ctypes.Structure):       # orbx_reloc_match_result
+    _fields_ = [(k, ctypes.c_void_p) for k in ("matches", "key_index", "p2d", "sigma2", "p3dw", "n", "nmatches", "discarded")]
+
+
 class TrackLocalResult(ctypes.Structure):       # orbx_track_local_result
     _fields_ = [(k, ctypes.c_void_p) for k in ("assigned", "in_view", "proj_x", "proj_y", "proj_xr", "scale_level", "view_cos", "pose", "outlier", "found", "cleared")] + \
                [(k, ctypes.c_int32) for k in ("nmatches", "n_correspondences", "pose_inliers", "inliers_map", "inliers_all")] + [("stats", ctypes.c_double * 8)]
@@ -1357,8 +1384,115 @@ class ORBmatcher(_Handle):
         call.keep = [keep, T, thr, pos, nrm, mx, mn, md, obs, hd, hp, is2, iv, px, py, pxr, lvl, vc, asg, po, outl, fnd, clr, R]
         return call
 
+    def TrackReferenceKeyFrame(self, keyframe, frame, nnratio=None):
+        return self.track_reference_prepare(keyframe, frame, nnratio)()
+
+    def track_reference_prepare(self, keyframe, frame, nnratio=None):
+        """Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:1189-1238) as one device chain with one host wait (orbx_track_reference_keyframe):
+        SearchByBoW(pKF, F) with nnratio (default the handle's; 0.7 at :1189) and the handle's checkOri, PoseOptimization from frame["Tcw"]
+        (= mLastFrame.mTcw) if it found >= 15, the discard loop.
+        keyframe: dict(kps (mvKeysUn), desc, pos (n, 3) world positions of the slots' points[, groups, valid, has_obs]);
+        frame: dict(kps (mvKeys), desc, kps_un (mvKeysUn), u_right, Tcw, cam (fx, fy, cx, cy, bf), inv_level_sigma2[, groups]).
+        Returns a prepared call (as track_motion_prepare): call() -> dict(matches, search_matches, discarded, pose, nmatches_search, n_correspondences,
+        pose_inliers, nmatches, nmatches_map, ran_pose, stats); matches name keyframe slots."""
+        fa, ka = _host_set(keyframe["kps"], keyframe["desc"], keyframe.get("groups"), keyframe.get("valid"))
+        fb, kb = _host_set(frame["kps"], frame["desc"], frame.get("groups"))
+        na, n = len(ka[0]), len(kb[0])
+        pos = np.ascontiguousarray(keyframe["pos"], np.float32)
+        obs = None if keyframe.get("has_obs") is None else np.ascontiguousarray(keyframe["has_obs"], np.uint8)
+        ku = np.ascontiguousarray(frame["kps_un"], KEYPOINT_DTYPE)
+        ur = np.ascontiguousarray(frame["u_right"], np.float32)
+        tc = np.ascontiguousarray(frame["Tcw"], np.float32).reshape(16)
+        is2 = np.ascontiguousarray(frame["inv_level_sigma2"], np.float32)
+        if pos.size != 3 * na or len(ku) != n or len(ur) != n or (obs is not None and len(obs) != na):
+            raise ValueError("pos / has_obs need one entry per keyframe feature, kps_un / u_right one per frame feature")
+        fx, fy, cx, cy, bf = [float(np.float32(v)) for v in frame["cam"]]
+        KF = ReferenceKeyFrame(ctypes.pointer(fa), _ptr(pos).value, None if obs is None else _ptr(obs).value)
+        FR = ReferenceFrame(ctypes.pointer(fb), _ptr(ku).value, _ptr(ur).value, _ptr(tc).value, fx, fy, cx, cy, bf, _ptr(is2).value, len(is2))
+        m1 = max(n, 1)
+        mt, sm, dc, po = np.full(m1, -1, np.int32), np.full(m1, -1, np.int32), np.zeros(m1, np.uint8), np.zeros(16, np.float32)
+        R = TrackReferenceResult(_ptr(mt).value, _ptr(sm).value, _ptr(dc).value, _ptr(po).value)
+        self._L.orbx_track_reference_keyframe.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReferenceKeyFrame), ctypes.POINTER(ReferenceFrame), ctypes.c_float, ctypes.c_int,
+                                                          ctypes.POINTER(TrackReferenceResult)]
+        fn, h, cnn, co = self._L.orbx_track_reference_keyframe, self._h, ctypes.c_float(self.nnratio if nnratio is None else nnratio), 1 if self.checkOri else 0
+
+        def raw():
+            return fn(h, ctypes.byref(KF), ctypes.byref(FR), cnn, co, ctypes.byref(R))
+
+        def result():
+            return dict(matches=mt[:n].copy(), search_matches=sm[:n].copy(), discarded=dc[:n].copy(), pose=po.reshape(4, 4).copy(), nmatches_search=R.nmatches_search,
+                        n_correspondences=R.n_correspondences, pose_inliers=R.pose_inliers, nmatches=R.nmatches, nmatches_map=R.nmatches_map, ran_pose=R.ran_pose,
+                        stats=np.array(R.stats[:], np.float64))
+
+        def call():
+            _check(raw())
+            return result()
+        call.raw, call.result, call.KF, call.FR = raw, result, KF, FR
+        call.keep = [fa, ka, fb, kb, pos, obs, ku, ur, tc, is2, mt, sm, dc, po, R]
+        return call
+
+    def RelocMatchCandidates(self, frame, keyframes, nnratio=None):
+        return self.reloc_match_prepare(frame, keyframes, nnratio)()
+
+    def reloc_match_prepare(self, frame, keyframes, nnratio=None):
+        """The head of Tracking::Relocalization (reference src/Tracking.cc:2063-2095) as one device chain with one host wait (orbx_reloc_match_candidates):
+        SearchByBoW(pKF, F) for every candidate keyframe with nnratio (default the handle's; 0.75 at :2048) and the handle's checkOri, the < 15 decision, and
+        the arrays the PnPsolver constructor collects (src/PnPsolver.cc:120-167).
+        frame: dict(kps (mvKeys), desc, kps_un (mvKeysUn), level_sigma2 (mvLevelSigma2)[, groups, cam (fx, fy, cx, cy, ..)]);
+        keyframes: list of dict(kps, desc, pos[, groups, valid, bad]) - a bad keyframe needs nothing but bad=True.
+        Returns a prepared call: call() -> dict(matches (K, N), nmatches (K), discarded (K), n (K), key_index / p2d / sigma2 / p3dw: lists of K arrays with
+        n[k] rows, problems: one dict(candidate, K, p2d, sigma2, p3d, indices, mN) per kept candidate - PnPsolver.Solve takes the list as its candidates
+        (K is there if the frame names cam), with the caller's sets or its own)."""
+        fb, kb = _host_set(frame["kps"], frame["desc"], frame.get("groups"))
+        n = len(kb[0])
+        ku = np.ascontiguousarray(frame["kps_un"], KEYPOINT_DTYPE)
+        s2 = np.ascontiguousarray(frame["level_sigma2"], np.float32)
+        if len(ku) != n:
+            raise ValueError("kps_un needs one entry per frame feature")
+        K = len(keyframes)
+        kfs, keep = (RelocMatchKeyFrame * max(K, 1))(), []
+        for k, kf in enumerate(keyframes):
+            if kf.get("bad"):
+                kfs[k] = RelocMatchKeyFrame(None, None, 1)
+                continue
+            fa, ka = _host_set(kf["kps"], kf["desc"], kf.get("groups"), kf.get("valid"))
+            pos = np.ascontiguousarray(kf["pos"], np.float32)
+            if pos.size != 3 * len(ka[0]):
+                raise ValueError("pos needs one row per keyframe feature")
+            keep.append((fa, ka, pos))
+            kfs[k] = RelocMatchKeyFrame(ctypes.pointer(fa), _ptr(pos).value, 0)
+        FR = RelocMatchFrame(ctypes.pointer(fb), _ptr(ku).value, _ptr(s2).value, len(s2))
+        k1, n1 = max(K, 1), max(n, 1)
+        mt, ki = np.full((k1, n1), -1, np.int32), np.full((k1, n1), -1, np.int32)
+        p2, sg, p3 = np.zeros((k1, n1, 2), np.float32), np.zeros((k1, n1), np.float32), np.zeros((k1, n1, 3), np.float32)
+        nn, nm, dc = np.zeros(k1, np.int32), np.zeros(k1, np.int32), np.zeros(k1, np.uint8)
+        if n == 0:
+            mt = np.full((k1, 0), -1, np.int32)
+        R = RelocMatchResult(*[_ptr(a).value if a.size else None for a in (mt, ki, p2, sg, p3, nn, nm, dc)])
+        self._L.orbx_reloc_match_candidates.argtypes = [ctypes.c_void_p, ctypes.POINTER(RelocMatchFrame), ctypes.POINTER(RelocMatchKeyFrame), ctypes.c_int, ctypes.c_float,
+                                                        ctypes.c_int, ctypes.POINTER(RelocMatchResult)]
+        fn, h, cnn, co = self._L.orbx_reloc_match_candidates, self._h, ctypes.c_float(self.nnratio if nnratio is None else nnratio), 1 if self.checkOri else 0
+        cam = frame.get("cam")
+
+        def raw():
+            return fn(h, ctypes.byref(FR), kfs, K, cnn, co, ctypes.byref(R))
+
+        def result():
+            cut = lambda a: [a[k, :nn[k]].copy() for k in range(K)]
+            out = dict(matches=mt[:K, :n].copy(), nmatches=nm[:K].copy(), discarded=dc[:K].copy(), n=nn[:K].copy(), key_index=cut(ki), p2d=cut(p2), sigma2=cut(sg), p3dw=cut(p3))
+            out["problems"] = [dict(candidate=k, p2d=out["p2d"][k], sigma2=out["sigma2"][k], p3d=out["p3dw"][k], indices=out["key_index"][k], mN=n,
+                                    **({} if cam is None else {"K": tuple(cam[:4])})) for k in range(K) if not dc[k]]
+            return out
+
+        def call():
+            _check(raw())
+            return result()
+        call.raw, call.result, call.FR, call.kfs = raw, result, FR, kfs
+        call.keep = [fb, kb, ku, s2, keep, mt, ki, p2, sg, p3, nn, nm, dc, R]
+        return call
+
     def track_kernel_times(self, on=None):
-        """profile_kernels tap of the two chains above: track_kernel_times(True / False) switches the events between their launches on or off;
+        """profile_kernels tap of the chains above: track_kernel_times(True / False) switches the events between their launches on or off;
         track_kernel_times() returns the device milliseconds between the launches of the last profiled call."""
         self._L.orbx_track_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._L.orbx_track_last_kernel_times.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]

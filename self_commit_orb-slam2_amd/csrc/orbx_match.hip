@@ -414,8 +414,8 @@ __global__ __launch_bounds__(256, 3) void k_bow_topk_mfma(FeatDev A, FeatDev B, 
 #define PAIR_SLICES 64                     /* B slices = lanes per A feature */
 #define PAIR_ROWS (4 * (64 / PAIR_SLICES))   /* A features per workgroup (four waves) */
 template <bool FILTER>
-__global__ __launch_bounds__(256) void k_bow_topk_pair(FeatDev A, FeatDev B, int mode, uint32_t dcut, int nRowBlocks, int per, uint32_t *__restrict__ topk,
-                                                       int32_t *__restrict__ order)
+__device__ __forceinline__ void bow_topk_pair_body(FeatDev A, FeatDev B, int mode, uint32_t dcut, int nRowBlocks, int per, uint32_t *__restrict__ topk,
+                                                   int32_t *__restrict__ order)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smemP[];
     const int nA = min(A.counts[0], A.cap), nB = min(B.counts[0], B.cap);
@@ -536,6 +536,32 @@ __global__ __launch_bounds__(256) void k_bow_topk_pair(FeatDev A, FeatDev B, int
         for (int q = 0; q < TOPK; q++) o[q] = (!act || kk[q] >= sentinel) ? KEY_EMPTY : kk[q];
         out[0] = make_uint4(o[0], o[1], o[2], o[3]); out[1] = make_uint4(o[4], o[5], o[6], o[7]);
     }
+}
+
+template <bool FILTER>
+__global__ __launch_bounds__(256) void k_bow_topk_pair(FeatDev A, FeatDev B, int mode, uint32_t dcut, int nRowBlocks, int per, uint32_t *__restrict__ topk,
+                                                       int32_t *__restrict__ order)
+{
+    bow_topk_pair_body<FILTER>(A, B, mode, dcut, nRowBlocks, per, topk, order);
+}
+
+// The K-PAIR form (the head of Tracking::Relocalization, src/Tracking.cc:2063-2095: K candidate KeyFrames against ONE Frame, mode 0): candidate c =
+// blockIdx.y, its features at c * A.cap, its lists and order at c * stride.  Every workgroup builds the LDS image of the one staged frame as above; the
+// grid is cut for the largest candidate (nRowBlocks row blocks, then the order's blocks) and the workgroups past a smaller candidate's end - all of
+// them for a candidate staged with count 0, which is how a bad KeyFrame arrives - leave at once.  k_bow_topk gives K pairs K * ceil(nA / 256)
+// workgroups that each walk all of B; this is K * nA / 4.
+template <bool FILTER>
+__global__ __launch_bounds__(256) void k_bow_topk_cands(FeatDev A, FeatDev B, uint32_t dcut, int nRowBlocks, int per, int stride, uint32_t *__restrict__ topk,
+                                                        int32_t *__restrict__ order)
+{
+    const int c = blockIdx.y, blk = blockIdx.x;
+    const int nA = min(A.counts[c], A.cap);
+    if (blk < nRowBlocks ? blk * PAIR_ROWS >= nA : (blk - nRowBlocks) * 32 >= nA) return;
+    FeatDev Ac = A;
+    Ac.desc = A.desc + (size_t)c * A.cap * 32;
+    Ac.groups = A.groups ? A.groups + (size_t)c * A.cap : nullptr;
+    Ac.counts = A.counts + c;
+    bow_topk_pair_body<FILTER>(Ac, B, 0, dcut, nRowBlocks, per, topk + (size_t)c * stride * TOPK, order + (size_t)c * stride);
 }
 
 // greedy replay + rotation histogram + three-maxima pruning; one workgroup per pair.
@@ -1702,6 +1728,94 @@ int stage_host(orbx_matcher *m, const orbx_feature_set *const *h, orbx_feature_s
 }
 }  // namespace orbx_match
 
+// k_bow_topk_pair (B split over the chip, the processing order in the same launch) + k_bow_greedy for ONE pair on `st`: the launches of the single-pair
+// host call, and a link of orbx_track.hip's reference-keyframe chain.
+namespace {
+// what both entries of the pair kernel take from the host: the distance beyond which the ratio test cannot pass, the B features per lane slice, the LDS bytes
+struct PairGeom { uint32_t dcut; int per; size_t lds; };
+PairGeom pair_geom(float nnRatio, int nB)
+{
+    PairGeom g;
+    g.dcut = TH_LOW + 1;
+    while (g.dcut < 257 && !(nnRatio * (float)g.dcut > (float)TH_LOW)) g.dcut++;
+    g.per = (nB + PAIR_SLICES - 1) / PAIR_SLICES;
+    g.lds = std::max((size_t)PAIR_SLICES * ((size_t)g.per * 32 + 16) + (size_t)PAIR_SLICES * g.per * 4, (size_t)4096 * 4);
+    return g;
+}
+}  // namespace
+
+namespace orbx_match {
+size_t bow_pair_replay_lds(int nA, int nB, bool publish)
+{
+    const size_t NA = (size_t)nA, NB = (size_t)nB;
+    return NB * 4 + NA * 4 + (size_t)((nA + 7) & ~7) * 2 * 2 + (publish ? NB * 4 + std::max(NA, NB) * 4 : 0);      // (+ the B angles and the match list: k_bow_greedy with pubFlag)
+}
+
+int enqueue_bow_pair(orbx_matcher *m, hipStream_t st, const FeatDev &A, const FeatDev &B, int mode, float nnRatio, int checkOri, int32_t *matches, int32_t *dists,
+                     int32_t *nmatches, int stride, int32_t *pubMatches, unsigned long long *pubFlag, unsigned long long pubSeq)
+{
+    const int nA = A.cap, nB = B.cap;
+    const size_t NA = (size_t)nA;
+    int rc;
+    const bool filter = B.groups != nullptr || (mode == 1 && B.valid != nullptr);
+    // geometry: PAIR_ROWS A features per workgroup (one per wave x 64 B slices), all of B in the workgroup's LDS; the order's workgroups behind them
+    const int nRowBlocks = (nA + PAIR_ROWS - 1) / PAIR_ROWS, nOrder = (nA + 31) / 32;
+    const PairGeom g = pair_geom(nnRatio, nB);
+    const uint32_t dcut = g.dcut;
+    const int per = g.per;
+    const size_t ldsPair = g.lds;
+    if ((rc = m->topk.ensure(NA * TOPK)) != ORBX_OK || (rc = m->order.ensure(NA)) != ORBX_OK) return rc;
+    const dim3 grid((unsigned)(nRowBlocks + nOrder));
+    if (filter) {
+        if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_pair<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
+        hipLaunchKernelGGL(k_bow_topk_pair<true>, grid, dim3(256), ldsPair, st, A, B, mode, dcut, nRowBlocks, per, m->topk.p, m->order.p);
+    } else {
+        if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
+        hipLaunchKernelGGL(k_bow_topk_pair<false>, grid, dim3(256), ldsPair, st, A, B, mode, dcut, nRowBlocks, per, m->topk.p, m->order.p);
+    }
+    ORBX_LAUNCH_CHECK();
+    const size_t ldsGreedy = bow_pair_replay_lds(nA, nB, pubFlag != nullptr);
+    if (ldsGreedy > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile", nA); return ORBX_ERR_CAPACITY; }
+    if (ldsGreedy > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsGreedy));
+    if (!m->sfZero.p) {
+        if ((rc = m->sfZero.ensure(4)) != ORBX_OK) return rc;
+        ORBX_HIP_CHECK(hipMemsetAsync(m->sfZero.p, 0, 4 * sizeof(int32_t), st));
+    }
+    hipLaunchKernelGGL(k_bow_greedy, dim3(1), dim3(GREEDY_THREADS), ldsGreedy, st, A, B, (const int32_t *)m->sfZero.p, (const int32_t *)m->sfZero.p, mode, nnRatio,
+                       checkOri, m->topk.p, m->order.p, matches, dists, nmatches, stride, TriDev(), pubMatches, pubFlag, pubSeq);
+    ORBX_LAUNCH_CHECK();
+    return ORBX_OK;
+}
+
+int enqueue_bow_candidates(orbx_matcher *m, hipStream_t st, const FeatDev &A, const FeatDev &B, int K, const int32_t *pairsA, const int32_t *pairsB, float nnRatio, int checkOri,
+                           int stride)
+{
+    const int capA = A.cap, nB = B.cap;
+    const int nRowBlocks = (capA + PAIR_ROWS - 1) / PAIR_ROWS, nOrder = (capA + 31) / 32;
+    const PairGeom g = pair_geom(nnRatio, nB);
+    const uint32_t dcut = g.dcut;
+    const int per = g.per;
+    const size_t ldsPair = g.lds;
+    const dim3 grid((unsigned)(nRowBlocks + nOrder), (unsigned)K);
+    if (B.groups) {
+        if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_cands<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
+        hipLaunchKernelGGL(k_bow_topk_cands<true>, grid, dim3(256), ldsPair, st, A, B, dcut, nRowBlocks, per, stride, m->topk.p, m->order.p);
+    } else {
+        if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_cands<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
+        hipLaunchKernelGGL(k_bow_topk_cands<false>, grid, dim3(256), ldsPair, st, A, B, dcut, nRowBlocks, per, stride, m->topk.p, m->order.p);
+    }
+    ORBX_LAUNCH_CHECK();
+    const size_t ldsGreedy = bow_pair_replay_lds(capA, nB, false);
+    if (ldsGreedy > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile", capA); return ORBX_ERR_CAPACITY; }
+    if (ldsGreedy > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsGreedy));
+    hipLaunchKernelGGL(k_bow_greedy, dim3((unsigned)K), dim3(GREEDY_THREADS), ldsGreedy, st, A, B, pairsA, pairsB, 0, nnRatio, checkOri, m->topk.p, m->order.p, m->matches.p,
+                       m->dists.p, m->nmatches.p, stride, TriDev(), nullptr, nullptr, 0ull);
+    ORBX_LAUNCH_CHECK();
+    m->lastPairs = K; m->lastStride = stride;
+    return ORBX_OK;
+}
+}  // namespace orbx_match
+
 // One pair from host arrays, the call src/Tracking.cc:1195 / 2073 make through shim/ORBmatcher_hip.cc.  No copy engine, no stream synchronisation
 // (OrbxCallBox): the arrays go into mapped pinned memory, k_stage_copy reads them once into the handle's arena, k_bow_topk_pair (B split over the
 // chip, the processing order in the same launch) and k_bow_greedy follow, the replay writes the match list into mapped pinned memory and raises the
@@ -1734,36 +1848,10 @@ static int search_by_bow_single(orbx_matcher *m, const orbx_feature_set *a, cons
     FeatDev A, B;
     A.kp = sKpA.in(ar); A.desc = sDescA.in(ar); A.groups = a->groups ? sGrA.in(ar) : nullptr; A.valid = a->valid ? sValA.in(ar) : nullptr; A.counts = dc; A.cap = nA;
     B.kp = sKpB.in(ar); B.desc = sDescB.in(ar); B.groups = b->groups ? sGrB.in(ar) : nullptr; B.valid = b->valid ? sValB.in(ar) : nullptr; B.counts = dc + 1; B.cap = nB;
-    uint32_t dcut = TH_LOW + 1;
-    while (dcut < 257 && !(prm->nn_ratio * (float)dcut > (float)TH_LOW)) dcut++;
-    const bool filter = b->groups != nullptr || (prm->mode == 1 && b->valid != nullptr);
-    // geometry: 16 A features per workgroup (4 per wave x 16 B slices), all of B in the workgroup's LDS; the order's workgroups behind them
-    const int nRowBlocks = (nA + PAIR_ROWS - 1) / PAIR_ROWS, nOrder = (nA + 31) / 32;
-    const int per = (nB + PAIR_SLICES - 1) / PAIR_SLICES;
-    const size_t ldsPair = std::max((size_t)PAIR_SLICES * ((size_t)per * 32 + 16) + (size_t)PAIR_SLICES * per * 4, (size_t)4096 * 4);
-    if ((rc = m->topk.ensure(NA * TOPK)) != ORBX_OK || (rc = m->order.ensure(NA)) != ORBX_OK) return rc;
-    const dim3 grid((unsigned)(nRowBlocks + nOrder));
-    if (filter) {
-        if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_pair<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
-        hipLaunchKernelGGL(k_bow_topk_pair<true>, grid, dim3(256), ldsPair, m->stream, A, B, prm->mode, dcut, nRowBlocks, per, m->topk.p, m->order.p);
-    } else {
-        if (ldsPair > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_topk_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsPair));
-        hipLaunchKernelGGL(k_bow_topk_pair<false>, grid, dim3(256), ldsPair, m->stream, A, B, prm->mode, dcut, nRowBlocks, per, m->topk.p, m->order.p);
-    }
-    ORBX_LAUNCH_CHECK();
-    const size_t ldsGreedy = NB * 4 + NA * 4 + (size_t)((nA + 7) & ~7) * 2 * 2 + NB * 4 + std::max(NA, NB) * 4;      // (+ the B angles and the match list: k_bow_greedy with pubFlag)
-    if (ldsGreedy > 160 * 1024) { orbx_set_error("feature count %d too large for the LDS tile", nA); return ORBX_ERR_CAPACITY; }
-    if (ldsGreedy > 48 * 1024) ORBX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bow_greedy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsGreedy));
-    if (!m->sfZero.p) {
-        if ((rc = m->sfZero.ensure(4)) != ORBX_OK) return rc;
-        ORBX_HIP_CHECK(hipMemsetAsync(m->sfZero.p, 0, 4 * sizeof(int32_t), m->stream));
-    }
-    const int stride = m->maxFeatures;
     const unsigned long long seq = bx.arm();
-    hipLaunchKernelGGL(k_bow_greedy, dim3(1), dim3(GREEDY_THREADS), ldsGreedy, m->stream, A, B, (const int32_t *)m->sfZero.p, (const int32_t *)m->sfZero.p, prm->mode, prm->nn_ratio,
-                       prm->check_orientation, m->topk.p, m->order.p, m->matches.p, m->dists.p, m->nmatches.p, stride, TriDev(), sg.dev(rRes), bx.flagDev, seq);
-    ORBX_LAUNCH_CHECK();
-    m->lastPairs = 1; m->lastStride = stride;
+    if ((rc = orbx_match::enqueue_bow_pair(m, m->stream, A, B, prm->mode, prm->nn_ratio, prm->check_orientation, m->matches.p, m->dists.p, m->nmatches.p, m->maxFeatures,
+                                           sg.dev(rRes), bx.flagDev, seq)) != ORBX_OK) return rc;
+    m->lastPairs = 1; m->lastStride = m->maxFeatures;
     if ((rc = bx.wait(m->stream)) != ORBX_OK) return rc;
     const int32_t *res = sg.host(rRes);
     if (nOut > 0) memcpy(matches, res, (size_t)nOut * 4);

@@ -149,7 +149,7 @@ struct orbx_matcher : OrbxHandle {
     std::vector<hipEvent_t> fcApplyEv;  // profile_kernels: one pair per Fuse call
     int fcApplyTimed = 0;
     std::vector<int32_t> fcOrder, fcPos, fcSIndex;      // slots in ascending rank, slot -> position, slot -> searchable index
-    // TrackWithMotionModel / TrackLocalMap (orbx_track.hip): match arrays, the gathered pose problem and the optimisation's results, all device memory
+    // TrackWithMotionModel / TrackLocalMap / TrackReferenceKeyFrame (orbx_track.hip): match arrays, the gathered pose problem and the optimisation's results, all device memory
     OrbxOwnedBuf<uint8_t> trWork;
     OrbxWorkPlan trPlan;
     std::vector<hipEvent_t> trEv;     // profile_kernels: one event per boundary between the chain's launches
@@ -259,6 +259,22 @@ int enqueue_local_points(orbx_matcher *m, hipStream_t st, const FrustumDev &Fr, 
  * orbx_area_search_greedy leaves them, untouched where status[f] != 0.  F.counts[0] features, shared by all problems.  Grows the handle's candidate buffer. */
 int enqueue_area_greedy(orbx_matcher *m, hipStream_t st, const ProjFrameDev &F, const AreaQueriesArgs &A, const AreaChainDev &C, int H, int maxDist,
                         int32_t *assigned, int32_t *dists, int32_t *nmatches);
+/* k_bow_topk_pair + k_bow_greedy for ONE (KeyFrame A, Frame / KeyFrame B) pair on `st` (every pointer device memory; A.cap / B.cap = the two feature
+ * counts, also at A.counts[0] / B.counts[0]): matches[0..stride), dists and nmatches[0] as orbx_search_by_bow_device leaves them for pair 0.
+ * pubFlag != nullptr: the replay also writes the match list and the count behind it to pubMatches (mapped host memory) and raises the sequence word -
+ * orbx_search_by_bow's single-pair path.  B.cap <= 4000 (B sits in the pair kernel's LDS); ORBX_ERR_CAPACITY if the replay's tile
+ * (bow_pair_replay_lds) exceeds 160 KB.  Grows the handle's candidate / order buffers. */
+size_t bow_pair_replay_lds(int nA, int nB, bool publish);
+int enqueue_bow_pair(orbx_matcher *m, hipStream_t st, const FeatDev &A, const FeatDev &B, int mode, float nnRatio, int checkOri, int32_t *matches, int32_t *dists,
+                     int32_t *nmatches, int stride, int32_t *pubMatches, unsigned long long *pubFlag, unsigned long long pubSeq);
+/* The K-pair form: k_bow_topk_cands + k_bow_greedy (K workgroups) for K candidate KeyFrames (A: candidate c's features at c * A.cap, A.counts[c] of them -
+ * 0 = its workgroups leave at once) against ONE Frame (B, B.cap features), mode 0.  pairsA / pairsB: device arrays 0..K-1 / K zeros.  Results in the
+ * handle's buffers as orbx_search_by_bow_device leaves them: matches / dists at c * stride, nmatches[c]; K <= max_pairs, A.cap and B.cap <= stride <=
+ * max_features, B.cap <= 4000. */
+int enqueue_bow_candidates(orbx_matcher *m, hipStream_t st, const FeatDev &A, const FeatDev &B, int K, const int32_t *pairsA, const int32_t *pairsB, float nnRatio, int checkOri,
+                           int stride);
+/* profile_kernels of the tracking thread's chains (orbx_track.hip): an event at boundary k of the chain on `st` while orbx_track_set_profiling is on */
+int track_mark(orbx_matcher *m, hipStream_t st, int k);
 }  // namespace orbx_match
 
 #endif

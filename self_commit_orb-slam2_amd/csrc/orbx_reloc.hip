@@ -1,5 +1,8 @@
 // orbx_reloc.hip -- the refine loop of Tracking::Relocalization (src/Tracking.cc:2135-2223) for ALL hypotheses of ALL candidates as ONE launch chain with
-// ONE host wait (include/orbx.h: orbx_relocalize_refine), and its projection stage on explicit inputs (orbx_reloc_project).
+// ONE host wait (include/orbx.h: orbx_relocalize_refine), and its projection stage on explicit inputs (orbx_reloc_project).  At the end of the file the
+// HEAD of the function (:2063-2095, orbx_reloc_match_candidates): SearchByBoW against all candidates through orbx_match::enqueue_bow_candidates and
+//   k_reloc_pnp_gather  :2075 and src/PnPsolver.cc:136-158  the < 15 decision and the arrays the PnPsolver constructor collects, every result + the
+//                       sequence word
 //
 // The numeric steps had kernels: Optimizer::PoseOptimization (k_pose_opt in orbx_lba.hip, here as a batch of H frames through
 // orbx_pose_opt_enqueue_batch) and the greedy part of SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (k_area_topk / k_area_greedy in
@@ -586,5 +589,153 @@ extern "C" int orbx_relocalize_refine(orbx_matcher *m, const orbx_reloc_frame *f
     if (res->map_point) memcpy(res->map_point, sg.host(rMp), N * 4);
     if (res->outlier) memcpy(res->outlier, sg.host(rOutl), N);
     res->winner = pk[0]; res->hypothesis = pk[1]; res->candidate = pk[2];
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The head of Tracking::Relocalization: K searches, the < 15 decision, the PnP solvers' arrays (include/orbx.h: orbx_reloc_match_candidates)
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct RelocMatchOut { int32_t *matches, *keyIndex; float *p2d, *sigma2, *p3dw; int32_t *ints; };      // mapped host memory; ints[3 k ..]: n, nmatches, discarded
+
+// One workgroup per candidate: its row of matches goes out as the search left it; if the search returned >= 15 (:2075) the frame features that hold a match,
+// in ascending order (rank from a ballot, as k_reloc_seed's gather), become mvKeyPointIndices / mvP2D / mvSigma2 / mvP3Dw (src/PnPsolver.cc:136-158; the
+// search only matches non-bad points, so :142 holds for each).  A discarded candidate's arrays are not written.
+__global__ __launch_bounds__(RL_THREADS) void k_reloc_pnp_gather(const int32_t *__restrict__ mat, const int32_t *__restrict__ nm, int stride, int N,
+                                                                 const orbx_keypoint *__restrict__ kpUn, const float *__restrict__ levelS2, int nlevels,
+                                                                 const float *__restrict__ pos, int capA, RelocMatchOut O, unsigned *counter, unsigned long long *pubFlag,
+                                                                 unsigned long long pubSeq)
+{
+    __shared__ int sh[RL_THREADS / 64];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const int32_t *mk = mat + (size_t)k * stride;
+    const float *pk = pos + 3 * (size_t)k * capA;
+    const int nms = nm[k];
+    const bool keep = nms >= 15;
+    const size_t row = (size_t)k * N;
+    int base = 0;
+    for (int i0 = 0; i0 < N; i0 += RL_THREADS) {
+        const int i = i0 + tid;
+        const int mi = i < N ? mk[i] : -1;
+        const bool has = keep && mi >= 0;
+        if (i < N) O.matches[row + i] = mi;
+        const int slot = block_ballot_rank<RL_THREADS>(has, &base, sh);
+        if (has) {
+            const orbx_keypoint kp = kpUn[i];
+            const size_t e = row + slot;
+            O.keyIndex[e] = i;
+            O.p2d[2 * e] = kp.x; O.p2d[2 * e + 1] = kp.y;
+            O.sigma2[e] = levelS2[min(max(kp.octave, 0), nlevels - 1)];
+            O.p3dw[3 * e] = pk[3 * (size_t)mi]; O.p3dw[3 * e + 1] = pk[3 * (size_t)mi + 1]; O.p3dw[3 * e + 2] = pk[3 * (size_t)mi + 2];
+        }
+    }
+    if (tid == 0) { O.ints[3 * k] = keep ? base : 0; O.ints[3 * k + 1] = nms; O.ints[3 * k + 2] = keep ? 0 : 1; }
+    orbx_publish(counter, pubFlag, pubSeq, gridDim.x);
+}
+
+}  // namespace
+
+extern "C" int orbx_reloc_match_candidates(orbx_matcher *m, const orbx_reloc_match_frame *fr, const orbx_reloc_match_keyframe *kfs, int K, float nn_ratio, int check_orientation,
+                                           const orbx_reloc_match_result *res)
+{
+    if (!m || !fr || !kfs || !res) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    if (K < 1) { orbx_set_error("no candidate"); return ORBX_ERR_ARG; }
+    if (!fr->features || !fr->features->counts || !fr->level_sigma2) { orbx_set_error("NULL counts or level table"); return ORBX_ERR_ARG; }
+    if (fr->nlevels < 1 || fr->nlevels > 64) { orbx_set_error("bad level table (%d levels, 1..64)", fr->nlevels); return ORBX_ERR_ARG; }
+    const orbx_feature_set *b = fr->features;
+    const int n = b->counts[0];
+    if (n > 0 && (!b->keypoints || !b->descriptors || !fr->keypoints_un)) { orbx_set_error("NULL array in the frame arguments"); return ORBX_ERR_ARG; }
+    int capA = 0, withGroups = 0, withValid = 0, live = 0;
+    std::vector<int32_t> cnt((size_t)K + 1, 0), iota((size_t)2 * K, 0);
+    for (int k = 0; k < K; k++) {
+        iota[(size_t)k] = k;
+        if (kfs[k].is_bad) continue;
+        const orbx_feature_set *a = kfs[k].features;
+        if (!a || !a->counts) { orbx_set_error("NULL features of candidate %d", k); return ORBX_ERR_ARG; }
+        const int nA = a->counts[0];
+        if (nA <= 0) continue;
+        if (!a->keypoints || !a->descriptors || !kfs[k].world_pos) { orbx_set_error("NULL array in candidate %d", k); return ORBX_ERR_ARG; }
+        cnt[(size_t)k] = nA;
+        capA = std::max(capA, nA);
+        live++; withGroups += a->groups ? 1 : 0; withValid += a->valid ? 1 : 0;
+    }
+    if (withGroups != 0 && withGroups != live) { orbx_set_error("groups on %d of %d candidates (every keyframe or none)", withGroups, live); return ORBX_ERR_ARG; }
+    cnt[(size_t)K] = std::max(n, 0);
+    if (n <= 0 || capA <= 0) {      // nothing to search: every candidate is discarded (:2066 / :2075), without a launch
+        for (int k = 0; k < K; k++) {
+            if (res->n) res->n[k] = 0;
+            if (res->nmatches) res->nmatches[k] = 0;
+            if (res->discarded) res->discarded[k] = 1;
+            for (int i = 0; i < n; i++) if (res->matches) res->matches[(size_t)k * n + i] = -1;
+        }
+        return ORBX_OK;
+    }
+    if (K > m->maxPairs) { orbx_set_error("%d candidates exceed the matcher's max_pairs %d", K, m->maxPairs); return ORBX_ERR_CAPACITY; }
+    if (n > m->maxFeatures || capA > m->maxFeatures) { orbx_set_error("%d / %d features exceed the matcher's max_features %d", capA, n, m->maxFeatures); return ORBX_ERR_CAPACITY; }
+    if (n > 4000) { orbx_set_error("%d frame features exceed the pair kernel's LDS bound 4000", n); return ORBX_ERR_CAPACITY; }
+    if (capA > 65535 || orbx_match::bow_pair_replay_lds(capA, n, false) > 160 * 1024) { orbx_set_error("feature counts %d / %d too large for the LDS tile of the replay", capA, n); return ORBX_ERR_CAPACITY; }
+    ORBX_HIP_CHECK(hipSetDevice(m->device));
+    int rc;
+    hipStream_t st = m->stream;
+    OrbxCallBox &bx = m->box;
+    const size_t N = (size_t)n, KK = (size_t)K, CA = (size_t)capA;
+    const int stride = std::max(capA, n);
+    auto [pin, pout] = bx.plan();
+    const auto sKpB = pin.add(b->keypoints, N);
+    const auto sDescB = pin.add(b->descriptors, N * 32);
+    const auto sGrB = pin.add(b->groups, b->groups ? N : 0);
+    const auto sKpUn = pin.add(fr->keypoints_un, N);
+    const auto sS2 = pin.add(fr->level_sigma2, (size_t)fr->nlevels);
+    const auto sCnt = pin.add(cnt.data(), KK + 1);
+    const auto sPairs = pin.add(iota.data(), 2 * KK);
+    const auto sKpA = pin.hole<orbx_keypoint>(KK * CA);
+    const auto sDescA = pin.hole<uint8_t>(KK * CA * 32);
+    const auto sGrA = pin.hole<int32_t>(withGroups ? KK * CA : 0);
+    const auto sValA = pin.hole<uint8_t>(withValid ? KK * CA : 0);
+    const auto sPos = pin.hole<float>(KK * CA * 3);
+    const auto rMat = pout.hole<int32_t>(KK * N), rKey = pout.hole<int32_t>(KK * N);
+    const auto rP2 = pout.hole<float>(KK * N * 2), rS2 = pout.hole<float>(KK * N), rP3 = pout.hole<float>(KK * N * 3);
+    const auto rInts = pout.hole<int32_t>(KK * 3);
+    const OrbxStaged sg = bx.begin(st, &rc);
+    if (rc != ORBX_OK) return rc;
+    for (int k = 0; k < K; k++) {      // (a candidate staged with count 0 - bad, or without features - keeps its rows unwritten: nothing reads them)
+        const size_t nA = (size_t)cnt[(size_t)k], at = (size_t)k * CA;
+        if (!nA) continue;
+        const orbx_feature_set *a = kfs[k].features;
+        orbx_put_at(sg, sKpA, at, a->keypoints, nA); orbx_put_at(sg, sDescA, at * 32, a->descriptors, nA * 32); orbx_put_at(sg, sPos, at * 3, kfs[k].world_pos, nA * 3);
+        if (withGroups) orbx_put_at(sg, sGrA, at, a->groups, nA);
+        if (withValid) { if (a->valid) orbx_put_at(sg, sValA, at, a->valid, nA); else memset(sg.host(sValA) + at, 1, nA); }
+    }
+    if ((rc = orbx_match::track_mark(m, st, 0)) != ORBX_OK) return rc;
+    uint8_t *ar;
+    if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
+    ORBX_LAUNCH_CHECK();
+    if ((rc = orbx_match::track_mark(m, st, 1)) != ORBX_OK) return rc;
+    const int32_t *dCnt = sCnt.in(ar);
+    FeatDev A, B;
+    A.kp = sKpA.in(ar); A.desc = sDescA.in(ar); A.groups = withGroups ? sGrA.in(ar) : nullptr; A.valid = withValid ? sValA.in(ar) : nullptr; A.counts = dCnt; A.cap = capA;
+    B.kp = sKpB.in(ar); B.desc = sDescB.in(ar); B.groups = b->groups ? sGrB.in(ar) : nullptr; B.valid = nullptr; B.counts = dCnt + K; B.cap = n;
+    if ((rc = orbx_match::enqueue_bow_candidates(m, st, A, B, K, sPairs.in(ar), sPairs.in(ar) + K, nn_ratio, check_orientation, stride)) != ORBX_OK) return rc;
+    if ((rc = orbx_match::track_mark(m, st, 2)) != ORBX_OK) return rc;
+    const RelocMatchOut O = {sg.dev(rMat), sg.dev(rKey), sg.dev(rP2), sg.dev(rS2), sg.dev(rP3), sg.dev(rInts)};
+    const unsigned long long seq = bx.arm();
+    hipLaunchKernelGGL(k_reloc_pnp_gather, dim3((unsigned)K), dim3(RL_THREADS), 0, st, (const int32_t *)m->matches.p, (const int32_t *)m->nmatches.p, stride, n, sKpUn.in(ar),
+                       sS2.in(ar), fr->nlevels, sPos.in(ar), capA, O, bx.counter, bx.flagDev, seq);
+    ORBX_LAUNCH_CHECK();
+    if ((rc = orbx_match::track_mark(m, st, 3)) != ORBX_OK) return rc;
+    if ((rc = bx.wait(st)) != ORBX_OK) return rc;
+    const int32_t *hi = sg.host(rInts);
+    if (res->matches) memcpy(res->matches, sg.host(rMat), KK * N * 4);
+    for (int k = 0; k < K; k++) {
+        const size_t nk = (size_t)hi[3 * k], row = (size_t)k * N;
+        if (res->n) res->n[k] = hi[3 * k];
+        if (res->nmatches) res->nmatches[k] = hi[3 * k + 1];
+        if (res->discarded) res->discarded[k] = (uint8_t)hi[3 * k + 2];
+        if (res->key_index) memcpy(res->key_index + row, sg.host(rKey) + row, nk * 4);
+        if (res->p2d) memcpy(res->p2d + 2 * row, sg.host(rP2) + 2 * row, nk * 8);
+        if (res->sigma2) memcpy(res->sigma2 + row, sg.host(rS2) + row, nk * 4);
+        if (res->p3dw) memcpy(res->p3dw + 3 * row, sg.host(rP3) + 3 * row, nk * 12);
+    }
     return ORBX_OK;
 }

@@ -1,15 +1,17 @@
-// orbx_track.hip -- a tracked frame on the device: Tracking::TrackWithMotionModel (src/Tracking.cc:1370-1421) and Tracking::TrackLocalMap
-// (:1454-1489) as ONE launch chain each with ONE host wait (include/orbx.h: orbx_track_with_motion_model, orbx_track_local_map).
+// orbx_track.hip -- a tracked frame on the device: Tracking::TrackWithMotionModel (src/Tracking.cc:1370-1421), Tracking::TrackLocalMap
+// (:1454-1489) and Tracking::TrackReferenceKeyFrame (:1181-1239) as ONE launch chain each with ONE host wait (include/orbx.h:
+// orbx_track_with_motion_model, orbx_track_local_map, orbx_track_reference_keyframe).
 //
 // Every numeric step already had a kernel: the two projection searches (orbx_match_proj.hip, chained here through orbx_match::enqueue_proj_last /
-// enqueue_local_points) and Optimizer::PoseOptimization (k_pose_opt in orbx_lba.hip, through orbx_pose_opt_enqueue).  What was missing is what the
+// enqueue_local_points), SearchByBoW for one pair (orbx_match.hip, enqueue_bow_pair) and Optimizer::PoseOptimization (k_pose_opt in orbx_lba.hip, through orbx_pose_opt_enqueue).  What was missing is what the
 // reference does between them on the host, and that is all this file adds:
-//   k_track_gather_last / k_track_gather_local   the features that hold a MapPoint after the search, compacted in ascending feature order into the
+//   k_track_gather_last / _local / _ref          the features that hold a MapPoint after the search, compacted in ascending feature order into the
 //                                                pose problem (world point, observation, information) in device memory, + the count the pose
 //                                                kernel reads there and the words that gate it
-//   k_track_discard                              :1403-1421  outliers leave mvpMapPoints, nmatches / nmatchesMap, every result + the sequence word
+//   k_track_discard                              :1403-1421 and :1215-1236  outliers leave mvpMapPoints, nmatches / nmatchesMap, every result + the
+//                                                sequence word
 //   k_track_local_stats                          :1464-1489  IncreaseFound / mnMatchesInliers / stereo outliers, every result + the sequence word
-// All three are one workgroup (a frame has a few thousand features and the chain is bound by latency, not by throughput): one coalesced pass, the order
+// All of them are one workgroup (a frame has a few thousand features and the chain is bound by latency, not by throughput): one coalesced pass, the order
 // of the compaction from a scan (orbx_wave.h), no atomics on global memory.
 #include "orbx_match_internal.h"
 #include <algorithm>
@@ -19,7 +21,7 @@ namespace {
 #define TRK_THREADS 1024
 // control words the gather kernels leave for the links behind them
 #define TC_COUNT 0      /* correspondences = edges of the pose problem (k_pose_opt's counts[0])                        */
-#define TC_SKIP 1       /* 1 = the search ended below 20 matches (:1393): the discard falls through                    */
+#define TC_SKIP 1       /* 1 = the search ended below 20 matches (:1393; 15 for the reference keyframe, :1201): the discard falls through */
 #define TC_WIDE 2       /* 1 = the 2 * th pass counted                                                                 */
 #define TC_NMS 3        /* the search's return value                                                                   */
 #define TC_GATE 4       /* k_pose_opt's gate: the count, or -1 = the optimisation does not run (:1393)                 */
@@ -81,6 +83,32 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track_gather_last(const int32_t
         base += tot;
     }
     if (tid == 0) { G.ctl[TC_COUNT] = base; G.ctl[TC_SKIP] = nms < 20 ? 1 : 0; G.ctl[TC_WIDE] = wide ? 1 : 0; G.ctl[TC_NMS] = nms; G.ctl[TC_GATE] = nms < 20 ? -1 : base; }
+}
+
+// TrackReferenceKeyFrame: the matches of SearchByBoW(pKF, F) (frame feature -> keyframe slot; a pruned match is already -1), whether the function goes
+// on (:1201), and the pose problem: the keyframe's map point at the matched slot against the frame's feature.
+__global__ __launch_bounds__(TRK_THREADS) void k_track_gather_ref(const int32_t *__restrict__ nm, const int32_t *__restrict__ mat, int n, const orbx_keypoint *__restrict__ kpUn,
+                                                                  const float *__restrict__ uRight, const float *__restrict__ kfPos, const float *__restrict__ invS2, int nlevels,
+                                                                  TrackProblem G)
+{
+    __shared__ int sWave[TRK_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int nms = nm[0];
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += TRK_THREADS) {
+        const int i = i0 + tid;
+        const int mi = i < n ? mat[i] : -1;
+        const bool has = mi >= 0;
+        orbx_keypoint k = {};
+        float ur = 0.f, X[3] = {0.f, 0.f, 0.f};
+        if (has) { k = kpUn[i]; ur = uRight[i]; X[0] = kfPos[3 * (size_t)mi]; X[1] = kfPos[3 * (size_t)mi + 1]; X[2] = kfPos[3 * (size_t)mi + 2]; }
+        int tot;
+        const int slot = base + tile_rank(has, sWave, tot);
+        if (i < n) G.featSlot[i] = has ? slot : -1;
+        if (has) put_edge(G, slot, X, k, ur, invS2, nlevels);
+        base += tot;
+    }
+    if (tid == 0) { G.ctl[TC_COUNT] = base; G.ctl[TC_SKIP] = nms < 15 ? 1 : 0; G.ctl[TC_WIDE] = 0; G.ctl[TC_NMS] = nms; G.ctl[TC_GATE] = nms < 15 ? -1 : base; }
 }
 
 // TrackLocalMap: the features that hold a MapPoint behind SearchLocalPoints - held on entry, or assigned by the search (which also overwrites a held point
@@ -215,18 +243,6 @@ struct TrackWork {
     TrackProblem problem() const { return TrackProblem{Xw.in(base), obs.in(base), is2.in(base), featSlot.in(base), ctl.in(base)}; }
 };
 
-#define TRK_MAX_MARKS 8
-// profile_kernels: an event at boundary k of the chain
-int mark(orbx_matcher *m, hipStream_t st, int k)
-{
-    if (!m->trProfile) return ORBX_OK;
-    if (m->trEv.size() < TRK_MAX_MARKS) m->trEv.resize(TRK_MAX_MARKS, nullptr);
-    if (!m->trEv[k]) { const int rc = orbx_event_create(&m->trEv[k]); if (rc != ORBX_OK) return rc; }
-    ORBX_HIP_CHECK(hipEventRecord(m->trEv[k], st));
-    m->trTimed = k + 1;
-    return ORBX_OK;
-}
-
 int pose_link(hipStream_t st, const TrackWork &w, const float *pose0, const float *cam, int cap, int maxCount)
 {
     OrbxPoseOptArgs a;
@@ -238,6 +254,19 @@ int pose_link(hipStream_t st, const TrackWork &w, const float *pose0, const floa
 }
 
 }  // namespace
+
+#define TRK_MAX_MARKS 8
+// profile_kernels: an event at boundary k of the chain
+int orbx_match::track_mark(orbx_matcher *m, hipStream_t st, int k)
+{
+    if (!m->trProfile) return ORBX_OK;
+    if (m->trEv.size() < TRK_MAX_MARKS) m->trEv.resize(TRK_MAX_MARKS, nullptr);
+    if (!m->trEv[k]) { const int rc = orbx_event_create(&m->trEv[k]); if (rc != ORBX_OK) return rc; }
+    ORBX_HIP_CHECK(hipEventRecord(m->trEv[k], st));
+    m->trTimed = k + 1;
+    return ORBX_OK;
+}
+using orbx_match::track_mark;
 
 extern "C" int orbx_track_set_profiling(orbx_matcher *m, int on)
 {
@@ -316,11 +345,11 @@ extern "C" int orbx_track_with_motion_model(orbx_matcher *m, const orbx_projecti
     if (rc != ORBX_OK) return rc;
     TrackWork w;
     if ((rc = w.plan(m, N)) != ORBX_OK) return rc;
-    if ((rc = mark(m, st, 0)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 0)) != ORBX_OK) return rc;
     uint8_t *ar;
     if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
-    if ((rc = mark(m, st, 1)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 1)) != ORBX_OK) return rc;
     const int32_t *dCnt = sCnt.in(ar);
     const float *dScales = sSc.in(ar);
     const uint8_t *dHasObs = ls->has_observations ? sObs.in(ar) : nullptr;
@@ -330,21 +359,21 @@ extern "C" int orbx_track_with_motion_model(orbx_matcher *m, const orbx_projecti
     int32_t *mat1 = w.mat1.in(w.base), *mat2 = w.mat2.in(w.base), *nm = w.nm.in(w.base);
     // pass 1 with th; pass 2 with 2 * th from cleared matches (its own array), decided on the device: its workgroups leave unless pass 1 counted < 20
     if ((rc = orbx_match::enqueue_proj_last(m, st, F, L, dScales, th, b_mono, check_orientation, mat1, nm, n, nullptr, nullptr, 0ull, ProjGate{nullptr, 0})) != ORBX_OK) return rc;
-    if ((rc = mark(m, st, 2)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 2)) != ORBX_OK) return rc;
     if ((rc = orbx_match::enqueue_proj_last(m, st, F, L, dScales, 2.0f * th, b_mono, check_orientation, mat2, nm + 1, n, nullptr, nullptr, 0ull, ProjGate{nm, 20})) != ORBX_OK) return rc;
-    if ((rc = mark(m, st, 3)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 3)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_track_gather_last, dim3(1), dim3(TRK_THREADS), 0, st, nm, mat1, mat2, n, sKp.in(ar), sUr.in(ar), sPos.in(ar), sIs.in(ar), nlevels, w.problem());
     ORBX_LAUNCH_CHECK();
-    if ((rc = mark(m, st, 4)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 4)) != ORBX_OK) return rc;
     // the count is known on the device only: one predicated launch per instantiation up to the host's upper bound (orbx_pose_opt_enqueue)
     if ((rc = pose_link(st, w, sTc.in(ar), sCam.in(ar), std::max(maxCount, 1), maxCount)) != ORBX_OK) return rc;
-    if ((rc = mark(m, st, 5)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 5)) != ORBX_OK) return rc;
     const MotionOut O = {sg.dev(rMat), sg.dev(rSearch), sg.dev(rDisc), sg.dev(rPose), sg.dev(rInts), sg.dev(rStats)};
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_track_discard, dim3(1), dim3(TRK_THREADS), 0, st, w.ctl.in(w.base), mat1, mat2, n, w.featSlot.in(w.base), w.outl.in(w.base), dHasObs, sTc.in(ar),
                        w.pose.in(w.base), w.ret.in(w.base), w.stats.in(w.base), O, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
-    if ((rc = mark(m, st, 6)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 6)) != ORBX_OK) return rc;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     if (res->matches) memcpy(res->matches, sg.host(rMat), N * 4);
     if (res->search_matches) memcpy(res->search_matches, sg.host(rSearch), N * 4);
@@ -353,6 +382,101 @@ extern "C" int orbx_track_with_motion_model(orbx_matcher *m, const orbx_projecti
     const int32_t *hi = sg.host(rInts);
     res->nmatches_search = hi[0]; res->wide = hi[1]; res->n_correspondences = hi[2]; res->pose_inliers = hi[3]; res->nmatches = hi[4]; res->nmatches_map = hi[5];
     res->ran_pose = hi[6];
+    memcpy(res->stats, sg.host(rStats), 64);
+    return ORBX_OK;
+}
+
+extern "C" int orbx_track_reference_keyframe(orbx_matcher *m, const orbx_reference_keyframe *kf, const orbx_reference_frame *fr, float nn_ratio, int check_orientation,
+                                             orbx_track_reference_result *res)
+{
+    if (!m || !kf || !fr || !res) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    if (!kf->features || !fr->features || !kf->features->counts || !fr->features->counts || !fr->tcw || !fr->inv_level_sigma2) { orbx_set_error("NULL counts, pose or level table"); return ORBX_ERR_ARG; }
+    if (fr->nlevels < 1 || fr->nlevels > 64) { orbx_set_error("bad level table (%d levels, 1..64)", fr->nlevels); return ORBX_ERR_ARG; }
+    const orbx_feature_set *a = kf->features, *b = fr->features;
+    const int nA = a->counts[0], n = b->counts[0];
+    if (nA > 0 && (!a->keypoints || !a->descriptors || !kf->world_pos)) { orbx_set_error("NULL array in the keyframe arguments"); return ORBX_ERR_ARG; }
+    if (n > 0 && (!b->keypoints || !b->descriptors || !fr->keypoints_un || !fr->u_right)) { orbx_set_error("NULL array in the frame arguments"); return ORBX_ERR_ARG; }
+    // what the function leaves when the search finds nothing (:1201): also the result for an empty side, without a launch
+    res->nmatches_search = 0; res->n_correspondences = 0; res->pose_inliers = 0; res->nmatches = 0; res->nmatches_map = 0; res->ran_pose = 0;
+    for (int k = 0; k < 8; k++) res->stats[k] = 0.0;
+    if (n <= 0 || nA <= 0) {
+        for (int i = 0; i < n; i++) { if (res->matches) res->matches[i] = -1; if (res->search_matches) res->search_matches[i] = -1; if (res->discarded) res->discarded[i] = 0; }
+        if (res->pose) memcpy(res->pose, fr->tcw, 64);
+        return ORBX_OK;
+    }
+    if (n > m->maxFeatures || nA > m->maxFeatures) { orbx_set_error("%d / %d features exceed the matcher's max_features %d", nA, n, m->maxFeatures); return ORBX_ERR_CAPACITY; }
+    if (n > 4000) { orbx_set_error("%d frame features exceed the pair kernel's LDS bound 4000", n); return ORBX_ERR_CAPACITY; }
+    if (nA > 65535 || orbx_match::bow_pair_replay_lds(nA, n, false) > 160 * 1024) { orbx_set_error("feature counts %d / %d too large for the LDS tile of the replay", nA, n); return ORBX_ERR_CAPACITY; }
+    int nvalid = nA;
+    if (a->valid) { nvalid = 0; for (int i = 0; i < nA; i++) nvalid += a->valid[i] ? 1 : 0; }
+    const int maxCount = std::min(n, nvalid);      // every correspondence takes a feature and a valid keyframe slot of its own
+    if (maxCount > ORBX_TRACK_MAX_CORRESPONDENCES) {
+        orbx_set_error("%d possible correspondences exceed the pose kernel's limit %d", maxCount, ORBX_TRACK_MAX_CORRESPONDENCES);
+        return ORBX_ERR_CAPACITY;
+    }
+    ORBX_HIP_CHECK(hipSetDevice(m->device));
+    int rc;
+    hipStream_t st = m->stream;
+    OrbxCallBox &bx = m->box;
+    const size_t N = (size_t)n, NA = (size_t)nA;
+    const int32_t cnt[2] = {nA, n};
+    const float cam[5] = {fr->fx, fr->fy, fr->cx, fr->cy, fr->mbf};
+    auto [pin, pout] = bx.plan();
+    const auto sKpA = pin.add(a->keypoints, NA);
+    const auto sDescA = pin.add(a->descriptors, NA * 32);
+    const auto sGrA = pin.add(a->groups, a->groups ? NA : 0);
+    const auto sValA = pin.add(a->valid, a->valid ? NA : 0);
+    const auto sKpB = pin.add(b->keypoints, N);
+    const auto sDescB = pin.add(b->descriptors, N * 32);
+    const auto sGrB = pin.add(b->groups, b->groups ? N : 0);
+    const auto sCnt = pin.add(cnt, 2);
+    const auto sPos = pin.add(kf->world_pos, NA * 3);
+    const auto sObs = pin.add(kf->has_observations, kf->has_observations ? NA : 0);
+    const auto sKpUn = pin.add(fr->keypoints_un, N);
+    const auto sUr = pin.add(fr->u_right, N);
+    const auto sTc = pin.add(fr->tcw, 16);
+    const auto sIs = pin.add(fr->inv_level_sigma2, (size_t)fr->nlevels), sCam = pin.add(cam, 5);
+    const auto rMat = pout.hole<int32_t>(N), rSearch = pout.hole<int32_t>(N);
+    const auto rDisc = pout.hole<uint8_t>(N);
+    const auto rPose = pout.hole<float>(16);
+    const auto rInts = pout.hole<int32_t>(8);
+    const auto rStats = pout.hole<double>(8);
+    const OrbxStaged sg = bx.begin(st, &rc);
+    if (rc != ORBX_OK) return rc;
+    TrackWork w;
+    if ((rc = w.plan(m, N)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 0)) != ORBX_OK) return rc;
+    uint8_t *ar;
+    if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
+    ORBX_LAUNCH_CHECK();
+    if ((rc = track_mark(m, st, 1)) != ORBX_OK) return rc;
+    const int32_t *dCnt = sCnt.in(ar);
+    const uint8_t *dHasObs = kf->has_observations ? sObs.in(ar) : nullptr;
+    FeatDev A, B;      // as orbx_search_by_bow's single-pair path builds them (the frame's valid flags play no part in mode 0)
+    A.kp = sKpA.in(ar); A.desc = sDescA.in(ar); A.groups = a->groups ? sGrA.in(ar) : nullptr; A.valid = a->valid ? sValA.in(ar) : nullptr; A.counts = dCnt; A.cap = nA;
+    B.kp = sKpB.in(ar); B.desc = sDescB.in(ar); B.groups = b->groups ? sGrB.in(ar) : nullptr; B.valid = nullptr; B.counts = dCnt + 1; B.cap = n;
+    int32_t *mat = w.mat1.in(w.base), *nm = w.nm.in(w.base);
+    if ((rc = orbx_match::enqueue_bow_pair(m, st, A, B, 0, nn_ratio, check_orientation, mat, m->dists.p, nm, n, nullptr, nullptr, 0ull)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 2)) != ORBX_OK) return rc;
+    hipLaunchKernelGGL(k_track_gather_ref, dim3(1), dim3(TRK_THREADS), 0, st, nm, mat, n, sKpUn.in(ar), sUr.in(ar), sPos.in(ar), sIs.in(ar), fr->nlevels, w.problem());
+    ORBX_LAUNCH_CHECK();
+    if ((rc = track_mark(m, st, 3)) != ORBX_OK) return rc;
+    if ((rc = pose_link(st, w, sTc.in(ar), sCam.in(ar), std::max(maxCount, 1), maxCount)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 4)) != ORBX_OK) return rc;
+    // :1215-1236 is :1403-1421 with the keyframe's points in the last frame's place: the same kernel (one pass: both match arrays are the search's)
+    const MotionOut O = {sg.dev(rMat), sg.dev(rSearch), sg.dev(rDisc), sg.dev(rPose), sg.dev(rInts), sg.dev(rStats)};
+    const unsigned long long seq = bx.arm();
+    hipLaunchKernelGGL(k_track_discard, dim3(1), dim3(TRK_THREADS), 0, st, w.ctl.in(w.base), mat, mat, n, w.featSlot.in(w.base), w.outl.in(w.base), dHasObs, sTc.in(ar),
+                       w.pose.in(w.base), w.ret.in(w.base), w.stats.in(w.base), O, bx.flagDev, seq);
+    ORBX_LAUNCH_CHECK();
+    if ((rc = track_mark(m, st, 5)) != ORBX_OK) return rc;
+    if ((rc = bx.wait(st)) != ORBX_OK) return rc;
+    if (res->matches) memcpy(res->matches, sg.host(rMat), N * 4);
+    if (res->search_matches) memcpy(res->search_matches, sg.host(rSearch), N * 4);
+    if (res->discarded) memcpy(res->discarded, sg.host(rDisc), N);
+    if (res->pose) memcpy(res->pose, sg.host(rPose), 64);
+    const int32_t *hi = sg.host(rInts);
+    res->nmatches_search = hi[0]; res->n_correspondences = hi[2]; res->pose_inliers = hi[3]; res->nmatches = hi[4]; res->nmatches_map = hi[5]; res->ran_pose = hi[6];
     memcpy(res->stats, sg.host(rStats), 64);
     return ORBX_OK;
 }
@@ -422,11 +546,11 @@ extern "C" int orbx_track_local_map(orbx_matcher *m, const orbx_projection_frame
     if (rc != ORBX_OK) return rc;
     TrackWork w;
     if ((rc = w.plan(m, N)) != ORBX_OK) return rc;
-    if ((rc = mark(m, st, 0)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 0)) != ORBX_OK) return rc;
     uint8_t *ar;
     if ((rc = orbx_stage_to_arena(bx, m->arena, st, 512, &ar)) != ORBX_OK) return rc;
     ORBX_LAUNCH_CHECK();
-    if ((rc = mark(m, st, 1)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 1)) != ORBX_OK) return rc;
     const int32_t *dCnt = sCnt.in(ar);
     const uint8_t *dOcc = fr->occupied ? sOcc.in(ar) : nullptr, *dObs = pt->has_observations ? sObs.in(ar) : nullptr;
     int32_t *as = nullptr, *nm = nullptr;
@@ -441,19 +565,19 @@ extern "C" int orbx_track_local_map(orbx_matcher *m, const orbx_projection_frame
         as = w.mat1.in(w.base); nm = w.nm.in(w.base);
         if ((rc = orbx_match::enqueue_local_points(m, st, Fr, Mp, F, sPd.in(ar), dObs, sSc.in(ar), th, nn_ratio, Ho, as, nm, n, nullptr, nullptr, 0ull)) != ORBX_OK) return rc;
     }
-    if ((rc = mark(m, st, 2)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 2)) != ORBX_OK) return rc;
     hipLaunchKernelGGL(k_track_gather_local, dim3(1), dim3(TRK_THREADS), 0, st, as, n, sHeld.in(ar), sHeldPos.in(ar), sPos.in(ar), sKp.in(ar), sUr.in(ar), sIs.in(ar), nlevels,
                        w.problem());
     ORBX_LAUNCH_CHECK();
-    if ((rc = mark(m, st, 3)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 3)) != ORBX_OK) return rc;
     if ((rc = pose_link(st, w, sTcw.in(ar), sCam.in(ar), std::max(maxCount, 1), maxCount)) != ORBX_OK) return rc;
-    if ((rc = mark(m, st, 4)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 4)) != ORBX_OK) return rc;
     const LocalOut O = {sg.dev(rAs), sg.dev(rOutl), sg.dev(rFound), sg.dev(rCleared), sg.dev(rPose), sg.dev(rInts), sg.dev(rStats)};
     const unsigned long long seq = bx.arm();
     hipLaunchKernelGGL(k_track_local_stats, dim3(1), dim3(TRK_THREADS), 0, st, w.ctl.in(w.base), as, nm, n, w.featSlot.in(w.base), w.outl.in(w.base), dOcc, dObs,
                        pt->has_observations ? 0 : 1, sensor_stereo ? 1 : 0, w.pose.in(w.base), w.ret.in(w.base), w.stats.in(w.base), O, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
-    if ((rc = mark(m, st, 5)) != ORBX_OK) return rc;
+    if ((rc = track_mark(m, st, 5)) != ORBX_OK) return rc;
     if ((rc = bx.wait(st)) != ORBX_OK) return rc;
     if (mm > 0) {
         const uint8_t *iv = sg.host(rIn);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "KeyFrameArrays.h"
 #include "MapPointAccess.h"
 #include "orbx.h"
 #include "shim_error.h"
@@ -18,19 +19,21 @@ namespace
 // one matcher handle per calling thread (a handle is not re-entrant); relocalisation runs on the tracking thread
 struct RelocMatcher {
     orbx_matcher *h;
-    int cap;
-    RelocMatcher() : h(0), cap(0) {}
+    int cap, pairs;
+    RelocMatcher() : h(0), cap(0), pairs(0) {}
     ~RelocMatcher() { if (h) orbx_matcher_destroy(h); }
 };
 thread_local RelocMatcher tReloc;
 
-orbx_matcher *Matcher(int need)
+orbx_matcher *Matcher(int need, int needPairs = 1)
 {
-    if (tReloc.h && need <= tReloc.cap) return tReloc.h;
+    if (tReloc.h && need <= tReloc.cap && needPairs <= tReloc.pairs) return tReloc.h;
     if (tReloc.h) { orbx_matcher_destroy(tReloc.h); tReloc.h = 0; }
-    int cap = 4096;
+    int cap = 4096, pairs = 8;
     while (cap < need) cap *= 2;
-    if (orbx_matcher_create(orbx_shim::Device(), cap, 1, &tReloc.h) != ORBX_OK) { tReloc.h = 0; tReloc.cap = 0; orbx_shim::Fail("Tracking::Relocalization"); return 0; }   // (the caller returns on the NULL handle)
+    while (pairs < needPairs) pairs *= 2;
+    tReloc.pairs = pairs;
+    if (orbx_matcher_create(orbx_shim::Device(), cap, pairs, &tReloc.h) != ORBX_OK) { tReloc.h = 0; tReloc.cap = 0; orbx_shim::Fail("Tracking::Relocalization"); return 0; }   // (the caller returns on the NULL handle)
     tReloc.cap = cap;
     return tReloc.h;
 }
@@ -57,6 +60,64 @@ int AddRelocHypothesis(std::vector<RelocHypothesis> &hyps, int candidate, const 
     h.candidate = candidate; h.Tcw = Tcw.clone(); h.vbInliers = vbInliers;
     hyps.push_back(h);
     return (int)hyps.size() - 1;
+}
+
+int RelocalizationMatchHIP(Frame &F, const std::vector<KeyFrame *> &vpCandidateKFs, std::vector<std::vector<MapPoint *> > &vvpMapPointMatches, std::vector<bool> &vbDiscarded,
+                           std::vector<RelocPnPProblem> &problems, float nnratio, bool checkOrientation)
+{
+    orbx_shim::Mark("RelocalizationMatch enters");
+    const int N = F.N, nKFs = (int)vpCandidateKFs.size();
+    vvpMapPointMatches.resize((size_t)nKFs);
+    vbDiscarded.assign((size_t)nKFs, true);
+    problems.assign((size_t)nKFs, RelocPnPProblem());
+    if (N == 0 || nKFs == 0) return 0;
+    // the gather: every candidate that is not bad, one visit per point (the arrays point into A: sized once, never copied)
+    std::vector<KeyFrameArrays> A((size_t)nKFs);
+    std::vector<orbx_reloc_match_keyframe> kfs((size_t)nKFs);
+    int maxN = N;
+    for (int c = 0; c < nKFs; c++) {
+        KeyFrame *pKF = vpCandidateKFs[(size_t)c];
+        const orbx_reloc_match_keyframe bad = {0, 0, 1};
+        kfs[(size_t)c] = bad;
+        if (pKF->isBad()) continue;                                                        // :2066
+        A[(size_t)c].Gather(pKF);
+        const orbx_reloc_match_keyframe k = {&A[(size_t)c].set, &A[(size_t)c].pos[0], 0};
+        kfs[(size_t)c] = k;
+        vvpMapPointMatches[(size_t)c] = std::vector<MapPoint *>((size_t)N, static_cast<MapPoint *>(NULL));      // src/ORBmatcher.cc:236
+        if (A[(size_t)c].n > maxN) maxN = A[(size_t)c].n;
+    }
+    std::vector<int32_t> gF;
+    FlatFeatureVector(F.mFeatVec, N, gF);
+    const orbx_feature_set fs = {(const orbx_keypoint *)&F.mvKeys[0], F.mDescriptors.data, &N, &gF[0], NULL, N, 1};      // kp angle: src/ORBmatcher.cc:320
+    const orbx_reloc_match_frame fr = {&fs, (const orbx_keypoint *)&F.mvKeysUn[0], &F.mvLevelSigma2[0], (int)F.mvLevelSigma2.size()};
+    const size_t KN = (size_t)nKFs * (size_t)N;
+    std::vector<int32_t> matches(KN, -1), keyIndex(KN), n((size_t)nKFs, 0), nm((size_t)nKFs, 0);
+    std::vector<float> p2d(KN * 2), sigma2(KN), p3dw(KN * 3);
+    std::vector<uint8_t> disc((size_t)nKFs, 1);
+    const orbx_reloc_match_result res = {&matches[0], &keyIndex[0], &p2d[0], &sigma2[0], &p3dw[0], &n[0], &nm[0], &disc[0]};
+    orbx_shim::Mark("RelocalizationMatch marshalled");
+    orbx_matcher *m = Matcher(maxN, nKFs);
+    if (!m) return 0;
+    if (orbx_reloc_match_candidates(m, &fr, &kfs[0], nKFs, nnratio, checkOrientation ? 1 : 0, &res) != ORBX_OK) { orbx_shim::Fail("Tracking::Relocalization"); return 0; }
+    orbx_shim::Mark("RelocalizationMatch device call returned");
+    int nCandidates = 0;
+    for (int c = 0; c < nKFs; c++) {
+        const size_t row = (size_t)c * (size_t)N;
+        if (!kfs[(size_t)c].is_bad)
+            for (int j = 0; j < N; j++)
+                if (matches[row + (size_t)j] >= 0) vvpMapPointMatches[(size_t)c][(size_t)j] = A[(size_t)c].vpMPs[(size_t)matches[row + (size_t)j]];      // :314
+        vbDiscarded[(size_t)c] = disc[(size_t)c] != 0;                                     // :2069, :2077
+        if (disc[(size_t)c]) continue;
+        const size_t k = (size_t)n[(size_t)c];
+        RelocPnPProblem &P = problems[(size_t)c];
+        P.keyIndex.assign(keyIndex.begin() + (long)row, keyIndex.begin() + (long)(row + k));
+        P.p2d.assign(p2d.begin() + (long)(2 * row), p2d.begin() + (long)(2 * (row + k)));
+        P.sigma2.assign(sigma2.begin() + (long)row, sigma2.begin() + (long)(row + k));
+        P.p3dw.assign(p3dw.begin() + (long)(3 * row), p3dw.begin() + (long)(3 * (row + k)));
+        nCandidates++;                                                                     // :2092
+    }
+    orbx_shim::Mark("RelocalizationMatch returns");
+    return nCandidates;
 }
 
 bool RelocalizationRefineHIP(Frame &CurrentFrame, const std::vector<KeyFrame *> &vpCandidateKFs, const std::vector<std::vector<MapPoint *> > &vvpMapPointMatches,

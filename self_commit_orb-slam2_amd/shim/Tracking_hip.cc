@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "KeyFrameArrays.h"
 #include "MapPointAccess.h"
 #include "orbx.h"
 #include "shim_error.h"
@@ -14,7 +15,7 @@ static_assert(sizeof(cv::KeyPoint) == sizeof(orbx_keypoint), "cv::KeyPoint must 
 
 namespace
 {
-// one matcher handle per calling thread (a handle is not re-entrant); both functions run on the tracking thread
+// one matcher handle per calling thread (a handle is not re-entrant); the functions run on the tracking thread
 struct TrackMatcher {
     orbx_matcher *h;
     int cap;
@@ -108,6 +109,51 @@ bool TrackWithMotionModelHIP(Frame &CurrentFrame, const Frame &LastFrame, int th
     if (!res.ran_pose) return false;                                                       // :1393
     SetPoseFrom(CurrentFrame, pose);
     orbx_shim::Mark("TrackWithMotionModel returns");
+    return true;
+}
+
+bool TrackReferenceKeyFrameHIP(Frame &F, KeyFrame *pKF, const cv::Mat &TcwInit, int &nmatches, int &nmatchesMap, float nnratio, bool checkOrientation)
+{
+    orbx_shim::Mark("TrackReferenceKeyFrame enters");
+    nmatches = 0; nmatchesMap = 0;
+    const int N = F.N;
+    if (N == 0) return false;
+    // the gather: what SearchByBoW(pKF, F) and PoseOptimization read of the keyframe's points, one visit each
+    KeyFrameArrays kfa;
+    kfa.Gather(pKF);
+    if (kfa.n == 0) return false;
+    std::vector<int32_t> gF;
+    FlatFeatureVector(F.mFeatVec, N, gF);
+    const orbx_feature_set fs = {(const orbx_keypoint *)&F.mvKeys[0], F.mDescriptors.data, &N, &gF[0], NULL, N, 1};      // kp angle: src/ORBmatcher.cc:320
+    float tc[16], pose[16];
+    PoseOf(TcwInit, tc);
+    const orbx_reference_keyframe kf = {&kfa.set, &kfa.pos[0], &kfa.hasObs[0]};
+    const orbx_reference_frame fr = {&fs, (const orbx_keypoint *)&F.mvKeysUn[0], &F.mvuRight[0], tc, Frame::fx, Frame::fy, Frame::cx, Frame::cy, F.mbf,
+                                     &F.mvInvLevelSigma2[0], (int)F.mvInvLevelSigma2.size()};
+    std::vector<int32_t> matches((size_t)N, -1), searched((size_t)N, -1);      // searched: which point a discarded feature held
+    std::vector<uint8_t> discarded((size_t)N, 0);
+    orbx_track_reference_result res;
+    memset(&res, 0, sizeof res);
+    res.matches = &matches[0]; res.search_matches = &searched[0]; res.discarded = &discarded[0]; res.pose = pose;
+    orbx_shim::Mark("TrackReferenceKeyFrame marshalled");
+    if (orbx_track_reference_keyframe(Matcher(N > kfa.n ? N : kfa.n), &kf, &fr, nnratio, checkOrientation ? 1 : 0, &res) != ORBX_OK)
+        { orbx_shim::Fail("Tracking::TrackReferenceKeyFrame"); return false; }
+    orbx_shim::Mark("TrackReferenceKeyFrame device call returned");
+    nmatches = res.nmatches; nmatchesMap = res.nmatches_map;
+    if (!res.ran_pose) return false;                                                       // :1201 (vpMapPointMatches is a local of the reference's function)
+    // the write-back: mvpMapPoints as :1205 and :1225 leave them, the discarded points' fields (:1227-1228), mvbOutlier (PoseOptimization sets it for
+    // every feature with a point, :1226 clears the discarded ones: all false behind this function), the pose
+    for (int i = 0; i < N; i++) {
+        F.mvpMapPoints[(size_t)i] = matches[(size_t)i] >= 0 ? kfa.vpMPs[(size_t)matches[(size_t)i]] : static_cast<MapPoint *>(NULL);
+        if (matches[(size_t)i] >= 0 || discarded[(size_t)i]) F.mvbOutlier[(size_t)i] = false;
+        if (discarded[(size_t)i]) {
+            MapPoint *pMP = kfa.vpMPs[(size_t)searched[(size_t)i]];
+            pMP->mbTrackInView = false;                                                    // :1227
+            pMP->mnLastFrameSeen = F.mnId;                                                 // :1228
+        }
+    }
+    SetPoseFrom(F, pose);
+    orbx_shim::Mark("TrackReferenceKeyFrame returns");
     return true;
 }
 
