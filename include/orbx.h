@@ -1744,6 +1744,112 @@ int orbx_optimize_sim3_linearize(orbx_sim3_optimizer *h, const orbx_sim3_opt_pro
 int orbx_sim3_optimizer_last_timing(orbx_sim3_optimizer *h, float *device_ms, int *launches);
 
 /* ----------------------------------------------------------------------------------
+ * The refine step of LoopClosing::ComputeSim3 (src/LoopClosing.cc:435-480) for EVERY event that Sim3Solver::iterate
+ * returns, for all H events of all K candidates as one launch chain with ONE host wait (a caller that asks for the
+ * diagnostic arrays of orbx_loop_refine_result pays a stream synchronisation and one blocking copy per array behind it).
+ * Lives on the matcher handle;
+ * host memory throughout; the handle keeps no state between calls.
+ *
+ * Per distinct hypothesis h = (candidate, R12, t12, s12, inlier mask), all H in parallel, one status word each:
+ *   seed     vpMapPointMatches[i] = bow_match[i] where inliers[i], else -1 (:437-443); vbAlreadyMatched1 = those
+ *            features, vbAlreadyMatched2 = the slots they name (src/ORBmatcher.cc:1347-1357)
+ *   project  both directions of SearchBySim3 (:1367-1411 and its mirror :1430-1474), one thread per slot, float, in the
+ *            reference's operation order: p3Dc1 = (R[0]*x + R[1]*y) + R[2]*z, then + t, from the keyframe's rcw / tcw;
+ *            sR12 = s12 * R12; sR21 = float((1.0 / s12) * R12^T), quotient and products in double; t21 = (-sR21) * t12
+ *            (k_sim3_models' arithmetic, see orbx_sim3_solve above); p3Dc2 = sR21 * p3Dc1 + t21 in the same 3-term
+ *            form; z < 0 rejects; invz = 1 / z as a float quotient; u = fx * (x * invz) + cx with KF1's intrinsics in
+ *            BOTH directions (as the reference); IsInImage (>= min, < max); dist3D = cv::norm (squares summed in
+ *            double) in [0.8 min_distance, 1.2 max_distance]; PredictScale through ratio_thresholds of the SEARCHED
+ *            keyframe; radius = th * scale_factors[level].  A slot whose u or v is NaN fails IsInImage and is turned away.
+ *            Output: one orbx_fuse_points record per slot and direction, in device memory.
+ *   search   k_fuse_best with chi2_gate = 0 for the 2 H (keyframe, list) problems in ONE launch: direction 1->2
+ *            searches the hypothesis' candidate, 2->1 searches KF1; KF1 and the K candidates are staged once.
+ *            Accepted up to TH_HIGH = 100 (:1444 / :1507).
+ *   mutual   vpMatches12[i1] = idx2 where vnMatch2[vnMatch1[i1]] == i1 (:1507-1521) -> n_found; then the pairs of
+ *            Optimizer::OptimizeSim3 (src/Optimizer.cc:1429-1520) in ascending i1 over every i1 with a match whose two
+ *            slots are valid -> n_pairs; world1, world2, obs1 = mvKeysUn1[i1].pt, obs2 = mvKeysUn2[i2].pt and the two
+ *            inv_level_sigma2[octave] in the layout of orbx_sim3_opt_problem, in device memory
+ *   optimise k_optsim3 (orbx_optimize_sim3 above: same kernel, same arithmetic, same order of sums), th2, fix_scale,
+ *            from g2o::Sim3(R12, t12, s12) with the floats widened
+ *   decide   pairs removed by either chi2 test are nulled in vpMatches12 (src/Optimizer.cc:1541 / :1578);
+ *            success = n_inliers >= 20 (:463); mg2oScw = gScm * gSmw in FP64 (sim3.h's operator*, gSmw from the
+ *            candidate's rcw / tcw widened, scale 1, :469-471); mScw = Converter::toCvMat: float(s * R), float(t).
+ *            The last workgroup to arrive walks the H status words in order - hypotheses are given in the order in which
+ *            the reference's round-robin loop (:403-482) meets the events, every event once - and reports winner = the
+ *            first success or -1.
+ * Every stage is enqueued unconditionally.  Launches: stage copy, seed, project, search, mutual, optimise, decide = 7;
+ * form (b) adds one in front = 8 (orbx_loop_sim3_last_timing reports the count of the last call).
+ *
+ * The identity of a map point is its keyframe slot: pMP->GetIndexInKeyFrame(pKF2) of a KF2 point is its slot, and the
+ * same MapPoint in two slots of one keyframe counts as two points.  PARITY UNPINNED: that identity, and everything
+ * orbx_optimize_sim3 lists.
+ *
+ * status: 0 = failed, 1 = success, 2 = overflow: the pair count is decided on the device and k_optsim3 holds
+ * ORBX_SIM3_OPT_MAX_PAIRS; a hypothesis that gathers more runs no optimisation (n_inliers = n_bad = 0, the estimate as
+ * passed in).  If the walk meets such a hypothesis before a winner the call returns ORBX_ERR_CAPACITY with the
+ * per-hypothesis results filled, winner = -1; nothing is silently truncated.
+ *
+ * ORBX_ERR_ARG: NULL arguments or arrays, nlevels outside 1..12, an empty keyframe / candidate list / hypothesis list,
+ * grid statics or image bounds of a candidate that differ from KF1's (they are statics of Frame in the reference), a
+ * bow_match outside -1..N2-1, a hypothesis' candidate out of range, non-finite th / th2 or th2 < 0; in form (b) a solver
+ * without a solve or on another device, a candidate or iteration outside that solve, an index1 count that is not that
+ * solve's n, an index1 outside 0..N1-1 or one feature named twice.  ORBX_ERR_CAPACITY: N beyond the matcher's
+ * max_features or 65535, H beyond ORBX_LOOP_SIM3_MAX_HYPOTHESES, K beyond max_pairs.  Neither launches anything.
+ *
+ * Contract: every field equals, bit for bit, the composition per hypothesis of the seed and the projection restated on
+ * the host, orbx_fuse_search (chi2_gate = 0) twice, the mutual check and the gather on the host, orbx_optimize_sim3 (one
+ * problem) and the decision on the host. */
+#define ORBX_LOOP_SIM3_MAX_HYPOTHESES 64
+typedef struct orbx_loop_sim3_keyframe {   /* host memory: one keyframe as arrays over its N = frame.counts[0] slots */
+    orbx_projection_frame frame;      /* keypoints_un, descriptors, counts, grid statics (u_right and occupied are not read) */
+    float rcw[9], tcw[3];             /* GetRotation / GetTranslation */
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y; /* (float) of KeyFrame::mnMinX .. mnMaxY: IsInImage and the cell window */
+    const float *scale_factors;       /* mvScaleFactors [nlevels] */
+    const float *ratio_thresholds;    /* [nlevels-1] from orbx_predict_scale_thresholds */
+    const float *inv_level_sigma2;    /* mvInvLevelSigma2 [nlevels] */
+    int nlevels;
+    const uint8_t *valid;             /* pMP && !pMP->isBad() */
+    const float *world_pos;           /* [3] */
+    const float *max_distance;        /* mfMaxDistance, as orbx_reloc_candidate */
+    const float *min_distance;        /* mfMinDistance */
+    const uint8_t *descriptors;       /* the map point's GetDescriptor() [32] */
+    const int32_t *bow_match;         /* candidates only: [N1] KF2 slot that vvpMapPointMatches[c][i1] holds, or -1 */
+} orbx_loop_sim3_keyframe;
+typedef struct orbx_loop_sim3_hypotheses {
+    int count;                        /* H distinct events, in walk order */
+    const int32_t *candidate;         /* [H] */
+    const float *r12, *t12, *s12;     /* form (a): [H*9], [H*3], [H] */
+    const uint8_t *inliers;           /* form (a): [H*N1] over KF1's features */
+    /* form (b), solver != NULL (r12 .. inliers are then not read): hypothesis h is iteration iteration[h] of candidate candidate[h]
+     * of the LAST orbx_sim3_solve of `solver` (same device, same candidate order as `cands`): R12 / t12 / s12 and the mask row are
+     * read where that chain left them in device memory, the mask scattered through index1[c][i] (mvnIndices1: compacted pair i of
+     * candidate c -> KF1 feature), index1_count[c] entries = that solve's n.  No mask crosses to the host. */
+    struct orbx_sim3_solver *solver;
+    const int32_t *iteration;         /* [H] */
+    const int32_t *const *index1;     /* [ncands] (entries of candidates no hypothesis names may be NULL) */
+    const int32_t *index1_count;      /* [ncands] */
+} orbx_loop_sim3_hypotheses;
+/* (orbx_loop_sim3_result is the result of orbx_loop_correct_sim3 below; this one is named after its entry point) */
+typedef struct orbx_loop_refine_result {   /* any pointer may be NULL */
+    int32_t *status, *n_found, *n_pairs, *n_inliers, *n_bad;   /* [H] each */
+    double *quat, *t, *s;             /* [H*4] (x, y, z, w), [H*3], [H]: gScm afterwards */
+    float *scw;                       /* [H*16] mScw (written for every hypothesis, meaningful where status == 1) */
+    int32_t *matches12;               /* [N1] the winner's mvpCurrentMatchedPoints as KF2 slots, -1 = none (all -1 without a winner) */
+    /* diagnostics (copies of their own behind the call); P = the largest slot count of the call's keyframes, NP = max(P, 1);
+     * list 2 h is direction 1->2 of hypothesis h, list 2 h + 1 direction 2->1 */
+    float *query_u, *query_v, *query_radius;   /* [2H*NP] */
+    int32_t *query_level;             /* [2H*NP] */
+    uint8_t *query_active;            /* [2H*NP] */
+    int32_t *match1, *match2;         /* [H*NP] vnMatch1 / vnMatch2 */
+    int32_t winner, hypothesis, candidate;   /* first successful hypothesis or -1 (every event occurs once: hypothesis == winner); its candidate or -1 */
+} orbx_loop_refine_result;
+int orbx_loop_refine_sim3(orbx_matcher *m, const orbx_loop_sim3_keyframe *kf1, const orbx_loop_sim3_keyframe *cands, int ncands,
+                          const orbx_loop_sim3_hypotheses *hyp, float th, float th2, int fix_scale, orbx_loop_refine_result *result);
+/* device time of the last orbx_loop_refine_sim3 chain (first to last kernel) and its kernel launches */
+int orbx_loop_sim3_last_timing(orbx_matcher *m, float *device_ms, int *launches);
+
+/* ----------------------------------------------------------------------------------
  * PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc): EPnP on RANSAC sets of four matches, for ALL relocalisation
  * candidates of Tracking::Relocalization (src/Tracking.cc) in one launch chain with one wait.
  *

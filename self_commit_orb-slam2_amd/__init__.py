@@ -821,6 +821,80 @@ def reloc_hypotheses(pnp_candidates, triples):
     return out
 
 
+class LoopSim3KeyFrame(ctypes.Structure):      # orbx_loop_sim3_keyframe
+    _fields_ = [("frame", ProjectionFrame), ("rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3)] + \
+               [(k, ctypes.c_float) for k in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y")] + \
+               [("scale_factors", ctypes.c_void_p), ("ratio_thresholds", ctypes.c_void_p), ("inv_level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)] + \
+               [(k, ctypes.c_void_p) for k in ("valid", "world_pos", "max_distance", "min_distance", "descriptors", "bow_match")]
+
+
+class LoopSim3Hypotheses(ctypes.Structure):    # orbx_loop_sim3_hypotheses
+    _fields_ = [("count", ctypes.c_int)] + [(k, ctypes.c_void_p) for k in ("candidate", "r12", "t12", "s12", "inliers", "solver", "iteration", "index1", "index1_count")]
+
+
+_LOOP_REFINE_ARRAYS = ("status", "n_found", "n_pairs", "n_inliers", "n_bad", "quat", "t", "s", "scw", "matches12", "query_u", "query_v", "query_radius", "query_level",
+                       "query_active", "match1", "match2")
+
+
+class LoopRefineResult(ctypes.Structure):      # orbx_loop_refine_result
+    _fields_ = [(k, ctypes.c_void_p) for k in _LOOP_REFINE_ARRAYS] + [(k, ctypes.c_int32) for k in ("winner", "hypothesis", "candidate")]
+
+
+LOOP_SIM3_MAX_HYPOTHESES = 64      # ORBX_LOOP_SIM3_MAX_HYPOTHESES
+
+
+def loop_sim3_sequence(candidates, nIterations=5):
+    """The order in which LoopClosing::ComputeSim3's loop (reference src/LoopClosing.cc:403-482) receives Sim3 estimates from its solvers: round-robin over
+    the undiscarded candidates, iterate(nIterations) on each (src/Sim3Solver.cc:199-285, replayed from what the device solved: count per iteration with n,
+    min_inliers and the iterations that were run), a candidate discarded when iterate reports bNoMore (:428-432).  candidates: Sim3Candidate objects (their
+    own iterate state is not touched) or dicts with n, min_inliers, count.  Returns the events in walk order as a list of dict(candidate, iteration); every
+    event occurs once.  Where the reference's loop would stop is not known here: the device's `winner` tells."""
+    def get(r, k):
+        return r[k] if isinstance(r, dict) else getattr(r, k)
+    st = [dict(n=int(get(r, "n")), min_inliers=int(get(r, "min_inliers")), count=np.asarray(get(r, "count")), it=0, best=0) for r in candidates]
+    K = len(st)
+    discarded, left, events = [False] * K, K, []
+    while left > 0:
+        for i in range(K):
+            if discarded[i]:
+                continue
+            c = st[i]
+            event, no_more = None, False
+            if c["n"] < c["min_inliers"]:                                      # src/Sim3Solver.cc:206-210
+                no_more = True
+            else:
+                cur = 0
+                while c["it"] < len(c["count"]) and cur < nIterations:         # :219
+                    it = c["it"]
+                    cur += 1
+                    c["it"] += 1
+                    if c["count"][it] >= c["best"]:                            # :258-277
+                        c["best"] = int(c["count"][it])
+                        if c["count"][it] > c["min_inliers"]:
+                            event = it
+                            break
+                if event is None and c["it"] >= len(c["count"]):               # :281-282
+                    no_more = True
+            if no_more:
+                discarded[i] = True
+                left -= 1
+            if event is not None:
+                events.append(dict(candidate=i, iteration=int(event)))
+    return events
+
+
+def loop_sim3_hypotheses(candidates, events):
+    """Form (a) of ORBmatcher.LoopRefineSim3's hypotheses from solved Sim3Candidate objects: for every (candidate, iteration) of loop_sim3_sequence the
+    iteration's R12 / t12 / s12 and its mask over KF1's features (through mvnIndices1), as Sim3Solver::iterate returns them."""
+    out = []
+    for e in events:
+        r, it = candidates[e["candidate"]], int(e["iteration"])
+        vb = np.zeros(r.mN1, np.uint8)
+        vb[r.indices1[r.inliers(it)]] = 1
+        out.append(dict(candidate=int(e["candidate"]), R12=r.r12[it].copy(), t12=r.t12[it].copy(), s12=np.float32(r.s12[it]), inliers=vb))
+    return out
+
+
 class ORBmatcher(_Handle):
     """Mirror of the Hamming paths of ORB_SLAM2::ORBmatcher (reference include/ORBmatcher.h:57-215)."""
     _destroy = "orbx_matcher_destroy"
@@ -1690,6 +1764,112 @@ class ORBmatcher(_Handle):
         call.raw, call.result = raw, result
         call.keep = [keep, cs, CA, hc, ht, hm, sq, HY, stage, succ, ng, na, nc, pose, stats, mp, outl, RS, R]
         return call
+
+    @staticmethod
+    def _loop_keyframe(kf, n1=None):
+        """orbx_loop_sim3_keyframe from dict(kps, desc, Rcw (3,3), tcw (3), cam = (fx, fy, cx, cy), scale_factors, log_scale_factor, inv_level_sigma2, width, height
+        [, min_x ..], valid, pos, max_distance (mfMaxDistance), min_distance, point_desc[, bow_match [N1]])."""
+        f4 = np.float32
+        k = np.ascontiguousarray(kf["kps"], KEYPOINT_DTYPE)
+        n = len(k)
+        d, cn = np.ascontiguousarray(kf["desc"], np.uint8), np.array([n], np.int32)
+        sf, is2 = np.ascontiguousarray(kf["scale_factors"], f4), np.ascontiguousarray(kf["inv_level_sigma2"], f4)
+        if len(is2) != len(sf):
+            raise ValueError("inv_level_sigma2 and scale_factors must have one entry per level")
+        rt = np.ascontiguousarray(np.concatenate([predict_scale_thresholds(kf["log_scale_factor"], len(sf)), np.zeros(1, f4)]), f4)
+        minx, miny = f4(kf.get("min_x", 0.0)), f4(kf.get("min_y", 0.0))
+        maxx, maxy = f4(kf.get("max_x", kf["width"])), f4(kf.get("max_y", kf["height"]))
+        gw, gh = f4(64) / (maxx - minx), f4(48) / (maxy - miny)
+        valid = np.ascontiguousarray(kf["valid"], np.uint8)
+        pos = np.ascontiguousarray(np.asarray(kf["pos"], f4).reshape(-1, 3))
+        mx, mn = np.ascontiguousarray(kf["max_distance"], f4), np.ascontiguousarray(kf["min_distance"], f4)
+        pd = np.ascontiguousarray(kf["point_desc"], np.uint8)
+        bow = None if kf.get("bow_match") is None else np.ascontiguousarray(kf["bow_match"], np.int32)
+        if not (len(valid) == len(pos) == len(mx) == len(mn) == len(pd) == len(d) == n):
+            raise ValueError("the arrays of a keyframe must have one entry per slot")
+        if bow is not None and n1 is not None and len(bow) != n1:
+            raise ValueError("bow_match must have one entry per feature of the first keyframe")
+        F = ProjectionFrame(_ptr(k).value, _ptr(d).value, None, None, _ptr(cn).value, max(n, 1), 1, float(minx), float(miny), float(gw), float(gh))
+        K = LoopSim3KeyFrame()
+        K.frame = F
+        K.rcw = (ctypes.c_float * 9)(*np.asarray(kf["Rcw"], f4).reshape(-1))
+        K.tcw = (ctypes.c_float * 3)(*np.asarray(kf["tcw"], f4).reshape(-1))
+        K.fx, K.fy, K.cx, K.cy = [float(f4(v)) for v in kf["cam"][:4]]
+        K.min_x, K.max_x, K.min_y, K.max_y = [float(f4(int(v))) for v in (minx, maxx, miny, maxy)]      # KeyFrame keeps the bounds as int
+        K.scale_factors, K.ratio_thresholds, K.inv_level_sigma2, K.nlevels = _ptr(sf).value, _ptr(rt).value, _ptr(is2).value, len(sf)
+        K.valid, K.world_pos, K.max_distance, K.min_distance, K.descriptors = [_ptr(a).value for a in (valid, pos, mx, mn, pd)]
+        K.bow_match = None if bow is None else _ptr(bow).value
+        return K, [k, d, cn, sf, is2, rt, valid, pos, mx, mn, pd, bow], n
+
+    def LoopRefineSim3(self, kf1, cands, hyps, sim3=None, index1=None, th=7.5, th2=10, fix_scale=False, full=False):
+        return self.loop_refine_prepare(kf1, cands, hyps, sim3, index1, th, th2, fix_scale, full)()
+
+    def loop_refine_prepare(self, kf1, cands, hyps, sim3=None, index1=None, th=7.5, th2=10, fix_scale=False, full=False):
+        """The refine step of LoopClosing::ComputeSim3 (reference src/LoopClosing.cc:435-480) for all Sim3Solver events of all candidates as one device chain with
+        one host wait (orbx_loop_refine_sim3).  kf1 / cands: dicts as _loop_keyframe takes them (cands with bow_match [N1]); hyps: the events in walk order
+        (loop_sim3_sequence), each dict(candidate, R12 (3,3), t12 (3), s12, inliers [N1]) (loop_sim3_hypotheses).
+        sim3 = a Sim3Solver whose last Solve was over these candidates, in this order: hyps is then a list of dict(candidate, iteration), every model and mask
+        is read where that solve left it on the device, and index1[c] = mvnIndices1 of candidate c (None for a candidate no hypothesis names).
+        Returns a prepared call: call() -> dict(status [H] (0 failed, 1 success, 2 more than 1024 pairs), n_found, n_pairs, n_inliers, n_bad [H], quat [H, 4], t [H, 3],
+        s [H], scw [H, 4, 4], matches12 [N1] of the winner, winner, hypothesis, candidate; full=True adds query_u / query_v / query_radius / query_level /
+        query_active [H, 2, NP] and match1 / match2 [H, NP]); call.raw() is the C call alone and returns its code, call.result() reads the arrays."""
+        K1, keep1, n1 = self._loop_keyframe(kf1)
+        cs = [self._loop_keyframe(c, n1) for c in cands]
+        CA = (LoopSim3KeyFrame * max(len(cs), 1))(*[c[0] for c in cs])
+        H = len(hyps)
+        NP = max([n1] + [c[2] for c in cs] + [1])
+        hc = np.ascontiguousarray([int(h["candidate"]) for h in hyps], np.int32)
+        HY = LoopSim3Hypotheses()
+        HY.count, HY.candidate = H, _ptr(hc).value
+        if sim3 is None:
+            hr = np.ascontiguousarray(np.stack([np.asarray(h["R12"], np.float32).reshape(9) for h in hyps]) if H else np.zeros((0, 9), np.float32))
+            ht = np.ascontiguousarray(np.stack([np.asarray(h["t12"], np.float32).reshape(3) for h in hyps]) if H else np.zeros((0, 3), np.float32))
+            hs = np.ascontiguousarray([np.float32(h["s12"]) for h in hyps], np.float32)
+            hm = np.ascontiguousarray(np.stack([np.asarray(h["inliers"], np.uint8) for h in hyps]) if H else np.zeros((0, n1), np.uint8))
+            if H and hm.shape[1] != n1:
+                raise ValueError("inliers must have one entry per feature of the first keyframe")
+            HY.r12, HY.t12, HY.s12, HY.inliers = _ptr(hr).value, _ptr(ht).value, _ptr(hs).value, _ptr(hm).value
+            hk = [hr, ht, hs, hm]
+        else:
+            hi = np.ascontiguousarray([int(h["iteration"]) for h in hyps], np.int32)
+            ix = [None if k is None else np.ascontiguousarray(k, np.int32) for k in (index1 if index1 is not None else [None] * len(cs))]
+            if len(ix) != len(cs):
+                raise ValueError("index1 must have one entry per candidate")
+            ip = (ctypes.c_void_p * max(len(ix), 1))(*[None if k is None else _ptr(k).value for k in ix])
+            ic = np.ascontiguousarray([0 if k is None else len(k) for k in ix], np.int32)
+            HY.solver, HY.iteration, HY.index1, HY.index1_count = sim3._h, _ptr(hi).value, ctypes.cast(ip, ctypes.c_void_p), _ptr(ic).value
+            hk = [hi, ix, ip, ic, sim3]
+        h1, m1 = max(H, 1), max(n1, 1)
+        i4, f4, f8, u1 = np.int32, np.float32, np.float64, np.uint8
+        o = dict(status=np.zeros(h1, i4), n_found=np.zeros(h1, i4), n_pairs=np.zeros(h1, i4), n_inliers=np.zeros(h1, i4), n_bad=np.zeros(h1, i4), quat=np.zeros((h1, 4), f8),
+                 t=np.zeros((h1, 3), f8), s=np.zeros(h1, f8), scw=np.zeros((h1, 4, 4), f4), matches12=np.full(m1, -1, i4))
+        if full:
+            o.update(query_u=np.zeros((h1, 2, NP), f4), query_v=np.zeros((h1, 2, NP), f4), query_radius=np.zeros((h1, 2, NP), f4), query_level=np.zeros((h1, 2, NP), i4),
+                     query_active=np.zeros((h1, 2, NP), u1), match1=np.full((h1, NP), -1, i4), match2=np.full((h1, NP), -1, i4))
+        RS = LoopRefineResult(*[_ptr(o[k]).value if k in o else None for k in _LOOP_REFINE_ARRAYS])
+        fn, hnd, nca = self._L.orbx_loop_refine_sim3, self._h, len(cs)
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(LoopSim3KeyFrame), ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(LoopSim3Hypotheses), ctypes.c_float, ctypes.c_float,
+                       ctypes.c_int, ctypes.POINTER(LoopRefineResult)]
+        cth, cth2, cfix = ctypes.c_float(th), ctypes.c_float(th2), 1 if fix_scale else 0
+
+        def raw():
+            return fn(hnd, ctypes.byref(K1), ctypes.cast(CA, ctypes.c_void_p), nca, ctypes.byref(HY), cth, cth2, cfix, ctypes.byref(RS))
+
+        def result():
+            r = {k: (v[:n1].copy() if k == "matches12" else v[:H].copy()) for k, v in o.items()}
+            r.update(winner=RS.winner, hypothesis=RS.hypothesis, candidate=RS.candidate)
+            return r
+
+        def call():
+            _check(raw())
+            return result()
+        call.raw, call.result = raw, result
+        call.keep = [keep1, cs, CA, hc, hk, HY, o, RS, K1]
+        return call
+
+    def loop_refine_last_timing(self):
+        """(device ms of the last LoopRefineSim3 chain, kernel launches)"""
+        return self._timing("orbx_loop_sim3_last_timing", ctypes.c_float, ctypes.c_int)
 
 
 # =====================================================================================

@@ -16,7 +16,7 @@ LIB = PKG / "lib" / "liborbx.so"
 HIP_SOURCES = ["orbx_kernels.hip", "orbx_extractor.hip", "orbx_match.hip", "orbx_match_proj.hip", "orbx_lba.hip", "orbx_bow.hip", "orbx_frame.hip",
                "orbx_mappoint.hip", "orbx_triangulate.hip", "orbx_initializer.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_optimize_sim3.hip",
                "orbx_essential_graph.hip", "orbx_kfdb.hip", "orbx_covis.hip", "orbx_loop_correct.hip", "orbx_image.hip", "orbx_voc_train.hip", "orbx_fuse_chain.hip",
-               "orbx_voc_text.hip", "orbx_track.hip", "orbx_reloc.hip"]
+               "orbx_voc_text.hip", "orbx_track.hip", "orbx_reloc.hip", "orbx_loop_sim3.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
              "-Wall", "-Wno-unused-function"]
 

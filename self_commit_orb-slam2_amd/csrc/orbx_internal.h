@@ -437,6 +437,13 @@ int orbx_pose_opt_enqueue_batch(hipStream_t st, const OrbxPoseOptArgs &a, int B)
 struct OrbxPnpRows { const double *refR, *refT; const unsigned long long *refMask; int n, words, nrec; };
 int orbx_pnp_device_rows_internal(orbx_pnp_solver *h, int candidate, int device, OrbxPnpRows *out);
 
+/* Where the last orbx_sim3_solve of a Sim3 handle left ONE candidate's iterations in device memory (orbx_loop_sim3.hip reads its hypotheses there, no
+ * mask crosses to the host): iteration k's R12 / t12 / s12 at r12 + 9 k / t12 + 3 k / s12 + k (floats), its mvbInliersi as bit i of
+ * mask[k * words + (i >> 6)] over the candidate's n compacted pairs; iters iterations were run.
+ * ORBX_ERR_ARG: no solve yet, a handle on another device than `device`, a candidate outside the last solve. */
+struct OrbxSim3Rows { const float *r12, *t12, *s12; const unsigned long long *mask; int n, words, iters; };
+int orbx_sim3_device_rows_internal(orbx_sim3_solver *h, int candidate, int device, OrbxSim3Rows *out);
+
 /* Device view of the LAST batch of an extractor: results + the unblurred pyramid (what the
  * reference keeps in ORBextractor::mvImagePyramid, read by Frame::ComputeStereoMatches). */
 struct OrbxLastBatchView {

@@ -56,11 +56,13 @@ __device__ __forceinline__ void three_maxima_wave(const int *hist, int lane, int
 }
 
 struct ProjFrameDev { const orbx_keypoint *kp; const uint8_t *desc; const float *uRight; const uint8_t *occupied; const int32_t *counts; int cap;
-                      float minX, minY, gwInv, ghInv; };
+                      float minX, minY, gwInv, ghInv;
+                      const int32_t *frameOf; };      // k_fuse_best only: problem f searches the staged frame frameOf[f]; nullptr (what every other caller leaves) = frame f
 
 // ORBmatcher::Fuse's search (k_fuse_best, orbx_match_proj.hip): the prepared points of one list per keyframe
 struct FusePointsDev { const float *u, *v, *ur; const int32_t *level; const float *radius; const uint8_t *active, *desc; const int32_t *counts; int cap;
-                       float kfMinX, kfMinY; };
+                       float kfMinX, kfMinY;
+                       const int32_t *descOf; };      // list f's descriptors are row descOf[f] of `desc` (lists that share a keyframe's points); nullptr = row f
 struct FuseLevels { float invSigma2[ORBX_MAX_LEVELS]; };
 
 // The views of the two tracking searches (kernels in orbx_match_proj.hip; orbx_track.hip chains them through enqueue_proj_last / enqueue_local_points)
@@ -158,6 +160,10 @@ struct orbx_matcher : OrbxHandle {
     // Relocalization's refine loop (orbx_reloc.hip): the per-hypothesis state, queries, pose problems and results of one call, all device memory
     OrbxOwnedBuf<uint8_t> rlWork;
     OrbxWorkPlan rlPlan;
+    // LoopClosing::ComputeSim3's refine step for every Sim3Solver event (orbx_loop_sim3.hip): seeds, query lists, search results, OptimizeSim3's problems and result blocks
+    OrbxOwnedBuf<uint8_t> lsWork;
+    OrbxWorkPlan lsPlan;
+    OrbxCallTimer lsTimer;            // (its events are made by the first call)
     ~orbx_matcher()
     {
         hipEvent_t *const one[] = {&evDep, &evDep2};
@@ -245,6 +251,8 @@ FeatDev to_dev(const orbx_feature_set *s);
 int stage_host(orbx_matcher *m, const orbx_feature_set *const *h, orbx_feature_set *const *d, int nsides);
 /* k_fuse_best (orbx_match_proj.hip) for one keyframe with chi2_gate = 1: P.cap slots, the list's length read on the device from P.counts */
 void launch_fuse_best(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int32_t *bestIdx, int32_t *bestDist);
+/* ... for nlists problems with chi2_gate = 0 in ONE launch: F.frameOf / P.descOf name each list's keyframe and descriptor row; results at [f * P.cap + i] */
+void launch_fuse_best_lists(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int nlists, int32_t *bestIdx, int32_t *bestDist);
 /* k_proj_last_topk + k_proj_last_greedy for ONE frame (F.cap features, L.cap last-frame features; every pointer device memory) on `st`:
  * matches[0..stride) and nmatches[0] as orbx_search_by_projection_last_device leaves them.  pubFlag != nullptr: the replay also writes
  * pubAssigned[0..n] (mapped host memory) and raises the sequence word.  Both launches obey `gate`.  Grows the handle's candidate / replay buffers. */

@@ -590,9 +590,10 @@ __global__ __launch_bounds__(256) void k_fuse_best(ProjFrameDev F, FusePointsDev
                                                    int32_t *__restrict__ bestDist, int stride)
 {
     const int f = blockIdx.y, lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int n = min(F.counts[f], F.cap), m = min(P.counts[f], P.cap);
+    const int ff = F.frameOf ? F.frameOf[f] : f;      // (orbx_loop_sim3.hip: 2 H problems over K + 1 staged keyframes)
+    const int n = min(F.counts[ff], F.cap), m = min(P.counts[f], P.cap);
     if (i >= m) return;
-    const size_t pi = (size_t)f * P.cap + i, fbase = (size_t)f * F.cap;
+    const size_t pi = (size_t)f * P.cap + i, fbase = (size_t)ff * F.cap, di = (size_t)(P.descOf ? P.descOf[f] : f) * P.cap + i;
     unsigned long long best = KEY64_EMPTY;
     if (!P.active || P.active[pi]) {
         const float x = P.u[pi], y = P.v[pi], r = P.radius[pi], xr = chi2Gate ? P.ur[pi] : 0.0f;
@@ -601,7 +602,7 @@ __global__ __launch_bounds__(256) void k_fuse_best(ProjFrameDev F, FusePointsDev
         const int cx0 = max(0, (int)floorf((x - P.kfMinX - r) * F.gwInv)), cx1 = min(GRID_COLS - 1, (int)ceilf((x - P.kfMinX + r) * F.gwInv));
         const int cy0 = max(0, (int)floorf((y - P.kfMinY - r) * F.ghInv)), cy1 = min(GRID_ROWS - 1, (int)ceilf((y - P.kfMinY + r) * F.ghInv));
         if (!(cx0 >= GRID_COLS || cx1 < 0 || cy0 >= GRID_ROWS || cy1 < 0)) {
-            const unsigned long long *dp = (const unsigned long long *)(P.desc + pi * 32);
+            const unsigned long long *dp = (const unsigned long long *)(P.desc + di * 32);
             const unsigned long long d[4] = {dp[0], dp[1], dp[2], dp[3]};
             for (int idx = lane; idx < n; idx += 64) {
                 const orbx_keypoint k = F.kp[fbase + idx];
@@ -641,6 +642,13 @@ __global__ __launch_bounds__(256) void k_fuse_best(ProjFrameDev F, FusePointsDev
 void orbx_match::launch_fuse_best(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int32_t *bestIdx, int32_t *bestDist)
 {
     hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)((P.cap + 3) / 4), 1u), dim3(256), 0, st, F, P, LV, 1, bestIdx, bestDist, P.cap);
+}
+
+// nlists (keyframe, list) problems with chi2_gate = 0 in one launch on `st` (orbx_loop_sim3.hip): list f searches keyframe F.frameOf[f] with the descriptors of
+// row P.descOf[f]; results at bestIdx / bestDist [f * P.cap + i]
+void orbx_match::launch_fuse_best_lists(hipStream_t st, const ProjFrameDev &F, const FusePointsDev &P, const FuseLevels &LV, int nlists, int32_t *bestIdx, int32_t *bestDist)
+{
+    hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)((P.cap + 3) / 4), (unsigned)nlists), dim3(256), 0, st, F, P, LV, 0, bestIdx, bestDist, P.cap);
 }
 
 static int fuse_launch(orbx_matcher *m, const ProjFrameDev &F, const FusePointsDev &P, int nframes, const float *inv_level_sigma2, int nlevels, int chi2_gate)

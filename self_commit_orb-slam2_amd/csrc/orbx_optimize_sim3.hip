@@ -24,31 +24,10 @@
 #include <vector>
 
 #include "orbx_handle.h"
-#include "orbx_sim3_group.h"
+#include "orbx_optsim3.h"
 
 #define OS_THREADS 256
 #define OS_NRED 36      /* 28 upper-triangle entries of H, 7 of b, the robust chi2 */
-
-struct OsProb {                  // one problem of a call: in mapped pinned memory (host-filled)
-    float rcw1[9], tcw1[3], rcw2[9], tcw2[3];
-    float k1[4], k2[4];          // fx, fy, cx, cy
-    double r12[9], t12[3], s12;
-    float th2;
-    int32_t n, fixScale, mb;     // mb: first pair of this problem in the call's arrays
-    unsigned long long outOff;   // the problem's result block in the mapped result buffer
-};
-static_assert(sizeof(OsProb) % 8 == 0, "holds 8-byte members");
-
-struct OsBlock {                 // layout of a problem's result block (mapped pinned); head = {n_inliers, n_bad, 0, 0}
-    size_t est, stats, r12, remFirst, remFinal, chi1, chi2, x1, x2, total;
-    __host__ __device__ OsBlock(int n)
-    {
-        const size_t m = (size_t)n, m8 = (m + 7) & ~(size_t)7;
-        est = 16; stats = est + 64; r12 = stats + 32; remFirst = r12 + 40; remFinal = remFirst + m8; chi1 = remFinal + m8; chi2 = chi1 + 16 * m;
-        x1 = chi2 + 16 * m; x2 = x1 + 12 * m;
-        total = (x2 + 12 * m + 255) & ~(size_t)255;
-    }
-};
 
 struct OsLinBlock {              // layout of orbx_optimize_sim3_linearize's results
     size_t err, chi, jac, H, b, total;
@@ -58,13 +37,6 @@ struct OsLinBlock {              // layout of orbx_optimize_sim3_linearize's res
         err = 0; chi = err + 32 * m; jac = chi + 16 * m; H = jac + 224 * m; b = H + 49 * 8;
         total = (b + 56 + 255) & ~(size_t)255;
     }
-};
-
-struct OsIn {                    // the call's inputs, device addresses of mapped pinned memory
-    const OsProb *prob;
-    const float *world1, *world2, *obs1, *obs2, *inv1, *inv2;
-    const uint8_t *active;       // LIN: [n] or nullptr = every pair
-    OsSim3 lin;                  // LIN: the estimate
 };
 
 // obs - cam_map(project(S.map(X))): EdgeSim3ProjectXYZ with (S, X2, obs1, K1), EdgeInverseSim3ProjectXYZ with (S^-1, X1, obs2, K2)
@@ -560,15 +532,20 @@ OsStaged os_stage(orbx_sim3_optimizer *h, const orbx_sim3_opt_problem *Ps, int n
     return S;
 }
 
-template <bool LIN> void os_launch(orbx_sim3_optimizer *h, int maxN, int np, const OsIn &I, uint8_t *res, unsigned long long seq)
+template <bool LIN> void os_launch(hipStream_t st, int maxN, int np, const OsIn &I, uint8_t *res, unsigned *counter, unsigned long long *flag, unsigned long long seq)
 {
-    OrbxCallBox &bx = h->box;
     const dim3 g((unsigned)np), b(OS_THREADS);
-    if (maxN <= OS_THREADS) hipLaunchKernelGGL((k_optsim3<1, LIN>), g, b, 0, h->stream, I, res, bx.counter, bx.flagDev, seq);
-    else if (maxN <= 2 * OS_THREADS) hipLaunchKernelGGL((k_optsim3<2, LIN>), g, b, 0, h->stream, I, res, bx.counter, bx.flagDev, seq);
-    else hipLaunchKernelGGL((k_optsim3<4, LIN>), g, b, 0, h->stream, I, res, bx.counter, bx.flagDev, seq);
+    if (maxN <= OS_THREADS) hipLaunchKernelGGL((k_optsim3<1, LIN>), g, b, 0, st, I, res, counter, flag, seq);
+    else if (maxN <= 2 * OS_THREADS) hipLaunchKernelGGL((k_optsim3<2, LIN>), g, b, 0, st, I, res, counter, flag, seq);
+    else hipLaunchKernelGGL((k_optsim3<4, LIN>), g, b, 0, st, I, res, counter, flag, seq);
 }
 }  // namespace
+
+// the launch of orbx_optimize_sim3 as a link of another file's chain (orbx_optsim3.h)
+void orbx_optsim3_enqueue(hipStream_t st, const OsIn &I, uint8_t *out, int np, int maxN, unsigned *counter, unsigned long long *flag, unsigned long long seq)
+{
+    os_launch<false>(st, maxN, np, I, out, counter, flag, seq);
+}
 
 extern "C" int orbx_sim3_optimizer_create(int device, int max_problems, int max_pairs, orbx_sim3_optimizer **out)
 {
@@ -604,7 +581,7 @@ extern "C" int orbx_optimize_sim3(orbx_sim3_optimizer *h, const orbx_sim3_opt_pr
     OrbxCallBox &bx = h->box;
     const unsigned long long seq = bx.arm();
     if ((rc = h->timer.begin(h->stream)) != ORBX_OK) return rc;
-    os_launch<false>(h, maxN, np, I, S.sg.dev(S.res), seq);
+    orbx_optsim3_enqueue(h->stream, I, S.sg.dev(S.res), np, maxN, bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_COUNT(h->timer);
     if ((rc = h->timer.end(h->stream)) != ORBX_OK) return rc;
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;      // the one synchronisation
@@ -650,7 +627,7 @@ extern "C" int orbx_optimize_sim3_linearize(orbx_sim3_optimizer *h, const orbx_s
     I.lin.s = s;
     OrbxCallBox &bx = h->box;
     const unsigned long long seq = bx.arm();
-    os_launch<true>(h, P->n, 1, I, S.sg.dev(S.res), seq);
+    os_launch<true>(h->stream, P->n, 1, I, S.sg.dev(S.res), bx.counter, bx.flagDev, seq);
     ORBX_LAUNCH_CHECK();
     if ((rc = bx.wait(h->stream)) != ORBX_OK) return rc;
     const size_t n = (size_t)P->n;

@@ -587,6 +587,19 @@ extern "C" int orbx_sim3_inliers(orbx_sim3_solver *h, int candidate, int iterati
     return ORBX_OK;
 }
 
+int orbx_sim3_device_rows_internal(orbx_sim3_solver *h, int candidate, int device, OrbxSim3Rows *out)
+{
+    if (!h || !out) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }
+    if (!h->solved) { orbx_set_error("the Sim3 solver has no orbx_sim3_solve call to read from"); return ORBX_ERR_ARG; }
+    if (h->device != device) { orbx_set_error("the Sim3 solver lives on device %d, the caller on device %d", h->device, device); return ORBX_ERR_ARG; }
+    if (candidate < 0 || candidate >= (int)h->last.size()) { orbx_set_error("candidate %d outside the last solve (%d candidates)", candidate, (int)h->last.size()); return ORBX_ERR_ARG; }
+    const Sim3Cand &H = h->last[(size_t)candidate];
+    const Sim3Dev D = dev_view(h);
+    out->r12 = D.r12 + 9 * (size_t)H.ib; out->t12 = D.t12 + 3 * (size_t)H.ib; out->s12 = D.s12 + H.ib; out->mask = D.mask + H.wb;
+    out->n = H.n; out->words = H.words; out->iters = H.iters;
+    return ORBX_OK;
+}
+
 extern "C" int orbx_sim3_check_models(orbx_sim3_solver *h, const orbx_sim3_problem *P, const float *t12, const float *t21, int m, int32_t *count, uint8_t *inliers)
 {
     if (!h || !P || !t12 || !t21 || !count) { orbx_set_error("NULL argument"); return ORBX_ERR_ARG; }

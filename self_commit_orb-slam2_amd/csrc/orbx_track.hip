@@ -260,6 +260,7 @@ int pose_link(hipStream_t st, const TrackWork &w, const float *pose0, const floa
 int orbx_match::track_mark(orbx_matcher *m, hipStream_t st, int k)
 {
     if (!m->trProfile) return ORBX_OK;
+    if (k < 0 || k >= TRK_MAX_MARKS) { orbx_set_error("chain boundary %d outside the %d events of the profiling tap", k, TRK_MAX_MARKS); return ORBX_ERR_ARG; }
     if (m->trEv.size() < TRK_MAX_MARKS) m->trEv.resize(TRK_MAX_MARKS, nullptr);
     if (!m->trEv[k]) { const int rc = orbx_event_create(&m->trEv[k]); if (rc != ORBX_OK) return rc; }
     ORBX_HIP_CHECK(hipEventRecord(m->trEv[k], st));
