@@ -162,6 +162,7 @@ struct orbx_extractor {
     // last run
     int lastBatch = 0;
     bool lastPyrFast = false;         // the last batch ran the detector inside the pyramid band launches (k_pyr_band_fast); read by the tests' developer tap
+    bool lastPyrBand = false;         // the last batch ran the band launches (k_pyr_band / k_pyr_band_fast), not the split ones; read by the tests' developer tap
     bool lastChunked = false;         // the last call was a host batch pipelined in chunks: the device holds its LAST chunk only, lastBatch = 0 (no device-side view)
     const uint8_t *lastImg0 = nullptr;
     int lastStride = 0;
@@ -640,12 +641,14 @@ int run_batch(orbx_extractor *h, const uint8_t *img0Dev, int batch, int W, int H
     if ((rc = orbx_launch_orient_describe(L)) != ORBX_OK) return rc;
     if (prof) { ORBX_HIP_CHECK(hipEventRecord(ev[ST_DESC + 1], h->stream)); h->profCount++; }
     h->lastBatch = batch; h->lastImg0 = img0Dev; h->lastStride = stride; h->lastFramePitch = framePitch;
-    h->lastCombined = false; h->hostSynced = false; h->lastChunked = false; h->lastPyrFast = pyrFast;
+    h->lastCombined = false; h->hostSynced = false; h->lastChunked = false; h->lastPyrFast = pyrFast; h->lastPyrBand = L.pyrBand;
     return ORBX_OK;
 }
 
 // developer tap (tests/test_pyr_fast.py; not part of include/orbx.h): 1 when the handle's last batch ran the joint band + detector launches
 extern "C" int orbx_debug_last_batch_pyr_fast(orbx_extractor *h) { return h && h->lastPyrFast ? 1 : 0; }
+// developer tap (tests/test_pyr_band_blend.py; not part of include/orbx.h): 1 when the handle's last batch ran the band launches (either form)
+extern "C" int orbx_debug_last_batch_pyr_band(orbx_extractor *h) { return h && h->lastPyrBand ? 1 : 0; }
 
 // host-side copies of a batch entry point (frames into pinned staging, results out of the pinned arena) on a few threads
 static int host_copy_threads()

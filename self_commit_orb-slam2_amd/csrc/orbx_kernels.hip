@@ -13,6 +13,7 @@
 #include <algorithm>
 #include "orbx_internal.h"
 #include "orbx_trig.h"
+#include "orbx_pack.h"
 
 namespace {
 
@@ -1162,8 +1163,40 @@ __global__ __launch_bounds__(64) void k_blur(const OrbxGeom *__restrict__ g, con
 // scalar where the runtime division cost every item a dozen instructions (v_rcp_iflag_f32 hoisted, v_mul_hi_u32 + v_mul_lo_u32 + the quotient's fix-up not)
 __device__ __forceinline__ int pb_div(int item, uint32_t dv) { return (int)(__umul24((uint32_t)item, dv & 0xfffffu) >> (dv >> 20)); }
 // bits 32 .. 47 of the product of two values below 2^24: v_mul_hi_u32_u24 where the compiler sees the callers' masks, v_mul_hi_u32 where it does not
-// (behind the row-reuse copies of the resize loop) - the same result and the same measured issue cost (profiles/pyr_band_valu_issue.txt)
+// (behind the conditional horizontal passes of the resize loop) - the same result and the same measured issue cost (profiles/pyr_band_valu_issue.txt)
 __device__ __forceinline__ uint32_t pb_mulhi24(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+// The addresses of eight consecutive rows from `row0`, each pinned in a scalar register pair: a store is then global_store_dword with that pair as its
+// base and the lane's 32-bit offset as it is (pb_store).  (Left to itself the compiler adds the lane's offset to the first row's pointer and then
+// q * pitch to that, a 64-bit vector add per row.)  The pinned values are integers: a pointer that has been through the asm is no longer known to point
+// to global memory, and pb_store says so again.  `row0` and `pitch` MUST be uniform in the workgroup (here: kernel arguments, the block's frame and band
+// and the level's plan): the "s" constraint would take the first lane's value of anything else and every other lane would store to the wrong row.
+__device__ __forceinline__ void pb_row_ptrs(uint64_t rows[8], uint8_t *row0, uint32_t pitch)
+{
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        rows[q] = (uint64_t)(row0 + (size_t)((uint32_t)q * pitch));
+        asm("" : "+s"(rows[q]));
+    }
+}
+typedef __attribute__((address_space(1))) uint32_t pb_global_u32;
+__device__ __forceinline__ void pb_store(uint64_t row, uint32_t &off, uint32_t v)
+{
+    // the offset's zero extension has to be formed HERE, in the store's own basic block, for the instruction selector to see base pair + 32-bit offset;
+    // hoisted in front of the eight stores it is a 64-bit value like any other and every store gets a 64-bit add.  The caller's variable passes
+    // through the (empty) asm, so the value stays in its register from one store to the next
+    asm volatile("" : "+v"(off));
+    *(pb_global_u32 *)(row + off) = v;
+}
+// One output word of the resize: k_resize's truncating blend ((b0 * h0) >> 16) + ((b1 * h1) >> 16) of four pixels, rounded (+ 2) >> 2.  Eight high
+// multiplies, then the sums packed in pairs as 16-bit lanes, rounded and shifted two at a time and gathered by one v_perm_b32 (orbx_pack.h).  The
+// byte-wise form ((m + 2) >> 2) << 8k, ORed, came out of the compiler as twelve shifts, masks and adds per word beside the multiplies.
+__device__ __forceinline__ uint32_t pb_blend4(uint32_t b0, uint32_t b1, const uint32_t ha[4], const uint32_t hb[4])
+{
+    uint32_t m[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) m[k] = pb_mulhi24(b0, ha[k]) + pb_mulhi24(b1, hb[k]);      // m + 2 < 1024 (see k_resize: the pixel is <= 255)
+    return orbx_pack4_round_shr2(m[0], m[1], m[2], m[3]);
+}
 // staging of a band's rows; EDGE = some of them lie above or below the level and are mirrored (first and last band of a level: uniform in the workgroup)
 template <bool EDGE>
 __device__ __forceinline__ void pb_stage(uint8_t *__restrict__ bb, const uint8_t *__restrict__ src, const int sp, const int readable, const int w, const int h, const int P,
@@ -1232,21 +1265,26 @@ __device__ __forceinline__ void pyr_band_body(const OrbxGeom *__restrict__ g, co
         const int G4 = (w + 3) >> 2, items = G4 * ((s1 - s0 + 7) >> 3), PW = P >> 2;
         const uint32_t pitch = (uint32_t)lv.pitch;
         const bool full = ((s1 - s0) & 7) == 0;      // (uniform: only the last band of a level ends inside an 8-row group)
-        uint8_t *dst = blur + (size_t)f * g->pyrBytes + lv.off;      // uniform base + 32-bit byte offsets (a level is far smaller than 4 GB)
+        // Row q of every item is stored through a UNIFORM row pointer (row s0 + q of the level: a scalar register pair, pb_row_ptrs) plus ONE
+        // per-lane byte offset that all eight stores share - the row pitch never enters a lane's arithmetic.  (One running offset, o += pitch, came
+        // back from the compiler as a v_mul_lo_u32 and three adds for each of the eight rows.)  A level is far smaller than 4 GB: 32-bit offsets.
+        uint64_t dst[8];
+        pb_row_ptrs(dst, blur + (size_t)f * g->pyrBytes + lv.off + (size_t)s0 * pitch, pitch);
+        const uint32_t grpPitch = 8u * pitch, grpPW = 8u * (uint32_t)PW;      // one 8-row group down: in the level, in the window (both < 2^24)
+        const uint32_t *win0 = band + PB_ORG / 4 - 1;
         for (int item = tid; item < items; item += PB_THREADS) {
             const int rgi = pb_div(item, lv.bandDivG4), gx = item - (int)__umul24((uint32_t)rgi, (uint32_t)G4);
             uint32_t outw[8];
-            blur_rows8<CLAMP>(g, band + (int)__umul24((uint32_t)(8 * rgi), (uint32_t)PW) + gx + PB_ORG / 4 - 1, PW, outw);      // word of pixels 4gx - 4 .. 4gx - 1
-            uint32_t o = (uint32_t)(s0 + 8 * rgi) * pitch + 4u * (uint32_t)gx;
+            blur_rows8<CLAMP>(g, win0 + (__umul24((uint32_t)rgi, grpPW) + (uint32_t)gx), PW, outw);      // word of pixels 4gx - 4 .. 4gx - 1
+            uint32_t o = __umul24((uint32_t)rgi, grpPitch) + 4u * (uint32_t)gx;
             if (full) {
 #pragma unroll
-                for (int q = 0; q < 8; q++, o += pitch) *(uint32_t *)(dst + o) = outw[q];
+                for (int q = 0; q < 8; q++) pb_store(dst[q], o, outw[q]);
             } else {
+                const int left = s1 - s0 - 8 * rgi;      // rows of this group inside the band
 #pragma unroll
-                for (int q = 0; q < 8; q++, o += pitch) {
-                    if (s0 + 8 * rgi + q >= s1) break;
-                    *(uint32_t *)(dst + o) = outw[q];
-                }
+                for (int q = 0; q < 8; q++)
+                    if (q < left) pb_store(dst[q], o, outw[q]);
             }
         }
     }
@@ -1258,7 +1296,9 @@ __device__ __forceinline__ void pyr_band_body(const OrbxGeom *__restrict__ g, co
     const uint32_t dpitch = (uint32_t)ln.pitch;
     const uint2 *rt = (const uint2 *)(rsTab + ln.rsRowOff);
     const uint32_t *ctab = rsTab + ln.rsColOff;
-    uint8_t *dstBase = pyr + (size_t)f * g->pyrBytes + ln.off;
+    uint64_t dstRow[8];      // rows d0 .. d0 + 7: uniform row pointers as in the blur's stores
+    pb_row_ptrs(dstRow, pyr + (size_t)f * g->pyrBytes + ln.off + (size_t)d0 * dpitch, dpitch);
+    const uint32_t chPitch = 8u * dpitch;
     const uint8_t *lrow0 = bb + PB_ORG - (s0 - 3) * P;       // LDS byte of pixel 0 of image row y: lrow0 + y * P
     for (int item = tid; item < items; item += PB_THREADS) {
         const int ch = pb_div(item, ln.bandDivG4), cg = item - (int)__umul24((uint32_t)ch, (uint32_t)Gd);
@@ -1268,18 +1308,18 @@ __device__ __forceinline__ void pyr_band_body(const OrbxGeom *__restrict__ g, co
         const uint32_t mis = (uint32_t)(sx0 & 3);
         const bool wide = (int)c0.y <= 7;      // (LDS rows are readable 12 bytes past every group window)
         const uint32_t sel[4] = {c0.z, c0.w, c1.x, c1.y}, coef[4] = {c1.z, c1.w, c2.x, c2.y};
+        const uint8_t *lcolA = lrow0 + sxa, *lcol0 = lrow0 + sx0;      // the group's first source column in row 0: a row is ONE multiply-add away
         // horizontal pass of source row y: k_resize's r0 / r1 before the blend, (dot >> 4) << 4.  The dot product of two 8-bit pixels with 11-bit
         // coefficients that add up to 2048 (+-1) is below 2^20, so the mask keeps every bit above the four that k_resize shifts out
         auto hpass = [&](int y, uint32_t hv[4]) {
-            const uint8_t *row = lrow0 + (int)__umul24((uint32_t)y, (uint32_t)P);
             if (wide) {
-                const uint32_t *p = (const uint32_t *)(row + sxa);
+                const uint32_t *p = (const uint32_t *)(lcolA + (int)__umul24((uint32_t)y, (uint32_t)P));
                 const uint32_t a0 = p[0], a1 = p[1], a2 = p[2];
                 const uint32_t v0 = __builtin_amdgcn_alignbyte(a1, a0, mis), v1 = __builtin_amdgcn_alignbyte(a2, a1, mis);
 #pragma unroll
                 for (int k = 0; k < 4; k++) hv[k] = udot2(__builtin_amdgcn_perm(v1, v0, sel[k]), coef[k], 0u) & 0x00fffff0u;
             } else {
-                const uint8_t *S = row + sx0;
+                const uint8_t *S = lcol0 + (int)__umul24((uint32_t)y, (uint32_t)P);
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int off = (int)((c2.z >> (8 * k)) & 0xffu), off1 = (int)((c2.w >> (8 * k)) & 0xffu);
@@ -1287,8 +1327,12 @@ __device__ __forceinline__ void pyr_band_body(const OrbxGeom *__restrict__ g, co
                 }
             }
         };
-        uint32_t ha[4], hb[4];      // horizontal passes of source rows ra, rb (consecutive output rows share a row: computed once)
-        int ra = -1, rb = -1;
+        // Horizontal passes of two source rows.  Consecutive output rows share a source row (scale < 2: y0 moves on by one or by two): the two sets
+        // SWAP their roles from one unrolled output row to the next, so the row that was y1 is y0 where it is already - no copy.  After output row
+        // r - 1 the set that row r reads as y0 holds y1 of row r - 1, and the other one y0 of row r - 1: a set is recomputed whenever the row it is
+        // to hold differs from that (when y0 moves on by two: both, as before), so any table is handled, and the rows' own table words are the tags.
+        uint32_t hs[2][4];
+        int py0 = -1, py1 = -1;      // y0, y1 of the output row before
         // the chunk's row-table entries requested together (one memory round trip, not one per output row) and unclamped: one address, eight
         // offsets; the entries behind row d1 - 1 are not used (the host pads the tables' array for the last chunk of the last level)
         const int dA = d0 + 8 * ch, nrow = min(8, d1 - dA);
@@ -1296,35 +1340,22 @@ __device__ __forceinline__ void pyr_band_body(const OrbxGeom *__restrict__ g, co
         uint2 tr[8];
 #pragma unroll
         for (int r = 0; r < 8; r++) tr[r] = rtc[r];
-        uint32_t o = (uint32_t)dA * dpitch + 4u * (uint32_t)cg;
+        uint32_t o = __umul24((uint32_t)ch, chPitch) + 4u * (uint32_t)cg;
 #pragma unroll
-        for (int r = 0; r < 8; r++, o += dpitch) {
+        for (int r = 0; r < 8; r++) {
             if (r >= nrow) break;
             const uint2 t = tr[r];
             const int y0 = (int)(t.x & 0xffffu), y1 = (int)(t.x >> 16);
-            if (y0 != ra) {
-                if (y0 == rb) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) ha[k] = hb[k];
-                } else hpass(y0, ha);
-                ra = y0;
-            }
-            if (y1 != rb) {
-                if (y1 == ra) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) hb[k] = ha[k];
-                } else hpass(y1, hb);
-                rb = y1;
-            }
+            const int ia = r & 1, ib = ia ^ 1;      // (compile time: the loop is unrolled)
+            if (y0 != py1) hpass(y0, hs[ia]);
+            if (y1 != py0) hpass(y1, hs[ib]);
+            py0 = y0; py1 = y1;
             // k_resize's truncating blend ((b0 * h0) >> 16) + ((b1 * h1) >> 16) with ONE multiply per term: the row weights (0 .. 2048) shifted
             // left by 12 (< 2^24) times the horizontal value still shifted left by 4 (< 2^24) is b * h * 2^16, and the high multiply returns bits
             // 32 .. 47 of that 48-bit product = (b * h) >> 16 exactly (tests/test_pyr_band_plan.py runs every pair); it issues at the cost of
             // v_mul_lo_u32 (tools/ubench_valu.hip), so the two v_lshrrev_b32 per pixel are simply gone
             const uint32_t b0 = (t.y << 12) & 0x00fff000u, b1 = (t.y >> 4) & 0x00fff000u;      // (weights are 0 .. 2048: twelve bits)
-            uint32_t out = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) out |= ((pb_mulhi24(b0, ha[k]) + pb_mulhi24(b1, hb[k]) + 2u) >> 2) << (8 * k);      // (<= 255, see k_resize)
-            *(uint32_t *)(dstBase + o) = out;
+            pb_store(dstRow[r], o, pb_blend4(b0, b1, hs[ia], hs[ib]));
         }
     }
 }
